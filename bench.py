@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: Harris + DoG keypoint detection on 1920x1080 frames (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Outside torchrun `--gpus N` with N > 1 starts the N ranks itself (a torch.distributed.run child job, launch_ranks) and
 relays rank 0's line: both forms measure BASELINE config 5.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given
+(dump_outputs) and prints the line.  Everything else the line can carry - the hooked roofline pass and the per-kernel
+figures, the live HBM traffic (rocprofv3 child passes), the list modes, two batches in flight, the opt-in matrix path,
+BASELINE configs 2 and 3, the C++ host and the CPU baseline - runs only with --full; the options that steer those
+figures (--modes, --mx, --live-traffic, --roofline-pass, --cxx-host, --cpu-sample, --kernel) take effect with it.
 
 A "step" is one pass of the fused hot path (vslam_detect_batch_dev) over one batch of F
 synthetic 1080p frames per GPU (BASELINE config 4: F = 256).  Frames are generated on the
@@ -225,6 +231,91 @@ def cxx_host_runs(rows, cols, n, octaves, rank=0, world=1, local_rank=0):
     return res
 
 
+DUMP_SEED = 0x5EED
+DUMP_FRAMES = 4            # frames whose keypoint lists are written whole
+DUMP_LIST_MAX = 1 << 17    # ... up to this many records per frame and list (list order)
+DUMP_SAMPLE = 1 << 20      # elements of response / nms_mask, and half as many candidate-mask words
+DUMP_PYR_SAMPLE = 1 << 21  # defined bytes of the pyramid
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, out, p, L):
+    """--dump-outputs: what the timed path handed its caller in the last step, as path/<name>.npy, so that two builds can
+    be compared output for output.  Every sample is drawn from a fixed seed and the run's shapes alone, so the same
+    arguments pick the same elements.  Per-frame counts are written whole (float64); the keypoint lists of DUMP_FRAMES
+    seeded frames are written record by record (float32: every field is exact in it), one row per record led by its frame
+    index; response and nms_mask as a seeded sample of their elements (float32); the pyramid as a seeded sample of its
+    defined bytes (plane padding is unspecified); the candidate masks as a seeded sample of their words, bits past a lattice
+    row's end cleared, each word as two float64 halves (low, high)."""
+    import numpy as np
+    import torch
+
+    from visualslam_amd import capi
+
+    rng = np.random.default_rng(DUMP_SEED)
+    n = out["harris_counts"].shape[0]
+    dev = out["harris_counts"].device
+    res = {}
+
+    def take(t, idx):
+        return t.reshape(-1).index_select(0, torch.from_numpy(idx).to(dev)).cpu().numpy()
+
+    def sample(total, k):
+        return np.arange(total, dtype=np.int64) if total <= k else np.sort(rng.integers(0, total, size=k, dtype=np.int64))
+
+    for name in ("harris_counts", "dog_counts", "oriented_counts", "oriented_survivors"):
+        if name in out:
+            res[name] = out[name].cpu().numpy().astype(np.float64)
+    sel = np.sort(rng.choice(n, size=min(n, DUMP_FRAMES), replace=False))
+    lists = (("harris_kps", "harris_counts", p.harris_cap, capi.KP_DTYPE, ("row", "col", "response")),
+             ("dog_points", "dog_counts", p.dog_cap, capi.POINT_DTYPE, ("row", "col", "value", "octave", "level")),
+             ("oriented_points", "oriented_counts", p.oriented_cap, capi.POINT_DTYPE, ("row", "col", "value", "octave", "level")))
+    for name, cname, cap, dt, fields in lists:
+        if name not in out:
+            continue
+        rows = []
+        for f in sel:
+            m = min(int(res[cname][f]), int(cap), DUMP_LIST_MAX)
+            rec = out[name][int(f), :m].cpu().numpy().view(dt).reshape(-1)
+            rows.append(np.stack([np.full(m, f, np.float32)] + [rec[k].astype(np.float32) for k in fields], axis=1))
+        res[name] = np.concatenate(rows)
+    for name in ("response", "nms_mask"):
+        res[name] = take(out[name], sample(out[name].numel(), DUMP_SAMPLE)).astype(np.float32)
+    if L.n_octaves > 0:
+        no = L.n_octaves
+        R, C = np.array(L.rows[:no], np.int64), np.array(L.cols[:no], np.int64)
+        pitch, off = np.array(L.pitch[:no], np.int64), np.array(L.octave_offset[:no], np.int64)
+        # the pyramid's defined bytes: 11 planes (6 Gaussian, 5 DoG) of rows x cols per octave and frame
+        span = 11 * R * C
+        start = np.concatenate([[0], np.cumsum(span)])
+        u = sample(n * int(start[-1]), DUMP_PYR_SAMPLE)
+        f, r = u // start[-1], u % start[-1]
+        o = np.searchsorted(start, r, side="right") - 1
+        r = r - start[o]
+        plane, r = r // (R[o] * C[o]), r % (R[o] * C[o])
+        res["pyramid"] = take(out["pyramid"], f * L.pyramid_frame_bytes + off[o] + (plane * R[o] + r // C[o]) * pitch[o] + r % C[o]).astype(np.float32)
+        # candidate masks: per octave 3 levels x lat_rows rows of lat_words words, lat_cols bits in each row (LSB first)
+        lr, lc, lw = (np.array(a[:no], np.int64) for a in (L.lat_rows, L.lat_cols, L.lat_words))
+        boff = np.array(L.bits_offset[:no], np.int64)
+        span = 3 * lr * lw
+        start = np.concatenate([[0], np.cumsum(span)])
+        if start[-1] > 0:
+            u = sample(n * int(start[-1]), DUMP_SAMPLE // 2)
+            f, r = u // start[-1], u % start[-1]
+            o = np.searchsorted(start, r, side="right") - 1
+            r = r - start[o]
+            words = take(out["extrema_bits"], f * L.bits_frame_words + boff[o] + r).view(np.uint64)
+            valid = np.where(r % lw[o] == lw[o] - 1, lc[o] - 64 * (lw[o] - 1), 64).astype(np.uint64)
+            keep = np.where(valid >= 64, np.uint64(0xFFFFFFFFFFFFFFFF), (np.uint64(1) << np.minimum(valid, np.uint64(63))) - np.uint64(1))
+            res["extrema_bits"] = (words & keep).view(np.uint32).reshape(-1, 2).astype(np.float64)
+    total = sum(a.nbytes for a in res.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in res.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """BASELINE config 5 from the plain command: `python bench.py --gpus N ...` outside torchrun starts
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same args>` as a CHILD process (never an
@@ -294,7 +385,14 @@ def main():
                     help="A/B: pin the library's side-stream level (vslam_ctx_pin_side_streams: 0 yielding, 1 the context stream's priority, 2 no side streams); -1 = the library's default + watchdog")
     ap.add_argument("--stream", choices=["side", "null"], default="side",
                     help="stream of the whole job: a torch side stream (default) or torch's default (NULL) stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, < 64 MB: see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (roofline passes, live traffic, list modes, two in flight, "
+                         "matrix path, configs 2 / 3, C++ host, CPU baseline); a plain run times the headline only")
     args = ap.parse_args()
+    if not args.full:  # the headline alone: the options of the secondary figures take effect with --full only
+        args.cpu_sample = args.modes = args.live_traffic = args.roofline_pass = args.cxx_host = args.mx = 0
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # the plain form `python bench.py --gpus N`: this process becomes the launcher (nothing here has touched the GPU)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -456,7 +554,7 @@ def main():
         fl = flags.tolist()
         if describe:
             del out["descriptors"], out["descriptor_defined"]
-        return {"p": p, "L": L, "dt": float(red.item()), "launches": launches, "kms": kms, "harris": totals[0], "dog": totals[1],
+        return {"p": p, "L": L, "out": out, "dt": float(red.item()), "launches": launches, "kms": kms, "harris": totals[0], "dog": totals[1],
                 "list_overflow": bool(fl[0]), "oriented": fl[1], "oriented_truncated": bool(fl[2])}
 
     def kernel_alone(kname, steps):
@@ -580,6 +678,9 @@ def main():
     # second pass of the same K steps with the hook around the dominant kernel's launches, outside `value`
     main = run_mode(args.localize, args.orient, args.steps, args.warmup, None)
     leg("value")
+    if args.dump_outputs and rank == 0:  # before any secondary pass overwrites the shared buffers
+        dump_outputs(args.dump_outputs, main["out"], main["p"], main["L"])
+    leg("dump_outputs")
     hooked = run_mode(args.localize, args.orient, args.steps, 0, kname) if args.roofline_pass else {"launches": 0, "kms": 0.0, "dt": 0.0}
     leg("roofline_pass")
     p, L, dt, launches, kms = main["p"], main["L"], main["dt"], hooked["launches"], hooked["kms"]
@@ -810,6 +911,7 @@ def main():
             "n_gpus": ranks_gathered,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),  # False: the secondary objects below are null (a plain run times the headline only)
             "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",

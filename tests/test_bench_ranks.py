@@ -21,7 +21,7 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, VSLAM_BENCH_BACKEND="gloo", VSLAM_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "4", "--rows", "240", "--cols", "320",
-           "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--live-traffic", "0"]
+           "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--live-traffic", "0", "--full"]
     import time
 
     t0 = time.time()
@@ -130,7 +130,7 @@ def test_bench_one_rank_goes_through_rccl():
     env.pop("VSLAM_BENCH_SHARE_GPU", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "8", "--rows", "240", "--cols", "320",
-           "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--live-traffic", "0"]
+           "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--live-traffic", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -162,7 +162,7 @@ def test_bench_measures_its_hbm_traffic_live():
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3 on this box")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "16", "--rows", "540", "--cols", "960", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "0", "--cxx-host", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--cpu-sample", "0", "--cxx-host", "0", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     roof = d["roofline"]

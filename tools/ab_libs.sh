@@ -8,7 +8,7 @@ for rep in $(seq $reps); do
   while read -r label lib rest; do
     [ -z "$label" ] && continue
     args="${rest%%::*}"; envs=""; [[ "$rest" == *::* ]] && envs="${rest#*::}"
-    env $envs VSLAM_LIBRARY=$PWD/visualslam_amd/lib/$lib python bench.py --steps 20 --warmup 5 --modes 1 --cxx-host 0 --cpu-sample 0 --live-traffic 0 --mx 0 $args 2>/dev/null | python -c "
+    env $envs VSLAM_LIBRARY=$PWD/visualslam_amd/lib/$lib python bench.py --full --steps 20 --warmup 5 --modes 1 --cxx-host 0 --cpu-sample 0 --live-traffic 0 --mx 0 $args 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k={}
 for e in d['roofline_by_kernel']: k[(e['kernel'],e['octave'])]=round(e['ms_per_step'],3)

@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $OUT/gputest.log 2>&1; rc=$?
 tail -4 $OUT/gputest.log
 [ $rc = 0 ] || exit $rc
-timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d=json.loads(open("$OUT/bench_default.json").read().strip().splitlines()[-1])

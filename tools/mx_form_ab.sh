@@ -10,6 +10,6 @@ for i in $(seq $R); do
   for f in 16 32; do
     VSLAM_MX_FORM=$f python3 tools/mx_alone.py --octaves 1 2>/dev/null | one "form $f, octave 0"
     VSLAM_MX_FORM=$f python3 tools/mx_alone.py --octaves 2 2>/dev/null | one "form $f, octaves 0-1"
-    VSLAM_MX_FORM=$f python3 bench.py --matrix-path 1 --cpu-sample 0 --modes 0 --mx 0 --cxx-host 0 --live-traffic 0 --steps 10 2>/dev/null | step "form $f"
+    VSLAM_MX_FORM=$f python3 bench.py --full --matrix-path 1 --cpu-sample 0 --modes 0 --mx 0 --cxx-host 0 --live-traffic 0 --steps 10 2>/dev/null | step "form $f"
   done
 done

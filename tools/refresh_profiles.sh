@@ -10,8 +10,8 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 B=$GRAFT_REPO_ROOT/bench.py
-python3 $B > $OUT/bench_default.json 2> $OUT/bench.err
-python3 $B --cpu-sample 0 --modes 0 --octaves 0 --kernel k_harris_strip --mx 0 > $OUT/bench_harris.json 2>> $OUT/bench.err
+python3 $B --full > $OUT/bench_default.json 2> $OUT/bench.err
+python3 $B --full --cpu-sample 0 --modes 0 --octaves 0 --kernel k_harris_strip --mx 0 > $OUT/bench_harris.json 2>> $OUT/bench.err
 Q="--cpu-sample 0 --modes 0 --mx 0 --cxx-host 0 --live-traffic 0"
 S="--frames 64 --steps 1 --warmup 1 --roofline-pass 0 $Q"  # exactly two batch calls per PMC pass (tools/make_traffic.py divides by them)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o runc -- python3 $B $Q > $OUT/prof.log 2>&1

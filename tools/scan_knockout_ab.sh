@@ -7,7 +7,7 @@
 R=${1:-3}
 cd /tmp && export TMPDIR=/tmp
 export VSLAM_LIBRARY=$GRAFT_REPO_ROOT/visualslam_amd/lib/libvslam_diag.so
-ARGS="--cpu-sample 0 --modes 0 --mx 0 --cxx-host 0 --live-traffic 0 --steps 10 --warmup 6"
+ARGS="--full --cpu-sample 0 --modes 0 --mx 0 --cxx-host 0 --live-traffic 0 --steps 10 --warmup 6"
 line() { python3 -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r=d['roofline']; print('%-26s %8.0f frames/s  %6.2f ms/step   k_pyr_octave %.3f ms/launch' % ('$1', d['value'], d['ms_per_step'], r['avg_launch_ms']))"; }
 for i in $(seq $R); do
   python3 $GRAFT_REPO_ROOT/bench.py $ARGS 2>/dev/null | line "scans in (default)"
