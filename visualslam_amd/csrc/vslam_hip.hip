@@ -19,6 +19,7 @@
 #include "kernels_generic.hip.h"
 #include "kernels_pyramid.hip.h"
 #include "kernels_strip.hip.h"
+#include "kernels_hdiff.hip.h"
 #include "kernels_aux.hip.h"
 #include "kernels_harris_strip.hip.h"
 #include "kernels_orient.hip.h"
@@ -49,7 +50,7 @@ struct vslam_pyramid {
 static const char* const kKernelNames =
     "k_resize_linear2x\nk_blur_h_generic\nk_blur_v_generic\n"
     "k_dog5\nk_resize_nearest_half\nk_extrema\nk_pyr_octave\nk_pyr_octave_mx\n"
-    "k_gauss_v_strip\nk_gauss_h_strip\nk_gauss_band\nk_resize_linear2x_slide\nk_resize_nearest_half_v4\nk_extrema_w3\nk_extrema_dense\nk_localize_points\nk_orient_keypoints\nk_edge_response_windows\nk_level_gradients\nk_pack_rows\nk_edge_flags\nk_survivor_ranges\nk_orient_survivors\n"
+    "k_gauss_v_strip\nk_gauss_h_strip\nk_gauss_h_diff\nk_gauss_band\nk_resize_linear2x_slide\nk_resize_nearest_half_v4\nk_extrema_w3\nk_extrema_dense\nk_localize_points\nk_orient_keypoints\nk_edge_response_windows\nk_level_gradients\nk_pack_rows\nk_edge_flags\nk_survivor_ranges\nk_orient_survivors\n"
     "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals";
 
 
@@ -186,6 +187,7 @@ struct OctPlan {
     int ke[6] = {};                 // zero-trimmed widths the fast kernels run with
     std::vector<uint16_t> taps[6];  // trimmed taps
     int sh = 0;                     // rows per horizontal strip workgroup
+    int hdiff = 0;                  // octave of diff_taps.gen.h with these taps: the difference-form horizontal pass (k_gauss_h_diff)
     int band_sh = 0, band_ri = 0, band_rm = 0, band_colsP = 0, band_pw = 0;  // fused band kernel (OctPath::Band)
     size_t band_lds = 0;
 };
@@ -229,6 +231,9 @@ static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
         pl.sh = cols <= 1024 ? 16 : cols <= 2048 ? 8 : cols <= 4096 ? 4 : 0;
         const size_t pw = (size_t)strip_pw(cols, nmax);
         if (pl.sh && v_lds <= 150 * 1024 && pl.sh * pw * 4 <= 150 * 1024) pl.path = OctPath::Strip;
+        // the default pyramid's octaves 2-3 (and any octave with the same taps): horizontal pass in difference form
+        if (pl.path == OctPath::Strip && (cols + HD_J - 1) / HD_J <= 256)
+            pl.hdiff = hd_octave_matches<2>(pl.taps) ? 2 : hd_octave_matches<3>(pl.taps) ? 3 : 0;
         // The fused band kernel (both passes in one launch, row sums stay in LDS) when a band of 16 or 8 rows
         // with its vertical halo fits one CU's LDS and gives every thread at most two horizontal items.
         // OPT-IN (VSLAM_BAND_KERNEL=1), not the default: measured on MI355X, 256 x 1080p, same box, it takes
@@ -290,7 +295,29 @@ static int launch_h_strip(vslam_ctx* c, const uint16_t* h, size_t hframe, uint8_
     return VSLAM_OK;
 }
 
-// Coarse octave: vertical strips (dot4) into the u16 scratch, then horizontal strips (dot2).
+template <int O>
+static int launch_h_diff(vslam_ctx* c, const uint16_t* h, size_t hframe, uint8_t* oct, size_t pframe, int rows, int cols, int pitch,
+                         int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch) {
+    using G = HdGeom<O>;
+    const int ncs = (cols + HD_J - 1) / HD_J, pw = hd_pw(cols, G::HL, G::rmax);
+    // row pairs per workgroup: at most 256 items (one per thread), LDS below the limit, and >= 256 workgroups for small batches
+    int npairs = std::max(1, std::min(8, 256 / ncs));
+    while (npairs > 1 && ((size_t)npairs * pw * 8 > (size_t)kMaxDynLds || (long)((rows + 2 * npairs - 1) / (2 * npairs)) * nf < 256)) --npairs;
+    const size_t lds = (size_t)npairs * pw * 8;
+    TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_h_diff<O>)));
+    {
+        // the timing hook's "k_gauss_h_strip" is the coarse octaves' horizontal pass whichever kernel runs it (bench.py's
+        // per-kernel figures, the dispatch tests); "k_gauss_h_diff" times this kernel alone
+        TimedScope ts(c, "k_gauss_h_strip", c->launch_tag);
+        TimedScope td(c, "k_gauss_h_diff", c->launch_tag);
+        hipLaunchKernelGGL(k_gauss_h_diff<O>, dim3(1, (rows + 2 * npairs - 1) / (2 * npairs), nf), dim3(256), lds, c->stream, h, hframe, oct,
+                           pframe, rows, cols, pitch, npairs, pw, next_base, nframe, nrows, ncols, npitch);
+    }
+    HIPCHK(c, hipGetLastError());
+    return VSLAM_OK;
+}
+
+// Coarse octave: vertical strips (dot4) into the u16 scratch, then horizontal strips (dot2, or the difference form).
 static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const uint8_t* base, size_t bframe,
                                 uint8_t* oct, size_t pframe, uint16_t* h, int rows, int cols, int pitch, int nf,
                                 uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch) {
@@ -313,8 +340,15 @@ static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPla
                            pitch, RM, rhq, taps);
     }
     HIPCHK(c, hipGetLastError());
-    const int pw = strip_pw(cols, nmax);
     c->launch_tag = o;
+    // Diagnostics build only: VSLAM_HDIFF=0 keeps the dot2 pass where the difference form would run (A/B runs, byte-equality test)
+    static const bool hdiff_off = [] {
+        const char* e = VSLAM_DIAG_ENV("VSLAM_HDIFF");
+        return e && e[0] == '0';
+    }();
+    if (pl.hdiff == 2 && !hdiff_off) return launch_h_diff<2>(c, h, 6 * P, oct, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch);
+    if (pl.hdiff == 3 && !hdiff_off) return launch_h_diff<3>(c, h, 6 * P, oct, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch);
+    const int pw = strip_pw(cols, nmax);
     // small batches: shorter row strips, more workgroups
     int sh = pl.sh;
     while (sh > 4 && (long)((rows + sh - 1) / sh) * nf < 256) sh >>= 1;

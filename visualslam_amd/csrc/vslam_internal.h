@@ -19,4 +19,9 @@ int auto_num_octaves(int rows, int cols);
 void half_size(int rows, int cols, int* r, int* c);
 void extrema_lattice(int rows, int cols, int window, int* lr, int* lc);
 int make_layout(const vslam_params* p, vslam_batch_layout* L);
+int diff_form(const uint16_t* w, int n, std::vector<int>& off, std::vector<int>& coef);
 }  // namespace vslam
+
+// Not part of include/vslam.h: the difference form of trimmed taps (vslam::diff_form) for tools/gen_diff_taps.py and
+// its test.  Fills offsets / coeffs (cap entries at most) and *nnz; returns 1 (difference form), 0 (dense), -1 (invalid).
+extern "C" int vslam_diff_form_q8(const uint16_t* taps, int n, int* offsets, int* coeffs, int cap, int* nnz);

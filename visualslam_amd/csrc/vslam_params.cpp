@@ -92,6 +92,29 @@ bool gauss_taps_q8_trimmed(int n, double sigma, std::vector<uint16_t>& out) {
     return true;
 }
 
+// Difference form of one horizontal pass (k_gauss_h_diff): with the row sums h (+ STRIP_HBIAS, <= DIFF_HMAX) and the
+// trimmed taps w (n odd, r = n/2), out[j] - out[j-1] = sum_e d[e] h[j + e], d[e] = w[e + r] - w[e + r + 1] for
+// e in [-r-1, r] (w = 0 outside [0, n)).  Every partial sum of that form is an integer of magnitude <= sum|d| * DIFF_HMAX,
+// and every prefix of the differences is a difference of two outputs (< 2^24), so f32 arithmetic is exact when
+// sum|d| * DIFF_HMAX < 2^24; the form is refused otherwise.  Cost model (VALU issue cycles per output, measured prices:
+// v_dot2_u32_u16 4.27 for 2 MACs, v_fma_f32 2.32): the dense pass (n+1)/2 * 4.27 against nnz(d) * 2.32; the difference
+// form is chosen only where it wins by at least 15 %.  Returns 1 (difference form), 0 (dense), -1 (invalid taps).
+static constexpr long DIFF_HMAX = 255 * 256 + 128;
+
+int diff_form(const uint16_t* w, int n, std::vector<int>& off, std::vector<int>& coef) {
+    off.clear(), coef.clear();
+    if (!w || n <= 0 || (n & 1) == 0) return -1;
+    const int r = n / 2;
+    long l1 = 0;
+    for (int e = -r - 1; e <= r; ++e) {
+        const int k = e + r;
+        const int d = (k >= 0 ? (int)w[k] : 0) - (k + 1 < n ? (int)w[k + 1] : 0);
+        if (d) off.push_back(e), coef.push_back(d), l1 += d < 0 ? -d : d;
+    }
+    if (l1 * DIFF_HMAX >= (1L << 24)) return 0;
+    return (double)off.size() * 2.32 * 1.15 <= (double)(n + 1) / 2 * 4.27 ? 1 : 0;
+}
+
 double sigma_at(double sigma0, int octave, int level) {
     const double k = std::pow(2.0f, 1.0f / (double)3);  // GaussPyramid.hpp:69
     return std::pow(2, octave) * sigma0 * std::pow(k, level);
@@ -175,6 +198,15 @@ int vslam_gauss_taps_q8(int n, double sigma, uint16_t* taps) {
 }
 
 double vslam_sigma_at(double sigma0, int octave, int level) { return vslam::sigma_at(sigma0, octave, level); }
+
+int vslam_diff_form_q8(const uint16_t* taps, int n, int* offsets, int* coeffs, int cap, int* nnz) {
+    std::vector<int> off, coef;
+    const int form = vslam::diff_form(taps, n, off, coef);
+    if (form < 0 || !nnz || (int)off.size() > cap || (!off.empty() && (!offsets || !coeffs))) return -1;
+    *nnz = (int)off.size();
+    for (size_t i = 0; i < off.size(); ++i) offsets[i] = off[i], coeffs[i] = coef[i];
+    return form;
+}
 int vslam_auto_num_octaves(int rows, int cols) { return vslam::auto_num_octaves(rows, cols); }
 
 void vslam_half_size(int rows, int cols, int* out_rows, int* out_cols) {
