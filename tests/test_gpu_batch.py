@@ -829,37 +829,6 @@ def test_serial_stream_mode_matches_oracle():
     assert r.returncode == 0 and "smoke ok" in r.stdout, r.stdout + r.stderr
 
 
-def test_fused_band_kernel_matches_oracle():
-    # the coarse octaves run two strip kernels by default; the fused band kernel (one launch, the row sums
-    # stay in LDS) is opt-in (VSLAM_BAND_KERNEL=1, read once per process: measured slower).
-    # One child process runs the shape sweep, the ragged / tiny / 1080p cases and the fast-path check under it.
-    import os
-    import subprocess
-    import sys
-
-    if os.environ.get("VSLAM_BAND_KERNEL") == "1":
-        pytest.skip("already inside the band-kernel run")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VSLAM_BAND_KERNEL="1", VSLAM_LIBRARY=capi.DIAG_LIB_PATH)  # the switch exists in the diagnostics build only
-    sel = "random_shapes or ragged or tiny_frames or config2_and_3 or small_frames_all_outputs or band_kernel_is_dispatched"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_batch.py"), "-m", "gpu", "-q", "-x", "-k", sel],
-                       capture_output=True, text=True, timeout=1200, env=env, cwd=root)
-    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-
-
-def test_band_kernel_is_dispatched_when_asked_for(env):
-    import os
-
-    if os.environ.get("VSLAM_BAND_KERNEL") != "1":
-        pytest.skip("runs inside test_fused_band_kernel_matches_oracle's child process")
-    ctx, torch = env
-    ctx.kernel_timing_enable("k_gauss_band")
-    run_batch(ctx, torch, synth.frames_np(1, 480, 640, stream_id=1))
-    launches, ms = ctx.kernel_timing_read()
-    ctx.kernel_timing_enable(None)
-    assert launches >= 2 and ms > 0
-
-
 def test_matrix_core_octave_kernel_matches_oracle():
     # OPT-IN path (VSLAM_MX=1 / vslam_ctx_set_matrix_path, never the default: the north star rules MFMA out): octaves 0
     # and 1 of the reference's pyramid as banded matrix products (k_pyr_octave_mx).  One child process runs the shape
@@ -878,27 +847,6 @@ def test_matrix_core_octave_kernel_matches_oracle():
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_batch.py"),
                         os.path.join(root, "tests", "test_gpu_ref_images.py"), os.path.join(root, "tests", "test_gpu_parity.py"),
                         "-m", "gpu", "-q", "-x", "-k", sel],
-                       capture_output=True, text=True, timeout=1500, env=env, cwd=root)
-    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-
-
-def test_matrix_path_on_16x16x64_tiles_matches_oracle():
-    # round 6: the second MFMA shape of octaves 0-1 (kernels_pyramid_mx16.hip.h: v_mfma_i32_16x16x64_i8, four accumulator registers,
-    # <= 128 vector registers, the operand fragments in LDS) - at parity with the 32-wide form, so it lives in the diagnostics build
-    # only (VSLAM_MX_FORM=16).  One child process runs every test that is parametrised over the two kernel families, the reference
-    # images and the per-image pyramid tests under it: the same oracle comparisons, bit for bit.
-    import os
-    import subprocess
-    import sys
-
-    if os.environ.get("VSLAM_MX_FORM") == "16":
-        pytest.skip("already inside the 16-wide run")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VSLAM_MX="1", VSLAM_MX_FORM="16", VSLAM_LIBRARY=capi.DIAG_LIB_PATH)
-    sel = "mx or matrix_kernel_is_dispatched or batch_on_the_reference_images or pyramid or golden_fixtures or two_chunks"
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_batch.py"),
-                        os.path.join(root, "tests", "test_gpu_ref_images.py"), os.path.join(root, "tests", "test_gpu_parity.py"),
-                        os.path.join(root, "tests", "test_gpu_large.py"), "-m", "gpu", "-q", "-x", "-k", sel],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 

@@ -2,7 +2,7 @@
 
     [VSLAM_MX=1] [VSLAM_SOAK_F32_FUSED=1] python tools/soak_batch.py <seed> <seconds> [big|deep]
 VSLAM_SOAK_F32_FUSED=1 (round 6): the f32 stages with fused multiply-adds on both sides (vslam_ctx_set_f32_fused against
-oracle.fma_variant); with VSLAM_LIBRARY=lib/libvslam_diag.so VSLAM_MX=1 VSLAM_MX_FORM=16 the matrix path runs its 16 x 16 x 64 kernels.
+oracle.fma_variant).
 `deep` (round 5): 1..6 octaves whatever the frame size (the reference's constructor takes any count) - octaves 4 and 5 run
 kernels of hundreds of taps on images of a few pixels (strip kernels up to 2047 taps, repeated BORDER_REFLECT_101).
 `big`: frames up to 400 x 700 in batches of 1-9 (octave 0 up to 800 x 1400: several seams and straddling lattice rows of the
@@ -80,5 +80,5 @@ while time.time() - t0 < (float(sys.argv[2]) if len(sys.argv) > 2 else 120):
     if time.time() - last_print > 45:
         print(f"... {it} cases, {time.time() - t0:.0f} s", flush=True)  # gpurun takes a silent run for a hung one
         last_print = time.time()
-print("soak ok", it, "cases", "(matrix path" + (", form " + os.environ.get("VSLAM_MX_FORM", "32") if ctx.matrix_path() else "") + ")" if ctx.matrix_path() else "(default path)",
+print("soak ok", it, "cases", "(matrix path)" if ctx.matrix_path() else "(default path)",
       "f32 fused" if fused else "f32 rounded", sys.argv[3] if len(sys.argv) > 3 else "")

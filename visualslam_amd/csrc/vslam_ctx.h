@@ -114,7 +114,6 @@ struct vslam_ctx {
     JoinWatch watch;      // steps the side streams down when their join lags (see JoinWatch)
     hipEvent_t ev_phase = nullptr;  // recorded by every vslam_detect_batch_dev call once its octave-0 kernels are enqueued (vslam_ctx_follow)
     bool phase_marked = false;
-    int batch_calls = 0;  // vslam_detect_batch_dev calls so far
     hipEvent_t ev_up2 = nullptr;  // the second half of a batch has been upsampled (enqueue_dog)
     hipEvent_t ev_chunk = nullptr;  // the main-stream kernels of a chunk (the readers of the octave bases) are enqueued up to here
     // matrix path, fused lattice scan: the side stream's k_extrema_pack launches of a chunk have read the site / seam maps

@@ -50,7 +50,7 @@ struct vslam_pyramid {
 static const char* const kKernelNames =
     "k_resize_linear2x\nk_blur_h_generic\nk_blur_v_generic\n"
     "k_dog5\nk_resize_nearest_half\nk_extrema\nk_pyr_octave\nk_pyr_octave_mx\n"
-    "k_gauss_v_strip\nk_gauss_h_strip\nk_gauss_h_diff\nk_gauss_band\nk_resize_linear2x_slide\nk_resize_nearest_half_v4\nk_extrema_w3\nk_extrema_dense\nk_localize_points\nk_orient_keypoints\nk_edge_response_windows\nk_level_gradients\nk_pack_rows\nk_edge_flags\nk_survivor_ranges\nk_orient_survivors\n"
+    "k_gauss_v_strip\nk_gauss_h_strip\nk_gauss_h_diff\nk_resize_linear2x_slide\nk_resize_nearest_half_v4\nk_extrema_w3\nk_extrema_dense\nk_localize_points\nk_orient_keypoints\nk_edge_response_windows\nk_level_gradients\nk_pack_rows\nk_edge_flags\nk_survivor_ranges\nk_orient_survivors\n"
     "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals";
 
 
@@ -78,12 +78,9 @@ struct StreamSwap {
 
 // Raises a kernel's dynamic shared memory ceiling to the most any launch of it may ask for.
 static constexpr int kMaxDynLds = 150 * 1024;
-// What one workgroup may really take (160 KB on MI355X), read from the device at the first context
-// creation; only the fused band kernel plans against it (plan_octave), the other kernels stay below kMaxDynLds.
-static int g_lds_limit = kMaxDynLds;
-static int raise_dyn_lds(vslam_ctx* c, const void* fn, int limit = kMaxDynLds) {
+static int raise_dyn_lds(vslam_ctx* c, const void* fn) {
     if (c->lds_raised.count(fn)) return VSLAM_OK;
-    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds));
     c->lds_raised.insert(fn);
     return VSLAM_OK;
 }
@@ -178,7 +175,7 @@ static inline dim3 grid_rows(int cols, int rows, int frames = 1) { return dim3((
 // ---------------------------------------------------------------- enqueue helpers (device)
 
 // ---- octave path selection -----------------------------------------------------------------
-enum class OctPath { Tile0, Tile1, Band, Strip, Generic };
+enum class OctPath { Tile0, Tile1, Strip, Generic };
 
 struct OctPlan {
     OctPath path = OctPath::Generic;
@@ -188,8 +185,6 @@ struct OctPlan {
     std::vector<uint16_t> taps[6];  // trimmed taps
     int sh = 0;                     // rows per horizontal strip workgroup
     int hdiff = 0;                  // octave of diff_taps.gen.h with these taps: the difference-form horizontal pass (k_gauss_h_diff)
-    int band_sh = 0, band_ri = 0, band_rm = 0, band_colsP = 0, band_pw = 0;  // fused band kernel (OctPath::Band)
-    size_t band_lds = 0;
 };
 
 static bool taps_fit_u8(const OctPlan& pl) {
@@ -234,28 +229,6 @@ static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
         // the default pyramid's octaves 2-3 (and any octave with the same taps): horizontal pass in difference form
         if (pl.path == OctPath::Strip && (cols + HD_J - 1) / HD_J <= 256)
             pl.hdiff = hd_octave_matches<2>(pl.taps) ? 2 : hd_octave_matches<3>(pl.taps) ? 3 : 0;
-        // The fused band kernel (both passes in one launch, row sums stay in LDS) when a band of 16 or 8 rows
-        // with its vertical halo fits one CU's LDS and gives every thread at most two horizontal items.
-        // OPT-IN (VSLAM_BAND_KERNEL=1), not the default: measured on MI355X, 256 x 1080p, same box, it takes
-        // 2.9 ms per launch against 1.9 ms for the two strip kernels of the same octave (20.1 vs 18.05 ms per
-        // step): the band's base rows fill the LDS, so one workgroup = 2 waves per SIMD runs per CU with three
-        // barriers per level, and that costs more than the 15.5 MB per frame of scratch traffic it removes.
-        static const bool use_band = [] {
-            const char* e = VSLAM_DIAG_ENV("VSLAM_BAND_KERNEL");
-            return e && e[0] == '1';
-        }();
-        if (use_band && pl.path == OctPath::Strip) {
-            const int colsP = ((cols + 3) & ~3) + 4;  // dword pitch of a row quad (+4: spreads the quads over the banks)
-            for (int sh : {16, 8}) {
-                const size_t lds = ((size_t)((sh + 2 * RM) / 4 + 1) * colsP + (size_t)sh * pw) * 4;
-                const int ri = ((cols + 7) / 8) * (sh / 2) <= 1024 ? 2 : 4;
-                if (lds <= (size_t)g_lds_limit && ((cols + 7) / 8) * (sh / ri) <= 1024) {
-                    pl.path = OctPath::Band;
-                    pl.band_sh = sh, pl.band_ri = ri, pl.band_rm = RM, pl.band_colsP = colsP, pl.band_pw = (int)pw, pl.band_lds = lds;
-                    break;
-                }
-            }
-        }
     }
     return pl;
 }
@@ -384,30 +357,6 @@ static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPla
     }
 }
 
-
-// Coarse octave, fused: one launch, the row sums stay in LDS (k_gauss_band).
-template <int SH, int RI>
-static int launch_band(vslam_ctx* c, const OctPlan& pl, const StripTaps* taps, const uint8_t* base, size_t bframe, uint8_t* oct, size_t pframe,
-                       int rows, int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch) {
-    TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_band<SH, RI>), g_lds_limit));  // no static LDS in this kernel
-    {
-        TimedScope ts(c, "k_gauss_band");
-        hipLaunchKernelGGL((k_gauss_band<SH, RI>), dim3(1, (rows + SH - 1) / SH, nf), dim3(512), pl.band_lds, c->stream, base, bframe, oct, pframe, rows,
-                           cols, pitch, pl.band_rm, pl.band_colsP, pl.band_pw, taps, next_base, nframe, nrows, ncols, npitch);
-    }
-    HIPCHK(c, hipGetLastError());
-    return VSLAM_OK;
-}
-static int enqueue_band_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const uint8_t* base, size_t bframe, uint8_t* oct,
-                               size_t pframe, int rows, int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols,
-                               int npitch) {
-    const StripTaps* taps;
-    TRY(get_strip_taps(c, sigma0, o, pl, &taps));
-#define VSLAM_BAND(SH, RI) launch_band<SH, RI>(c, pl, taps, base, bframe, oct, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch)
-    if (pl.band_sh == 16) return pl.band_ri == 2 ? VSLAM_BAND(16, 2) : VSLAM_BAND(16, 4);
-    return pl.band_ri == 2 ? VSLAM_BAND(8, 2) : VSLAM_BAND(8, 4);
-#undef VSLAM_BAND
-}
 
 // GaussianBlur CV_8U on nf dense images; h = u16 scratch of nf*rows*cols elements.
 static int enqueue_blur(vslam_ctx* c, const uint8_t* src, size_t sstep, size_t sframe, uint8_t* dst, size_t dstep,
@@ -641,24 +590,6 @@ static int mark_phase(vslam_ctx* c) {
     return VSLAM_OK;
 }
 
-// Diagnostics build only: VSLAM_DIAG_SKIP_SCAN="<octave mask>,<n>" leaves the plain lattice scan (k_extrema_w3) of the octaves in
-// the mask out of every batch call of a context after its n-th - a TIMING knock-out (profiles/r06_scan_knockout.txt: the upper
-// bound of what folding that scan into the octave kernel could win).  The list kernels then compact the flag words the earlier
-// calls left, so their work is unchanged when the frames are.  Never in the shipped library.
-static bool diag_skip_scan(const vslam_ctx* c, int octave) {
-    static const std::pair<unsigned, int> cfg = [] {
-        const char* e = VSLAM_DIAG_ENV("VSLAM_DIAG_SKIP_SCAN");
-        unsigned mask = 0;
-        int after = 0;
-        if (e) {
-            mask = (unsigned)std::strtoul(e, nullptr, 0);
-            if (const char* comma = std::strchr(e, ',')) after = std::atoi(comma + 1);
-        }
-        return std::make_pair(mask, after);
-    }();
-    return cfg.first && ((cfg.first >> octave) & 1u) && c->batch_calls > cfg.second;
-}
-
 static int dog_side_gate(const vslam_params& p, const vslam_batch_layout& L, int nf) {
     int gate = -1;
     if (nf >= 32)
@@ -741,7 +672,6 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
         HIPCHK(c, hipEventRecord(c->ev_up2, c->stream));
     }
     bool fused[VSLAM_MAX_OCTAVES] = {};
-    int fused_rows[VSLAM_MAX_OCTAVES] = {};  // rows of a wave's strip in the octave kernel that ran the fused scan (32, or 16 for the 16 x 16 x 64 form)
     // a later chunk reuses the site / seam maps: its octave kernels (main stream) must not overwrite them while the previous
     // chunk's k_extrema_pack launches (side stream, low priority, possibly on a slow hardware queue) are still reading
     if (later_chunk && c->pack_pending) {
@@ -782,7 +712,6 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
             scan = MxScan{s.sitemap + s.site_off[o], s.site_frame, L.lat_rows[o], L.lat_cols[o], s.site_pitch[o], p.min_contrast,
                           s.colmap + s.col_off[o], s.col_frame, mx_seams(cols)};
         fused[o] = fused_scan;
-        fused_rows[o] = fused_scan ? mx_strip_rows(mx_config_for(pl.ke)) : 0;
         // frames [f_lo, f_lo + n) of this octave through the LDS-tiled kernel
         auto tiled = [&](int f_lo, int n) -> int {
             const uint8_t* b = base + (size_t)f_lo * s.bases_frame;
@@ -814,8 +743,6 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
             TRY(tiled(nf_a, nf - nf_a));
         } else if (is_tiled)
             TRY(tiled(0, nf));
-        else if (pl.path == OctPath::Band)
-            TRY(enqueue_band_octave(c, p.sigma0, o, pl, base, s.bases_frame, oct, pframe, rows, cols, pitch, nf, nb, s.bases_frame, nr, nc, np));
         else if (pl.path == OctPath::Strip)
             TRY(enqueue_strip_octave(c, p.sigma0, o, pl, base, s.bases_frame, oct, pframe, s.h, rows, cols, pitch, nf, nb, s.bases_frame, nr, nc, np));
         else {
@@ -854,11 +781,11 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
                 {
                     TimedScope ts(c, "k_extrema_pack", o, es);
                     HIPCHK(c, mx_launch_pack(es, sc, L.rows[o], L.lat_words[o], nf, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o],
-                                             L.bits_frame_words, fused_rows[o]));
+                                             L.bits_frame_words, kMxStripRows));
                 }
                 // the lattice rows whose windows straddle a strip's first image row (3a a multiple of the strip's rows, a power of two:
-                // a = 32, 64, ... or 16, 32, ...) are not in the site map: the plain scan kernel runs on exactly those rows
-                const int sr = fused_rows[o];
+                // a = 32, 64, ...) are not in the site map: the plain scan kernel runs on exactly those rows
+                const int sr = kMxStripRows;
                 const int n_straddle = (L.lat_rows[o] - 1) / sr;
                 TimedScope ts(c, "k_extrema_w3", o, es);
                 if (n_straddle > 0)
@@ -868,8 +795,6 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
                     HIPCHK(c, hipEventRecord(c->ev_pack, es));
                     c->pack_pending = true;
                 }
-            } else if (p.extrema_window == 3 && diag_skip_scan(c, o)) {
-                // (diagnostics build, VSLAM_DIAG_SKIP_SCAN: timing knock-out - the flag words keep what an earlier call wrote)
             } else if (p.extrema_window == 3) {
                 const dim3 eg((L.lat_words[o] + 3) / 4, L.lat_rows[o], nf);
                 TimedScope ts(c, "k_extrema_w3", o, es);
@@ -977,11 +902,6 @@ int vslam_ctx_create(int device, void* stream, vslam_ctx** out) {
     vslam_ctx* c = new (std::nothrow) vslam_ctx();
     if (!c) return VSLAM_ERR_NOMEM;
     c->device = device;
-    {
-        int lds = 0;
-        if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds > kMaxDynLds) g_lds_limit = lds;
-        (void)hipGetLastError();
-    }
     if (stream == VSLAM_STREAM_LEGACY) {
         c->stream = nullptr;  // the NULL stream itself: every HIP call below takes it as "stream 0"
     } else if (stream) {
@@ -996,7 +916,6 @@ int vslam_ctx_create(int device, void* stream, vslam_ctx** out) {
     {
         const char* e = std::getenv("VSLAM_MX");
         c->mx = e && e[0] == '1';
-        if (const char* mf = VSLAM_DIAG_ENV("VSLAM_MX_FORM")) mx_set_form(std::atoi(mf));  // diagnostics build: A/B of the two MFMA shapes
         const char* ff = std::getenv("VSLAM_F32_FUSED");
         c->f32_fused = ff && ff[0] == '1';
         const char* es = VSLAM_DIAG_ENV("VSLAM_ORIENT_SCALAR");
@@ -1946,7 +1865,6 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
                 ws_need(4 * compaction_ws_elems(harris_flag_words(p.rows, p.cols), chunk));
     if (orient) need += orient_scratch_bytes(p, chunk);
     c->phase_marked = false;
-    ++c->batch_calls;
     c->pack_pending = false;  // the previous call joined its side streams back
     TRY(ws_reserve(c, need));
     DogScratch s;

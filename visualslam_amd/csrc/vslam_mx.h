@@ -11,11 +11,9 @@ namespace vslam {
 
 // Which matrix-core configuration runs an octave with these zero-trimmed kernel widths: 0 = none.
 int mx_config_for(const int ke[6]);
-// Rows of a wave's strip in configuration `cfg` (32: the 32 x 32 x 32 kernels; 16: the diagnostics build's 16 x 16 x 64 kernels): the
-// lattice rows a fused scan leaves to k_extrema_w3 are the multiples of it.
-int mx_strip_rows(int cfg);
-// 32 (default) or - diagnostics build only - 16: which MFMA shape mx_config_for hands out for octaves 0-1 (process-wide; VSLAM_MX_FORM)
-void mx_set_form(int form);
+// Rows of a wave's strip in the matrix-core kernels (one 32 x 32 x 32 MFMA block high): the lattice rows a fused scan leaves to
+// k_extrema_w3 are the multiples of it.
+constexpr int kMxStripRows = 32;
 // Bytes of the device table of configuration `cfg`; mx_pack fills a host copy (false: a tap does not fit a signed byte).
 size_t mx_taps_bytes(int cfg);
 bool mx_pack(int cfg, const uint16_t* const taps[6], void* host_table);
