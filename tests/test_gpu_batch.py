@@ -816,17 +816,23 @@ def test_batch_tiny_frames(env, shape, n_oct, path):
 
 
 def test_serial_stream_mode_matches_oracle():
-    # the default run forks the Harris / extrema chains onto auxiliary streams; the single-stream
-    # mode (VSLAM_AUX_STREAMS=0 in the diagnostics build lib/libvslam_diag.so, read once per process) must give the same results
-    import os
-    import subprocess
-    import sys
+    # the default run forks the Harris / extrema chains onto auxiliary streams; a context pinned to the single-stream mode
+    # (vslam_ctx_pin_side_streams level 2) must give the same results, on both kernel families and through orientation
+    import torch
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VSLAM_AUX_STREAMS="0", VSLAM_LIBRARY=capi.DIAG_LIB_PATH)  # a diagnostics-build switch (the API: pin_side_streams(2))
-    r = subprocess.run([sys.executable, os.path.join(root, "__graft_entry__.py"), "smoke"], capture_output=True, text=True,
-                       timeout=600, env=env, cwd=root)
-    assert r.returncode == 0 and "smoke ok" in r.stdout, r.stdout + r.stderr
+    capi.build()
+    ctx = capi.Context(0, torch.cuda.current_stream().cuda_stream)
+    try:
+        ctx.pin_side_streams(2)
+        assert ctx.join_watch_report()[:2] == (2, True)
+        frames = synth.frames_np(2, 120, 160, stream_id=0)
+        for mx, kw in ((False, {}), (True, {}), (False, dict(localize=1, orient=1))):
+            ctx.set_matrix_path(mx)
+            p, L, out = run_batch(ctx, torch, frames, n_octaves=3, **kw)
+            for f in range(len(frames)):
+                check_frame(p, L, out, f, frames[f], 3)
+    finally:
+        ctx.close()
 
 
 def test_matrix_core_octave_kernel_matches_oracle():

@@ -26,7 +26,9 @@
 // 2 + 4 with up to 33 taps (FORM 2: K windows of 64, the output block sits between two input blocks).
 //
 //   hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-mfma-vgpr-form -o tools/mfma_probe tools/mfma_probe.hip
-//   tools/mfma_probe <in.bin> <out.bin> [planes] [reps]      (driver + bit-exact check: tools/mfma_probe.py)
+//   tools/mfma_probe <in.bin> <out.bin> [planes] [reps]
+// (the round-3 driver that fed it frames and compared its planes with the oracle is gone; profiles/r03_mfma_probe.txt
+// records its result)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

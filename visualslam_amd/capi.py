@@ -15,9 +15,9 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VSLAM_LIBRARY: development switch for A/B timing of two builds of the same library on one box
-# (tools/ab.sh); everything else uses the in-tree build.
+# (tools/ab_libs.sh); everything else uses the in-tree build.
 LIB_PATH = os.environ.get("VSLAM_LIBRARY") or os.path.join(_HERE, "lib", "libvslam.so")
-# the diagnostics build (-DVSLAM_DIAGNOSTICS: the A/B environment switches); a test / tool that needs one starts its child
+# the diagnostics build (-DVSLAM_DIAGNOSTICS: the reference-path environment switches); a test / tool that needs one starts its child
 # process with VSLAM_LIBRARY=DIAG_LIB_PATH
 DIAG_LIB_PATH = os.path.join(_HERE, "lib", "libvslam_diag.so")
 CSRC = os.path.join(_HERE, "csrc")
@@ -153,7 +153,7 @@ SIGNATURES = {
 
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU): lib/libvslam.so, and beside it
-    lib/libvslam_diag.so (DIAG_LIB_PATH: the same sources with -DVSLAM_DIAGNOSTICS, for the tests / tools that need an A/B
+    lib/libvslam_diag.so (DIAG_LIB_PATH: the same sources with -DVSLAM_DIAGNOSTICS, for the tests / tools that need a reference-path
     switch - never loaded by default)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "vslam.h")]
     newest = max(os.path.getmtime(s) for s in srcs)

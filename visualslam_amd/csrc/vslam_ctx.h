@@ -18,7 +18,7 @@ namespace vslam {
 struct StripTaps;
 }
 
-// Diagnostic environment switches (A/B leftovers, the capture-fault reproducer's knobs) exist only in a build with
+// Diagnostic environment switches (the reference paths of VSLAM_HDIFF and VSLAM_ORIENT_SCALAR) exist only in a build with
 // -DVSLAM_DIAGNOSTICS (lib/libvslam_diag.so, `make diag`): the shipped library never reads them.
 #ifdef VSLAM_DIAGNOSTICS
 #define VSLAM_DIAG_ENV(name) std::getenv(name)
@@ -61,7 +61,7 @@ struct StreamTuner {
 // a median lag above the level's limit (3 % at level 0, 10 % at level 1) start a TRIAL of the next level - same priority,
 // then no side streams at all (level 2) - and the trial is kept only if its fastest call beats the previous level's fastest
 // by 1 %; otherwise the context goes back.  Either way the watch ends after at most ten measured calls.  Off while a capture
-// is on, while the opt-in tuner is comparing pairs, and under VSLAM_JOIN_WATCH=0; VSLAM_JOIN_WATCH_LEVEL pins a level.
+// is on, while the opt-in tuner is comparing pairs, and under VSLAM_JOIN_WATCH=0; vslam_ctx_pin_side_streams pins a level.
 // Results never depend on the level.
 struct JoinWatch {
     static constexpr int RING = 4, NEED = 3;

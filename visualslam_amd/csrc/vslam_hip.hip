@@ -332,21 +332,16 @@ static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPla
         // rows per item (round 5): the items of a workgroup should fill whole waves.  960 columns x 16 rows are 480 items of 8
         // columns x 4 rows = 7.5 waves (every eighth wave-instruction wasted: the kernel runs AT its VALU issue time), but 960
         // items of 2 rows = 15 waves; 480 columns need 1 row per item.  Fewer rows per item amortise the scalar tap loads over
-        // fewer dots, so the smaller item must be at least 2 % fuller to be chosen.  VSLAM_STRIP_RI forces a value (A/B runs).
+        // fewer dots, so the smaller item must be at least 2 % fuller to be chosen.
         const int ncg = (cols + 7) / 8;
         auto waste = [&](int ri) {
             const long items = (long)ncg * (16 / ri);
             if (items > (ri == 4 ? 512 : 1024)) return 1e9;
             return (double)((items + 63) / 64 * 64 - items) / (double)items;
         };
-        static const int force_ri = [] {
-            const char* e = VSLAM_DIAG_ENV("VSLAM_STRIP_RI");
-            return e ? std::atoi(e) : 0;
-        }();
         int ri = 4;
         for (int r : {2, 1})
             if (waste(r) + 0.02 < waste(ri)) ri = r;
-        if ((force_ri == 1 || force_ri == 2 || force_ri == 4) && waste(force_ri) < 1e8) ri = force_ri;
         if (ri == 2) return launch_h_strip<16, 2>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
         if (ri == 1) return launch_h_strip<16, 1>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
     }
@@ -572,17 +567,8 @@ static int enqueue_pyr_octave_mx(vslam_ctx* c, int cfg, double sigma0, int o, co
     return VSLAM_OK;
 }
 
-// The octave whose kernels the held-back side work of a batch waits for (enqueue_dog): the last
-// LDS-tiled one for batches of 32 frames or more, -1 (no gate) otherwise.
-// vslam_ctx_follow: the point of a batch call behind which a second context's batch may start (its heavy octave-0
-// kernels then run beside this call's remaining, shorter kernels instead of beside its own octave 0).
-static int follow_octave() {
-    static const int o = [] {
-        const char* e = VSLAM_DIAG_ENV("VSLAM_FOLLOW_OCTAVE");
-        return e ? atoi(e) : 0;
-    }();
-    return o;
-}
+// vslam_ctx_follow: the point of a batch call, the end of octave 0, behind which a second context's batch may start (its
+// heavy octave-0 kernels then run beside this call's remaining, shorter kernels instead of beside its own octave 0).
 static int mark_phase(vslam_ctx* c) {
     if (!c->ev_phase) HIPCHK(c, hipEventCreateWithFlags(&c->ev_phase, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->ev_phase, c->stream));
@@ -590,6 +576,8 @@ static int mark_phase(vslam_ctx* c) {
     return VSLAM_OK;
 }
 
+// The octave whose kernels the held-back side work of a batch waits for (enqueue_dog): the last
+// LDS-tiled one for batches of 32 frames or more, -1 (no gate) otherwise.
 static int dog_side_gate(const vslam_params& p, const vslam_batch_layout& L, int nf) {
     int gate = -1;
     if (nf >= 32)
@@ -697,12 +685,7 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
         // tile shape: the wide tile (256 x 32) when it needs no more tile area than the tall one (128 x 64).
         // A 384 x 32 tile (1920 = 5 x 384) on 384-thread workgroups was measured in round 3: six waves per
         // workgroup sit 2-2-1-1 on the four SIMDs and meet at every barrier: 21.3 vs 18.3 ms per step.
-        static const int force_shape = [] {
-            const char* e = VSLAM_DIAG_ENV("VSLAM_TILE_SHAPE");  // A/B runs: 0 = 128 x 64 everywhere, 1 = 256 x 32 everywhere
-            return e ? std::atoi(e) : -1;
-        }();
-        const int shape = force_shape >= 0 ? (force_shape ? 1 : 0)
-                                           : ((long)((cols + 255) / 256) * ((rows + 31) / 32) <= (long)((cols + 127) / 128) * ((rows + 63) / 64) ? 1 : 0);
+        const int shape = (long)((cols + 255) / 256) * ((rows + 31) / 32) <= (long)((cols + 127) / 128) * ((rows + 63) / 64) ? 1 : 0;
         // matrix path: the plain lattice scan (window 3, candidates + contrast list) runs inside the octave kernel
         // while the DoG rows are in LDS (kernels_pyramid_mx.hip.h); k_extrema_pack then replaces k_extrema_w3
         MxScan scan{};
@@ -757,7 +740,7 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
                    dim3(256), oct + (size_t)3 * P, pframe, pitch, s.bases + s.base_off[o + 1], s.bases_frame, L.pitch[o + 1], rows,
                    L.rows[o + 1], L.cols[o + 1]);
         if (side) HIPCHK(c, hipEventRecord(c->ev_oct[o], c->stream));
-        if (o == follow_octave() || (o == L.n_octaves - 1 && o < follow_octave())) TRY(mark_phase(c));
+        if (o == 0) TRY(mark_phase(c));
         if (after_octave) TRY(after_octave(o));  // octave o's kernels are enqueued and ev_oct[o] marks their end
         if (o < gate) continue;  // scan + compaction of this octave are enqueued behind octave `gate`
         const int o_done = o;    // the octave whose kernels were enqueued last
@@ -1876,44 +1859,26 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     float* resp_ws = (harris && !out->response) ? ws_take<float>(c, (size_t)chunk * N) : nullptr;
     unsigned long long* hflags = harris ? ws_take<unsigned long long>(c, (size_t)chunk * harris_flag_words(p.rows, p.cols)) : nullptr;
     unsigned int* hcws = harris ? ws_take<unsigned int>(c, compaction_ws_elems(harris_flag_words(p.rows, p.cols), chunk)) : nullptr;
-    // Fork (VSLAM_AUX_STREAMS=0 disables): the Harris chain and the extrema/compaction chain run on
-    // the context's auxiliary streams beside the octave kernels.  Measured on MI355X: +2.8 %
-    // (11.2k vs 10.9k frames/s) -- small, because every kernel of the batch is VALU-issue-bound
-    // rather than HBM-bound; per-kernel durations grow accordingly when kernels share the chip.
-    static const bool use_aux = [] {
-        const char* e = VSLAM_DIAG_ENV("VSLAM_AUX_STREAMS");
-        return !(e && e[0] == '0');
-    }();
-    static const bool orient_spread = [] {
-        const char* e = VSLAM_DIAG_ENV("VSLAM_ORIENT_SPREAD");
-        return !(e && e[0] == '0');
-    }();
+    // Fork: the Harris chain and the extrema/compaction chain run on the context's auxiliary streams beside the octave
+    // kernels.  Measured on MI355X: +2.8 % (11.2k vs 10.9k frames/s) -- small, because every kernel of the batch is
+    // VALU-issue-bound rather than HBM-bound; per-kernel durations grow accordingly when kernels share the chip.
     // Under stream capture (hipGraph) no two SIDE streams of the call may wait on each other's events.  The topology is legal
     // (fork from the origin stream, cross edges between the forked streams, all joined back) and every event is recorded on
     // a stream that is already part of the capture; but this HIP runtime (ROCm 7.2's libamdhip64.so.7 and the copy torch 2.10
     // bundles alike) never returns from hipStreamEndCapture then: a function that calls itself for every entry of a
     // per-stream vector (the shape of hip::Stream::EndCapture over parallelCaptureStreams_) recurses 174,000 frames deep and
-    // the process dies of stack exhaustion - no HIP status is ever seen.  tools/graph_try.py reproduces it through this
-    // library (each case in a child process; both ends of the stack in profiles/r05_graph_try.json), and
-    // tools/capture_cycle_repro.hip WITHOUT it: two side streams that wait on each other's events are harmless by themselves
-    // (modes 2-4) and fatal as soon as each also waits on an origin-stream event again in between (mode 5) - which this
-    // library's side streams do on every octave's event.  The orientation stage has two such pairs - the early edge test
-    // (list stream -> Harris stream -> back) and the spread launches (list stream -> two idle side streams -> back); each
-    // alone reproduces the crash.  While a capture is on, both stay on the list stream; everything else forks from and joins
-    // to the main (origin) stream.
-    bool capturing = false, cap_early = false, cap_spread = false;  // the nested forks stay out of a capture
+    // the process dies of stack exhaustion - no HIP status is ever seen.  It was reproduced through this library and without
+    // it (profiles/r05_graph_try.json, profiles/r05_capture_cycle_repro.txt): two side streams that wait on each other's
+    // events are harmless by themselves and fatal as soon as each also waits on an origin-stream event again in between -
+    // which this library's side streams do on every octave's event.  The orientation stage has two such pairs - the early
+    // edge test (list stream -> Harris stream -> back) and the spread launches (list stream -> two idle side streams ->
+    // back); each alone reproduces the crash.  While a capture is on, both stay on the list stream; everything else forks
+    // from and joins to the main (origin) stream.
+    bool capturing = false;  // the nested forks stay out of a capture
     {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess) (void)hipGetLastError();
         capturing = cap != hipStreamCaptureStatusNone;
-        // diagnostic switch for tools/graph_try.py (the reproducer of that fault): leave the nested forks in while capturing
-        // (1: both nested forks stay in, 2: only the early edge test's, 3: only the spread orientation launches')
-        static const int nested_in_capture = [] {
-            const char* e = VSLAM_DIAG_ENV("VSLAM_CAPTURE_NESTED_FORKS");
-            return e ? std::atoi(e) : 0;
-        }();
-        cap_early = capturing && !(nested_in_capture == 1 || nested_in_capture == 2);
-        cap_spread = capturing && !(nested_in_capture == 1 || nested_in_capture == 3);
     }
     hipStream_t sh = c->stream, sx = nullptr;  // Harris stream, extrema stream (nullptr = main)
     // Any early return between the fork and the join must not leave the side streams running into
@@ -1932,13 +1897,10 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     const unsigned long long call_key = ((unsigned long long)(unsigned)n_frames << 40) ^ ((unsigned long long)(unsigned)p.rows << 20) ^ (unsigned)p.cols ^
                                         ((unsigned long long)(p.localize + 2 * p.orient + 4 * p.extrema_dense + 8 * (out->descriptors != nullptr)) << 60) ^
                                         ((unsigned long long)(unsigned)p.n_octaves << 56) ^ ((unsigned long long)(c->mx ? 1 : 0) << 39);
-    bool side_streams = use_aux;
-    if (use_aux) {
-        TRY(sched_ensure_aux(c));
-        // (calls of a few megapixels are dominated by launch latencies: their lag says nothing about starvation)
-        TRY(sched_watch_before_call(c, call_key, dog && harris && n_frames >= 32 && (size_t)n_frames * N >= ((size_t)16 << 20), capturing));
-        if (c->watch.level == 2) side_streams = false;  // the watchdog's last step: everything on the caller's stream
-    }
+    TRY(sched_ensure_aux(c));
+    // (calls of a few megapixels are dominated by launch latencies: their lag says nothing about starvation)
+    TRY(sched_watch_before_call(c, call_key, dog && harris && n_frames >= 32 && (size_t)n_frames * N >= ((size_t)16 << 20), capturing));
+    const bool side_streams = c->watch.level != 2;  // the watchdog's last step: everything on the caller's stream
     if (side_streams) {
         // the side-stream pair of this call (StreamTuner): only full-size batches with both paths are compared
         TRY(sched_tuner_before_call(c, call_key, dog && harris && n_frames >= 32));
@@ -1976,7 +1938,7 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
             const std::function<int(int)> after_list = [&](int o) -> int {
                 if (orient && o == 0 && L.n_octaves > 1)
                     return enqueue_edge_flags_early(c, p, opl, nf, out->pyramid + (size_t)f0 * L.pyramid_frame_bytes, L.pyramid_frame_bytes,
-                                                    out->dog_points + (size_t)f0 * p.dog_cap, out->dog_counts + f0, os, (side_streams && !cap_early) ? sh : nullptr);
+                                                    out->dog_points + (size_t)f0 * p.dog_cap, out->dog_counts + f0, os, (side_streams && !capturing) ? sh : nullptr);
                 return VSLAM_OK;
             };
             const std::function<int(int)> after_octave = [&](int o) -> int {
@@ -1997,8 +1959,8 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
                 TRY(enqueue_orient_batch(c, p, L, opl, nf, out->pyramid + (size_t)f0 * L.pyramid_frame_bytes, L.pyramid_frame_bytes,
                                          out->dog_points + (size_t)f0 * p.dog_cap, out->dog_counts + f0, os,
                                          out->oriented_points + (size_t)f0 * p.oriented_cap, out->oriented_counts + f0,
-                                         (side_streams && orient_spread && !cap_spread) ? sh : nullptr,
-                                         (side_streams && orient_spread && !cap_spread) ? c->aux[2] : nullptr));
+                                         (side_streams && !capturing) ? sh : nullptr,
+                                         (side_streams && !capturing) ? c->aux[2] : nullptr));
                 if (out->oriented_survivors)
                     HIPCHK(c, hipMemcpyAsync(out->oriented_survivors + f0, os.scounts, sizeof(unsigned int) * (size_t)nf,
                                              hipMemcpyDeviceToDevice, c->stream));

@@ -260,10 +260,6 @@ void sched_init_from_env(vslam_ctx* c) {
     const char* jw = std::getenv("VSLAM_JOIN_WATCH");
     c->watch.disabled = jw && jw[0] == '0';
     if (const char* sp = std::getenv("VSLAM_SIDE_PRIORITY")) c->watch.level = (sp[0] == 'l' || sp[0] == 'L') ? 0 : 1;  // low | main
-    if (const char* lv = VSLAM_DIAG_ENV("VSLAM_JOIN_WATCH_LEVEL")) {  // A/B runs: start (and stay) at a level; the API is vslam_ctx_pin_side_streams
-        c->watch.level = std::min(2, std::max(0, std::atoi(lv)));
-        c->watch.done = c->watch.pinned = true;
-    }
     const char* t = std::getenv("VSLAM_STREAM_TUNER");
     if (t && t[0] == '1') (void)vslam_ctx_tune_side_streams(c, 1);
 }
