@@ -9,14 +9,11 @@
 #include <map>
 #include <set>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
 #include "../../include/vslam.h"
-
-namespace vslam {
-struct StripTaps;
-}
 
 // Diagnostic environment switches (the reference paths of VSLAM_HDIFF and VSLAM_ORIENT_SCALAR) exist only in a build with
 // -DVSLAM_DIAGNOSTICS (lib/libvslam_diag.so, `make diag`): the shipped library never reads them.
@@ -89,10 +86,10 @@ struct vslam_ctx {
     std::string err;
     // bump workspace in HBM, grown between calls only (never inside a launch sequence)
     char* ws = nullptr;
-    size_t ws_cap = 0, ws_off = 0;
-    std::map<std::pair<int, uint64_t>, uint16_t*> taps;  // device copies of quantised taps
-    std::map<std::pair<uint64_t, int>, vslam::StripTaps*> strip_taps;  // (sigma0 bits, octave) -> device tables
-    std::map<std::pair<uint64_t, int>, void*> tile_taps;        // (sigma0 bits, octave) -> PyrTaps<CFG>
+    size_t ws_cap = 0;
+    // device copies of the tap tables, each made once (get_table in vslam_hip.hip): (TableKind, bits of sigma or sigma0,
+    // kernel width or octave) -> quantised taps / StripTaps / PyrTaps<CFG> / MxTaps<CFG> / f32 Gaussian taps
+    std::map<std::tuple<int, uint64_t, int>, void*> tables;
     // OPT-IN matrix-core form of the LDS-tiled octave kernels (VSLAM_MX=1 / vslam_ctx_set_matrix_path): never the default
     bool mx = false;
     // vslam_ctx_set_f32_fused / VSLAM_F32_FUSED=1: the f32 stages (separable f32 filter of filterKeypoints / SIFT, the arctangent of
@@ -100,7 +97,6 @@ struct vslam_ctx {
     // product and sum rounded, OpenCV's SSE2 baseline)
     bool f32_fused = false;
     bool orient_scalar_form = false;  // VSLAM_ORIENT_SCALAR=1: k_orient_survivors for every octave (the round-3 form, kept for comparison)
-    std::map<std::pair<uint64_t, int>, void*> mx_taps;          // (sigma0 bits, octave) -> MxTaps<CFG>
     // auxiliary streams of the batched path: the HBM-bound chains (Harris; extrema + compaction)
     // run beside the VALU-bound pyramid kernels; forked from / joined to `stream` by events
     // aux[2] carries only the second-half upsample of a large batch (enqueue_dog): it must not queue behind
@@ -130,7 +126,6 @@ struct vslam_ctx {
     std::set<const void*> lds_raised;
     float* loc_lut = nullptr;  // FeaturePointLocalization table (kernels_localize.hip.h), built on first use
     uint8_t* dump = nullptr;   // 256 bytes nobody reads: where the Harris kernel's margin lanes store in its steady rows
-    std::map<std::pair<uint64_t, int>, float*> orient_taps;  // (sigma bits, kernel width) -> f32 Gaussian taps on the device
     // bench timing hook
     std::string timing_name;
     int launch_tag = -1;  // octave of the launch being enqueued, for helpers that do not get it as an argument

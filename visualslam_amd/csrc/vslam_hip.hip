@@ -54,15 +54,17 @@ static const char* const kKernelNames =
     "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals";
 
 
-// Launch on the context stream (no dynamic LDS).
-#define LAUNCH(ctx, name, kern, grid, block, ...)                                 \
-    do {                                                                          \
-        {                                                                         \
-            TimedScope ts_(ctx, name, (ctx)->launch_tag);                         \
-            hipLaunchKernelGGL(kern, grid, block, 0, (ctx)->stream, __VA_ARGS__); \
-        }                                                                         \
-        HIPCHK(ctx, hipGetLastError());                                           \
+// Launch on `stream` with `lds` bytes of dynamic LDS, bracketed for the timing hook as "name@tag".
+#define LAUNCH_ON(ctx, name, tag, stream, lds, kern, grid, block, ...)        \
+    do {                                                                      \
+        {                                                                     \
+            TimedScope ts_(ctx, name, tag, stream);                           \
+            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);  \
+        }                                                                     \
+        HIPCHK(ctx, hipGetLastError());                                       \
     } while (0)
+// ... on the context stream, no dynamic LDS, tagged with the octave being enqueued.
+#define LAUNCH(ctx, name, kern, grid, block, ...) LAUNCH_ON(ctx, name, (ctx)->launch_tag, (ctx)->stream, 0, kern, grid, block, __VA_ARGS__)
 
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -115,7 +117,6 @@ static void block_release(vslam_ctx* c, void* p, size_t cap) {
 }
 
 static int ws_reserve(vslam_ctx* c, size_t bytes) {
-    c->ws_off = 0;
     if (bytes <= c->ws_cap) return VSLAM_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < vslam_ctx::kAux; ++i)
@@ -129,13 +130,42 @@ static int ws_reserve(vslam_ctx* c, size_t bytes) {
     return VSLAM_OK;
 }
 
-template <typename T>
-static T* ws_take(vslam_ctx* c, size_t count) {
-    char* p = c->ws + c->ws_off;
-    c->ws_off += align_up(count * sizeof(T), 256);
-    return c->ws_off <= c->ws_cap ? (T*)p : nullptr;  // sized by ws_reserve; nullptr = sizing bug
-}
-static inline size_t ws_need(size_t bytes) { return align_up(bytes, 256); }
+// The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
+// and commit() reserves the sum and sets every pointer: the size reserved cannot differ from the size handed out.
+// Buffers lie in the order of the add() calls, each on a 256-byte boundary.  No heap: the per-image entry points are
+// bound by launch latency, so a request list costs them nothing but a few stores.
+// (anonymous namespace, here and below: the member functions of these host-only types stay out of the library's dynamic symbols)
+namespace {
+class WsPlan {
+    struct Slot {
+        void* where;                   // the caller's T*
+        void (*set)(void*, char*);     // stores a T* there
+        size_t off;
+    };
+    static constexpr int kMaxSlots = 32;  // the most any entry point asks for is 18 (vslam_filter_keypoints)
+    Slot slots[kMaxSlots];
+    int n = 0;
+    size_t total = 0;
+
+  public:
+    WsPlan() = default;
+    WsPlan(const WsPlan&) = delete;  // (the slots point at the caller's variables)
+    WsPlan& operator=(const WsPlan&) = delete;
+    template <typename T>
+    void add(T*& p, size_t count) {
+        if (n < kMaxSlots) slots[n] = Slot{&p, [](void* w, char* q) { *static_cast<T**>(w) = reinterpret_cast<T*>(q); }, total};
+        ++n;
+        total += align_up(count * sizeof(T), 256);
+    }
+    // The pointers given to add() must still be where they were: structs that hold them are not moved or copied in between.
+    int commit(vslam_ctx* c) {
+        if (n > kMaxSlots) return fail(c, VSLAM_ERR_NOMEM, "workspace plan: more buffers than WsPlan::kMaxSlots");
+        TRY(ws_reserve(c, total));
+        for (int i = 0; i < n; ++i) slots[i].set(slots[i].where, c->ws + slots[i].off);
+        return VSLAM_OK;
+    }
+};
+}  // namespace
 
 // One-time device tables (tap matrices) are allocated and copied with blocking calls: inside a stream capture that would
 // invalidate the capture, so a call that still needs one says so instead (include/vslam.h: the warm-up call must run with
@@ -145,29 +175,51 @@ static bool stream_is_capturing(vslam_ctx* c) {
     if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess) (void)hipGetLastError();
     return cap != hipStreamCaptureStatusNone;
 }
-#define NO_TABLE_IN_CAPTURE(ctx, what)                                                                                         \
-    if (stream_is_capturing(ctx))                                                                                              \
-    return fail(ctx, VSLAM_ERR_UNSUPPORTED, what ": its tap tables are not on the device yet and cannot be put there during a stream capture - " \
-                                            "run one warm-up call with the same parameters and the same matrix-path setting first")
+#define NO_TABLE_IN_CAPTURE(ctx, what)                                                                                                      \
+    if (stream_is_capturing(ctx))                                                                                                           \
+    return fail(ctx, VSLAM_ERR_UNSUPPORTED, std::string(what) + ": its tap tables are not on the device yet and cannot be put there during a stream capture - " \
+                                                                "run one warm-up call with the same parameters and the same matrix-path setting first")
+
+// The context's device tables (vslam_ctx::tables).  `v` of the key: the bits of sigma (Blur, Orient) or of sigma0 (the others);
+// `i`: the kernel width (Blur, Orient) or the octave.
+enum TableKind { kTableBlur, kTableStrip, kTableTile, kTableMx, kTableOrient };
+
+// The device table (kind, v, i), made on first use: `fill(host)` fills a zeroed host copy of `bytes` bytes and returns a status.
+// The copy is raw storage from operator new (aligned for any of the table structs, all trivially copyable aggregates of
+// integers / floats); the fill functions write their struct into it member by member.
+// `what` names the caller in the refusal of a call that would have to make the table inside a stream capture.
+template <class T, class Fill>
+static int get_table(vslam_ctx* c, TableKind kind, double v, int i, const char* what, size_t bytes, Fill fill, const T** out) {
+    uint64_t vb;
+    std::memcpy(&vb, &v, 8);
+    const auto key = std::make_tuple((int)kind, vb, i);
+    auto it = c->tables.find(key);
+    if (it == c->tables.end()) {
+        NO_TABLE_IN_CAPTURE(c, what);
+        std::vector<char> host(bytes);
+        TRY(fill(static_cast<void*>(host.data())));
+        void* d = nullptr;
+        HIPCHK(c, hipMalloc(&d, bytes));
+        HIPCHK(c, hipMemcpy(d, host.data(), bytes, hipMemcpyHostToDevice));
+        it = c->tables.emplace(key, d).first;
+    }
+    *out = static_cast<const T*>(it->second);
+    return VSLAM_OK;
+}
+
+static inline void tap_pointers(const std::vector<uint16_t> taps[6], const uint16_t* tp[6]) {
+    for (int l = 0; l < 6; ++l) tp[l] = taps[l].data();
+}
 
 // Device copy of the (zero-trimmed) quantised taps of one GaussianBlur; *n_eff = trimmed width.
 static int get_taps(vslam_ctx* c, int n, double sigma, const uint16_t** out, int* n_eff) {
-    uint64_t sb;
-    std::memcpy(&sb, &sigma, 8);
-    auto key = std::make_pair(n, sb);
     std::vector<uint16_t> h;
     if (!gauss_taps_q8_trimmed(n, sigma, h)) return fail(c, VSLAM_ERR_INVALID, "invalid Gaussian kernel size");
     *n_eff = (int)h.size();
-    auto it = c->taps.find(key);
-    if (it == c->taps.end()) {
-        NO_TABLE_IN_CAPTURE(c, "Gaussian blur");
-        uint16_t* d = nullptr;
-        HIPCHK(c, hipMalloc((void**)&d, sizeof(uint16_t) * h.size()));
-        HIPCHK(c, hipMemcpy(d, h.data(), sizeof(uint16_t) * h.size(), hipMemcpyHostToDevice));
-        it = c->taps.emplace(key, d).first;
-    }
-    *out = it->second;
-    return VSLAM_OK;
+    return get_table(c, kTableBlur, sigma, n, "Gaussian blur", sizeof(uint16_t) * h.size(), [&](void* host) -> int {
+        std::memcpy(host, h.data(), sizeof(uint16_t) * h.size());
+        return VSLAM_OK;
+    }, out);
 }
 
 static inline dim3 grid_rows(int cols, int rows, int frames = 1) { return dim3((cols + 255) / 256, rows, frames); }
@@ -175,6 +227,7 @@ static inline dim3 grid_rows(int cols, int rows, int frames = 1) { return dim3((
 // ---------------------------------------------------------------- enqueue helpers (device)
 
 // ---- octave path selection -----------------------------------------------------------------
+namespace {
 enum class OctPath { Tile0, Tile1, Strip, Generic };
 
 struct OctPlan {
@@ -185,7 +238,9 @@ struct OctPlan {
     std::vector<uint16_t> taps[6];  // trimmed taps
     int sh = 0;                     // rows per horizontal strip workgroup
     int hdiff = 0;                  // octave of diff_taps.gen.h with these taps: the difference-form horizontal pass (k_gauss_h_diff)
+    int mx = 0;                     // matrix-core configuration that runs these widths (mx_config_for), 0 = none; used on the opt-in path only
 };
+}  // namespace
 
 static bool taps_fit_u8(const OctPlan& pl) {
     for (int l = 0; l < 6; ++l)
@@ -230,104 +285,82 @@ static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
         if (pl.path == OctPath::Strip && (cols + HD_J - 1) / HD_J <= 256)
             pl.hdiff = hd_octave_matches<2>(pl.taps) ? 2 : hd_octave_matches<3>(pl.taps) ? 3 : 0;
     }
+    if (pl.path != OctPath::Generic) pl.mx = mx_config_for(pl.ke);
     return pl;
 }
 
-static int get_strip_taps(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const StripTaps** out) {
-    uint64_t sb;
-    std::memcpy(&sb, &sigma0, 8);
-    auto key = std::make_pair(sb, o);
-    auto it = c->strip_taps.find(key);
-    if (it == c->strip_taps.end()) {
-        NO_TABLE_IN_CAPTURE(c, "strip kernels");
-        const uint16_t* tp[6];
-        for (int l = 0; l < 6; ++l) tp[l] = pl.taps[l].data();
-        std::vector<StripTaps> st(1);
-        if (!strip_pack_taps(tp, pl.ke, st[0])) return fail(c, VSLAM_ERR_UNSUPPORTED, "strip kernels: taps out of range");
-        StripTaps* d = nullptr;
-        HIPCHK(c, hipMalloc((void**)&d, sizeof(StripTaps)));
-        HIPCHK(c, hipMemcpy(d, st.data(), sizeof(StripTaps), hipMemcpyHostToDevice));
-        it = c->strip_taps.emplace(key, d).first;
-    }
-    *out = it->second;
-    return VSLAM_OK;
+// The plan of every octave of a call: made once by the entry point; scratch sizing, side gate and launches all read this array.
+static std::vector<OctPlan> plan_octaves(double sigma0, const vslam_batch_layout& L) {
+    std::vector<OctPlan> plans;
+    for (int o = 0; o < L.n_octaves; ++o) plans.push_back(plan_octave(sigma0, o, L.rows[o], L.cols[o]));
+    return plans;
 }
 
 template <int SH, int RI>
-static int launch_h_strip(vslam_ctx* c, const uint16_t* h, size_t hframe, uint8_t* oct, size_t pframe, int rows, int cols,
-                          int pitch, int pw, int nf, const StripTaps* taps, uint8_t* next_base, size_t nframe, int nrows, int ncols,
-                          int npitch) {
+static int launch_h_strip(vslam_ctx* c, const uint16_t* h, size_t hframe, const OctIO& io, int pw, const StripTaps* taps) {
     const size_t lds = (size_t)SH * pw * 4;
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_h_strip<SH, RI>)));
-    {
-        TimedScope ts(c, "k_gauss_h_strip", c->launch_tag);
-        hipLaunchKernelGGL((k_gauss_h_strip<SH, RI>), dim3(1, (rows + SH - 1) / SH, nf), dim3(256), lds, c->stream, h, hframe, oct,
-                           pframe, rows, cols, pitch, pw, taps, next_base, nframe, nrows, ncols, npitch);
-    }
-    HIPCHK(c, hipGetLastError());
+    LAUNCH_ON(c, "k_gauss_h_strip", c->launch_tag, c->stream, lds, (k_gauss_h_strip<SH, RI>), dim3(1, (io.rows + SH - 1) / SH, io.nf), dim3(256), h,
+              hframe, io.oct, io.pframe, io.rows, io.cols, io.pitch, pw, taps, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
     return VSLAM_OK;
 }
 
 template <int O>
-static int launch_h_diff(vslam_ctx* c, const uint16_t* h, size_t hframe, uint8_t* oct, size_t pframe, int rows, int cols, int pitch,
-                         int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch) {
+static int launch_h_diff(vslam_ctx* c, const uint16_t* h, size_t hframe, const OctIO& io) {
     using G = HdGeom<O>;
+    const int rows = io.rows, cols = io.cols;
     const int ncs = (cols + HD_J - 1) / HD_J, pw = hd_pw(cols, G::HL, G::rmax);
     // row pairs per workgroup: at most 256 items (one per thread), LDS below the limit, and >= 256 workgroups for small batches
     int npairs = std::max(1, std::min(8, 256 / ncs));
-    while (npairs > 1 && ((size_t)npairs * pw * 8 > (size_t)kMaxDynLds || (long)((rows + 2 * npairs - 1) / (2 * npairs)) * nf < 256)) --npairs;
+    while (npairs > 1 && ((size_t)npairs * pw * 8 > (size_t)kMaxDynLds || (long)((rows + 2 * npairs - 1) / (2 * npairs)) * io.nf < 256)) --npairs;
     const size_t lds = (size_t)npairs * pw * 8;
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_h_diff<O>)));
-    {
-        // the timing hook's "k_gauss_h_strip" is the coarse octaves' horizontal pass whichever kernel runs it (bench.py's
-        // per-kernel figures, the dispatch tests); "k_gauss_h_diff" times this kernel alone
-        TimedScope ts(c, "k_gauss_h_strip", c->launch_tag);
-        TimedScope td(c, "k_gauss_h_diff", c->launch_tag);
-        hipLaunchKernelGGL(k_gauss_h_diff<O>, dim3(1, (rows + 2 * npairs - 1) / (2 * npairs), nf), dim3(256), lds, c->stream, h, hframe, oct,
-                           pframe, rows, cols, pitch, npairs, pw, next_base, nframe, nrows, ncols, npitch);
-    }
-    HIPCHK(c, hipGetLastError());
+    // the timing hook's "k_gauss_h_strip" is the coarse octaves' horizontal pass whichever kernel runs it (bench.py's
+    // per-kernel figures, the dispatch tests); "k_gauss_h_diff" times this kernel alone
+    TimedScope ts(c, "k_gauss_h_strip", c->launch_tag);
+    LAUNCH_ON(c, "k_gauss_h_diff", c->launch_tag, c->stream, lds, k_gauss_h_diff<O>, dim3(1, (rows + 2 * npairs - 1) / (2 * npairs), io.nf), dim3(256), h,
+              hframe, io.oct, io.pframe, rows, cols, io.pitch, npairs, pw, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
     return VSLAM_OK;
 }
 
 // Coarse octave: vertical strips (dot4) into the u16 scratch, then horizontal strips (dot2, or the difference form).
-static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const uint8_t* base, size_t bframe,
-                                uint8_t* oct, size_t pframe, uint16_t* h, int rows, int cols, int pitch, int nf,
-                                uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch) {
+static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const OctIO& io, uint16_t* h) {
     const StripTaps* taps;
-    TRY(get_strip_taps(c, sigma0, o, pl, &taps));
+    TRY(get_table(c, kTableStrip, sigma0, o, "strip kernels", sizeof(StripTaps), [&](void* host) -> int {
+        const uint16_t* tp[6];
+        tap_pointers(pl.taps, tp);
+        if (!strip_pack_taps(tp, pl.ke, *static_cast<StripTaps*>(host))) return fail(c, VSLAM_ERR_UNSUPPORTED, "strip kernels: taps out of range");
+        return VSLAM_OK;
+    }, &taps));
+    const int rows = io.rows, cols = io.cols, nf = io.nf;
     int nmax = 0;
     for (int l = 0; l < 6; ++l) nmax = std::max(nmax, pl.ke[l]);
     const int RM = (nmax / 2 + 3) & ~3;
     const int rhq = (((rows + 3) & ~3) + 2 * RM + 16) / 4;
     const size_t v_lds = (size_t)rhq * STRIP_W * 4;
-    const size_t P = (size_t)rows * pitch;
+    const size_t P = (size_t)rows * io.pitch;
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_v_strip)));
-    {
-        TimedScope ts(c, "k_gauss_v_strip", o);
-        // small batches: split the six levels over workgroups until the launch has >= 256 of them
-        const int strips = (cols + STRIP_W - 1) / STRIP_W;
-        const int want = (256 + strips * nf - 1) / (strips * nf);
-        const int lsplit = want >= 6 ? 6 : want >= 3 ? 3 : want >= 2 ? 2 : 1;
-        hipLaunchKernelGGL(k_gauss_v_strip, dim3(strips, lsplit, nf), dim3(256), v_lds, c->stream, base, bframe, h, 6 * P, rows, cols,
-                           pitch, RM, rhq, taps);
-    }
-    HIPCHK(c, hipGetLastError());
+    // small batches: split the six levels over workgroups until the launch has >= 256 of them
+    const int strips = (cols + STRIP_W - 1) / STRIP_W;
+    const int want = (256 + strips * nf - 1) / (strips * nf);
+    const int lsplit = want >= 6 ? 6 : want >= 3 ? 3 : want >= 2 ? 2 : 1;
+    LAUNCH_ON(c, "k_gauss_v_strip", o, c->stream, v_lds, k_gauss_v_strip, dim3(strips, lsplit, nf), dim3(256), io.base, io.bframe, h, 6 * P, rows, cols,
+              io.pitch, RM, rhq, taps);
     c->launch_tag = o;
     // Diagnostics build only: VSLAM_HDIFF=0 keeps the dot2 pass where the difference form would run (A/B runs, byte-equality test)
     static const bool hdiff_off = [] {
         const char* e = VSLAM_DIAG_ENV("VSLAM_HDIFF");
         return e && e[0] == '0';
     }();
-    if (pl.hdiff == 2 && !hdiff_off) return launch_h_diff<2>(c, h, 6 * P, oct, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch);
-    if (pl.hdiff == 3 && !hdiff_off) return launch_h_diff<3>(c, h, 6 * P, oct, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch);
+    if (pl.hdiff == 2 && !hdiff_off) return launch_h_diff<2>(c, h, 6 * P, io);
+    if (pl.hdiff == 3 && !hdiff_off) return launch_h_diff<3>(c, h, 6 * P, io);
     const int pw = strip_pw(cols, nmax);
     // small batches: shorter row strips, more workgroups
     int sh = pl.sh;
     while (sh > 4 && (long)((rows + sh - 1) / sh) * nf < 256) sh >>= 1;
     // ... and, when even that leaves most threads without an item, one row per item
     const bool fine = sh == 4 && (long)((rows + 3) / 4) * nf < 256 && ((cols + 7) / 8) * 4 <= 512;
-    if (fine) return launch_h_strip<4, 1>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
+    if (fine) return launch_h_strip<4, 1>(c, h, 6 * P, io, pw, taps);
     if (sh == 16) {
         // rows per item (round 5): the items of a workgroup should fill whole waves.  960 columns x 16 rows are 480 items of 8
         // columns x 4 rows = 7.5 waves (every eighth wave-instruction wasted: the kernel runs AT its VALU issue time), but 960
@@ -342,13 +375,13 @@ static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPla
         int ri = 4;
         for (int r : {2, 1})
             if (waste(r) + 0.02 < waste(ri)) ri = r;
-        if (ri == 2) return launch_h_strip<16, 2>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
-        if (ri == 1) return launch_h_strip<16, 1>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
+        if (ri == 2) return launch_h_strip<16, 2>(c, h, 6 * P, io, pw, taps);
+        if (ri == 1) return launch_h_strip<16, 1>(c, h, 6 * P, io, pw, taps);
     }
     switch (sh) {
-        case 16: return launch_h_strip<16, 4>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
-        case 8: return launch_h_strip<8, 4>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
-        default: return launch_h_strip<4, 4>(c, h, 6 * P, oct, pframe, rows, cols, pitch, pw, nf, taps, next_base, nframe, nrows, ncols, npitch);
+        case 16: return launch_h_strip<16, 4>(c, h, 6 * P, io, pw, taps);
+        case 8: return launch_h_strip<8, 4>(c, h, 6 * P, io, pw, taps);
+        default: return launch_h_strip<4, 4>(c, h, 6 * P, io, pw, taps);
     }
 }
 
@@ -439,39 +472,22 @@ struct DogScratch {
 };
 
 static inline int site_pitch_of(int lat_cols) { return (lat_cols + 63) & ~63; }
-static size_t site_frame_bytes(const vslam_batch_layout& L) {
-    size_t b = 0;
-    for (int o = 0; o < L.n_octaves; ++o) b += (size_t)L.lat_rows[o] * site_pitch_of(L.lat_cols[o]);
-    return b;
-}
 static size_t col_octave_bytes(const vslam_batch_layout& L, int o) { return align_up((size_t)5 * mx_seams(L.cols[o]) * L.rows[o] * 2, 16); }
-static size_t col_frame_bytes(const vslam_batch_layout& L) {
-    size_t b = 0;
-    for (int o = 0; o < L.n_octaves; ++o) b += col_octave_bytes(L, o);
-    return b;
-}
 
 // u16 scratch elements per frame: 6 row-sum images for a strip octave, 1 for a generic octave,
 // none for the LDS-tiled octaves.
-static size_t dog_h_elems(const vslam_batch_layout& L, double sigma0) {
+static size_t dog_h_elems(const vslam_batch_layout& L, const std::vector<OctPlan>& plans) {
     size_t m = 0;
     for (int o = 0; o < L.n_octaves; ++o) {
         const size_t P = (size_t)L.rows[o] * L.pitch[o];
-        const OctPath path = plan_octave(sigma0, o, L.rows[o], L.cols[o]).path;
-        if (path == OctPath::Strip) m = std::max(m, 6 * P);
-        if (path == OctPath::Generic) m = std::max(m, P);
+        if (plans[o].path == OctPath::Strip) m = std::max(m, 6 * P);
+        if (plans[o].path == OctPath::Generic) m = std::max(m, P);
     }
     return m;
 }
 
-static size_t dog_scratch_bytes(const vslam_batch_layout& L, double sigma0, int nf, bool sitemap = false) {
-    size_t sum_p = 0;
-    for (int o = 0; o < L.n_octaves; ++o) sum_p += (size_t)L.rows[o] * L.pitch[o];
-    return (sitemap ? ws_need((size_t)nf * site_frame_bytes(L)) + ws_need((size_t)nf * col_frame_bytes(L) + 16) : 0) + ws_need((size_t)nf * sum_p) + ws_need((size_t)nf * dog_h_elems(L, sigma0) * 2 + 256) +
-           ws_need((size_t)nf * L.bits_frame_words * 8) + ws_need(4 * compaction_ws_elems(L.bits_frame_words, nf)) + ws_need(4 * (size_t)nf);
-}
-
-static int dog_scratch_take(vslam_ctx* c, const vslam_batch_layout& L, double sigma0, int nf, DogScratch& s, bool sitemap = false) {
+// The DoG path's scratch for nf frames: fills the geometry of `s` and asks `ws` for its buffers.
+static void dog_scratch_plan(WsPlan& ws, const vslam_batch_layout& L, const std::vector<OctPlan>& plans, int nf, DogScratch& s, bool sitemap = false) {
     if (sitemap) {
         size_t off = 0;
         for (int o = 0; o < L.n_octaves; ++o) {
@@ -480,15 +496,14 @@ static int dog_scratch_take(vslam_ctx* c, const vslam_batch_layout& L, double si
             off += (size_t)L.lat_rows[o] * s.site_pitch[o];
         }
         s.site_frame = off;
-        s.sitemap = ws_take<uint8_t>(c, (size_t)nf * off);
+        ws.add(s.sitemap, (size_t)nf * off);
         size_t coff = 0;
         for (int o = 0; o < L.n_octaves; ++o) {
             s.col_off[o] = coff;
             coff += col_octave_bytes(L, o);
         }
         s.col_frame = coff;
-        s.colmap = ws_take<uint8_t>(c, (size_t)nf * coff + 16);
-        if (!s.sitemap || !s.colmap) return fail(c, VSLAM_ERR_NOMEM, "workspace sizing error (site map)");
+        ws.add(s.colmap, (size_t)nf * coff + 16);
     }
     size_t sum_p = 0;
     for (int o = 0; o < L.n_octaves; ++o) {
@@ -496,72 +511,45 @@ static int dog_scratch_take(vslam_ctx* c, const vslam_batch_layout& L, double si
         sum_p += (size_t)L.rows[o] * L.pitch[o];
     }
     s.bases_frame = sum_p;
-    s.bases = ws_take<uint8_t>(c, (size_t)nf * sum_p);
-    s.h = ws_take<uint16_t>(c, (size_t)nf * dog_h_elems(L, sigma0) + 128);
-    s.lflags = ws_take<unsigned long long>(c, (size_t)nf * L.bits_frame_words);
-    s.cws = ws_take<unsigned int>(c, compaction_ws_elems(L.bits_frame_words, nf));
-    s.pbegin = ws_take<unsigned int>(c, nf);
-    if (!s.bases || !s.h || !s.lflags || !s.cws || !s.pbegin) return fail(c, VSLAM_ERR_NOMEM, "workspace sizing error (dog)");
-    return VSLAM_OK;
+    ws.add(s.bases, (size_t)nf * sum_p);
+    ws.add(s.h, (size_t)nf * dog_h_elems(L, plans) + 128);
+    ws.add(s.lflags, (size_t)nf * L.bits_frame_words);
+    ws.add(s.cws, compaction_ws_elems(L.bits_frame_words, nf));
+    ws.add(s.pbegin, nf);
 }
 
 
 // Fused LDS-tiled octave (kernels_pyramid.hip.h); the plan has already matched CFG's widths.
 template <class CFG>
-static int enqueue_pyr_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const uint8_t* base, size_t bframe,
-                              uint8_t* oct_out, size_t pframe, int rows, int cols, int pitch, int nf, uint8_t* next_base,
-                              size_t nframe, int nrows, int ncols, int npitch) {
-    uint64_t sb;
-    std::memcpy(&sb, &sigma0, 8);
-    auto key = std::make_pair(sb, o);
-    auto it = c->tile_taps.find(key);
-    if (it == c->tile_taps.end()) {
-        NO_TABLE_IN_CAPTURE(c, "octave kernel");
+static int enqueue_pyr_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const OctIO& io) {
+    const PyrTaps<CFG>* taps;
+    TRY(get_table(c, kTableTile, sigma0, o, "octave kernel", sizeof(PyrTaps<CFG>), [&](void* host) -> int {
         const uint16_t* tp[6];
-        for (int l = 0; l < 6; ++l) tp[l] = pl.taps[l].data();
-        std::vector<PyrTaps<CFG>> host(1);
-        pyr_pack_taps<CFG>(tp, host[0]);
-        void* d = nullptr;
-        HIPCHK(c, hipMalloc(&d, sizeof(PyrTaps<CFG>)));
-        HIPCHK(c, hipMemcpy(d, host.data(), sizeof(PyrTaps<CFG>), hipMemcpyHostToDevice));
-        it = c->tile_taps.emplace(key, d).first;
-    }
+        tap_pointers(pl.taps, tp);
+        pyr_pack_taps<CFG>(tp, *static_cast<PyrTaps<CFG>*>(host));
+        return VSLAM_OK;
+    }, &taps));
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_pyr_octave<CFG>)));  // once per kernel (both tile shapes share the taps)
-    const PyrTaps<CFG>* taps = static_cast<const PyrTaps<CFG>*>(it->second);
-    const dim3 grid((cols + CFG::TW - 1) / CFG::TW, (rows + CFG::TH - 1) / CFG::TH, nf);
-    {
-        TimedScope ts(c, "k_pyr_octave", o);
-        hipLaunchKernelGGL(k_pyr_octave<CFG>, grid, dim3(CFG::NT), CFG::LDS_BYTES, c->stream, base, bframe, oct_out, pframe, rows,
-                           cols, pitch, taps, next_base, nframe, nrows, ncols, npitch);
-    }
-    HIPCHK(c, hipGetLastError());
+    const dim3 grid((io.cols + CFG::TW - 1) / CFG::TW, (io.rows + CFG::TH - 1) / CFG::TH, io.nf);
+    LAUNCH_ON(c, "k_pyr_octave", o, c->stream, CFG::LDS_BYTES, k_pyr_octave<CFG>, grid, dim3(CFG::NT), io.base, io.bframe, io.oct, io.pframe, io.rows,
+              io.cols, io.pitch, taps, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
     return VSLAM_OK;
 }
 
-// The same octave through the matrix-core kernel (kernels_pyramid_mx.hip.h, vslam_mx.hip); `cfg` from mx_config_for.
-static int enqueue_pyr_octave_mx(vslam_ctx* c, int cfg, double sigma0, int o, const OctPlan& pl, const uint8_t* base, size_t bframe,
-                                 uint8_t* oct_out, size_t pframe, int rows, int cols, int pitch, int nf, uint8_t* next_base, size_t nframe,
-                                 int nrows, int ncols, int npitch, const MxScan* scan, int up2_step = 0) {
-    uint64_t sb;
-    std::memcpy(&sb, &sigma0, 8);
-    auto key = std::make_pair(sb, o);
-    auto it = c->mx_taps.find(key);
-    if (it == c->mx_taps.end()) {
-        NO_TABLE_IN_CAPTURE(c, "matrix-core octave kernel");
+// The same octave through the matrix-core kernel (kernels_pyramid_mx.hip.h, vslam_mx.hip), configuration pl.mx.
+static int enqueue_pyr_octave_mx(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const OctIO& io, const MxScan* scan, int up2_step = 0) {
+    const void* table;
+    TRY(get_table(c, kTableMx, sigma0, o, "matrix-core octave kernel", mx_taps_bytes(pl.mx), [&](void* host) -> int {
         const uint16_t* tp[6];
-        for (int l = 0; l < 6; ++l) tp[l] = pl.taps[l].data();
-        std::vector<char> host(mx_taps_bytes(cfg));
-        if (!mx_pack(cfg, tp, host.data())) return fail(c, VSLAM_ERR_UNSUPPORTED, "matrix-core octave kernel: a tap exceeds 127");
-        HIPCHK(c, mx_prepare(cfg));
-        void* d = nullptr;
-        HIPCHK(c, hipMalloc(&d, host.size()));
-        HIPCHK(c, hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice));
-        it = c->mx_taps.emplace(key, d).first;
-    }
+        tap_pointers(pl.taps, tp);
+        if (!mx_pack(pl.mx, tp, host)) return fail(c, VSLAM_ERR_UNSUPPORTED, "matrix-core octave kernel: a tap exceeds 127");
+        HIPCHK(c, mx_prepare(pl.mx));
+        return VSLAM_OK;
+    }, &table));
     hipError_t e;
     {
         TimedScope ts(c, "k_pyr_octave_mx", o);
-        e = mx_launch(cfg, c->stream, it->second, base, bframe, oct_out, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch, scan, up2_step);
+        e = mx_launch(pl.mx, c->stream, table, io, scan, up2_step);
     }
     HIPCHK(c, e);
     return VSLAM_OK;
@@ -578,13 +566,11 @@ static int mark_phase(vslam_ctx* c) {
 
 // The octave whose kernels the held-back side work of a batch waits for (enqueue_dog): the last
 // LDS-tiled one for batches of 32 frames or more, -1 (no gate) otherwise.
-static int dog_side_gate(const vslam_params& p, const vslam_batch_layout& L, int nf) {
+static int dog_side_gate(const std::vector<OctPlan>& plans, int nf) {
     int gate = -1;
     if (nf >= 32)
-        for (int o = 0; o < L.n_octaves; ++o) {
-            const OctPath path = plan_octave(p.sigma0, o, L.rows[o], L.cols[o]).path;
-            if (path == OctPath::Tile0 || path == OctPath::Tile1) gate = o;
-        }
+        for (int o = 0; o < (int)plans.size(); ++o)
+            if (plans[o].path == OctPath::Tile0 || plans[o].path == OctPath::Tile1) gate = o;
     return gate;
 }
 
@@ -604,17 +590,101 @@ static DenseGeom dense_geom(const vslam_batch_layout& L, int o, int min_contrast
     return g;
 }
 
-// createPyramid (GaussPyramid.cpp:106-131) + initialKeypointDetection (Diff_of_Gauss.cpp:254)
-// for nf frames; pyr/bits/points are per-frame blocks with the given strides.
-static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const uint8_t* frames,
-                       size_t fstep, size_t fframe, int nf, uint8_t* pyr, size_t pframe, DogScratch& s,
-                       unsigned long long* bits, bool do_extrema, vslam_point* points, unsigned int* counts,
-                       hipStream_t side = nullptr, const std::function<int(int)>& after_list = nullptr,
-                       const std::function<int(int)>& after_octave = nullptr, hipStream_t up = nullptr, bool later_chunk = false,
-                       bool bases_are_scratch = false) {
+namespace {
+// Where enqueue_dog writes: per-frame blocks with the given strides.
+struct DogOut {
+    uint8_t* pyr;
+    size_t pframe;
+    unsigned long long* bits = nullptr;  // candidate bits (optional)
+    bool do_extrema = false;             // run the lattice scans at all
+    vslam_point* points = nullptr;       // the frames' point lists and their lengths (optional, both or none)
+    unsigned int* counts = nullptr;
+};
+
+// How a batched call runs enqueue_dog beside its other work; the defaults put everything on the context's stream.
+struct DogRun {
     // `side`: stream for the extrema scans and the list compaction (they only read what the
     // octave kernels wrote); ordered after the octave kernels by events.  nullptr = same stream.
-    //
+    hipStream_t side = nullptr;
+    hipStream_t up = nullptr;                 // stream for the second half's upsample of a large batch (with `side`)
+    std::function<int(int)> after_list;       // called with o once octave o's points are in the lists, on the stream they are written on
+    std::function<int(int)> after_octave;     // called with o once octave o's kernels are enqueued and ev_oct[o] marks their end
+    bool later_chunk = false;                 // not the first chunk of its call: the scratch still has readers from the chunk before
+    bool bases_are_scratch = false;           // nobody reads the octave bases after the call
+};
+}  // namespace
+
+// The lattice scan of octave o and the compaction of its points into the frames' lists; on the side stream both wait for
+// ev_oct[o_done], the octave whose kernels were enqueued last.  `fused`: the octave kernel has left the site / seam maps.
+static int enqueue_octave_scan(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const ExtGeom& g, const DogScratch& s,
+                               const MxScan* fused, int o, int o_done, int nf, const DogOut& out, const DogRun& run) {
+    uint8_t* const pyr = out.pyr;
+    const size_t pframe = out.pframe;
+    unsigned long long* const bits = out.bits;
+    const hipStream_t side = run.side;
+    if (out.do_extrema && L.lat_rows[o] > 0 && L.lat_cols[o] > 0) {
+        hipStream_t es = c->stream;
+        if (side) {
+            HIPCHK(c, hipStreamWaitEvent(side, c->ev_oct[o_done], 0));
+            es = side;
+        }
+        if (p.extrema_dense) {
+            // extension: the dense 3x3x3 test on every pixel (kernels_extrema_dense.hip.h); the layout's
+            // lattice of this mode is the image itself
+            const DenseGeom dg = dense_geom(L, o, p.min_contrast, nf);
+            hipLaunchKernelGGL(k_extrema_dense, dim3(((dg.cols + 3) / 4 + 255) / 256, (dg.rows + dg.seg - 1) / dg.seg, nf), dim3(256), 0, es,
+                               pyr, pframe, dg, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o], L.bits_frame_words);
+        } else if (fused) {
+            {
+                TimedScope ts(c, "k_extrema_pack", o, es);
+                HIPCHK(c, mx_launch_pack(es, *fused, L.rows[o], L.lat_words[o], nf, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o],
+                                         L.bits_frame_words, kMxStripRows));
+            }
+            // the lattice rows whose windows straddle a strip's first image row (3a a multiple of the strip's rows, a power of two:
+            // a = 32, 64, ...) are not in the site map: the plain scan kernel runs on exactly those rows
+            const int sr = kMxStripRows;
+            const int n_straddle = (L.lat_rows[o] - 1) / sr;
+            TimedScope ts(c, "k_extrema_w3", o, es);
+            if (n_straddle > 0)
+                hipLaunchKernelGGL(k_extrema_w3<false>, dim3((L.lat_words[o] + 3) / 4, n_straddle, nf), dim3(256), 0, es, pyr, pframe, g, o, bits, s.lflags,
+                                   L.bits_frame_words, sr, sr);
+            if (es != c->stream) {  // the maps' reader is on another stream than their writer: mark its end for the next chunk
+                HIPCHK(c, hipEventRecord(c->ev_pack, es));
+                c->pack_pending = true;
+            }
+        } else if (p.extrema_window == 3) {
+            const dim3 eg((L.lat_words[o] + 3) / 4, L.lat_rows[o], nf);
+            if (p.localize)
+                LAUNCH_ON(c, "k_extrema_w3", o, es, 0, k_extrema_w3<true>, eg, dim3(256), pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
+            else
+                LAUNCH_ON(c, "k_extrema_w3", o, es, 0, k_extrema_w3<false>, eg, dim3(256), pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
+        } else
+            hipLaunchKernelGGL(k_extrema, dim3((L.lat_cols[o] + 255) / 256, L.lat_rows[o], nf * 3), dim3(256), 0, es, pyr,
+                               pframe, g, o, bits, s.lflags, L.bits_frame_words);
+        HIPCHK(c, hipGetLastError());
+    }
+    // compact this octave's points right away (appending to the frame's list): on the side
+    // stream it overlaps the next octave's kernels instead of forming a serial tail
+    if (out.do_extrema && out.points && out.counts) {
+        StreamSwap sw(c, side ? side : c->stream);
+        const size_t entries = (size_t)3 * L.lat_rows[o] * L.lat_words[o];
+        if (p.extrema_dense) {
+            DenseDogEntries ent{s.lflags + L.bits_offset[o], L.bits_frame_words, pyr, pframe, dense_geom(L, o, p.min_contrast, nf), o, out.points};
+            TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, out.counts, o > 0 ? 1 : 0));
+        } else {
+            DogEntries ent{s.lflags, L.bits_frame_words, pyr, pframe, g, o, o + 1, out.points};
+            TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, out.counts, o > 0 ? 1 : 0));
+        }
+        if (run.after_list) TRY(run.after_list(o));  // on the stream the list is written on, behind octave o's records
+    }
+    return VSLAM_OK;
+}
+
+// createPyramid (GaussPyramid.cpp:106-131) + initialKeypointDetection (Diff_of_Gauss.cpp:254)
+// for nf frames; `plans`: plan_octaves() of the same (sigma0, layout), as given to dog_scratch_plan.
+static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const std::vector<OctPlan>& plans, const uint8_t* frames,
+                       size_t fstep, size_t fframe, int nf, DogScratch& s, const DogOut& out, const DogRun& run = DogRun()) {
+    const hipStream_t side = run.side, up = run.up;
     // Where the side work runs decides how much of the VALU-issue-bound octave kernels it costs
     // (gate = dog_side_gate(): the last LDS-tiled octave, -1 = none; 256 x 1080p, same box):
     //  * the Harris chain (VALU-heavy) always waits for that octave's kernel - the caller enqueues it
@@ -627,7 +697,7 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
     //  * the scan with FeaturePointLocalization inside (params.localize, ~8x the instructions) is
     //    held back like the Harris chain: +0.5 % in the localize / orient / describe modes.
     // Small batches keep the eager order: there the chain's latency matters, not the issue slots.
-    const int gate = (side && p.localize) ? dog_side_gate(p, L, nf) : -1;
+    const int gate = (side && p.localize) ? dog_side_gate(plans, nf) : -1;
     ExtGeom g;
     if (p.localize) TRY(ensure_loc_lut(c));
     fill_geom(c, p, L, g);
@@ -642,17 +712,14 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
     // 21.44 ms against 21.29 for halves in the same configuration - no gain)
     // Matrix path, batched entry (the octave bases are scratch nobody reads afterwards): octave 0's kernel forms its base from
     // the frame while it stages a tile (kernels_pyramid_mx.hip.h: mx_stage_tile_up2) - no upsample kernel, no base in HBM.
-    const bool up2_fused = c->mx && bases_are_scratch && L.n_octaves > 0 && L.rows[0] == 2 * p.rows && L.cols[0] == 2 * p.cols && fstep <= 0x7fffffff &&
-                           [&] {
-                               const OctPlan pl0 = plan_octave(p.sigma0, 0, L.rows[0], L.cols[0]);
-                               return pl0.path != OctPath::Generic && mx_up2_supported(mx_config_for(pl0.ke));
-                           }();
+    const bool up2_fused = c->mx && run.bases_are_scratch && L.n_octaves > 0 && L.rows[0] == 2 * p.rows && L.cols[0] == 2 * p.cols && fstep <= 0x7fffffff &&
+                           mx_up2_supported(plans[0].mx);
     const int nf_a = (!up2_fused && side && up && nf >= 64) ? nf / 2 : nf;
     if (!up2_fused)
         LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3(((p.cols + 3) / 4 + 255) / 256, (p.rows + 15) / 16, nf_a), dim3(256),
                frames, fstep, fframe, s.bases + s.base_off[0], s.bases_frame, L.pitch[0], p.rows, p.cols, 16);
     if (nf_a < nf) {
-        if (later_chunk) HIPCHK(c, hipStreamWaitEvent(up, c->ev_chunk, 0));
+        if (run.later_chunk) HIPCHK(c, hipStreamWaitEvent(up, c->ev_chunk, 0));
         StreamSwap sw(c, up);
         LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3(((p.cols + 3) / 4 + 255) / 256, (p.rows + 15) / 16, nf - nf_a), dim3(256),
                frames + (size_t)nf_a * fframe, fstep, fframe, s.bases + s.base_off[0] + (size_t)nf_a * s.bases_frame, s.bases_frame, L.pitch[0],
@@ -662,10 +729,11 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
     bool fused[VSLAM_MAX_OCTAVES] = {};
     // a later chunk reuses the site / seam maps: its octave kernels (main stream) must not overwrite them while the previous
     // chunk's k_extrema_pack launches (side stream, low priority, possibly on a slow hardware queue) are still reading
-    if (later_chunk && c->pack_pending) {
+    if (run.later_chunk && c->pack_pending) {
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pack, 0));
         c->pack_pending = false;
     }
+    MxScan scan[VSLAM_MAX_OCTAVES] = {};  // of the octaves whose lattice scan runs inside the octave kernel (fused[o])
     struct TagReset {
         vslam_ctx* c;
         ~TagReset() { c->launch_tag = -1; }
@@ -674,51 +742,39 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
         c->launch_tag = o;  // the timing hook's "name@o" (TimedScope) for every launch of this octave
         const int rows = L.rows[o], cols = L.cols[o], pitch = L.pitch[o];
         const size_t P = (size_t)rows * pitch;
-        const uint8_t* base = s.bases + s.base_off[o];
-        uint8_t* oct = pyr + L.octave_offset[o];
-        const OctPlan pl = plan_octave(p.sigma0, o, rows, cols);
+        const OctPlan& pl = plans[o];
         // the fast octave kernels also emit the next octave's base (Gaussian[3] decimated 2:1)
         const bool has_next = o + 1 < L.n_octaves;
         const bool fuse_next = has_next && pl.path != OctPath::Generic;
-        uint8_t* nb = fuse_next ? s.bases + s.base_off[o + 1] : nullptr;
-        const int nr = has_next ? L.rows[o + 1] : 0, nc = has_next ? L.cols[o + 1] : 0, np = has_next ? L.pitch[o + 1] : 0;
+        OctIO io{s.bases + s.base_off[o], s.bases_frame, out.pyr + L.octave_offset[o], out.pframe, rows, cols, pitch, nf,
+                 fuse_next ? s.bases + s.base_off[o + 1] : nullptr, s.bases_frame, has_next ? L.rows[o + 1] : 0, has_next ? L.cols[o + 1] : 0,
+                 has_next ? L.pitch[o + 1] : 0};
+        if (o == 0 && up2_fused) io.base = frames, io.bframe = fframe;  // the kernel reads the source frames (mx_launch: up2_step)
         // tile shape: the wide tile (256 x 32) when it needs no more tile area than the tall one (128 x 64).
         // A 384 x 32 tile (1920 = 5 x 384) on 384-thread workgroups was measured in round 3: six waves per
         // workgroup sit 2-2-1-1 on the four SIMDs and meet at every barrier: 21.3 vs 18.3 ms per step.
         const int shape = (long)((cols + 255) / 256) * ((rows + 31) / 32) <= (long)((cols + 127) / 128) * ((rows + 63) / 64) ? 1 : 0;
         // matrix path: the plain lattice scan (window 3, candidates + contrast list) runs inside the octave kernel
         // while the DoG rows are in LDS (kernels_pyramid_mx.hip.h); k_extrema_pack then replaces k_extrema_w3
-        MxScan scan{};
-        const bool fused_scan = c->mx && s.sitemap && do_extrema && !p.localize && !p.extrema_dense && p.extrema_window == 3 && L.lat_rows[o] > 0 &&
-                                L.lat_cols[o] > 0 && pl.path != OctPath::Generic && mx_scan_supported(mx_config_for(pl.ke));
-        if (fused_scan)
-            scan = MxScan{s.sitemap + s.site_off[o], s.site_frame, L.lat_rows[o], L.lat_cols[o], s.site_pitch[o], p.min_contrast,
-                          s.colmap + s.col_off[o], s.col_frame, mx_seams(cols)};
-        fused[o] = fused_scan;
+        fused[o] = c->mx && s.sitemap && out.do_extrema && !p.localize && !p.extrema_dense && p.extrema_window == 3 && L.lat_rows[o] > 0 &&
+                   L.lat_cols[o] > 0 && mx_scan_supported(pl.mx);
+        if (fused[o])
+            scan[o] = MxScan{s.sitemap + s.site_off[o], s.site_frame, L.lat_rows[o], L.lat_cols[o], s.site_pitch[o], p.min_contrast,
+                             s.colmap + s.col_off[o], s.col_frame, mx_seams(cols)};
         // frames [f_lo, f_lo + n) of this octave through the LDS-tiled kernel
         auto tiled = [&](int f_lo, int n) -> int {
-            const uint8_t* b = base + (size_t)f_lo * s.bases_frame;
-            uint8_t* oc = oct + (size_t)f_lo * pframe;
-            uint8_t* nbh = nb ? nb + (size_t)f_lo * s.bases_frame : nullptr;
-            if (c->mx)
-                if (const int cfg = mx_config_for(pl.ke))
-                {
-                    MxScan sc = scan;
-                    sc.sitemap += (size_t)f_lo * s.site_frame;
-                    sc.colmap += (size_t)f_lo * s.col_frame;
-                    if (o == 0 && up2_fused)
-                        return enqueue_pyr_octave_mx(c, cfg, p.sigma0, o, pl, frames + (size_t)f_lo * fframe, fframe, oc, pframe, rows, cols, pitch, n, nbh,
-                                                     s.bases_frame, nr, nc, np, fused_scan ? &sc : nullptr, (int)fstep);
-                    return enqueue_pyr_octave_mx(c, cfg, p.sigma0, o, pl, b, s.bases_frame, oc, pframe, rows, cols, pitch, n, nbh, s.bases_frame, nr, nc, np,
-                                                 fused_scan ? &sc : nullptr);
-                }
-#define VSLAM_TILED(CFG) enqueue_pyr_octave<CFG>(c, p.sigma0, o, pl, b, s.bases_frame, oc, pframe, rows, cols, pitch, n, nbh, s.bases_frame, nr, nc, np)
-            if (pl.path == OctPath::Tile0) return shape == 1 ? VSLAM_TILED(PyrCfgOct0W) : VSLAM_TILED(PyrCfgOct0);
-            return shape == 1 ? VSLAM_TILED(PyrCfgOct1W) : VSLAM_TILED(PyrCfgOct1);
-#undef VSLAM_TILED
+            const OctIO part = io.frames(f_lo, n);
+            if (c->mx && pl.mx) {
+                MxScan sc = scan[o];
+                if (fused[o]) sc.sitemap += (size_t)f_lo * s.site_frame, sc.colmap += (size_t)f_lo * s.col_frame;
+                return enqueue_pyr_octave_mx(c, p.sigma0, o, pl, part, fused[o] ? &sc : nullptr, o == 0 && up2_fused ? (int)fstep : 0);
+            }
+            if (pl.path == OctPath::Tile0)
+                return shape == 1 ? enqueue_pyr_octave<PyrCfgOct0W>(c, p.sigma0, o, pl, part) : enqueue_pyr_octave<PyrCfgOct0>(c, p.sigma0, o, pl, part);
+            return shape == 1 ? enqueue_pyr_octave<PyrCfgOct1W>(c, p.sigma0, o, pl, part) : enqueue_pyr_octave<PyrCfgOct1>(c, p.sigma0, o, pl, part);
         };
         // opt-in matrix path: also the octaves the default path runs through the strip kernels (no u16 scratch round trip)
-        const bool is_tiled = pl.path == OctPath::Tile0 || pl.path == OctPath::Tile1 || (c->mx && pl.path != OctPath::Generic && mx_config_for(pl.ke) != 0);
+        const bool is_tiled = pl.path == OctPath::Tile0 || pl.path == OctPath::Tile1 || (c->mx && pl.mx != 0);
         if (o == 0 && nf_a < nf && !is_tiled) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_up2, 0));  // octave 0 needs every base
         if (is_tiled && o == 0 && nf_a < nf) {
             TRY(tiled(0, nf_a));
@@ -727,84 +783,24 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
         } else if (is_tiled)
             TRY(tiled(0, nf));
         else if (pl.path == OctPath::Strip)
-            TRY(enqueue_strip_octave(c, p.sigma0, o, pl, base, s.bases_frame, oct, pframe, s.h, rows, cols, pitch, nf, nb, s.bases_frame, nr, nc, np));
+            TRY(enqueue_strip_octave(c, p.sigma0, o, pl, io, s.h));
         else {
             for (int l = 0; l < VSLAM_NUM_LEVELS; ++l)
-                TRY(enqueue_blur(c, base, (size_t)pitch, s.bases_frame, oct + (size_t)l * P, (size_t)pitch, pframe, s.h, rows,
+                TRY(enqueue_blur(c, io.base, (size_t)pitch, s.bases_frame, io.oct + (size_t)l * P, (size_t)pitch, out.pframe, s.h, rows,
                                  cols, nf, pl.ks[l], pl.sg[l]));
-            LAUNCH(c, "k_dog5", k_dog5, dim3((unsigned)((P + 255) / 256), 1, nf), dim3(256), oct,
-                   oct + (size_t)VSLAM_NUM_LEVELS * P, P, pframe);
+            LAUNCH(c, "k_dog5", k_dog5, dim3((unsigned)((P + 255) / 256), 1, nf), dim3(256), io.oct,
+                   io.oct + (size_t)VSLAM_NUM_LEVELS * P, P, out.pframe);
         }
         if (has_next && !fuse_next)
             LAUNCH(c, "k_resize_nearest_half_v4", k_resize_nearest_half_v4, dim3((L.cols[o + 1] / 4 + 256) / 256, L.rows[o + 1], nf),
-                   dim3(256), oct + (size_t)3 * P, pframe, pitch, s.bases + s.base_off[o + 1], s.bases_frame, L.pitch[o + 1], rows,
+                   dim3(256), io.oct + (size_t)3 * P, out.pframe, pitch, s.bases + s.base_off[o + 1], s.bases_frame, L.pitch[o + 1], rows,
                    L.rows[o + 1], L.cols[o + 1]);
         if (side) HIPCHK(c, hipEventRecord(c->ev_oct[o], c->stream));
         if (o == 0) TRY(mark_phase(c));
-        if (after_octave) TRY(after_octave(o));  // octave o's kernels are enqueued and ev_oct[o] marks their end
+        if (run.after_octave) TRY(run.after_octave(o));  // octave o's kernels are enqueued and ev_oct[o] marks their end
         if (o < gate) continue;  // scan + compaction of this octave are enqueued behind octave `gate`
-        const int o_done = o;    // the octave whose kernels were enqueued last
-        for (int oo = (o_done == gate ? 0 : o_done); oo <= o_done; ++oo) {
-        const int o = oo;
-        if (do_extrema && L.lat_rows[o] > 0 && L.lat_cols[o] > 0) {
-            hipStream_t es = c->stream;
-            if (side) {
-                HIPCHK(c, hipStreamWaitEvent(side, c->ev_oct[o_done], 0));
-                es = side;
-            }
-            if (p.extrema_dense) {
-                // extension: the dense 3x3x3 test on every pixel (kernels_extrema_dense.hip.h); the layout's
-                // lattice of this mode is the image itself
-                const DenseGeom dg = dense_geom(L, o, p.min_contrast, nf);
-                hipLaunchKernelGGL(k_extrema_dense, dim3(((dg.cols + 3) / 4 + 255) / 256, (dg.rows + dg.seg - 1) / dg.seg, nf), dim3(256), 0, es,
-                                   pyr, pframe, dg, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o], L.bits_frame_words);
-            } else if (fused[o]) {
-                const MxScan sc{s.sitemap + s.site_off[o], s.site_frame, L.lat_rows[o], L.lat_cols[o], s.site_pitch[o], p.min_contrast,
-                                s.colmap + s.col_off[o], s.col_frame, mx_seams(L.cols[o])};
-                {
-                    TimedScope ts(c, "k_extrema_pack", o, es);
-                    HIPCHK(c, mx_launch_pack(es, sc, L.rows[o], L.lat_words[o], nf, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o],
-                                             L.bits_frame_words, kMxStripRows));
-                }
-                // the lattice rows whose windows straddle a strip's first image row (3a a multiple of the strip's rows, a power of two:
-                // a = 32, 64, ...) are not in the site map: the plain scan kernel runs on exactly those rows
-                const int sr = kMxStripRows;
-                const int n_straddle = (L.lat_rows[o] - 1) / sr;
-                TimedScope ts(c, "k_extrema_w3", o, es);
-                if (n_straddle > 0)
-                    hipLaunchKernelGGL(k_extrema_w3<false>, dim3((L.lat_words[o] + 3) / 4, n_straddle, nf), dim3(256), 0, es, pyr, pframe, g, o, bits, s.lflags,
-                                       L.bits_frame_words, sr, sr);
-                if (es != c->stream) {  // the maps' reader is on another stream than their writer: mark its end for the next chunk
-                    HIPCHK(c, hipEventRecord(c->ev_pack, es));
-                    c->pack_pending = true;
-                }
-            } else if (p.extrema_window == 3) {
-                const dim3 eg((L.lat_words[o] + 3) / 4, L.lat_rows[o], nf);
-                TimedScope ts(c, "k_extrema_w3", o, es);
-                if (p.localize)
-                    hipLaunchKernelGGL(k_extrema_w3<true>, eg, dim3(256), 0, es, pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
-                else
-                    hipLaunchKernelGGL(k_extrema_w3<false>, eg, dim3(256), 0, es, pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
-            } else
-                hipLaunchKernelGGL(k_extrema, dim3((L.lat_cols[o] + 255) / 256, L.lat_rows[o], nf * 3), dim3(256), 0, es, pyr,
-                                   pframe, g, o, bits, s.lflags, L.bits_frame_words);
-            HIPCHK(c, hipGetLastError());
-        }
-        // compact this octave's points right away (appending to the frame's list): on the side
-        // stream it overlaps the next octave's kernels instead of forming a serial tail
-        if (do_extrema && points && counts) {
-            StreamSwap sw(c, side ? side : c->stream);
-            const size_t entries = (size_t)3 * L.lat_rows[o] * L.lat_words[o];
-            if (p.extrema_dense) {
-                DenseDogEntries ent{s.lflags + L.bits_offset[o], L.bits_frame_words, pyr, pframe, dense_geom(L, o, p.min_contrast, nf), o, points};
-                TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, counts, o > 0 ? 1 : 0));
-            } else {
-                DogEntries ent{s.lflags, L.bits_frame_words, pyr, pframe, g, o, o + 1, points};
-                TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, counts, o > 0 ? 1 : 0));
-            }
-            if (after_list) TRY(after_list(o));  // on the stream the list is written on, behind octave o's records
-        }
-        }  // oo
+        // ... which is when the octaves held back until then get theirs, in order
+        for (int oo = (o == gate ? 0 : o); oo <= o; ++oo) TRY(enqueue_octave_scan(c, p, L, g, s, fused[oo] ? &scan[oo] : nullptr, oo, o, nf, out, run));
     }
     if (side && up) HIPCHK(c, hipEventRecord(c->ev_chunk, c->stream));
     return VSLAM_OK;
@@ -871,6 +867,21 @@ static int d2h(vslam_ctx* c, void* dst, size_t dpitch, const void* src, size_t s
     return VSLAM_OK;
 }
 
+// The end of the entry points that return a list: wait for the stream, then *count = what the kernels counted (it may
+// exceed cap) and the first min(count, cap) records.  `bits`: candidate words to fetch in the same wait (bits_bytes = 0: none).
+template <class R>
+static int read_list(vslam_ctx* c, const unsigned int* d_count, const R* d_list, size_t cap, R* out, size_t* count, uint64_t* bits = nullptr,
+                     const unsigned long long* d_bits = nullptr, size_t bits_bytes = 0) {
+    unsigned int n = 0;
+    HIPCHK(c, hipMemcpyAsync(&n, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+    if (bits_bytes) HIPCHK(c, hipMemcpyAsync(bits, d_bits, bits_bytes, hipMemcpyDeviceToHost, c->stream));
+    TRY(vslam_ctx_sync(c));
+    *count = n;
+    const size_t m = std::min<size_t>(n, cap);
+    if (m) HIPCHK(c, hipMemcpy(out, d_list, m * sizeof(R), hipMemcpyDeviceToHost));
+    return VSLAM_OK;
+}
+
 
 extern "C" {
 
@@ -931,15 +942,11 @@ int vslam_ctx_destroy(vslam_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < vslam_ctx::kAux; ++i)  // a failed batch call may have left side-stream work un-joined
         if (c->aux[i]) (void)hipStreamSynchronize(c->aux[i]);
-    for (auto& kv : c->taps) (void)hipFree(kv.second);
-    for (auto& kv : c->strip_taps) (void)hipFree(kv.second);
-    for (auto& kv : c->tile_taps) (void)hipFree(kv.second);
-    for (auto& kv : c->mx_taps) (void)hipFree(kv.second);
+    for (auto& kv : c->tables) (void)hipFree(kv.second);
     if (c->ws) (void)hipFree(c->ws);
     for (auto& b : c->block_cache) (void)hipFree(b.second);
     if (c->loc_lut) (void)hipFree(c->loc_lut);
     if (c->dump) (void)hipFree(c->dump);
-    for (auto& kv : c->orient_taps) (void)hipFree(kv.second);
     sched_destroy(c);
     for (hipEvent_t e : {c->ev_phase, c->ev_up2, c->ev_chunk, c->ev_pack, c->ev_list0, c->ev_edge, c->ev_or_fork, c->ev_or_join[0], c->ev_or_join[1]})
         if (e) (void)hipEventDestroy(e);
@@ -969,10 +976,11 @@ int vslam_gaussian_blur_u8(vslam_ctx* c, const uint8_t* src, int rows, int cols,
     const int n = ksize > 0 ? ksize : (sigma > 0 ? gauss_ksize_u8(sigma) : -1);
     ARGCHK(c, n > 0 && (n & 1) && n <= VSLAM_MAX_KSIZE, "blur: kernel size must be odd (or 0 with sigma > 0)");
     const size_t P = (size_t)rows * cols;
-    TRY(ws_reserve(c, 2 * ws_need(P) + ws_need(2 * P)));
-    uint8_t* d_src = ws_take<uint8_t>(c, P);
-    uint8_t* d_dst = ws_take<uint8_t>(c, P);
-    uint16_t* d_h = ws_take<uint16_t>(c, P);
+    uint8_t *d_src, *d_dst;
+    uint16_t* d_h;
+    WsPlan ws;
+    ws.add(d_src, P), ws.add(d_dst, P), ws.add(d_h, P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_src, cols, src, step, cols, rows));
     TRY(enqueue_blur(c, d_src, cols, P, d_dst, cols, P, d_h, rows, cols, 1, n, sigma));
     TRY(d2h(c, dst, dst_step, d_dst, cols, cols, rows));
@@ -985,9 +993,11 @@ int vslam_sobel_k1_u8_f32(vslam_ctx* c, const uint8_t* src, int rows, int cols, 
     ARGCHK(c, src && dst && rows > 0 && cols > 0 && step >= (size_t)cols && dst_step >= 4 * (size_t)cols, "sobel: bad image");
     ARGCHK(c, (dx == 1 && dy == 0) || (dx == 0 && dy == 1), "sobel: (dx,dy) must be (1,0) or (0,1)");
     const size_t P = (size_t)rows * cols;
-    TRY(ws_reserve(c, ws_need(P) + ws_need(4 * P)));
-    uint8_t* d_src = ws_take<uint8_t>(c, P);
-    float* d_dst = ws_take<float>(c, P);
+    uint8_t* d_src;
+    float* d_dst;
+    WsPlan ws;
+    ws.add(d_src, P), ws.add(d_dst, P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_src, cols, src, step, cols, rows));
     LAUNCH(c, "k_sobel_k1", k_sobel_k1, grid_rows(cols, rows), dim3(256), d_src, (size_t)cols, d_dst, (size_t)cols, rows,
            cols, dx);
@@ -1000,9 +1010,10 @@ int vslam_resize_linear2x_u8(vslam_ctx* c, const uint8_t* src, int rows, int col
     TRY(bind_device(c));
     ARGCHK(c, src && dst && rows > 0 && cols > 0 && step >= (size_t)cols && dst_step >= 2 * (size_t)cols, "resize2x: bad image");
     const size_t P = (size_t)rows * cols;
-    TRY(ws_reserve(c, ws_need(P) + ws_need(4 * P)));
-    uint8_t* d_src = ws_take<uint8_t>(c, P);
-    uint8_t* d_dst = ws_take<uint8_t>(c, 4 * P);
+    uint8_t *d_src, *d_dst;
+    WsPlan ws;
+    ws.add(d_src, P), ws.add(d_dst, 4 * P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_src, cols, src, step, cols, rows));
     if (cols % 4 == 0)
         LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3((cols / 4 + 255) / 256, (rows + 15) / 16, 1), dim3(256),
@@ -1022,9 +1033,10 @@ int vslam_resize_nearest_half_u8(vslam_ctx* c, const uint8_t* src, int rows, int
     ARGCHK(c, src && dst && rows > 0 && cols > 0 && dr > 0 && dc > 0 && step >= (size_t)cols && dst_step >= (size_t)dc,
            "resize half: bad image");
     const size_t P = (size_t)rows * cols, Q = (size_t)dr * dc;
-    TRY(ws_reserve(c, ws_need(P) + ws_need(Q)));
-    uint8_t* d_src = ws_take<uint8_t>(c, P);
-    uint8_t* d_dst = ws_take<uint8_t>(c, Q);
+    uint8_t *d_src, *d_dst;
+    WsPlan ws;
+    ws.add(d_src, P), ws.add(d_dst, Q);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_src, cols, src, step, cols, rows));
     LAUNCH(c, "k_resize_nearest_half", k_resize_nearest_half, grid_rows(dc, dr), dim3(256), d_src, (size_t)cols, P, d_dst,
            (size_t)dc, Q, rows, cols, dr, dc);
@@ -1037,9 +1049,11 @@ int vslam_convert_scale_abs_f32(vslam_ctx* c, const float* src, int rows, int co
     TRY(bind_device(c));
     ARGCHK(c, src && dst && rows > 0 && cols > 0 && step >= 4 * (size_t)cols && dst_step >= (size_t)cols, "convertScaleAbs: bad image");
     const size_t P = (size_t)rows * cols;
-    TRY(ws_reserve(c, ws_need(4 * P) + ws_need(P)));
-    float* d_src = ws_take<float>(c, P);
-    uint8_t* d_dst = ws_take<uint8_t>(c, P);
+    float* d_src;
+    uint8_t* d_dst;
+    WsPlan ws;
+    ws.add(d_src, P), ws.add(d_dst, P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_src, 4 * (size_t)cols, src, step, 4 * (size_t)cols, rows));
     LAUNCH(c, "k_convert_scale_abs", k_convert_scale_abs, grid_rows(cols, rows), dim3(256), d_src, (size_t)cols, d_dst,
            (size_t)cols, rows, cols);
@@ -1056,10 +1070,10 @@ int vslam_harris_from_grad_f32(vslam_ctx* c, const float* ix, const float* iy, i
            "HarrisCorner: bad image");
     ARGCHK(c, window >= 1 && (window & 1), "HarrisCorner: window must be odd");
     const size_t P = (size_t)rows * cols, rb = 4 * (size_t)cols;
-    TRY(ws_reserve(c, 3 * ws_need(4 * P)));
-    float* d_ix = ws_take<float>(c, P);
-    float* d_iy = ws_take<float>(c, P);
-    float* d_r = ws_take<float>(c, P);
+    float *d_ix, *d_iy, *d_r;
+    WsPlan ws;
+    ws.add(d_ix, P), ws.add(d_iy, P), ws.add(d_r, P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_ix, rb, ix, step, rb, rows));
     TRY(h2d(c, d_iy, rb, iy, step, rb, rows));
     LAUNCH(c, "k_harris_from_grad", k_harris_from_grad, grid_rows(cols, rows), dim3(256), d_ix, d_iy, (size_t)cols, rows,
@@ -1075,9 +1089,11 @@ int vslam_harris_response_u8(vslam_ctx* c, const uint8_t* img, int rows, int col
            "harris_response: bad image");
     if (window != 3) return fail(c, VSLAM_ERR_UNSUPPORTED, "harris_response: fused kernel implements windowSize 3 (Harris_corners.cpp:34); use the per-stage entry points for other windows");
     const size_t P = (size_t)rows * cols;
-    TRY(ws_reserve(c, ws_need(P) + ws_need(4 * P)));
-    uint8_t* d_img = ws_take<uint8_t>(c, P);
-    float* d_r = ws_take<float>(c, P);
+    uint8_t* d_img;
+    float* d_r;
+    WsPlan ws;
+    ws.add(d_img, P), ws.add(d_r, P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_img, cols, img, step, cols, rows));
     TRY(enqueue_harris(c, d_img, P, rows, cols, 1, k, d_r, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
     TRY(d2h(c, resp, resp_step, d_r, 4 * (size_t)cols, 4 * (size_t)cols, rows));
@@ -1090,9 +1106,11 @@ static int nms_strict_common(vslam_ctx* c, const void* src, int elem, int rows, 
     ARGCHK(c, src && mask && rows > 0 && cols > 0 && step >= (size_t)elem * cols && mask_step >= (size_t)cols, "NonMaximumSuppression: bad image");
     ARGCHK(c, window >= 1 && (window & 1), "NonMaximumSuppression: windowSize must be odd");
     const size_t P = (size_t)rows * cols, rb = (size_t)elem * cols;
-    TRY(ws_reserve(c, ws_need(elem * P) + ws_need(P)));
-    char* d_src = ws_take<char>(c, elem * P);
-    uint8_t* d_m = ws_take<uint8_t>(c, P);
+    char* d_src;
+    uint8_t* d_m;
+    WsPlan ws;
+    ws.add(d_src, elem * P), ws.add(d_m, P);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_src, rb, src, step, rb, rows));
     const int p = (window - 1) / 2;
     if (elem == 1)
@@ -1120,10 +1138,11 @@ int vslam_nms2_f32(vslam_ctx* c, const float* resp, int rows, int cols, size_t s
     ARGCHK(c, resp && out && rows > 0 && cols > 0 && step >= 4 * (size_t)cols && out_step >= 4 * (size_t)cols && window >= 1,
            "NMS2: bad arguments");
     const size_t P = (size_t)rows * cols, rb = 4 * (size_t)cols;
-    TRY(ws_reserve(c, 2 * ws_need(4 * P) + 256));
-    float* d_r = ws_take<float>(c, P);
-    float* d_o = ws_take<float>(c, P);
-    unsigned int* d_max = ws_take<unsigned int>(c, 1);
+    float *d_r, *d_o;
+    unsigned int* d_max;
+    WsPlan ws;
+    ws.add(d_r, P), ws.add(d_o, P), ws.add(d_max, 1);
+    TRY(ws.commit(c));
     TRY(h2d(c, d_r, rb, resp, step, rb, rows));
     HIPCHK(c, hipMemsetAsync(d_max, 0, 4, c->stream));
     LAUNCH(c, "k_nms2_generic", k_nms2_generic, grid_rows(cols, rows), dim3(256), d_r, (size_t)cols, rows, cols,
@@ -1142,23 +1161,18 @@ int vslam_harris_keypoints_u8(vslam_ctx* c, const uint8_t* img, int rows, int co
     ARGCHK(c, img && count && rows > 0 && cols > 0 && step >= (size_t)cols && (out || cap == 0), "harris_keypoints: bad arguments");
     const size_t P = (size_t)rows * cols;
     const unsigned int dcap = (unsigned int)std::min<size_t>(cap, 0x7fffffff);
-    TRY(ws_reserve(c, ws_need(P) + ws_need(4 * P) + ws_need(harris_flag_words(rows, cols) * 8) + ws_need(sizeof(vslam_kp) * (size_t)dcap) + 256 +
-                          ws_need(4 * compaction_ws_elems(harris_flag_words(rows, cols), 1))));
-    uint8_t* d_img = ws_take<uint8_t>(c, P);
-    float* d_r = ws_take<float>(c, P);
-    unsigned long long* d_f = ws_take<unsigned long long>(c, harris_flag_words(rows, cols));
-    vslam_kp* d_k = ws_take<vslam_kp>(c, dcap);
-    unsigned int* d_n = ws_take<unsigned int>(c, 1);
-    unsigned int* d_cws = ws_take<unsigned int>(c, compaction_ws_elems(harris_flag_words(rows, cols), 1));
+    uint8_t* d_img;
+    float* d_r;
+    unsigned long long* d_f;
+    vslam_kp* d_k;
+    unsigned int *d_n, *d_cws;
+    WsPlan ws;
+    ws.add(d_img, P), ws.add(d_r, P), ws.add(d_f, harris_flag_words(rows, cols)), ws.add(d_k, dcap), ws.add(d_n, 1);
+    ws.add(d_cws, compaction_ws_elems(harris_flag_words(rows, cols), 1));
+    TRY(ws.commit(c));
     TRY(h2d(c, d_img, cols, img, step, cols, rows));
     TRY(enqueue_harris(c, d_img, P, rows, cols, 1, k, d_r, nullptr, nullptr, d_f, d_k, dcap, d_n, d_cws));
-    unsigned int n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, c->stream));
-    TRY(vslam_ctx_sync(c));
-    *count = n;
-    const size_t m = std::min<size_t>(n, dcap);
-    if (m) HIPCHK(c, hipMemcpy(out, d_k, m * sizeof(vslam_kp), hipMemcpyDeviceToHost));
-    return VSLAM_OK;
+    return read_list(c, d_n, d_k, dcap, out, count);
 }
 
 // ------------------------------------------------------------------------------ DoG pyramid
@@ -1204,15 +1218,16 @@ int vslam_pyramid_build_u8(vslam_ctx* c, const uint8_t* img, int rows, int cols,
     py->d_bases = (uint8_t*)block_alloc(c, sum_p, &py->bases_cap);
     if (!py->d_block || !py->d_bases) return cleanup(fail(c, VSLAM_ERR_NOMEM, "device allocation failed (pyramid)"));
     const size_t N = (size_t)rows * cols;
-    int rc = ws_reserve(c, ws_need(N) + dog_scratch_bytes(L, sigma0, 1));
-    if (rc) return cleanup(rc);
-    uint8_t* d_img = ws_take<uint8_t>(c, N);
+    const std::vector<OctPlan> plans = plan_octaves(sigma0, L);
+    uint8_t* d_img;
     DogScratch s;
-    if ((rc = dog_scratch_take(c, L, sigma0, 1, s))) return cleanup(rc);
+    WsPlan ws;
+    ws.add(d_img, N);
+    dog_scratch_plan(ws, L, plans, 1, s);
+    int rc = ws.commit(c);
+    if (rc) return cleanup(rc);
     if ((rc = h2d(c, d_img, cols, img, step, cols, rows))) return cleanup(rc);
-    if ((rc = enqueue_dog(c, p, L, d_img, cols, N, 1, py->d_block, L.pyramid_frame_bytes, s, nullptr, false, nullptr,
-                          nullptr)))
-        return cleanup(rc);
+    if ((rc = enqueue_dog(c, p, L, plans, d_img, cols, N, 1, s, DogOut{py->d_block, L.pyramid_frame_bytes}))) return cleanup(rc);
     if (hipMemcpyAsync(py->d_bases, s.bases, sum_p, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
         return cleanup(fail(c, VSLAM_ERR_HIP, "device copy failed (bases)"));
     if ((rc = vslam_ctx_sync(c))) return cleanup(rc);
@@ -1242,8 +1257,10 @@ static int pyramid_fetch(const vslam_pyramid* py, int octave, const uint8_t* d_s
     ARGCHK(c, dst && dst_step >= (size_t)cols, "pyramid getter: bad destination");
     if (pitch != cols) {  // pitched plane: pack the rows on the device, then one linear copy
         const size_t P = (size_t)rows * cols;
-        TRY(ws_reserve(c, ws_need(P)));
-        uint8_t* d_dense = ws_take<uint8_t>(c, P);
+        uint8_t* d_dense;
+        WsPlan ws;
+        ws.add(d_dense, P);
+        TRY(ws.commit(c));
         LAUNCH(c, "k_pack_rows", k_pack_rows, grid_rows(cols, rows), dim3(256), d_src, pitch, d_dense, rows, cols);
         d_src = d_dense;
     }
@@ -1286,12 +1303,12 @@ int vslam_pyramid_get_gradients(const vslam_pyramid* py, int octave, int level, 
     ARGCHK(c, dst_step >= 4 * (size_t)cols, "pyramid gradients: bad destination step");
     float* host[4] = {grad_x, grad_y, mag, orient};
     const size_t P = (size_t)rows * cols;
-    TRY(ws_reserve(c, 4 * ws_need(4 * P)));
     float* dev[4];
-    for (int i = 0; i < 4; ++i) {
-        float* d = ws_take<float>(c, P);
-        dev[i] = host[i] ? d : nullptr;
-    }
+    WsPlan ws;
+    for (int i = 0; i < 4; ++i) ws.add(dev[i], P);
+    TRY(ws.commit(c));
+    for (int i = 0; i < 4; ++i)
+        if (!host[i]) dev[i] = nullptr;
     const int pitch = py->layout.pitch[octave];
     const uint8_t* g = py->d_block + py->layout.octave_offset[octave] + (size_t)level * rows * pitch;
     if (c->f32_fused)
@@ -1320,12 +1337,12 @@ static int dog_points_host(vslam_ctx* c, const vslam_pyramid* py, int octave, in
     if (p.localize) TRY(ensure_loc_lut(c));
     fill_geom(c, p, L, g);
     const size_t words = L.bits_frame_words;
-    TRY(ws_reserve(c, 2 * ws_need(words * 8) + ws_need(sizeof(vslam_point) * (size_t)p.dog_cap) + 256 + ws_need(4 * compaction_ws_elems(words, 1))));
-    unsigned long long* d_bits = ws_take<unsigned long long>(c, words);
-    unsigned long long* d_lf = ws_take<unsigned long long>(c, words);
-    vslam_point* d_pts = ws_take<vslam_point>(c, p.dog_cap);
-    unsigned int* d_n = ws_take<unsigned int>(c, 1);
-    unsigned int* d_cws = ws_take<unsigned int>(c, compaction_ws_elems(words, 1));
+    unsigned long long *d_bits, *d_lf;
+    vslam_point* d_pts;
+    unsigned int *d_n, *d_cws;
+    WsPlan ws;
+    ws.add(d_bits, words), ws.add(d_lf, words), ws.add(d_pts, p.dog_cap), ws.add(d_n, 1), ws.add(d_cws, compaction_ws_elems(words, 1));
+    TRY(ws.commit(c));
     HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
     const size_t ow = (size_t)3 * L.lat_rows[octave] * L.lat_words[octave];
     if (ow) {
@@ -1342,15 +1359,7 @@ static int dog_points_host(vslam_ctx* c, const vslam_pyramid* py, int octave, in
         DogEntries ent{d_lf, words, py->d_block, L.pyramid_frame_bytes, g, octave, octave + 1, d_pts};
         TRY(enqueue_compaction(c, ent, ow, 1, d_cws, p.dog_cap, d_n, 0));
     }
-    unsigned int n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, c->stream));
-    if (bits && ow)
-        HIPCHK(c, hipMemcpyAsync(bits, d_bits + L.bits_offset[octave], ow * 8, hipMemcpyDeviceToHost, c->stream));
-    TRY(vslam_ctx_sync(c));
-    *count = n;
-    const size_t m = std::min<size_t>(n, p.dog_cap);
-    if (m) HIPCHK(c, hipMemcpy(out, d_pts, m * sizeof(vslam_point), hipMemcpyDeviceToHost));
-    return VSLAM_OK;
+    return read_list(c, d_n, d_pts, p.dog_cap, out, count, bits, d_bits + L.bits_offset[octave], bits ? ow * 8 : 0);
 }
 
 int vslam_dog_extrema(vslam_ctx* c, const vslam_pyramid* py, int octave, int window, int min_contrast, uint64_t* bits,
@@ -1368,25 +1377,18 @@ int vslam_dog_extrema_dense(vslam_ctx* c, const vslam_pyramid* py, int octave, i
     DenseGeom g = dense_geom(L, octave, min_contrast, 1);
     const size_t words = (size_t)3 * g.rows * g.wpr;
     const unsigned int ocap = (unsigned int)std::min<size_t>(cap, 0x7fffffff);
-    TRY(ws_reserve(c, 2 * ws_need(words * 8) + ws_need(sizeof(vslam_point) * (size_t)ocap) + 256 + ws_need(4 * compaction_ws_elems(words, 1))));
-    unsigned long long* d_bits = ws_take<unsigned long long>(c, words);
-    unsigned long long* d_lf = ws_take<unsigned long long>(c, words);
-    vslam_point* d_pts = ws_take<vslam_point>(c, ocap);
-    unsigned int* d_n = ws_take<unsigned int>(c, 1);
-    unsigned int* d_cws = ws_take<unsigned int>(c, compaction_ws_elems(words, 1));
+    unsigned long long *d_bits, *d_lf;
+    vslam_point* d_pts;
+    unsigned int *d_n, *d_cws;
+    WsPlan ws;
+    ws.add(d_bits, words), ws.add(d_lf, words), ws.add(d_pts, ocap), ws.add(d_n, 1), ws.add(d_cws, compaction_ws_elems(words, 1));
+    TRY(ws.commit(c));
     HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
     LAUNCH(c, "k_extrema_dense", k_extrema_dense, dim3(((g.cols + 3) / 4 + 255) / 256, (g.rows + g.seg - 1) / g.seg, 1), dim3(256),
            py->d_block, L.pyramid_frame_bytes, g, bits ? d_bits : nullptr, d_lf, words);
     DenseDogEntries ent{d_lf, words, py->d_block, L.pyramid_frame_bytes, g, octave, d_pts};
     TRY(enqueue_compaction(c, ent, words, 1, d_cws, ocap, d_n, 0));
-    unsigned int n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, c->stream));
-    if (bits) HIPCHK(c, hipMemcpyAsync(bits, d_bits, words * 8, hipMemcpyDeviceToHost, c->stream));
-    TRY(vslam_ctx_sync(c));
-    *count = n;
-    const size_t m = std::min<size_t>(n, ocap);
-    if (m) HIPCHK(c, hipMemcpy(out, d_pts, m * sizeof(vslam_point), hipMemcpyDeviceToHost));
-    return VSLAM_OK;
+    return read_list(c, d_n, d_pts, ocap, out, count, bits, d_bits, bits ? words * 8 : 0);
 }
 
 int vslam_dog_keypoints(vslam_ctx* c, const vslam_pyramid* py, int octave, int window, vslam_point* out, size_t cap,
@@ -1399,9 +1401,11 @@ int vslam_localize_points(vslam_ctx* c, const int* diffs, size_t n, int* keep, i
     ARGCHK(c, (diffs && keep && value) || n == 0, "FeaturePointLocalization: bad arguments");
     ARGCHK(c, n <= 0x7fffffff, "FeaturePointLocalization: too many points");
     if (n == 0) return VSLAM_OK;
-    TRY(ws_reserve(c, ws_need(16 * n) + ws_need(8 * n)));
-    int4* d_in = ws_take<int4>(c, n);
-    int2* d_out = ws_take<int2>(c, n);
+    int4* d_in;
+    int2* d_out;
+    WsPlan ws;
+    ws.add(d_in, n), ws.add(d_out, n);
+    TRY(ws.commit(c));
     HIPCHK(c, hipMemcpyAsync(d_in, diffs, 16 * n, hipMemcpyHostToDevice, c->stream));
     TRY(ensure_loc_lut(c));  // same path as the fused kernels: table for small differences, closed form otherwise
     LAUNCH(c, "k_localize_points", k_localize_points, dim3((unsigned)((n + 255) / 256)), dim3(256), d_in, (int)n, d_out, c->loc_lut);
@@ -1431,63 +1435,51 @@ int vslam_filter_keypoints(vslam_ctx* c, const vslam_pyramid* py, int octave, co
         used[k.level] = true;
     }
     std::vector<float> taps[VSLAM_NUM_LEVELS];
-    int n_used = 0, max_r = 0;
+    int max_r = 0;
     size_t tap_elems = 0;
     for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
         if (!used[l]) continue;
         const double sigma = 1.5 * py->info.sigma[octave][l];  // Diff_of_Gauss.cpp:346
         if (!gauss_kernel_f32(gauss_ksize_f32(sigma), sigma, taps[l])) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");
-        ++n_used;
         max_r = std::max(max_r, (int)taps[l].size() / 2);
         tap_elems += align_up(taps[l].size(), 64);
     }
     const size_t lds = orient_lds_bytes(max_r);
     if (lds > 150 * 1024) return fail(c, VSLAM_ERR_UNSUPPORTED, "filterKeypoints: blur kernel too wide for the LDS strip");
     const unsigned int ocap = (unsigned int)std::min<size_t>(cap, 0x7fffffff);
-    TRY(ws_reserve(c, ws_need(sizeof(vslam_point) * n) + ws_need(8 * n) + ws_need(sizeof(vslam_point) * (size_t)ocap) + 256 +
-                          ws_need(4 * compaction_ws_elems(n, 1)) + (size_t)n_used * 2 * ws_need(4 * P) + ws_need(4 * tap_elems)));
-    vslam_point* d_kps = ws_take<vslam_point>(c, n);
-    unsigned long long* d_masks = ws_take<unsigned long long>(c, n);
-    vslam_point* d_out = ws_take<vslam_point>(c, ocap);
-    unsigned int* d_n = ws_take<unsigned int>(c, 1);
-    unsigned int* d_cws = ws_take<unsigned int>(c, compaction_ws_elems(n, 1));
-    float* d_taps = ws_take<float>(c, tap_elems);
+    vslam_point *d_kps, *d_out;
+    unsigned long long* d_masks;
+    unsigned int *d_n, *d_cws;
+    float *d_taps, *d_mag[VSLAM_NUM_LEVELS], *d_ori[VSLAM_NUM_LEVELS];
+    WsPlan ws;
+    ws.add(d_kps, n), ws.add(d_masks, n), ws.add(d_out, ocap), ws.add(d_n, 1), ws.add(d_cws, compaction_ws_elems(n, 1)), ws.add(d_taps, tap_elems);
+    for (int l = 0; l < VSLAM_NUM_LEVELS; ++l)
+        if (used[l]) ws.add(d_mag[l], P), ws.add(d_ori[l], P);
+    TRY(ws.commit(c));
     OrientLevels lv{};
     HIPCHK(c, hipMemcpyAsync(d_kps, kps, sizeof(vslam_point) * n, hipMemcpyHostToDevice, c->stream));
     size_t toff = 0;
     for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
         if (!used[l]) continue;
-        float* d_mag = ws_take<float>(c, P);
-        float* d_ori = ws_take<float>(c, P);
         const uint8_t* g = py->d_block + py->layout.octave_offset[octave] + (size_t)l * rows * pitch;
         // processGradients for the level (GaussPyramid.cpp:65-104): magnitude and orientation only
         // (the orientation image is only BINNED here: no bin depends on the arctangent's variant, kernels_aux.hip.h)
         LAUNCH(c, "k_level_gradients", k_level_gradients<false>, grid_rows(cols, rows), dim3(256), g, pitch, rows, cols, (float*)nullptr,
-               (float*)nullptr, d_mag, d_ori);
+               (float*)nullptr, d_mag[l], d_ori[l]);
         HIPCHK(c, hipMemcpyAsync(d_taps + toff, taps[l].data(), 4 * taps[l].size(), hipMemcpyHostToDevice, c->stream));
         lv.gauss[l] = g;
-        lv.mag[l] = d_mag;
-        lv.orient[l] = d_ori;
+        lv.mag[l] = d_mag[l];
+        lv.orient[l] = d_ori[l];
         lv.kern[l] = d_taps + toff;
         lv.kn[l] = (int)taps[l].size();
         toff += align_up(taps[l].size(), 64);
     }
     const auto k_orient = c->f32_fused ? k_orient_keypoints<true> : k_orient_keypoints<false>;
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(k_orient)));
-    {
-        TimedScope ts(c, "k_orient_keypoints");
-        hipLaunchKernelGGL(k_orient, dim3((unsigned)n), dim3(256), lds, c->stream, d_kps, (int)n, lv, pitch, rows, cols, d_masks);
-    }
-    HIPCHK(c, hipGetLastError());
+    LAUNCH_ON(c, "k_orient_keypoints", -1, c->stream, lds, k_orient, dim3((unsigned)n), dim3(256), d_kps, (int)n, lv, pitch, rows, cols, d_masks);
     OrientEntries ent{d_masks, d_kps, n, d_out};
     TRY(enqueue_compaction(c, ent, n, 1, d_cws, ocap, d_n, 0));
-    unsigned int total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, d_n, 4, hipMemcpyDeviceToHost, c->stream));
-    TRY(vslam_ctx_sync(c));
-    *count = total;
-    const size_t m = std::min<size_t>(total, ocap);
-    if (m) HIPCHK(c, hipMemcpy(out, d_out, m * sizeof(vslam_point), hipMemcpyDeviceToHost));
-    return VSLAM_OK;
+    return read_list(c, d_n, d_out, ocap, out, count);
 }
 
 int vslam_sift_descriptors(vslam_ctx* c, const vslam_pyramid* py, int octave, const vslam_point* kps, size_t n, float* desc,
@@ -1517,14 +1509,13 @@ int vslam_sift_descriptors(vslam_ctx* c, const vslam_pyramid* py, int octave, co
         if (!gauss_kernel_f32(gauss_ksize_f32(sigma), sigma, taps[l])) return fail(c, VSLAM_ERR_INVALID, "SIFT: bad blur kernel");
         tap_elems += align_up(taps[l].size(), 64);
     }
-    TRY(ws_reserve(c, ws_need(sizeof(vslam_point) * n) + ws_need(sizeof(float2) * n) + ws_need(sizeof(float) * 128 * n) + ws_need(n) +
-                          ws_need(4 * tap_elems)));
-    vslam_point* d_kps = ws_take<vslam_point>(c, n);
-    float2* d_cs = ws_take<float2>(c, n);
-    float* d_desc = ws_take<float>(c, 128 * n);
-    uint8_t* d_def = ws_take<uint8_t>(c, n);
-    float* d_taps = ws_take<float>(c, tap_elems);
-    if (!d_kps || !d_cs || !d_desc || !d_def || !d_taps) return fail(c, VSLAM_ERR_NOMEM, "workspace sizing error (sift)");
+    vslam_point* d_kps;
+    float2* d_cs;
+    float *d_desc, *d_taps;
+    uint8_t* d_def;
+    WsPlan ws;
+    ws.add(d_kps, n), ws.add(d_cs, n), ws.add(d_desc, 128 * n), ws.add(d_def, n), ws.add(d_taps, tap_elems);
+    TRY(ws.commit(c));
     HIPCHK(c, hipMemcpyAsync(d_kps, kps, sizeof(vslam_point) * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_cs, cs.data(), sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
     SiftLevels lv{};
@@ -1560,11 +1551,10 @@ static int gradient_windows(vslam_ctx* c, const float* gx_windows, const float* 
     ARGCHK(c, n <= 0x7fffffff / 3, what);
     if (n == 0) return VSLAM_OK;
     const size_t we = (size_t)window_elems * n;
-    TRY(ws_reserve(c, 2 * ws_need(4 * we + 4) + ws_need(12 * n) + ws_need(4 * n)));
-    float* d_gx = ws_take<float>(c, we + 1);
-    float* d_gy = ws_take<float>(c, we + 1);
-    float* d_s = ws_take<float>(c, 3 * n);
-    float* d_r = ws_take<float>(c, n);
+    float *d_gx, *d_gy, *d_s, *d_r;
+    WsPlan ws;
+    ws.add(d_gx, we + 1), ws.add(d_gy, we + 1), ws.add(d_s, 3 * n), ws.add(d_r, n);
+    TRY(ws.commit(c));
     if (we) {
         HIPCHK(c, hipMemcpyAsync(d_gx, gx_windows, 4 * we, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_gy, gy_windows, 4 * we, hipMemcpyHostToDevice, c->stream));
@@ -1591,26 +1581,18 @@ int vslam_structure_matrix_windows(vslam_ctx* c, const float* gx_windows, const 
 // Device copy of getGaussianKernel(n, sigma, CV_32F) for the orientation blur, cached per context.
 static int get_orient_taps(vslam_ctx* c, double sigma, const float** out, int* n_out) {
     const int n = gauss_ksize_f32(sigma);
-    uint64_t sb;
-    std::memcpy(&sb, &sigma, 8);
-    auto key = std::make_pair(sb, n);
-    auto it = c->orient_taps.find(key);
-    if (it == c->orient_taps.end()) {
-        NO_TABLE_IN_CAPTURE(c, "filterKeypoints");
-        std::vector<float> t;
-        if (!gauss_kernel_f32(n, sigma, t)) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");
+    if (n <= 0 || n > (1 << 20)) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");  // before n sizes the table
+    *n_out = n;
+    return get_table(c, kTableOrient, sigma, n, "filterKeypoints", 4 * (size_t)orient_taps_pk_floats(n), [&](void* host) -> int {
+        std::vector<float> k;
+        if (!gauss_kernel_f32(n, sigma, k)) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");
+        float* t = static_cast<float*>(host);
+        std::copy(k.begin(), k.end(), t);
         // behind the taps: the zero-padded row / column forms k_orient_survivors_pk reads through scalar loads
-        t.resize((size_t)orient_taps_pk_floats(n), 0.0f);
         for (int i = 0; i < n; ++i) t[(size_t)orient_taps_row_off(n) + 3 + i] = t[(size_t)i];
         for (int i = 1; i <= n / 2; ++i) t[(size_t)orient_taps_col_off(n) + i - 1] = t[(size_t)(n / 2 + i)];
-        float* d = nullptr;
-        HIPCHK(c, hipMalloc((void**)&d, 4 * t.size()));
-        HIPCHK(c, hipMemcpy(d, t.data(), 4 * t.size(), hipMemcpyHostToDevice));
-        it = c->orient_taps.emplace(key, d).first;
-    }
-    *out = it->second;
-    *n_out = n;
-    return VSLAM_OK;
+        return VSLAM_OK;
+    }, out);
 }
 
 struct OrientScratch {
@@ -1625,25 +1607,16 @@ struct OrientScratch {
     bool early_forked = false;            // ... on another stream: ev_edge marks its end
     size_t fwords = 0;
 };
-static size_t orient_scratch_bytes(const vslam_params& p, int nf) {
-    const size_t fwords = ((size_t)p.dog_cap + 63) / 64, scap = p.oriented_cap;
-    return ws_need((size_t)nf * fwords * 8) + ws_need((size_t)nf * scap * 4) + 2 * ws_need((size_t)nf * 4) + ws_need((size_t)nf * scap * 8) +
-           ws_need((size_t)nf * OR_RANGE_STRIDE * 4) +
-           ws_need(4 * compaction_ws_elems(std::max(fwords, scap), nf));
-}
-static int orient_scratch_take(vslam_ctx* c, const vslam_params& p, int nf, OrientScratch& s) {
+static void orient_scratch_plan(WsPlan& ws, const vslam_params& p, int nf, OrientScratch& s) {
     s.fwords = ((size_t)p.dog_cap + 63) / 64;
     const size_t scap = p.oriented_cap;
-    s.flags = ws_take<unsigned long long>(c, (size_t)nf * s.fwords);
-    s.surv = ws_take<unsigned int>(c, (size_t)nf * scap);
-    s.scounts = ws_take<unsigned int>(c, nf);
-    s.obegin = ws_take<unsigned int>(c, nf);
-    s.ranges = ws_take<unsigned int>(c, (size_t)nf * OR_RANGE_STRIDE);
-    s.early_done = false;
-    s.masks = ws_take<unsigned long long>(c, (size_t)nf * scap);
-    s.cws = ws_take<unsigned int>(c, compaction_ws_elems(std::max(s.fwords, scap), nf));
-    if (!s.flags || !s.surv || !s.scounts || !s.obegin || !s.ranges || !s.masks || !s.cws) return fail(c, VSLAM_ERR_NOMEM, "workspace sizing error (orient)");
-    return VSLAM_OK;
+    ws.add(s.flags, (size_t)nf * s.fwords);
+    ws.add(s.surv, (size_t)nf * scap);
+    ws.add(s.scounts, nf);
+    ws.add(s.obegin, nf);
+    ws.add(s.ranges, (size_t)nf * OR_RANGE_STRIDE);
+    ws.add(s.masks, (size_t)nf * scap);
+    ws.add(s.cws, compaction_ws_elems(std::max(s.fwords, scap), nf));
 }
 
 // Geometry / blur taps of the batched filterKeypoints and the LDS budget of each octave's launch.
@@ -1793,6 +1766,27 @@ static int enqueue_sift_batch(vslam_ctx* c, const vslam_params& p, const vslam_b
     return VSLAM_OK;
 }
 
+// The outputs of the chunk of a batch call that starts at frame f0: every buffer the caller gave, f0 frames further on
+// (and that much shorter: a pointer still travels with the size of what lies behind it).
+static vslam_batch_out chunk_out(const vslam_batch_out& out, const vslam_params& p, const vslam_batch_layout& L, int f0) {
+    const size_t N = (size_t)p.rows * p.cols;
+    vslam_batch_out co = out;
+    auto advance = [f0](auto*& ptr, size_t& bytes, size_t per_frame) {
+        if (!ptr) return;
+        ptr += (size_t)f0 * per_frame;
+        bytes -= (size_t)f0 * per_frame * sizeof(*ptr);
+    };
+#define VSLAM_ADVANCE(field, per_frame) advance(co.field, co.field##_bytes, per_frame)
+    VSLAM_ADVANCE(response, N), VSLAM_ADVANCE(nms_mask, N), VSLAM_ADVANCE(nms2, N);
+    VSLAM_ADVANCE(harris_kps, p.harris_cap), VSLAM_ADVANCE(harris_counts, 1);
+    VSLAM_ADVANCE(pyramid, L.pyramid_frame_bytes), VSLAM_ADVANCE(extrema_bits, L.bits_frame_words);
+    VSLAM_ADVANCE(dog_points, p.dog_cap), VSLAM_ADVANCE(dog_counts, 1);
+    VSLAM_ADVANCE(oriented_points, p.oriented_cap), VSLAM_ADVANCE(oriented_counts, 1), VSLAM_ADVANCE(oriented_survivors, 1);
+    VSLAM_ADVANCE(descriptors, (size_t)p.oriented_cap * 128), VSLAM_ADVANCE(descriptor_defined, p.oriented_cap);
+#undef VSLAM_ADVANCE
+    return co;
+}
+
 int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* d_frames, size_t frame_stride,
                            int n_frames, const vslam_batch_out* out) {
     TRY(bind_device(c));
@@ -1840,25 +1834,26 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     // Whole-batch launches: every kernel sees all frames (grid.z = frames), so even the coarse
     // octaves fill the chip.  Scratch: octave bases (+ u16 row sums of the non-tiled octaves).
     const int chunk = std::min(n_frames, 256);
-    size_t need = 0;
     const bool want_sitemap = dog && c->mx && !p.localize && !p.extrema_dense && p.extrema_window == 3;
-    if (dog) need += dog_scratch_bytes(L, p.sigma0, chunk, want_sitemap);
-    if (harris)
-        need += (out->response ? 0 : ws_need((size_t)chunk * N * 4)) + ws_need((size_t)chunk * harris_flag_words(p.rows, p.cols) * 8) +
-                ws_need(4 * compaction_ws_elems(harris_flag_words(p.rows, p.cols), chunk));
-    if (orient) need += orient_scratch_bytes(p, chunk);
+    const std::vector<OctPlan> plans = plan_octaves(p.sigma0, L);
+    DogScratch s;
+    OrientScratch os;
+    float* resp_ws = nullptr;
+    unsigned long long* hflags = nullptr;
+    unsigned int* hcws = nullptr;
+    WsPlan ws;
+    if (dog) dog_scratch_plan(ws, L, plans, chunk, s, want_sitemap);
+    if (orient) orient_scratch_plan(ws, p, chunk, os);
+    if (harris) {
+        if (!out->response) ws.add(resp_ws, (size_t)chunk * N);
+        ws.add(hflags, (size_t)chunk * harris_flag_words(p.rows, p.cols));
+        ws.add(hcws, compaction_ws_elems(harris_flag_words(p.rows, p.cols), chunk));
+    }
     c->phase_marked = false;
     c->pack_pending = false;  // the previous call joined its side streams back
-    TRY(ws_reserve(c, need));
-    DogScratch s;
-    if (dog) TRY(dog_scratch_take(c, L, p.sigma0, chunk, s, want_sitemap));
-    OrientScratch os;
-    if (orient) TRY(orient_scratch_take(c, p, chunk, os));
+    TRY(ws.commit(c));
     OrientPlan opl;
     if (orient) TRY(make_orient_plan(c, p, L, opl));
-    float* resp_ws = (harris && !out->response) ? ws_take<float>(c, (size_t)chunk * N) : nullptr;
-    unsigned long long* hflags = harris ? ws_take<unsigned long long>(c, (size_t)chunk * harris_flag_words(p.rows, p.cols)) : nullptr;
-    unsigned int* hcws = harris ? ws_take<unsigned int>(c, compaction_ws_elems(harris_flag_words(p.rows, p.cols), chunk)) : nullptr;
     // Fork: the Harris chain and the extrema/compaction chain run on the context's auxiliary streams beside the octave
     // kernels.  Measured on MI355X: +2.8 % (11.2k vs 10.9k frames/s) -- small, because every kernel of the batch is
     // VALU-issue-bound rather than HBM-bound; per-kernel durations grow accordingly when kernels share the chip.
@@ -1874,12 +1869,7 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     // edge test (list stream -> Harris stream -> back) and the spread launches (list stream -> two idle side streams ->
     // back); each alone reproduces the crash.  While a capture is on, both stay on the list stream; everything else forks
     // from and joins to the main (origin) stream.
-    bool capturing = false;  // the nested forks stay out of a capture
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess) (void)hipGetLastError();
-        capturing = cap != hipStreamCaptureStatusNone;
-    }
+    const bool capturing = stream_is_capturing(c);  // the nested forks stay out of a capture
     hipStream_t sh = c->stream, sx = nullptr;  // Harris stream, extrema stream (nullptr = main)
     // Any early return between the fork and the join must not leave the side streams running into
     // buffers the caller (or the next ws_reserve) is about to reuse: drain them on the error path.
@@ -1913,14 +1903,11 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int nf = std::min(chunk, n_frames - f0);
         const uint8_t* fr = d_frames + (size_t)f0 * frame_stride;
+        const vslam_batch_out co = chunk_out(*out, p, L, f0);
         auto do_harris = [&]() -> int {
             StreamSwap sw(c, sh);
-            float* resp = out->response ? out->response + (size_t)f0 * N : resp_ws;
-            TRY(enqueue_harris(c, fr, frame_stride, p.rows, p.cols, nf, p.harris_k, resp,
-                               out->nms_mask ? out->nms_mask + (size_t)f0 * N : nullptr,
-                               out->nms2 ? out->nms2 + (size_t)f0 * N : nullptr, want_kps ? hflags : nullptr,
-                               want_kps ? out->harris_kps + (size_t)f0 * p.harris_cap : nullptr, p.harris_cap,
-                               want_kps ? out->harris_counts + f0 : nullptr, hcws));
+            TRY(enqueue_harris(c, fr, frame_stride, p.rows, p.cols, nf, p.harris_k, co.response ? co.response : resp_ws, co.nms_mask, co.nms2,
+                               want_kps ? hflags : nullptr, want_kps ? co.harris_kps : nullptr, p.harris_cap, want_kps ? co.harris_counts : nullptr, hcws));
             return VSLAM_OK;
         };
         // The Harris chain: without the DoG path or the side streams it is simply enqueued here.  With
@@ -1929,46 +1916,40 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
         // right after that octave's event, so that nothing enqueued on its stream later can get in front of it.
         // (matrix path: starting the Harris chain at once, or behind octave 0 / 2 / 3 instead of 1, moved the step by less than
         // +-1.5 % - 14.54 .. 14.90 ms on one box - so the gate stays where the default path has it)
-        const int harris_gate = (dog && side_streams) ? dog_side_gate(p, L, nf) : -1;
+        const int harris_gate = (dog && side_streams) ? dog_side_gate(plans, nf) : -1;
         if (harris && harris_gate < 0) TRY(do_harris());
         if (dog) {
-            const bool ext = out->extrema_bits || (out->dog_points && out->dog_counts);
+            const size_t pframe = L.pyramid_frame_bytes;
             os.early_done = os.early_forked = false;
+            DogRun run;
+            run.side = sx;
+            run.up = side_streams ? c->aux[2] : nullptr;
+            run.later_chunk = f0 > 0;
+            run.bases_are_scratch = true;
             // filterKeypoints' edge test for octave 0's records as soon as that octave's part of the list exists
-            const std::function<int(int)> after_list = [&](int o) -> int {
+            run.after_list = [&](int o) -> int {
                 if (orient && o == 0 && L.n_octaves > 1)
-                    return enqueue_edge_flags_early(c, p, opl, nf, out->pyramid + (size_t)f0 * L.pyramid_frame_bytes, L.pyramid_frame_bytes,
-                                                    out->dog_points + (size_t)f0 * p.dog_cap, out->dog_counts + f0, os, (side_streams && !capturing) ? sh : nullptr);
+                    return enqueue_edge_flags_early(c, p, opl, nf, co.pyramid, pframe, co.dog_points, co.dog_counts, os, (side_streams && !capturing) ? sh : nullptr);
                 return VSLAM_OK;
             };
-            const std::function<int(int)> after_octave = [&](int o) -> int {
+            run.after_octave = [&](int o) -> int {
                 if (harris && o == harris_gate) {
                     HIPCHK(c, hipStreamWaitEvent(sh, c->ev_oct[o], 0));
                     return do_harris();
                 }
                 return VSLAM_OK;
             };
-            TRY(enqueue_dog(c, p, L, fr, p.cols, frame_stride, nf, out->pyramid + (size_t)f0 * L.pyramid_frame_bytes,
-                            L.pyramid_frame_bytes, s,
-                            out->extrema_bits ? (unsigned long long*)out->extrema_bits + (size_t)f0 * L.bits_frame_words : nullptr,
-                            ext, out->dog_points ? out->dog_points + (size_t)f0 * p.dog_cap : nullptr,
-                            out->dog_counts ? out->dog_counts + f0 : nullptr, sx, after_list, after_octave,
-                            side_streams ? c->aux[2] : nullptr, f0 > 0, /*bases_are_scratch=*/true));
+            const bool ext = out->extrema_bits || (out->dog_points && out->dog_counts);
+            TRY(enqueue_dog(c, p, L, plans, fr, p.cols, frame_stride, nf, s,
+                            DogOut{co.pyramid, pframe, (unsigned long long*)co.extrema_bits, ext, co.dog_points, co.dog_counts}, run));
             if (orient) {  // filterKeypoints behind the list, on the stream that produced it
                 StreamSwap sw(c, sx ? sx : c->stream);
-                TRY(enqueue_orient_batch(c, p, L, opl, nf, out->pyramid + (size_t)f0 * L.pyramid_frame_bytes, L.pyramid_frame_bytes,
-                                         out->dog_points + (size_t)f0 * p.dog_cap, out->dog_counts + f0, os,
-                                         out->oriented_points + (size_t)f0 * p.oriented_cap, out->oriented_counts + f0,
-                                         (side_streams && !capturing) ? sh : nullptr,
-                                         (side_streams && !capturing) ? c->aux[2] : nullptr));
-                if (out->oriented_survivors)
-                    HIPCHK(c, hipMemcpyAsync(out->oriented_survivors + f0, os.scounts, sizeof(unsigned int) * (size_t)nf,
-                                             hipMemcpyDeviceToDevice, c->stream));
-                if (out->descriptors)
-                    TRY(enqueue_sift_batch(c, p, L, nf, out->pyramid + (size_t)f0 * L.pyramid_frame_bytes, L.pyramid_frame_bytes,
-                                           out->oriented_points + (size_t)f0 * p.oriented_cap, out->oriented_counts + f0,
-                                           out->descriptors + (size_t)f0 * p.oriented_cap * 128,
-                                           out->descriptor_defined ? out->descriptor_defined + (size_t)f0 * p.oriented_cap : nullptr));
+                TRY(enqueue_orient_batch(c, p, L, opl, nf, co.pyramid, pframe, co.dog_points, co.dog_counts, os, co.oriented_points, co.oriented_counts,
+                                         (side_streams && !capturing) ? sh : nullptr, (side_streams && !capturing) ? c->aux[2] : nullptr));
+                if (co.oriented_survivors)
+                    HIPCHK(c, hipMemcpyAsync(co.oriented_survivors, os.scounts, sizeof(unsigned int) * (size_t)nf, hipMemcpyDeviceToDevice, c->stream));
+                if (co.descriptors)
+                    TRY(enqueue_sift_batch(c, p, L, nf, co.pyramid, pframe, co.oriented_points, co.oriented_counts, co.descriptors, co.descriptor_defined));
             }
         }
     }

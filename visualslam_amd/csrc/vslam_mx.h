@@ -31,13 +31,31 @@ struct MxScan {
 // Seams of an octave `cols` wide: lattice columns whose window straddles two 128-column strips (3b = 384 s <= cols - 2).
 inline int mx_seams(int cols) { return cols >= 2 ? (cols - 2) / 384 : 0; }
 bool mx_scan_supported(int cfg);
+// One octave's input and output, as every octave kernel takes them (the kernels receive these scalars in this order).
+struct OctIO {
+    const uint8_t* base;  // the octave's base image, frame f at base + f * bframe
+    size_t bframe;
+    uint8_t* oct;  // the octave's block of the pyramid (6 Gaussian + 5 DoG planes), frame f at oct + f * pframe
+    size_t pframe;
+    int rows, cols, pitch, nf;
+    uint8_t* next_base;  // where the fast kernels leave the next octave's base (Gaussian[3] decimated 2:1); nullptr: nowhere
+    size_t nframe;
+    int nrows, ncols, npitch;
+    // frames [f_lo, f_lo + n) of the same octave
+    OctIO frames(int f_lo, int n) const {
+        OctIO io = *this;
+        io.base += (size_t)f_lo * bframe;
+        io.oct += (size_t)f_lo * pframe;
+        if (next_base) io.next_base += (size_t)f_lo * nframe;
+        io.nf = n;
+        return io;
+    }
+};
 // Raises the kernel's dynamic-LDS ceiling (once per device) and launches it on `stream`; scan = nullptr: no fused scan.
 hipError_t mx_prepare(int cfg);
-// up2_step > 0: `base` / `bframe` are the SOURCE frames (rows / 2 x cols / 2 pixels, `up2_step` bytes per row) and the octave's base is
+// up2_step > 0: `io.base` / `io.bframe` are the SOURCE frames (rows / 2 x cols / 2 pixels, `up2_step` bytes per row) and the octave's base is
 // their 2x bilinear upsample, formed while each tile is staged (configuration 1 only: octave 0 of createPyramid).
-hipError_t mx_launch(int cfg, hipStream_t stream, const void* d_table, const uint8_t* base, size_t bframe, uint8_t* oct_out, size_t pframe,
-                     int rows, int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch,
-                     const MxScan* scan, int up2_step = 0);
+hipError_t mx_launch(int cfg, hipStream_t stream, const void* d_table, const OctIO& io, const MxScan* scan, int up2_step = 0);
 bool mx_up2_supported(int cfg);
 // bits / lflags: word 0 of frame 0's octave (bits may be nullptr).
 hipError_t mx_launch_pack(hipStream_t stream, const MxScan& scan, int rows, int wpr, int nf, unsigned long long* bits, unsigned long long* lflags,

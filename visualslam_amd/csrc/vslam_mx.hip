@@ -16,8 +16,7 @@ namespace vslam {
 // alternations, that scheduling takes octave 0 from 6.8-7.1 to 6.4-6.6 ms per 256-frame step and costs the other three
 // configurations 4-5 % (profiles/r05_mx_maxilp_ab.txt) - so only octave 0 gets it.
 hipError_t mx_prepare_oct0();
-hipError_t mx_launch_oct0(hipStream_t stream, const void* d_table, const uint8_t* base, size_t bframe, uint8_t* oct_out, size_t pframe, int rows,
-                          int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch, const MxScan* scan, int up2_step);
+hipError_t mx_launch_oct0(hipStream_t stream, const void* d_table, const OctIO& io, const MxScan* scan, int up2_step);
 
 #ifndef VSLAM_MX_OCT0_TU
 template <class CFG>
@@ -75,42 +74,40 @@ hipError_t mx_prepare(int cfg) {
 #endif
 
 template <class CFG>
-static hipError_t launch(hipStream_t stream, const void* d_table, const uint8_t* base, size_t bframe, uint8_t* oct_out, size_t pframe, int rows,
-                         int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch, const MxScan* scan, int up2_step) {
-    const dim3 grid((cols + CFG::TW - 1) / CFG::TW, (rows + CFG::TH - 1) / CFG::TH, nf);
+static hipError_t launch(hipStream_t stream, const void* d_table, const OctIO& io, const MxScan* scan, int up2_step) {
+    const dim3 grid((io.cols + CFG::TW - 1) / CFG::TW, (io.rows + CFG::TH - 1) / CFG::TH, io.nf);
     MxExtArgs ext{};
     if (up2_step > 0) {
       if constexpr (!std::is_same<CFG, MxCfgOct0>::value) {
         return hipErrorInvalidValue;
       } else {
-        if ((rows & 1) || (cols & 1)) return hipErrorInvalidValue;
+        if ((io.rows & 1) || (io.cols & 1)) return hipErrorInvalidValue;
         if (scan) {
             ext = MxExtArgs{scan->sitemap, scan->mframe, scan->lat_rows, scan->lat_cols, scan->mpitch, scan->min_contrast, scan->colmap, scan->cframe, scan->nseams};
-            hipLaunchKernelGGL((k_pyr_octave_mx<MxCfgOct0, true, true>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, base, bframe, oct_out, pframe, rows, cols, pitch,
-                               static_cast<const MxTaps<MxCfgOct0>*>(d_table), next_base, nframe, nrows, ncols, npitch, ext, up2_step);
+            hipLaunchKernelGGL((k_pyr_octave_mx<MxCfgOct0, true, true>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, io.base, io.bframe, io.oct, io.pframe, io.rows, io.cols,
+                               io.pitch, static_cast<const MxTaps<MxCfgOct0>*>(d_table), io.next_base, io.nframe, io.nrows, io.ncols, io.npitch, ext, up2_step);
         } else {
-            hipLaunchKernelGGL((k_pyr_octave_mx<MxCfgOct0, false, true>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, base, bframe, oct_out, pframe, rows, cols, pitch,
-                               static_cast<const MxTaps<MxCfgOct0>*>(d_table), next_base, nframe, nrows, ncols, npitch, ext, up2_step);
+            hipLaunchKernelGGL((k_pyr_octave_mx<MxCfgOct0, false, true>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, io.base, io.bframe, io.oct, io.pframe, io.rows, io.cols,
+                               io.pitch, static_cast<const MxTaps<MxCfgOct0>*>(d_table), io.next_base, io.nframe, io.nrows, io.ncols, io.npitch, ext, up2_step);
         }
         return hipGetLastError();
       }
     }
     if (scan && CFG::DBUF) {
         ext = MxExtArgs{scan->sitemap, scan->mframe, scan->lat_rows, scan->lat_cols, scan->mpitch, scan->min_contrast, scan->colmap, scan->cframe, scan->nseams};
-        hipLaunchKernelGGL((k_pyr_octave_mx<CFG, CFG::DBUF != 0, false>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, base, bframe, oct_out, pframe, rows, cols, pitch,
-                           static_cast<const MxTaps<CFG>*>(d_table), next_base, nframe, nrows, ncols, npitch, ext, 0);
+        hipLaunchKernelGGL((k_pyr_octave_mx<CFG, CFG::DBUF != 0, false>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, io.base, io.bframe, io.oct, io.pframe, io.rows, io.cols,
+                           io.pitch, static_cast<const MxTaps<CFG>*>(d_table), io.next_base, io.nframe, io.nrows, io.ncols, io.npitch, ext, 0);
     } else {
         if (scan) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_pyr_octave_mx<CFG, false, false>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, base, bframe, oct_out, pframe, rows, cols, pitch,
-                           static_cast<const MxTaps<CFG>*>(d_table), next_base, nframe, nrows, ncols, npitch, ext, 0);
+        hipLaunchKernelGGL((k_pyr_octave_mx<CFG, false, false>), grid, dim3(CFG::NT), CFG::LDS_BYTES, stream, io.base, io.bframe, io.oct, io.pframe, io.rows, io.cols,
+                           io.pitch, static_cast<const MxTaps<CFG>*>(d_table), io.next_base, io.nframe, io.nrows, io.ncols, io.npitch, ext, 0);
     }
     return hipGetLastError();
 }
 
 #ifdef VSLAM_MX_OCT0_TU
-hipError_t mx_launch_oct0(hipStream_t stream, const void* d_table, const uint8_t* base, size_t bframe, uint8_t* oct_out, size_t pframe, int rows,
-                          int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch, const MxScan* scan, int up2_step) {
-    return launch<MxCfgOct0>(stream, d_table, base, bframe, oct_out, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch, scan, up2_step);
+hipError_t mx_launch_oct0(hipStream_t stream, const void* d_table, const OctIO& io, const MxScan* scan, int up2_step) {
+    return launch<MxCfgOct0>(stream, d_table, io, scan, up2_step);
 }
 #else
 hipError_t mx_launch_pack(hipStream_t stream, const MxScan& scan, int rows, int wpr, int nf, unsigned long long* bits, unsigned long long* lflags,
@@ -123,12 +120,11 @@ hipError_t mx_launch_pack(hipStream_t stream, const MxScan& scan, int rows, int 
     return hipGetLastError();
 }
 
-hipError_t mx_launch(int cfg, hipStream_t stream, const void* d_table, const uint8_t* base, size_t bframe, uint8_t* oct_out, size_t pframe,
-                     int rows, int cols, int pitch, int nf, uint8_t* next_base, size_t nframe, int nrows, int ncols, int npitch, const MxScan* scan, int up2_step) {
-    if (cfg == 1) return mx_launch_oct0(stream, d_table, base, bframe, oct_out, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch, scan, up2_step);
-    if (cfg == 2) return launch<MxCfgOct1>(stream, d_table, base, bframe, oct_out, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch, scan, up2_step);
-    if (cfg == 3) return launch<MxCfgOct2>(stream, d_table, base, bframe, oct_out, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch, scan, up2_step);
-    if (cfg == 4) return launch<MxCfgOct3>(stream, d_table, base, bframe, oct_out, pframe, rows, cols, pitch, nf, next_base, nframe, nrows, ncols, npitch, scan, up2_step);
+hipError_t mx_launch(int cfg, hipStream_t stream, const void* d_table, const OctIO& io, const MxScan* scan, int up2_step) {
+    if (cfg == 1) return mx_launch_oct0(stream, d_table, io, scan, up2_step);
+    if (cfg == 2) return launch<MxCfgOct1>(stream, d_table, io, scan, up2_step);
+    if (cfg == 3) return launch<MxCfgOct2>(stream, d_table, io, scan, up2_step);
+    if (cfg == 4) return launch<MxCfgOct3>(stream, d_table, io, scan, up2_step);
     return hipErrorInvalidValue;
 }
 #endif  // VSLAM_MX_OCT0_TU
