@@ -20,11 +20,6 @@ namespace vslam {
 //   dst(2m+1) = (((3 A(m)) >> 2) + (A(m+1) >> 2) + 2) >> 2
 // which is bit-identical to the literal formula (k_resize_linear2x in kernels_generic.hip.h;
 // clamped reads at the borders reproduce OpenCV's border rule because the weights sum to 2048).  Any width and source step; dpitch >= 2*cols rounded up to 8.  grid = (ceil(ceil(cols/4)/256), ceil(rows/seg), frames).
-typedef unsigned short us2r_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_lshr_u16(uint32_t a, int sh) {
-    return __builtin_bit_cast(uint32_t, (us2r_t)(__builtin_bit_cast(us2r_t, a) >> (unsigned short)sh));
-}
-
 __global__ __launch_bounds__(256) void k_resize_linear2x_slide(const uint8_t* __restrict__ src, size_t sstep, size_t sframe,
                                                                 uint8_t* __restrict__ dst, size_t dframe, int dpitch,
                                                                 int rows, int cols, int seg) {
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256) void k_resize_nearest_half_v4(const uint8_t* _
     const int sy = min(2 * y, rows - 1);
     const uint2 w = *reinterpret_cast<const uint2*>(src + blockIdx.z * sframe + (size_t)sy * spitch + 8 * k);
     *reinterpret_cast<uint32_t*>(dst + blockIdx.z * dframe + (size_t)y * dpitch + 4 * k) =
-        __builtin_amdgcn_perm(w.y, w.x, 0x06040200);
+        even_bytes(w.x, w.y);
 }
 
 // ---- K-D3: initialKeypointDetection for windowSize 3 (Diff_of_Gauss.cpp:254-297) -----------
@@ -102,14 +97,6 @@ __global__ __launch_bounds__(256) void k_resize_nearest_half_v4(const uint8_t* _
 // with a per-site selector, landing as (a, b) in 16-bit lanes for packed min/max.  A wave's 64
 // candidate flags leave as one ballot word = the bitmask layout of include/vslam.h.
 // Row pitch a multiple of 16 (any width).  grid = (ceil(words_per_row/4), lattice rows to scan, frames).
-typedef unsigned short us2e_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(us2e_t, a), __builtin_bit_cast(us2e_t, b)));
-}
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2e_t, a), __builtin_bit_cast(us2e_t, b)));
-}
-
 constexpr int EXT_SPAN = 768;            // image columns per workgroup (256 sites x stride 3)
 constexpr int EXT_PITCH = EXT_SPAN + 16; // 16 guard bytes in front: column -1 of the span
 
@@ -305,9 +292,8 @@ __global__ __launch_bounds__(256) void k_level_gradients(const uint8_t* __restri
     const int c = blockIdx.x * 256 + threadIdx.x;
     const int r = blockIdx.y;
     if (c >= cols) return;
-    const uint8_t* row = g + (size_t)r * gpitch;
-    const float x = (float)((int)row[reflect101(c + 1, cols)] - (int)row[reflect101(c - 1, cols)]);
-    const float y = (float)((int)g[(size_t)reflect101(r + 1, rows) * gpitch + c] - (int)g[(size_t)reflect101(r - 1, rows) * gpitch + c]);
+    float x, y;
+    gradient_at(g, gpitch, rows, cols, r, c, x, y);
     const size_t o = (size_t)r * cols + c;
     if (gx) gx[o] = x;
     if (gy) gy[o] = y;

@@ -6,21 +6,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "kernels_common.hip.h"
 #include "kernels_localize.hip.h"
 
 #include <cfloat>
 #include <cstdint>
 
 namespace vslam {
-
-// cv::borderInterpolate(p, len, BORDER_REFLECT_101), repeated until inside.
-__device__ __forceinline__ int reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Correctly rounded f32 square root (cv::magnitude on x86 is sqrtss / sqrtps) for the arguments this
 // library has: x*x + y*y of integer Sobel differences, i.e. integers in [0, 2 * 255^2] - normal numbers

@@ -59,17 +59,12 @@ struct HarrisStripArgs {
     uint8_t* dump;  // 64 writable bytes nobody reads (may be null): where the four margin lanes of a strip "store" in the steady rows
 };
 
-typedef unsigned short hs_us2_t __attribute__((ext_vector_type(2)));
-
 // lane-1 / lane+1 value, 0 where the wave has no such lane (bound_ctrl): one v_mov_b32_dpp, and the
 // DPP-combine pass folds it into a VOP2 consumer (v_add_u32_dpp, v_max_f32_dpp)
 __device__ __forceinline__ uint32_t dpp_left(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x138, 0xf, 0xf, true); }
 __device__ __forceinline__ uint32_t dpp_right(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x130, 0xf, 0xf, true); }
 __device__ __forceinline__ float dpp_left_f(float v) { return __uint_as_float(dpp_left(__float_as_uint(v))); }
 __device__ __forceinline__ float dpp_right_f(float v) { return __uint_as_float(dpp_right(__float_as_uint(v))); }
-__device__ __forceinline__ uint32_t pk_lshr4_u16(uint32_t a) {
-    return __builtin_bit_cast(uint32_t, (hs_us2_t)(__builtin_bit_cast(hs_us2_t, a) >> (hs_us2_t)4));
-}
 __device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
 __device__ __forceinline__ uint32_t umax3(uint32_t a, uint32_t b, uint32_t c) { return max(max(a, b), c); }
@@ -156,7 +151,7 @@ __device__ __forceinline__ void harris_strip_rows(const HarrisStripArgs& a, cons
         const uint32_t lvo = dpp_left(vo), rve = dpp_right(ve);
         const uint32_t he = __builtin_amdgcn_alignbit(vo, lvo, 16) + vo + (ve << 1) + 0x00080008u;  // (V-1,V1)+(V1,V3)+2(V0,V2)+8
         const uint32_t ho = __builtin_amdgcn_alignbit(rve, ve, 16) + ve + (vo << 1) + 0x00080008u;  // (V2,V4)+(V0,V2)+2(V1,V3)+8
-        const uint32_t be0 = pk_lshr4_u16(he), bo0 = pk_lshr4_u16(ho);                             // blurred row t-1 (<= 255 per lane)
+        const uint32_t be0 = pk_lshr_u16(he, 4), bo0 = pk_lshr_u16(ho, 4);                           // blurred row t-1 (<= 255 per lane)
         e1 = e2, o1 = o2, e2 = e3, o2 = o3;
 
         // ---- gradients + products of row g = t-2 ---------------------------------------------------

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void k_gauss_h_diff(const uint16_t* __restrict
                     if constexpr (L == 3 && rho == 0)
                         if (next_base && (y >> 1) < nrows && (x >> 1) < ncols)
                             *reinterpret_cast<uint2*>(next_base + blockIdx.z * nframe + (size_t)(y >> 1) * npitch + (x >> 1)) =
-                                make_uint2(__builtin_amdgcn_perm(g[1], g[0], 0x06040200), __builtin_amdgcn_perm(g[3], g[2], 0x06040200));
+                                make_uint2(even_bytes(g[0], g[1]), even_bytes(g[2], g[3]));
                 }
             });
         }

@@ -40,8 +40,8 @@ __device__ __forceinline__ float edge_response_u8(const uint8_t* __restrict__ G,
         const int r = clampi(u, 0, rows - 1);
         for (int v = x - pad; v < x + pad; ++v) {
             const int c = clampi(v, 0, cols - 1);
-            const float gx = (float)((int)G[(size_t)r * gpitch + reflect101(c + 1, cols)] - (int)G[(size_t)r * gpitch + reflect101(c - 1, cols)]);
-            const float gy = (float)((int)G[(size_t)reflect101(r + 1, rows) * gpitch + c] - (int)G[(size_t)reflect101(r - 1, rows) * gpitch + c]);
+            float gx, gy;
+            gradient_at(G, gpitch, rows, cols, r, c, gx, gy);
             Ix2 += gx * gx;
             Iy2 += gy * gy;
             IxIy += gx * gy;

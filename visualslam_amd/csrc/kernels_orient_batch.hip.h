@@ -67,12 +67,7 @@ __global__ __launch_bounds__(256) void k_edge_flags(const vslam_point* __restric
     }
 }
 
-// cv::magnitude / cv::phase of the level's Sobel gradients at one pixel (processGradients,
-// GaussPyramid.cpp:65-104), formed from the u8 Gaussian level like k_level_gradients does.
-__device__ __forceinline__ void gradient_at(const uint8_t* __restrict__ G, int gpitch, int rows, int cols, int r, int c, float& x, float& y) {
-    x = (float)((int)G[(size_t)r * gpitch + reflect101(c + 1, cols)] - (int)G[(size_t)r * gpitch + reflect101(c - 1, cols)]);
-    y = (float)((int)G[(size_t)reflect101(r + 1, rows) * gpitch + c] - (int)G[(size_t)reflect101(r - 1, rows) * gpitch + c]);
-}
+// cv::magnitude of the level's Sobel gradients at one pixel (processGradients, GaussPyramid.cpp:65-104)
 __device__ __forceinline__ float magnitude_at(const uint8_t* __restrict__ G, int gpitch, int rows, int cols, int r, int c) {
     float x, y;
     gradient_at(G, gpitch, rows, cols, r, c, x, y);

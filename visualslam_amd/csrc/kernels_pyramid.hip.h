@@ -33,19 +33,6 @@
 
 namespace vslam {
 
-typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t udot4(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_udot4(a, b, c, false);
-}
-__device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b), c, false);
-}
-// packed u16 saturating subtract (v_pk_sub_u16 clamp)
-__device__ __forceinline__ uint32_t pk_sub_sat_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b)));
-}
-
 template <int TW_, int TH_, int N0, int N1, int N2, int N3, int N4, int N5>
 struct PyrCfg {
     static constexpr int TW = TW_, TH = TH_;
@@ -191,17 +178,9 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
         const int y = tile_y0 + 4 * rg + jr;
         uint32_t g[2], d[2];
 #pragma unroll
-        for (int hw = 0; hw < 2; ++hw) {
-            // G = acc >> 16 is byte 2 of each accumulator.  Pick the even / odd pixels straight
-            // into 16-bit lanes (the shape the saturating subtract wants), then interleave.
-            const uint32_t e = __builtin_amdgcn_perm(acc[jr][4 * hw + 2], acc[jr][4 * hw + 0], 0x0c060c02);  // (G0, G2)
-            const uint32_t o = __builtin_amdgcn_perm(acc[jr][4 * hw + 3], acc[jr][4 * hw + 1], 0x0c060c02);  // (G1, G3)
-            g[hw] = __builtin_amdgcn_perm(o, e, 0x06020400);  // bytes (e0, o0, e1, o1): interleave in one v_perm
-            if (L > 0)  // D_{L-1} = saturate_u8(G_L - G_{L-1}), GaussPyramid.cpp:197
-                d[hw] = __builtin_amdgcn_perm(pk_sub_sat_u16(o, prev_o[jr][hw]), pk_sub_sat_u16(e, prev_e[jr][hw]), 0x06020400);
-            prev_e[jr][hw] = e;
-            prev_o[jr][hw] = o;
-        }
+        for (int hw = 0; hw < 2; ++hw)
+            level_pack4(acc[jr][4 * hw], acc[jr][4 * hw + 1], acc[jr][4 * hw + 2], acc[jr][4 * hw + 3], L, g[hw], d[hw], prev_e[jr][hw],
+                        prev_o[jr][hw]);
         if (y < rows && x < cols) {
             // 32-bit offset inside a wave-uniform plane pointer (a frame's octave block is far below
             // 4 GB): scalar base + VGPR offset addressing, no 64-bit address arithmetic per store.
@@ -216,8 +195,7 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
             // next octave's base = Gaussian[3] decimated 2:1, INTER_NEAREST (GaussPyramid.cpp:123-126):
             // pixel (2y', 2x'); tile origins and (jr, x) are even, so it is the even bytes of even rows
             if (L == 3 && next_base && (jr & 1) == 0 && (y >> 1) < nrows && (x >> 1) < ncols)
-                *reinterpret_cast<uint32_t*>(next_base + ((uint32_t)(y >> 1) * (uint32_t)npitch + (uint32_t)(x >> 1))) =
-                    __builtin_amdgcn_perm(g[1], g[0], 0x06040200);
+                *reinterpret_cast<uint32_t*>(next_base + ((uint32_t)(y >> 1) * (uint32_t)npitch + (uint32_t)(x >> 1))) = even_bytes(g[0], g[1]);
         }
     }
 }
@@ -237,10 +215,7 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
     uint32_t* hp = smem + CFG::RQ * CFG::RWP;
     constexpr int R = CFG::R, RW = CFG::RW, RWP = CFG::RWP, RQ = CFG::RQ;
     const int tid = threadIdx.x;
-    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an
-    // L2), so the linear id is remapped to give every XCD one contiguous run of tiles - row-major
-    // neighbours, which share their halo rows and columns, then meet in the same 4 MB L2 instead
-    // of each fetching the halo from HBM.  Placement is a speed matter only.
+    // (the tile order of xcd_tile_id, written out: through the helper this kernel's 256 x 32 octave-1 instance is scheduled differently)
     unsigned int bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     const unsigned int per_xcd = (gridDim.x * gridDim.y * gridDim.z) >> 3;
     if (bid < (per_xcd << 3)) bid = (bid & 7u) * per_xcd + (bid >> 3);
@@ -253,6 +228,8 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
     const size_t P = (size_t)rows * pitch;
 
     // ---- stage the base tile, byte-transposed ------------------------------------------------
+    // (stage_tile_transposed with bias 0 and two items in flight, written out with this kernel's per-byte tiny-image loader:
+    // called through it every instance of this kernel comes out longer - profiles/kernel_common_isa_identity.txt)
     const bool interior = tile_x0 - R >= 0 && tile_x0 + CFG::TW + R <= cols && tile_y0 - R >= 0 &&
                           tile_y0 + CFG::TH + R <= rows;
     if (interior) {
@@ -266,24 +243,12 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
             for (int k = 0; k < 4; ++k) a[k] = *reinterpret_cast<const uint4*>(p + (size_t)k * pitch);
             const uint32_t* aw[4] = {&a[0].x, &a[1].x, &a[2].x, &a[3].x};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {  // dword q of each row = pixels 4q..4q+3
-                const uint32_t r0 = aw[0][q], r1 = aw[1][q], r2 = aw[2][q], r3 = aw[3][q];
-                const uint32_t p01l = __builtin_amdgcn_perm(r1, r0, 0x05010400), p01h = __builtin_amdgcn_perm(r1, r0, 0x07030602);
-                const uint32_t p23l = __builtin_amdgcn_perm(r3, r2, 0x05010400), p23h = __builtin_amdgcn_perm(r3, r2, 0x07030602);
-                uint4 t;
-                t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100);
-                t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302);
-                t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100);
-                t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302);
-                *reinterpret_cast<uint4*>(rp + yq * RWP + 16 * xs + 4 * q) = t;
-            }
+            for (int q = 0; q < 4; ++q)  // dword q of each row = pixels 4q..4q+3
+                *reinterpret_cast<uint4*>(rp + yq * RWP + 16 * xs + 4 * q) = transpose4x4_u8(aw[0][q], aw[1][q], aw[2][q], aw[3][q]);
         }
     } else if (cols >= 4 && R < cols && tile_x0 + CFG::TW + R - 1 <= 2 * (cols - 1) && R < rows && tile_y0 + CFG::TH + R - 1 <= 2 * (rows - 1)) {
-        // Border tiles whose halo reaches at most ONE reflection on either side (16 % of the tiles of a 3840 x 2160 octave,
-        // 24 % of a 1920 x 1080 one).  Round 5, from the matrix path's staging: four pixels at columns x .. x+3 under
-        // BORDER_REFLECT_101 always lie within four consecutive bytes of the row (a forward run, a mirrored run, or a run folded
-        // around column 0 / cols-1), so every case is ONE unaligned dword load at `base` and one v_perm whose selector holds
-        // the four byte positions relative to base - no divergent paths, four loads per item instead of sixteen byte loads.
+        // border tiles whose halo reaches at most ONE reflection on either side: one dword load and one v_perm per row
+        // (the border branch of stage_tile_transposed, kernels_common.hip.h, which says why), two items in flight
         auto f1 = [](int x, int n) { return x < 0 ? -x : (x >= n ? 2 * (n - 1) - x : x); };
 #pragma unroll 2
         for (int it = tid; it < RQ * (RW / 4); it += CFG::NT) {
@@ -299,14 +264,7 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
                 __builtin_memcpy(&v, src + (size_t)f1(gy + k, rows) * pitch + b0, 4);
                 a[k] = __builtin_amdgcn_perm(0u, v, sel);
             }
-            const uint32_t p01l = __builtin_amdgcn_perm(a[1], a[0], 0x05010400), p01h = __builtin_amdgcn_perm(a[1], a[0], 0x07030602);
-            const uint32_t p23l = __builtin_amdgcn_perm(a[3], a[2], 0x05010400), p23h = __builtin_amdgcn_perm(a[3], a[2], 0x07030602);
-            uint4 t;
-            t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100);
-            t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302);
-            t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100);
-            t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302);
-            *reinterpret_cast<uint4*>(rp + yq * RWP + 4 * xq) = t;
+            *reinterpret_cast<uint4*>(rp + yq * RWP + 4 * xq) = transpose4x4_u8(a[0], a[1], a[2], a[3]);
         }
     } else {
         // tiny images (a halo wider than the image: repeated reflection): one dword x 4 rows per item, BORDER_REFLECT_101 resolved per byte
@@ -320,14 +278,7 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
                 a[k] = (uint32_t)row[reflect101(gx, cols)] | ((uint32_t)row[reflect101(gx + 1, cols)] << 8) |
                        ((uint32_t)row[reflect101(gx + 2, cols)] << 16) | ((uint32_t)row[reflect101(gx + 3, cols)] << 24);
             }
-            const uint32_t p01l = __builtin_amdgcn_perm(a[1], a[0], 0x05010400), p01h = __builtin_amdgcn_perm(a[1], a[0], 0x07030602);
-            const uint32_t p23l = __builtin_amdgcn_perm(a[3], a[2], 0x05010400), p23h = __builtin_amdgcn_perm(a[3], a[2], 0x07030602);
-            uint4 t;
-            t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100);
-            t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302);
-            t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100);
-            t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302);
-            *reinterpret_cast<uint4*>(rp + yq * RWP + 4 * xq) = t;
+            *reinterpret_cast<uint4*>(rp + yq * RWP + 4 * xq) = transpose4x4_u8(a[0], a[1], a[2], a[3]);
         }
     }
     // the 4 pad dwords per row quad feed only h columns that pass 2 never reads (integers:
@@ -353,24 +304,28 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
     pyr_level<CFG, 5>(taps, rp, hp, out, P, cols, pitch, rows, tile_x0, tile_y0, prev_e, prev_o, nb, nrows, ncols, npitch, row_off);
 }
 
-// Host side: pack quantised taps into the operand shapes described at the top.
+// Host side: pack quantised taps into the operand shapes described at the top (zero outside the n taps).
+// dword m of window alignment o: byte b = taps[4m + b - o], the operand of a vertical dot4
+static inline uint32_t pack_taps_u8x4(const uint16_t* t, int n, int m, int o) {
+    uint32_t w = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int k = 4 * m + b - o;
+        if (k >= 0 && k < n) w |= (uint32_t)(t[k] & 0xff) << (8 * b);
+    }
+    return w;
+}
+// taps (e-1, e) as a u16 pair, the operand of a horizontal dot2
+static inline uint32_t pack_taps_u16x2(const uint16_t* t, int n, int e) {
+    const uint32_t lo = (e >= 1 && e - 1 < n) ? t[e - 1] : 0, hi = (e >= 0 && e < n) ? t[e] : 0;
+    return lo | (hi << 16);
+}
+
 template <class CFG>
 static void pyr_pack_taps(const uint16_t* const t[6], PyrTaps<CFG>& out) {
     for (int l = 0; l < 6; ++l) {
-        const int n = CFG::n(l);
         for (int o = 0; o < 4; ++o)
-            for (int m = 0; m < CFG::T4M; ++m) {
-                uint32_t w = 0;
-                for (int b = 0; b < 4; ++b) {
-                    const int k = 4 * m + b - o;
-                    if (k >= 0 && k < n) w |= (uint32_t)(t[l][k] & 0xff) << (8 * b);
-                }
-                out.t4[l][o][m] = w;
-            }
-        for (int e = 0; e < CFG::TPM; ++e) {
-            const uint32_t lo = (e - 1 >= 0 && e - 1 < n) ? t[l][e - 1] : 0, hi = e < n ? t[l][e] : 0;
-            out.tp[l][e] = lo | (hi << 16);
-        }
+            for (int m = 0; m < CFG::T4M; ++m) out.t4[l][o][m] = pack_taps_u8x4(t[l], CFG::n(l), m, o);
+        for (int e = 0; e < CFG::TPM; ++e) out.tp[l][e] = pack_taps_u16x2(t[l], CFG::n(l), e);
     }
 }
 

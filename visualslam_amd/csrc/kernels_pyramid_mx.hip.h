@@ -24,7 +24,7 @@
 //                        output column 16 h + v: each lane ends up with 16 CONSECUTIVE bytes of its image
 //                        row, no lane exchange.  One product per byte plane;
 //                        G = ((C2hi << 8) + C2lo) >> 16, the biases and the rounding constant in C2lo's start value.
-//   epilogue             as k_pyr_octave: byte 2 of each sum into 16-bit lanes, v_pk_sub_u16 clamp against the
+//   epilogue             level_pack4: byte 2 of each sum into 16-bit lanes, v_pk_sub_u16 clamp against the
 //                        previous level (kept in registers), 16-byte stores of G and D.
 //
 // A wave owns a strip of 32 rows x SW columns of the tile and walks along it: input block ib goes through
@@ -37,19 +37,9 @@
 #include <cstring>
 
 #include "../../include/vslam.h"
+#include "kernels_common.hip.h"
 
 namespace vslam {
-
-// (self-contained: this header is compiled in its own translation unit, the kernels of the other headers are not)
-__device__ __forceinline__ int mx_reflect101(int p, int len) {  // cv::borderInterpolate(p, len, BORDER_REFLECT_101), repeated until inside
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * (len - 1) - p;
-    return p;
-}
-typedef unsigned short mx_us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t mx_pk_sub_sat_u16(uint32_t a, uint32_t b) {  // v_pk_sub_u16 clamp
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(mx_us2, a), __builtin_bit_cast(mx_us2, b)));
-}
 
 constexpr int MX_SITE_PAIRS_32 = 6;  // 11 lattice rows per 32-row strip, two per register
 typedef int mx_v4i __attribute__((ext_vector_type(4)));
@@ -97,107 +87,6 @@ struct MxTaps {
     mx_v4i a2[6][CFG::NSMAX][64];
 };
 
-// Stages the TW x TH tile with halo R, byte-transposed (a dword = 4 vertically adjacent pixels of one column),
-// BORDER_REFLECT_101 resolved at fill time, every byte ^ bias (0x80: pixels - 128 as signed bytes).
-// Four pixels of one image row at columns x .. x+3 under BORDER_REFLECT_101: one dword load where the four lie inside the
-// row, one dword load of the mirrored run with its bytes reversed where they lie wholly in the first reflection on either
-// side, byte by byte (repeated reflection) only where they straddle an edge or the row is shorter than the halo.
-__device__ __forceinline__ uint32_t mx_load4_reflect(const uint8_t* __restrict__ row, int x, int cols) {
-    if (x >= 0 && x + 3 < cols) return *reinterpret_cast<const uint32_t*>(row + x);
-    if (x + 3 < 0 && -x < cols) {  // columns x..x+3 mirror to -x, -x-1, -x-2, -x-3 (all >= 1)
-        uint32_t v;
-        __builtin_memcpy(&v, row + (-x - 3), 4);
-        return __builtin_amdgcn_perm(0u, v, 0x00010203);
-    }
-    if (x >= cols && 2 * (cols - 1) - x - 3 >= 0) {  // mirror to 2(cols-1)-x, ... - 3 (all <= cols - 2)
-        uint32_t v;
-        __builtin_memcpy(&v, row + (2 * (cols - 1) - x - 3), 4);
-        return __builtin_amdgcn_perm(0u, v, 0x00010203);
-    }
-    return (uint32_t)row[mx_reflect101(x, cols)] | ((uint32_t)row[mx_reflect101(x + 1, cols)] << 8) | ((uint32_t)row[mx_reflect101(x + 2, cols)] << 16) |
-           ((uint32_t)row[mx_reflect101(x + 3, cols)] << 24);
-}
-
-template <int TW, int TH, int R, int RWP, int NT>
-__device__ __forceinline__ void mx_stage_tile(const uint8_t* __restrict__ src, int rows, int cols, int pitch, int tile_x0, int tile_y0,
-                                              uint32_t* __restrict__ rp, uint32_t bias) {
-    constexpr int RW = TW + 2 * R, RQ = (TH + 2 * R) / 4;
-    const int tid = threadIdx.x;
-    const bool interior = tile_x0 - R >= 0 && tile_x0 + TW + R <= cols && tile_y0 - R >= 0 && tile_y0 + TH + R <= rows;
-    if (interior) {
-        for (int it = tid; it < RQ * (RW / 16); it += NT) {
-            const int yq = it / (RW / 16), xs = it - yq * (RW / 16);
-            const uint8_t* p = src + (size_t)(tile_y0 - R + 4 * yq) * pitch + (tile_x0 - R + 16 * xs);
-            uint4 a[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = *reinterpret_cast<const uint4*>(p + (size_t)k * pitch);
-            const uint32_t* aw[4] = {&a[0].x, &a[1].x, &a[2].x, &a[3].x};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t r0 = aw[0][q], r1 = aw[1][q], r2 = aw[2][q], r3 = aw[3][q];
-                const uint32_t p01l = __builtin_amdgcn_perm(r1, r0, 0x05010400), p01h = __builtin_amdgcn_perm(r1, r0, 0x07030602);
-                const uint32_t p23l = __builtin_amdgcn_perm(r3, r2, 0x05010400), p23h = __builtin_amdgcn_perm(r3, r2, 0x07030602);
-                uint4 t;
-                t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100) ^ bias;
-                t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302) ^ bias;
-                t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100) ^ bias;
-                t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302) ^ bias;
-                *reinterpret_cast<uint4*>(rp + yq * RWP + 16 * xs + 4 * q) = t;
-            }
-        }
-    } else if (cols >= 4 && R < cols && tile_x0 + TW + R - 1 <= 2 * (cols - 1) && R < rows && tile_y0 + TH + R - 1 <= 2 * (rows - 1)) {
-        // Border tiles whose halo reaches at most ONE reflection on either side (every tile of the coarse octaves at camera
-        // sizes: 30 of 40 tiles of a 960 x 540 octave, all of a 480 x 270 one).  Round 5: branch-free.  Four pixels at columns
-        // x .. x+3 under BORDER_REFLECT_101 always lie within four consecutive bytes of the row - a forward run, a mirrored
-        // run, or a run folded around column 0 / cols-1 - so every case is ONE unaligned dword load at `base` and one v_perm
-        // whose selector holds the four byte positions relative to base.  No divergent paths: the four row loads of an item
-        // issue back to back and four items are in flight per thread (the loop is unrolled by four).  These kernels run with
-        // one workgroup per CU beside the HBM-bound Harris chain and are bound by the latency of exactly these loads.
-        auto f1 = [](int x, int n) { return x < 0 ? -x : (x >= n ? 2 * (n - 1) - x : x); };
-#pragma unroll 4
-        for (int it = tid; it < RQ * (RW / 4); it += NT) {
-            const int yq = it / (RW / 4), xq = it - yq * (RW / 4);
-            const int gy = tile_y0 - R + 4 * yq, gx = tile_x0 - R + 4 * xq;
-            const int p0 = f1(gx, cols), p1 = f1(gx + 1, cols), p2 = f1(gx + 2, cols), p3 = f1(gx + 3, cols);
-            const int base = min(min(min(p0, p1), min(p2, p3)), cols - 4);
-            const uint32_t sel = (uint32_t)(p0 - base) | ((uint32_t)(p1 - base) << 8) | ((uint32_t)(p2 - base) << 16) | ((uint32_t)(p3 - base) << 24);
-            uint32_t a[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t v;
-                __builtin_memcpy(&v, src + (size_t)f1(gy + k, rows) * pitch + base, 4);
-                a[k] = __builtin_amdgcn_perm(0u, v, sel);
-            }
-            const uint32_t p01l = __builtin_amdgcn_perm(a[1], a[0], 0x05010400), p01h = __builtin_amdgcn_perm(a[1], a[0], 0x07030602);
-            const uint32_t p23l = __builtin_amdgcn_perm(a[3], a[2], 0x05010400), p23h = __builtin_amdgcn_perm(a[3], a[2], 0x07030602);
-            uint4 t;
-            t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100) ^ bias;
-            t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302) ^ bias;
-            t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100) ^ bias;
-            t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302) ^ bias;
-            *reinterpret_cast<uint4*>(rp + yq * RWP + 4 * xq) = t;
-        }
-    } else {
-        // tiny images (a halo wider than the image: repeated reflection): one dword column (4 pixels) x 4 rows per item, rows
-        // reflected per row, columns per dword (mx_load4_reflect)
-        for (int it = tid; it < RQ * (RW / 4); it += NT) {
-            const int yq = it / (RW / 4), xq = it - yq * (RW / 4);
-            const int gy = tile_y0 - R + 4 * yq, gx = tile_x0 - R + 4 * xq;
-            uint32_t a[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) a[k] = mx_load4_reflect(src + (size_t)mx_reflect101(gy + k, rows) * pitch, gx, cols);
-            const uint32_t p01l = __builtin_amdgcn_perm(a[1], a[0], 0x05010400), p01h = __builtin_amdgcn_perm(a[1], a[0], 0x07030602);
-            const uint32_t p23l = __builtin_amdgcn_perm(a[3], a[2], 0x05010400), p23h = __builtin_amdgcn_perm(a[3], a[2], 0x07030602);
-            uint4 t;
-            t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100) ^ bias;
-            t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302) ^ bias;
-            t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100) ^ bias;
-            t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302) ^ bias;
-            *reinterpret_cast<uint4*>(rp + yq * RWP + 4 * xq) = t;
-        }
-    }
-}
-
 // ---- octave 0's base formed while the tile is staged: createPyramid's 2x bilinear upsample (GaussPyramid.cpp:110) -----------
 // cv::resize(img, Size(), 2, 2, INTER_LINEAR) on CV_8U, bit for bit as k_resize_linear2x_slide (kernels_aux.hip.h): with
 // A = s_i + 3 s_{i+1} (or 3 s_i + s_{i+1}) per source row, X = A >> 2, Y = 3A >> 2, the destination rows are
@@ -205,10 +94,6 @@ __device__ __forceinline__ void mx_stage_tile(const uint8_t* __restrict__ src, i
 // and clamped source reads reproduce OpenCV's border rule.  The default path writes that base to HBM (8.3 MB per 1080p
 // frame) and the octave kernel reads it back with its halo (13 MB); here the tile's base pixels are computed from the
 // SOURCE frame into the same byte-transposed LDS image, and the base never exists in HBM.
-typedef unsigned short mx_us2c __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t mx_pk_lshr2_u16(uint32_t a) {
-    return __builtin_bit_cast(uint32_t, (mx_us2c)(__builtin_bit_cast(mx_us2c, a) >> (unsigned short)2));
-}
 // A of source row m (clamped) for base columns 2 c0 .. 2 c0 + 7 as (j0,j2) (j1,j3) (j4,j6) (j5,j7) 16-bit pairs; c0..c0+3 inside the row
 __device__ __forceinline__ void mx_up_hrow(const uint8_t* __restrict__ s, int sstep, int rows_s, int cols_s, int m, int c0, uint32_t (&A)[4]) {
     const uint8_t* r = s + (size_t)min(max(m, 0), rows_s - 1) * sstep;
@@ -227,7 +112,7 @@ __device__ __forceinline__ void mx_up_hrow(const uint8_t* __restrict__ s, int ss
 __device__ __forceinline__ uint2 mx_up_emit(const uint32_t (&U)[4], const uint32_t (&V)[4]) {
     uint32_t v[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = mx_pk_lshr2_u16(U[i] + V[i] + 0x00020002u);
+    for (int i = 0; i < 4; ++i) v[i] = pk_lshr_u16(U[i] + V[i] + 0x00020002u, 2);
     return make_uint2(v[0] | (v[1] << 8), v[2] | (v[3] << 8));
 }
 // one base pixel, the literal formula (k_resize_linear2x): dy, dx inside the upsampled image
@@ -272,14 +157,8 @@ __device__ __forceinline__ void mx_stage_tile_up2(const uint8_t* __restrict__ s,
         auto put_quad = [&](int q, const uint2& a0, const uint2& a1, const uint2& a2, const uint2& a3) {
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
-                const uint32_t r0 = hh ? a0.y : a0.x, r1 = hh ? a1.y : a1.x, r2 = hh ? a2.y : a2.x, r3 = hh ? a3.y : a3.x;
-                const uint32_t p01l = __builtin_amdgcn_perm(r1, r0, 0x05010400), p01h = __builtin_amdgcn_perm(r1, r0, 0x07030602);
-                const uint32_t p23l = __builtin_amdgcn_perm(r3, r2, 0x05010400), p23h = __builtin_amdgcn_perm(r3, r2, 0x07030602);
-                uint4 t;
-                t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100) ^ bias;
-                t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302) ^ bias;
-                t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100) ^ bias;
-                t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302) ^ bias;
+                uint4 t = transpose4x4_u8(hh ? a0.y : a0.x, hh ? a1.y : a1.x, hh ? a2.y : a2.x, hh ? a3.y : a3.x);
+                t.x ^= bias, t.y ^= bias, t.z ^= bias, t.w ^= bias;
                 *reinterpret_cast<uint4*>(rp + (SQ * seg + q) * RWP + 8 * g + 4 * hh) = t;
             }
         };
@@ -291,7 +170,7 @@ __device__ __forceinline__ void mx_stage_tile_up2(const uint8_t* __restrict__ s,
                 mx_up_hrow(s, sstep, rows_s, cols_s, m0 - 1, c0, Ap);
                 mx_up_hrow(s, sstep, rows_s, cols_s, m0, c0, Ac);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) Xp[i] = mx_pk_lshr2_u16(Ap[i]), Xc[i] = mx_pk_lshr2_u16(Ac[i]), Yc[i] = mx_pk_lshr2_u16(Ac[i] + (Ac[i] << 1));
+                for (int i = 0; i < 4; ++i) Xp[i] = pk_lshr_u16(Ap[i], 2), Xc[i] = pk_lshr_u16(Ac[i], 2), Yc[i] = pk_lshr_u16(Ac[i] + (Ac[i] << 1), 2);
 #pragma unroll QU
                 for (int q = 0; q < SQ; ++q) {
                     uint2 row[4];
@@ -300,11 +179,11 @@ __device__ __forceinline__ void mx_stage_tile_up2(const uint8_t* __restrict__ s,
                         mx_up_hrow(s, sstep, rows_s, cols_s, m0 + 2 * q + j + 1, c0, An);
                         uint32_t Xn[4];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) Xn[i] = mx_pk_lshr2_u16(An[i]);
+                        for (int i = 0; i < 4; ++i) Xn[i] = pk_lshr_u16(An[i], 2);
                         row[2 * j] = mx_up_emit(Xp, Yc);      // rows (m-1, m), weights (512, 1536)
                         row[2 * j + 1] = mx_up_emit(Yc, Xn);  // rows (m, m+1), weights (1536, 512)
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) Xp[i] = Xc[i], Xc[i] = Xn[i], Yc[i] = mx_pk_lshr2_u16(An[i] + (An[i] << 1));
+                        for (int i = 0; i < 4; ++i) Xp[i] = Xc[i], Xc[i] = Xn[i], Yc[i] = pk_lshr_u16(An[i] + (An[i] << 1), 2);
                     }
                     put_quad(q, row[0], row[1], row[2], row[3]);
                 }
@@ -314,15 +193,15 @@ __device__ __forceinline__ void mx_stage_tile_up2(const uint8_t* __restrict__ s,
                     uint2 row[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const int yr = mx_reflect101(by + 4 * q + j, H2), m = yr >> 1;
+                        const int yr = reflect101(by + 4 * q + j, H2), m = yr >> 1;
                         uint32_t A0[4], A1[4], U[4], V[4];
                         // even row 2m: X(m-1) + Y(m); odd row 2m+1: Y(m) + X(m+1)
                         mx_up_hrow(s, sstep, rows_s, cols_s, (yr & 1) ? m : m - 1, c0, A0);
                         mx_up_hrow(s, sstep, rows_s, cols_s, (yr & 1) ? m + 1 : m, c0, A1);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const uint32_t x0 = mx_pk_lshr2_u16(A0[i]), y0 = mx_pk_lshr2_u16(A0[i] + (A0[i] << 1));
-                            const uint32_t x1 = mx_pk_lshr2_u16(A1[i]), y1 = mx_pk_lshr2_u16(A1[i] + (A1[i] << 1));
+                            const uint32_t x0 = pk_lshr_u16(A0[i], 2), y0 = pk_lshr_u16(A0[i] + (A0[i] << 1), 2);
+                            const uint32_t x1 = pk_lshr_u16(A1[i], 2), y1 = pk_lshr_u16(A1[i] + (A1[i] << 1), 2);
                             U[i] = (yr & 1) ? y0 : x0, V[i] = (yr & 1) ? x1 : y1;
                         }
                         row[j] = mx_up_emit(U, V);
@@ -335,10 +214,10 @@ __device__ __forceinline__ void mx_stage_tile_up2(const uint8_t* __restrict__ s,
             // there are; this branch runs for the few items that straddle an image edge - byte by byte into the transposed tile)
 #pragma unroll 1
             for (int rr = 0; rr < 4 * SQ; ++rr) {
-                const int yr = mx_reflect101(by + rr, H2);
+                const int yr = reflect101(by + rr, H2);
                 uint8_t* dst = reinterpret_cast<uint8_t*>(rp + (SQ * seg + (rr >> 2)) * RWP + 8 * g) + (rr & 3);
 #pragma unroll 1
-                for (int k = 0; k < 8; ++k) dst[4 * k] = (uint8_t)(mx_up_pixel(s, sstep, rows_s, cols_s, yr, mx_reflect101(bx + k, W2)) ^ (bias & 0xffu));
+                for (int k = 0; k < 8; ++k) dst[4 * k] = (uint8_t)(mx_up_pixel(s, sstep, rows_s, cols_s, yr, reflect101(bx + k, W2)) ^ (bias & 0xffu));
             }
         } else {
 #pragma unroll 1
@@ -346,12 +225,12 @@ __device__ __forceinline__ void mx_stage_tile_up2(const uint8_t* __restrict__ s,
                 uint2 row[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int yr = mx_reflect101(by + 4 * q + j, H2);
+                    const int yr = reflect101(by + 4 * q + j, H2);
                     uint32_t lo = 0, hi = 0;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        lo |= mx_up_pixel(s, sstep, rows_s, cols_s, yr, mx_reflect101(bx + k, W2)) << (8 * k);
-                        hi |= mx_up_pixel(s, sstep, rows_s, cols_s, yr, mx_reflect101(bx + 4 + k, W2)) << (8 * k);
+                        lo |= mx_up_pixel(s, sstep, rows_s, cols_s, yr, reflect101(bx + k, W2)) << (8 * k);
+                        hi |= mx_up_pixel(s, sstep, rows_s, cols_s, yr, reflect101(bx + 4 + k, W2)) << (8 * k);
                     }
                     row[j] = make_uint2(lo, hi);
                 }
@@ -394,17 +273,6 @@ struct MxExtArgs {
     int nseams;
 };
 
-typedef unsigned short mx_us2b __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t mx_pk_min_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(mx_us2b, a), __builtin_bit_cast(mx_us2b, b)));
-}
-__device__ __forceinline__ uint32_t mx_pk_max_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(mx_us2b, a), __builtin_bit_cast(mx_us2b, b)));
-}
-__device__ __forceinline__ uint32_t mx_pk_sub_u16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(mx_us2b, a) - __builtin_bit_cast(mx_us2b, b));
-}
-
 constexpr int MX_SITE_PAIRS = MX_SITE_PAIRS_32;
 
 template <int PAIRS>
@@ -441,21 +309,21 @@ __device__ __forceinline__ void mx_sites_level(MxSitesT<CFG::SITE_PAIRS>& st) {
             const uint32_t* qb = reinterpret_cast<const uint32_t*>(st.slr + (3 * k + 1) * RB);
             const uint32_t v0 = __builtin_amdgcn_perm(qa[1], qa[0], st.sel);  // (D(3a-1, 3b-1), D(3a-1, 3b)) in 16-bit lanes
             v1[j] = __builtin_amdgcn_perm(qb[1], qb[0], st.sel);             // (D(3a, 3b-1), D(3a, 3b))
-            lo[j] = mx_pk_min_u16(v0, v1[j]);
-            hi[j] = mx_pk_max_u16(v0, v1[j]);
+            lo[j] = pk_min_u16(v0, v1[j]);
+            hi[j] = pk_max_u16(v0, v1[j]);
         }
         // lattice rows 2p (low half) and 2p+1 (high half) side by side
-        const uint32_t mn = mx_pk_min_u16(__builtin_amdgcn_perm(lo[1], lo[0], 0x05040100), __builtin_amdgcn_perm(lo[1], lo[0], 0x07060302));
-        const uint32_t mx = mx_pk_max_u16(__builtin_amdgcn_perm(hi[1], hi[0], 0x05040100), __builtin_amdgcn_perm(hi[1], hi[0], 0x07060302));
+        const uint32_t mn = pk_min_u16(__builtin_amdgcn_perm(lo[1], lo[0], 0x05040100), __builtin_amdgcn_perm(lo[1], lo[0], 0x07060302));
+        const uint32_t mx = pk_max_u16(__builtin_amdgcn_perm(hi[1], hi[0], 0x05040100), __builtin_amdgcn_perm(hi[1], hi[0], 0x07060302));
         const uint32_t sf = __builtin_amdgcn_perm(v1[1], v1[0], 0x07060302);
         if constexpr (l >= 2) {
             constexpr int c = l - 1;
-            const uint32_t lo3 = mx_pk_min_u16(mx_pk_min_u16(st.mn[old][p], st.mn[mid][p]), mn);
-            const uint32_t hi3 = mx_pk_max_u16(mx_pk_max_u16(st.mx[old][p], st.mx[mid][p]), mx);
+            const uint32_t lo3 = pk_min_u16(pk_min_u16(st.mn[old][p], st.mn[mid][p]), mn);
+            const uint32_t hi3 = pk_max_u16(pk_max_u16(st.mx[old][p], st.mx[mid][p]), mx);
             const uint32_t self = st.sf[mid][p];
-            const uint32_t z = mx_pk_min_u16(self ^ lo3, self ^ hi3);                            // a zero lane = candidate
-            const uint32_t cand = mx_pk_sub_u16(0x00010001u, mx_pk_min_u16(z, 0x00010001u));    // 1 / 0 per lane
-            const uint32_t below = mx_pk_min_u16(mx_pk_sub_sat_u16(st.mc2, self), 0x00010001u);  // 1 iff value < min_contrast
+            const uint32_t z = pk_min_u16(self ^ lo3, self ^ hi3);                            // a zero lane = candidate
+            const uint32_t cand = pk_sub_u16(0x00010001u, pk_min_u16(z, 0x00010001u));    // 1 / 0 per lane
+            const uint32_t below = pk_min_u16(pk_sub_sat_u16(st.mc2, self), 0x00010001u);  // 1 iff value < min_contrast
             const uint32_t listed = cand & ~below;
             const uint32_t bits = cand | (listed << 1);
             st.out[p] = c == 1 ? bits : (st.out[p] | (bits << (2 * (c - 1))));
@@ -566,13 +434,7 @@ __device__ __forceinline__ void mx_level(const MxTaps<CFG>* __restrict__ taps, c
             uint32_t w[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) w[j] = ((uint32_t)chi[4 * k + j] << 8) + (uint32_t)clo[4 * k + j];
-            const uint32_t e = __builtin_amdgcn_perm(w[2], w[0], 0x0c060c02);  // (G0, G2) in 16-bit lanes
-            const uint32_t o = __builtin_amdgcn_perm(w[3], w[1], 0x0c060c02);  // (G1, G3)
-            g[k] = __builtin_amdgcn_perm(o, e, 0x06020400);
-            if (L > 0)  // D_{L-1} = saturate_u8(G_L - G_{L-1}), GaussPyramid.cpp:197
-                dd[ob][k] = __builtin_amdgcn_perm(mx_pk_sub_sat_u16(o, po[ob][k]), mx_pk_sub_sat_u16(e, pe[ob][k]), 0x06020400);
-            pe[ob][k] = e;
-            po[ob][k] = o;
+            level_pack4(w[0], w[1], w[2], w[3], L, g[k], dd[ob][k], pe[ob][k], po[ob][k]);
         }
         *reinterpret_cast<uint4*>(ln.wb + 8 * ob) = make_uint4(g[0], g[1], g[2], g[3]);
         if (CFG::DBUF && L > 0) *reinterpret_cast<uint4*>(ln.wb + CFG::OBUF + 8 * ob) = make_uint4(dd[ob][0], dd[ob][1], dd[ob][2], dd[ob][3]);
@@ -580,7 +442,7 @@ __device__ __forceinline__ void mx_level(const MxTaps<CFG>* __restrict__ taps, c
         // columns of the even rows; 16 ob < ncols_left keeps the 8-byte store inside the row (pitch: multiple of 16)
         if (L == 3 && ln.nb && 16 * ob < ln.ncols_left)
             *reinterpret_cast<uint2*>(ln.nb + 16 * ob) =
-                make_uint2(__builtin_amdgcn_perm(pe[ob][1], pe[ob][0], 0x06040200), __builtin_amdgcn_perm(pe[ob][3], pe[ob][2], 0x06040200));
+                make_uint2(even_bytes(pe[ob][0], pe[ob][1]), even_bytes(pe[ob][2], pe[ob][3]));
     }
     if constexpr (L < 5) {  // the next level's fragments, in front of this level's stores (see above)
 #pragma unroll
@@ -645,19 +507,14 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave_mx(const uint8_t* __rest
                                                            const MxTaps<CFG>* __restrict__ taps, uint8_t* __restrict__ next_base,
                                                            size_t nframe, int nrows, int ncols, int npitch, MxExtArgs ext, int sstep) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    // XCD-aware tile order, as k_pyr_octave: every XCD walks one contiguous run of tiles (neighbours share halo lines in its L2)
-    unsigned int bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned int per_xcd = (gridDim.x * gridDim.y * gridDim.z) >> 3;
-    if (bid < (per_xcd << 3)) bid = (bid & 7u) * per_xcd + (bid >> 3);
-    const unsigned int tiles_per_frame = gridDim.x * gridDim.y;
-    const unsigned int fz = bid / tiles_per_frame, rem = bid - fz * tiles_per_frame;
-    const unsigned int by = rem / gridDim.x, bx = rem - by * gridDim.x;
+    unsigned int fz, by, bx;
+    xcd_tile_id(blockIdx, gridDim, fz, by, bx);
     const int tile_x0 = bx * CFG::TW, tile_y0 = by * CFG::TH;
 
     if constexpr (UP2)
         mx_stage_tile_up2<CFG::TW, CFG::TH, CFG::R, CFG::RWP, CFG::NT>(base + fz * bframe, sstep, rows / 2, cols / 2, tile_x0, tile_y0, smem, 0x80808080u);
     else
-        mx_stage_tile<CFG::TW, CFG::TH, CFG::R, CFG::RWP, CFG::NT>(base + fz * bframe, rows, cols, pitch, tile_x0, tile_y0, smem, 0x80808080u);
+        stage_tile_transposed<CFG::TW, CFG::TH, CFG::R, CFG::RWP, CFG::NT, 4>(base + fz * bframe, rows, cols, pitch, tile_x0, tile_y0, smem, 0x80808080u);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -90,8 +90,8 @@ __device__ __forceinline__ void sift_one_keypoint(SiftShared& sh, const vslam_po
         if ((t & 63) == 0) sh.badw[t >> 6] = wave_bad;
         if (!outside) {
             const int r = clampi(prow - SIFT_PAD, 0, rows - 1), c = clampi(pcol - SIFT_PAD, 0, cols - 1);  // padOctave(20): replicate
-            const float gx = (float)((int)G[(size_t)r * gpitch + reflect101(c + 1, cols)] - (int)G[(size_t)r * gpitch + reflect101(c - 1, cols)]);
-            const float gy = (float)((int)G[(size_t)reflect101(r + 1, rows) * gpitch + c] - (int)G[(size_t)reflect101(r - 1, rows) * gpitch + c]);
+            float gx, gy;
+            gradient_at(G, gpitch, rows, cols, r, c, gx, gy);
             const float xx = gx * gx, yy = gy * gy;
             mval = sqrt_rn_small_nr(xx + yy);            // cv::magnitude, correctly rounded (kernels_generic.hip.h)
             sh.mag[t] = mval;

@@ -66,14 +66,7 @@ __global__ __launch_bounds__(256) void k_gauss_v_strip(const uint8_t* __restrict
             for (int k = 0; k < 4; ++k)
                 a[k] = *reinterpret_cast<const uint32_t*>(src + (size_t)reflect101(4 * yq + k - RM, rows) * pitch + gx);
         }
-        const uint32_t p01l = __builtin_amdgcn_perm(a[1], a[0], 0x05010400), p01h = __builtin_amdgcn_perm(a[1], a[0], 0x07030602);
-        const uint32_t p23l = __builtin_amdgcn_perm(a[3], a[2], 0x05010400), p23h = __builtin_amdgcn_perm(a[3], a[2], 0x07030602);
-        uint4 t;
-        t.x = __builtin_amdgcn_perm(p23l, p01l, 0x05040100);
-        t.y = __builtin_amdgcn_perm(p23l, p01l, 0x07060302);
-        t.z = __builtin_amdgcn_perm(p23h, p01h, 0x05040100);
-        t.w = __builtin_amdgcn_perm(p23h, p01h, 0x07060302);
-        *reinterpret_cast<uint4*>(rp + yq * STRIP_W + 4 * xq) = t;
+        *reinterpret_cast<uint4*>(rp + yq * STRIP_W + 4 * xq) = transpose4x4_u8(a[0], a[1], a[2], a[3]);
     }
     __syncthreads();
 
@@ -89,8 +82,8 @@ __global__ __launch_bounds__(256) void k_gauss_v_strip(const uint8_t* __restrict
         const int nq = (rows - ty_start + 3) >> 2;
         const uint4* tab = reinterpret_cast<const uint4*>(&taps->v4[l][0][0]);
         uint16_t* hl = h + blockIdx.z * hframe + (size_t)l * P;
-        // the partial last round of items rotates over the waves with the level (as in k_pyr_octave: it
-        // would otherwise always load the SIMDs that hold waves 0 and 1)
+        // the partial last round of items rotates over the waves with the level (it would otherwise always load the SIMDs
+        // that hold waves 0 and 1: see pyr_level)
         const int n_items = nq * (STRIP_W / 4), full = n_items & ~255;
         for (int base_it = 0; base_it < n_items; base_it += 256) {
             int it = base_it + tid;
@@ -253,14 +246,9 @@ __global__ __launch_bounds__(256) void k_gauss_h_strip(const uint16_t* __restric
                     const int y = y0 + RI * rg + jr;
                     uint32_t g[2], d[2] = {0, 0};
 #pragma unroll
-                    for (int hw = 0; hw < 2; ++hw) {
-                        const uint32_t e = __builtin_amdgcn_perm(acc[jr][4 * hw + 2], acc[jr][4 * hw + 0], 0x0c060c02);
-                        const uint32_t o = __builtin_amdgcn_perm(acc[jr][4 * hw + 3], acc[jr][4 * hw + 1], 0x0c060c02);
-                        g[hw] = __builtin_amdgcn_perm(o, e, 0x06020400);  // bytes (e0, o0, e1, o1): interleave in one v_perm
-                        if (l > 0) d[hw] = __builtin_amdgcn_perm(pk_sub_sat_u16(o, prev_o[ii][jr][hw]), pk_sub_sat_u16(e, prev_e[ii][jr][hw]), 0x06020400);
-                        prev_e[ii][jr][hw] = e;
-                        prev_o[ii][jr][hw] = o;
-                    }
+                    for (int hw = 0; hw < 2; ++hw)
+                        level_pack4(acc[jr][4 * hw], acc[jr][4 * hw + 1], acc[jr][4 * hw + 2], acc[jr][4 * hw + 3], l, g[hw], d[hw],
+                                    prev_e[ii][jr][hw], prev_o[ii][jr][hw]);
                     if (y < rows) {
                         const uint32_t off = item_off[ii] + (uint32_t)(jr * pitch);  // 32-bit offset in a uniform plane pointer
                         uint8_t* gp = out + (size_t)l * P;
@@ -271,8 +259,7 @@ __global__ __launch_bounds__(256) void k_gauss_h_strip(const uint16_t* __restric
                         }
                         // next octave's base = Gaussian[3] decimated 2:1 (GaussPyramid.cpp:123-126)
                         if (l == 3 && next_base && (y & 1) == 0 && (y >> 1) < nrows && (x >> 1) < ncols)
-                            *reinterpret_cast<uint32_t*>(next_base + blockIdx.z * nframe + (size_t)(y >> 1) * npitch + (x >> 1)) =
-                                __builtin_amdgcn_perm(g[1], g[0], 0x06040200);
+                            *reinterpret_cast<uint32_t*>(next_base + blockIdx.z * nframe + (size_t)(y >> 1) * npitch + (x >> 1)) = even_bytes(g[0], g[1]);
                     }
                 }
             }
@@ -293,18 +280,8 @@ static bool strip_pack_taps(const uint16_t* const t[6], const int n[6], StripTap
         }
         if (sum != 256) return false;  // STRIP_HBIAS relies on it
         for (int m = 0; m < STRIP_MAXM; ++m)
-            for (int j = 0; j < 4; ++j) {
-                uint32_t w = 0;
-                for (int b = 0; b < 4; ++b) {
-                    const int k = 4 * m + b - j;
-                    if (k >= 0 && k < n[l]) w |= (uint32_t)t[l][k] << (8 * b);
-                }
-                out.v4[l][m][j] = w;
-            }
-        for (int e = 0; e <= n[l]; ++e) {
-            const uint32_t lo = e >= 1 ? t[l][e - 1] : 0, hi = e < n[l] ? t[l][e] : 0;
-            out.hp[l][8 + e] = lo | (hi << 16);
-        }
+            for (int j = 0; j < 4; ++j) out.v4[l][m][j] = pack_taps_u8x4(t[l], n[l], m, j);
+        for (int e = 0; e <= n[l]; ++e) out.hp[l][8 + e] = pack_taps_u16x2(t[l], n[l], e);
     }
     return true;
 }
