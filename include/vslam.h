@@ -528,6 +528,68 @@ void vslam_points16_expand(const vslam_point16* in, size_t n, vslam_point* out);
 int vslam_count_totals_dev(vslam_ctx* ctx, const uint32_t* harris_counts, const uint32_t* dog_counts, int n_frames,
                            uint64_t* totals);
 
+/* ---------------------------------------------------------------- descriptor matching
+ * The step the reference stops short of (Diff_of_Gauss.cpp:687: "final step is graphing and comparing two images with each
+ * other"; its README's step 2, "Feature description / Image Matching"): for every query descriptor the nearest and the
+ * second-nearest train descriptor by squared Euclidean distance, and Lowe's ratio test on the two.  The search is exact,
+ * and its arithmetic is fixed here so that a CPU can restate it bit for bit (tests/matchref.py):
+ *   s(a, b)  = acc = +0.0f; acc = fmaf(a[k], b[k], acc) for k = 0 .. 127 ascending  (what v_mfma_f32_32x32x2_f32 computes)
+ *   n(a)     = s(a, a)
+ *   d2(a, b) = (n(a) + n(b)) - 2 s(a, b) in f32: the sum rounded, the doubling exact, the difference rounded.
+ * d2 is a pure function of the two rows and is stored as computed, WITHOUT a clamp: d2(a, a) is exactly 0, but for two
+ * nearly identical rows it can be slightly NEGATIVE.
+ * Selection for one query row over the train rows j = 0 .. nt-1 ascending: best = second = +inf, index = -1; if d2 < best
+ * then second = best, best = d2, index = j; otherwise if d2 < second then second = d2.  Ties keep the lowest index, a NaN
+ * distance never wins, and two equal minima give second_dist2 == dist2.  Skipped: a train row whose `defined` byte is 0,
+ * and with same_octave a train row whose points[j].octave differs from the query's.  A query row whose `defined` byte is 0
+ * gets {-1, +inf, +inf}.  A query is ACCEPTED iff index >= 0 and (second == +inf or best < ratio2 * second), the product
+ * rounded once to f32.  Results depend neither on vslam_ctx_set_f32_fused nor on vslam_ctx_set_matrix_path. */
+typedef struct {
+    int32_t index; /* train row, -1: none */
+    float dist2, second_dist2;
+} vslam_nn2;
+typedef struct {
+    int32_t query, train;
+    float dist2;
+} vslam_match;
+/* n sets of descriptor rows, DEVICE pointers, set j at j * cap rows: exactly the descriptors / descriptor_defined /
+ * oriented_points / oriented_counts buffers of vslam_detect_batch_dev with cap = oriented_cap. */
+typedef struct {
+    const float* desc;         /* [n][cap][128], 16-byte aligned */
+    const uint8_t* defined;    /* [n][cap], NULL = all defined */
+    const vslam_point* points; /* [n][cap], required with same_octave, else may be NULL */
+    const uint32_t* counts;    /* [n] on the device; rows in use = min(counts[j], cap) */
+    uint32_t cap;
+} vslam_desc_sets;
+/* Like vslam_batch_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;     /* = sizeof(vslam_match_out) */
+    vslam_nn2* nn;          /* [n_pairs][query.cap] optional; rows past a set's count are left untouched */
+    size_t nn_bytes;
+    vslam_match* matches;   /* [n_pairs][match_cap] optional, needs match_counts: the accepted queries, ascending query order */
+    size_t matches_bytes;
+    uint32_t* match_counts; /* [n_pairs] totals (may exceed match_cap) */
+    size_t match_counts_bytes;
+    uint32_t match_cap;
+} vslam_match_out;
+/* Pair j matches set j of `query` against set j of `train`, j < n_pairs (at most 65535; 0 does nothing).  Consecutive frames
+ * of a batch: train = query advanced by one set, n_pairs = n - 1; the seam between two batches is a one-pair call.
+ * Asynchronous on the context stream, never waits on the host (the counts are read on the device); scratch belongs to the
+ * context and is sized from the capacities before the launches.  ratio2: the SQUARED ratio of Lowe's test (0.64 for 0.8).
+ * VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null struct, a wrong struct_size, an
+ * undersized buffer, no output at all, matches without match_counts, same_octave without points, a misaligned desc,
+ * n_pairs < 0, a ratio2 that is not finite or not positive; then VSLAM_ERR_HIP when there is no usable HIP device (no
+ * context can exist there, so also with a NULL context - which is VSLAM_ERR_INVALID otherwise).  Not for stream capture. */
+int vslam_match_dev(vslam_ctx* ctx, const vslam_desc_sets* query, const vslam_desc_sets* train, int n_pairs, float ratio2,
+                    int same_octave, const vslam_match_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call): query [nq][128], train [nt][128];
+ * *_defined ([n] bytes) and *_points ([n]) as in vslam_desc_sets (NULL = all defined / required with same_octave).
+ * nn [nq] and (matches [match_cap], n_matches) are each optional; *n_matches is the total, which may exceed match_cap.
+ * Errors as for vslam_match_dev. */
+int vslam_match_host(vslam_ctx* ctx, const float* query, const uint8_t* query_defined, const vslam_point* query_points, size_t nq,
+                     const float* train, const uint8_t* train_defined, const vslam_point* train_points, size_t nt, float ratio2,
+                     int same_octave, vslam_nn2* nn, vslam_match* matches, size_t match_cap, size_t* n_matches);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

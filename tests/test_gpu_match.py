@@ -1,0 +1,329 @@
+"""Descriptor matching on the GPU (vslam_match_dev / vslam_match_host, include/vslam.h): every comparison is bytes-equal
+against the CPU restatement of the arithmetic in tests/matchref.py - nn, matches and match_counts."""
+import numpy as np
+import pytest
+
+import oracle
+from tests import matchref, refimg
+from visualslam_amd import capi, synth
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def env():
+    import torch
+
+    capi.build()
+    c = capi.Context(0, torch.cuda.current_stream().cuda_stream)
+    yield c, torch
+    c.close()
+
+
+def crafted(rng, n, base=None):
+    """n rows like the reference's descriptors; with `base`, half of them are copies / near copies of base rows."""
+    d = matchref.reference_like_descriptors(rng, n)
+    if base is not None and len(base) and n:
+        k = rng.integers(0, len(base), n)
+        noisy = np.abs(base[k] + rng.normal(0, 0.02, (n, 128)).astype(np.float32)).astype(np.float32)
+        pick = rng.random(n)
+        d[pick < 0.25] = base[k][pick < 0.25]           # exact copies: distance exactly 0
+        d[(pick >= 0.25) & (pick < 0.5)] = noisy[(pick >= 0.25) & (pick < 0.5)]
+    return d
+
+
+def sets_to_device(torch, sets, cap, with_points):
+    """sets: list of (desc [m, 128], defined [m] or None, octave [m] or None, count) -> DescSets + the tensors behind it."""
+    n = len(sets)
+    desc = np.full((n, cap, 128), 3.5, np.float32)
+    defined = np.ones((n, cap), np.uint8)
+    points = np.zeros((n, cap, 6), np.int32)
+    counts = np.zeros(n, np.int32)
+    for j, (d, df, oc, cnt) in enumerate(sets):
+        m = min(len(d), cap)
+        desc[j, :m] = d[:m]
+        if df is not None:
+            defined[j, :m] = df[:m]
+        if oc is not None:
+            points[j, :m, 4] = oc[:m]
+        counts[j] = cnt
+    t = [torch.from_numpy(a).to(DEV) for a in (desc, counts, defined, points)]
+    return capi.desc_sets(t[0], t[1], t[2], t[3] if with_points else None), t
+
+
+SENT = -77
+
+
+def run_dev(ctx, torch, qsets, tsets, qcap, tcap, ratio2=0.64, same_octave=False, match_cap=None):
+    n = len(qsets)
+    Q, keepq = sets_to_device(torch, qsets, qcap, same_octave)
+    T, keept = sets_to_device(torch, tsets, tcap, same_octave)
+    match_cap = qcap if match_cap is None else match_cap
+    nn = torch.full((n, qcap, 3), SENT, dtype=torch.int32, device=DEV)
+    matches = torch.full((n, match_cap, 3), SENT, dtype=torch.int32, device=DEV)
+    counts = torch.full((n,), SENT, dtype=torch.int32, device=DEV)
+    ctx.match(Q, T, n, ratio2, same_octave, nn=nn, matches=matches, match_counts=counts)
+    torch.cuda.synchronize()
+    return nn.cpu().numpy(), matches.cpu().numpy(), counts.cpu().numpy()
+
+
+def check_pair(got, j, qs, ts, qcap, tcap, ratio2, same_octave, match_cap):
+    nn, matches, counts = got
+    (qd, qdf, qoc, qcnt), (td, tdf, toc, tcnt) = qs, ts
+    nq, nt = min(qcnt, qcap), min(tcnt, tcap)
+    wnn, wm = matchref.match(qd[:nq], td[:nt], ratio2, same_octave, None if qdf is None else qdf[:nq], None if tdf is None else tdf[:nt],
+                             None if qoc is None else qoc[:nq], None if toc is None else toc[:nt])
+    assert nn[j, :nq].tobytes() == wnn.tobytes(), ("nn", j, int((nn[j, :nq].view(np.uint8).reshape(nq, 12) != wnn.view(np.uint8).reshape(nq, 12)).any(axis=1).sum()), nq)
+    assert (nn[j, nq:] == SENT).all(), "nn rows past the count were written"
+    assert counts[j] == len(wm), ("match_counts", j, int(counts[j]), len(wm))
+    m = min(len(wm), match_cap)
+    assert matches[j, :m].tobytes() == wm[:m].tobytes(), ("matches", j)
+    assert (matches[j, m:] == SENT).all(), "matches past the count were written"
+    return wnn, wm
+
+
+def make_pair(rng, nq, nt, octaves=False, specials=True):
+    td = crafted(rng, nt)
+    qd = crafted(rng, nq, td)
+    qdf, tdf = np.ones(nq, np.uint8), np.ones(nt, np.uint8)
+    if specials and nt >= 8 and nq >= 8:
+        td[nt // 2] = td[1]            # duplicated train rows: ties go to the lower index
+        td[nt - 1] = td[1]
+        qd[0] = td[1]                  # a query equal to two train rows: 0 < r * 0 is false, rejected
+        td[3] = np.nan                 # all-NaN rows never match
+        qd[5] = np.nan
+        tdf[2] = 0                     # undefined rows are skipped
+        qdf[4] = 0
+        qd[6] = td[2]                  # ... even where they would be the best
+        qd[7] = td[4]                  # a unique exact copy: accepted with dist2 == 0
+    qoc = np.sort(rng.integers(0, 3, nq)).astype(np.int32) if octaves else None
+    toc = np.sort(rng.integers(0, 3, nt)).astype(np.int32) if octaves else None
+    return (qd, qdf, qoc, nq), (td, tdf, toc, nt)
+
+
+SIZES = [(0, 0), (0, 5), (5, 0), (1, 1), (2, 2), (63, 64), (64, 63), (65, 127), (127, 129), (129, 65), (1000, 777)]
+
+
+@pytest.mark.parametrize("same_octave", [False, True])
+@pytest.mark.parametrize("nq,nt", SIZES)
+def test_crafted_sets_match_the_restatement(env, nq, nt, same_octave):
+    ctx, torch = env
+    rng = np.random.default_rng(1000 * nq + nt)
+    qs, ts = make_pair(rng, nq, nt, octaves=same_octave)
+    qcap, tcap = max(nq, 1) + 3, max(nt, 1) + 2
+    got = run_dev(ctx, torch, [qs], [ts], qcap, tcap, same_octave=same_octave)
+    wnn, wm = check_pair(got, 0, qs, ts, qcap, tcap, 0.64, same_octave, qcap)
+    if nq >= 8 and nt >= 8 and not same_octave:
+        assert wnn[0]["index"] == 1 and wnn[0]["dist2"] == 0.0 and wnn[0]["second_dist2"] == 0.0 and 0 not in wm["query"]
+        assert wnn[4]["index"] == -1 and np.isinf(wnn[4]["dist2"]) and wnn[5]["index"] == -1
+        assert wnn[6]["index"] != 2 and (wnn["index"] != 3).all()
+        assert wnn[7]["index"] == 4 and wnn[7]["dist2"] == 0.0 and 7 in wm["query"]
+
+
+def test_large_pair_4096_by_5000(env):
+    ctx, torch = env
+    qs, ts = make_pair(np.random.default_rng(7), 4096, 5000)
+    got = run_dev(ctx, torch, [qs], [ts], 4096, 5000)
+    _, wm = check_pair(got, 0, qs, ts, 4096, 5000, 0.64, False, 4096)
+    assert 500 < len(wm) < 4096
+    again = run_dev(ctx, torch, [qs], [ts], 4096, 5000)  # two runs of the same call: byte-identical
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(got, again))
+
+
+def test_counts_above_cap_and_a_small_match_cap(env):
+    ctx, torch = env
+    rng = np.random.default_rng(11)
+    (qd, qdf, qoc, _), (td, tdf, toc, _) = make_pair(rng, 300, 260, octaves=True)
+    qs, ts = (qd, qdf, qoc, 100000), (td, tdf, toc, 4000)  # the counts exceed the capacities: min(count, cap) rows are used
+    for same_octave in (False, True):
+        got = run_dev(ctx, torch, [qs], [ts], 200, 190, same_octave=same_octave, match_cap=17)
+        _, wm = check_pair(got, 0, qs, ts, 200, 190, 0.64, same_octave, 17)
+        assert len(wm) > 17  # the total is reported, the list is cut
+
+
+def test_ratio_values(env):
+    ctx, torch = env
+    qs, ts = make_pair(np.random.default_rng(5), 257, 300)
+    seen = []
+    for r2 in (0.01, 0.49, 0.64, 1.0, 1e30):
+        got = run_dev(ctx, torch, [qs], [ts], 257, 300, ratio2=r2)
+        seen.append(len(check_pair(got, 0, qs, ts, 257, 300, r2, False, 257)[1]))
+    assert seen == sorted(seen) and seen[0] < seen[-1]
+
+
+def test_seventy_unequal_pairs_in_one_call_equal_seventy_calls(env):
+    ctx, torch = env
+    rng = np.random.default_rng(70)
+    n, qcap, tcap = 70, 260, 300
+    pairs = [make_pair(rng, int(rng.integers(0, qcap + 1)), int(rng.integers(0, tcap + 1)), octaves=True, specials=(j % 3 == 0)) for j in range(n)]
+    qsets, tsets = [p[0] for p in pairs], [p[1] for p in pairs]
+    for same_octave in (False, True):
+        whole = run_dev(ctx, torch, qsets, tsets, qcap, tcap, same_octave=same_octave, match_cap=64)
+        for j in range(n):
+            one = run_dev(ctx, torch, qsets[j:j + 1], tsets[j:j + 1], qcap, tcap, same_octave=same_octave, match_cap=64)
+            assert all(w[j].tobytes() == o[0].tobytes() for w, o in zip(whole, one)), j
+        for j in (0, 1, 35, 69):
+            check_pair(whole, j, qsets[j], tsets[j], qcap, tcap, 0.64, same_octave, 64)
+
+
+def test_host_entry_point_and_optional_outputs(env):
+    ctx, torch = env
+    (qd, qdf, qoc, nq), (td, tdf, toc, nt) = make_pair(np.random.default_rng(3), 150, 140, octaves=True)
+    qp, tp = np.zeros(nq, capi.POINT_DTYPE), np.zeros(nt, capi.POINT_DTYPE)
+    qp["octave"], tp["octave"] = qoc, toc
+    for same_octave in (False, True):
+        wnn, wm = matchref.match(qd, td, 0.64, same_octave, qdf, tdf, qoc, toc)
+        nn, m, total = ctx.match_host(qd, td, 0.64, same_octave, qdf, tdf, qp, tp)
+        assert nn.tobytes() == wnn.tobytes() and m.tobytes() == wm.tobytes() and total == len(wm)
+        nn, m, total = ctx.match_host(qd, td, 0.64, same_octave, qdf, tdf, qp, tp, match_cap=5)
+        assert m.tobytes() == wm[:5].tobytes() and total == len(wm)
+    nn, m, total = ctx.match_host(np.zeros((0, 128), np.float32), td)
+    assert len(nn) == 0 and total == 0
+    nn, m, total = ctx.match_host(qd, np.zeros((0, 128), np.float32))
+    assert (nn["index"] == -1).all() and np.isinf(nn["dist2"]).all() and np.isinf(nn["second_dist2"]).all() and total == 0
+    # match_counts alone / nn alone
+    Q, kq = sets_to_device(torch, [(qd, qdf, qoc, nq)], 160, False)
+    T, kt = sets_to_device(torch, [(td, tdf, toc, nt)], 160, False)
+    counts = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ctx.match(Q, T, 1, match_counts=counts)
+    nn_t = torch.zeros((1, 160, 3), dtype=torch.int32, device=DEV)
+    ctx.match(Q, T, 1, nn=nn_t)
+    torch.cuda.synchronize()
+    wnn, wm = matchref.match(qd, td, 0.64, False, qdf, tdf)
+    assert int(counts[0]) == len(wm) and nn_t.cpu().numpy()[0, :nq].tobytes() == wnn.tobytes()
+    with pytest.raises(capi.VslamError):
+        ctx.match(Q, T, 1, nn=torch.zeros((1, 159, 3), dtype=torch.int32, device=DEV))  # undersized
+    with pytest.raises(capi.VslamError):
+        ctx.match(Q, T, 1, same_octave=True, nn=nn_t)  # no points
+    # the result depends neither on the f32-fused switch nor on the matrix-path switch
+    ctx.set_f32_fused(True)
+    ctx.set_matrix_path(True)
+    nn2 = torch.zeros((1, 160, 3), dtype=torch.int32, device=DEV)
+    ctx.match(Q, T, 1, nn=nn2)
+    torch.cuda.synchronize()
+    ctx.set_f32_fused(False)
+    ctx.set_matrix_path(False)
+    assert torch.equal(nn_t, nn2)
+
+
+def detect(ctx, torch, frames_np, n_oct=3):
+    n, rows, cols = frames_np.shape
+    p = capi.default_params(rows, cols, n_octaves=n_oct, localize=1, orient=1)
+    L = capi.batch_layout(p)
+    o = dict(pyramid=torch.empty((n, L.pyramid_frame_bytes), dtype=torch.uint8, device=DEV),
+             dog_points=torch.zeros((n, p.dog_cap, 6), dtype=torch.int32, device=DEV), dog_counts=torch.zeros(n, dtype=torch.int32, device=DEV),
+             oriented_points=torch.zeros((n, p.oriented_cap, 6), dtype=torch.int32, device=DEV),
+             oriented_counts=torch.zeros(n, dtype=torch.int32, device=DEV),
+             descriptors=torch.zeros((n, p.oriented_cap, 128), dtype=torch.float32, device=DEV),
+             descriptor_defined=torch.zeros((n, p.oriented_cap), dtype=torch.uint8, device=DEV))
+    p.do_harris = 0
+    ctx.detect_batch(p, torch.from_numpy(frames_np).to(DEV), **o)
+    return p, o
+
+
+def test_end_to_end_consecutive_frames_and_a_seam(env):
+    ctx, torch = env
+    frames = synth.frames_np(5, 120, 160, stream_id=2)
+    p, o = detect(ctx, torch, frames)
+    n, cap = 5, p.oriented_cap
+    d, c, df, pts = o["descriptors"], o["oriented_counts"], o["descriptor_defined"], o["oriented_points"]
+    for same_octave in (False, True):
+        nn = torch.full((n - 1, cap, 3), SENT, dtype=torch.int32, device=DEV)
+        matches = torch.full((n - 1, cap, 3), SENT, dtype=torch.int32, device=DEV)
+        counts = torch.full((n - 1,), SENT, dtype=torch.int32, device=DEV)
+        ctx.match(capi.desc_sets(d, c, df, pts), capi.desc_sets(d[1:], c[1:], df[1:], pts[1:]), n - 1, 0.64, same_octave, nn=nn, matches=matches, match_counts=counts)
+        # the seam: the last frame against the first, a one-pair call
+        snn = torch.full((1, cap, 3), SENT, dtype=torch.int32, device=DEV)
+        scounts = torch.zeros(1, dtype=torch.int32, device=DEV)
+        ctx.match(capi.desc_sets(d[4:], c[4:], df[4:], pts[4:]), capi.desc_sets(d[:1], c[:1], df[:1], pts[:1]), 1, 0.64, same_octave, nn=snn, match_counts=scounts)
+        torch.cuda.synchronize()
+        hd, hc, hdf, hp = d.cpu().numpy(), c.cpu().numpy(), df.cpu().numpy(), pts.cpu().numpy()
+        assert (hc > 0).all() and (hc <= cap).all()
+        got = (nn.cpu().numpy(), matches.cpu().numpy(), counts.cpu().numpy())
+        sets = [(hd[f], hdf[f], hp[f, :, 4], int(hc[f])) for f in range(n)]
+        for j in range(n - 1):
+            check_pair(got, j, sets[j], sets[j + 1], cap, cap, 0.64, same_octave, cap)
+        wnn, wm = matchref.match(hd[4][:hc[4]], hd[0][:hc[0]], 0.64, same_octave, hdf[4][:hc[4]], hdf[0][:hc[0]], hp[4, :hc[4], 4], hp[0, :hc[0], 4])
+        assert snn.cpu().numpy()[0, :hc[4]].tobytes() == wnn.tobytes() and int(scounts[0]) == len(wm)
+
+
+def building_crops():
+    img = refimg.load("building")
+    return np.ascontiguousarray(img[:576, :576]), np.ascontiguousarray(img[24:600, 24:600])
+
+
+def oracle_chain(img, n_oct=3):
+    """keypoints -> filter_keypoints -> sift_descriptors of the CPU oracle: (oriented points, descriptors, defined)."""
+    pyr = oracle.Pyramid(img, n_oct, 1.6)
+    pts, desc, ok = [], [], []
+    for o in range(n_oct):
+        op = pyr.filter_keypoints(o, pyr.keypoints(o, 3))
+        dd, kk = pyr.sift_descriptors(o, op)
+        pts.append(op), desc.append(dd), ok.append(kk)
+    pyr.close()
+    return np.concatenate(pts), np.concatenate(desc), np.concatenate(ok).astype(np.uint8)
+
+
+def exact_translations(m, qp, tp, shift):
+    """Accepted matches whose two points are the same feature: same octave, level and angle, displaced by the crop shift
+    (octave o of the pyramid is sampled at 2 / 2^o of the image's pitch)."""
+    q, t = qp[m["query"]], tp[m["train"]]
+    s = (2 * shift) >> q["octave"]
+    return int(((q["octave"] == t["octave"]) & (q["level"] == t["level"]) & (q["value"] == t["value"]) &
+                (q["row"] - t["row"] == s) & (q["col"] - t["col"] == s)).sum())
+
+
+def test_building_crops_match_like_the_cpu_chain(env):
+    ctx, torch = env
+    a, b = building_crops()
+    (qp, qd, qk), (tp, td, tk) = oracle_chain(a), oracle_chain(b)
+    wnn, wm = matchref.match(qd, td, 0.64, False, qk, tk)
+    valid = lambda desc, ok: int((ok.astype(bool) & ~np.isnan(desc).any(axis=1)).sum())  # defined and free of 0 / 0
+    want = (valid(qd, qk), valid(td, tk), len(wm), exact_translations(wm, qp, tp, 24))
+    assert want == (884, 818, 730, 710)  # the CPU chain alone: 97 % of the accepted matches are exact translations
+    p, o = detect(ctx, torch, np.stack([a, b]))
+    cap = p.oriented_cap
+    d, c, df, pts = o["descriptors"], o["oriented_counts"], o["descriptor_defined"], o["oriented_points"]
+    nn = torch.zeros((1, cap, 3), dtype=torch.int32, device=DEV)
+    matches = torch.zeros((1, cap, 3), dtype=torch.int32, device=DEV)
+    counts = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ctx.match(capi.desc_sets(d[:1], c[:1], df[:1]), capi.desc_sets(d[1:], c[1:], df[1:]), 1, 0.64, False, nn=nn, matches=matches, match_counts=counts)
+    torch.cuda.synchronize()
+    hc, hdf = c.cpu().numpy(), df.cpu().numpy()
+    hp = pts.cpu().numpy().view(capi.POINT_DTYPE).reshape(2, cap)
+    assert (int(hc[0]), int(hc[1])) == (len(qp), len(tp))
+    gm = matches.cpu().numpy()[0, :int(counts[0])].copy().view(capi.MATCH_DTYPE).reshape(-1)
+    hd = d.cpu().numpy()
+    got = (valid(hd[0, :hc[0]], hdf[0, :hc[0]]), valid(hd[1, :hc[1]], hdf[1, :hc[1]]), len(gm), exact_translations(gm, hp[0], hp[1], 24))
+    print("building crops: valid query, valid train, accepted, exact translations: gpu", got, "cpu chain", want)
+    assert got == want
+    assert gm.tobytes() == wm.tobytes() and nn.cpu().numpy()[0, :hc[0]].tobytes() == wnn.tobytes()
+    assert got[3] >= 0.9 * got[2] and got[2] > 100
+
+
+def test_match_executable_reports_the_counts_of_the_python_path(env, tmp_path):
+    import json
+    import os
+    import subprocess
+
+    ctx, torch = env
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "visualslam_amd", "bin", "Match")
+    assert os.path.exists(exe), "visualslam_amd/bin/Match is missing: __graft_entry__.build() builds it"
+    paths = []
+    for k, img in enumerate(building_crops()):
+        paths.append(str(tmp_path / f"crop{k}.pgm"))
+        with open(paths[-1], "wb") as f:
+            f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]) + img.tobytes())
+    r = subprocess.run([exe, paths[0], paths[1], "3"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    rep = json.loads(r.stdout.strip().splitlines()[-1])
+    p, o = detect(ctx, torch, np.stack(building_crops()))
+    d, c, df = o["descriptors"], o["oriented_counts"], o["descriptor_defined"]
+    counts = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ctx.match(capi.desc_sets(d[:1], c[:1], df[:1]), capi.desc_sets(d[1:], c[1:], df[1:]), 1, 0.64, False, match_counts=counts)
+    torch.cuda.synchronize()
+    hc, hdf = c.cpu().numpy(), df.cpu().numpy()
+    assert (rep["query"]["descriptors"], rep["train"]["descriptors"]) == (int(hc[0]), int(hc[1]))
+    assert (rep["query"]["defined"], rep["train"]["defined"]) == (int(hdf[0, :hc[0]].sum()), int(hdf[1, :hc[1]].sum()))
+    assert rep["accepted"] == int(counts[0])

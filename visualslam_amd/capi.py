@@ -28,6 +28,8 @@ NUM_DOGS = 5
 
 POINT_DTYPE = np.dtype([(n, "<i4") for n in ("row", "col", "value", "padding", "octave", "level")], align=True)
 KP_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("response", "<f4")], align=True)
+NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4")], align=True)  # vslam_nn2
+MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 
 
 class VslamError(RuntimeError):
@@ -71,6 +73,25 @@ class HostLists(C.Structure):
     _fields_ = [("struct_size", C.c_size_t),
                 ("harris", C.c_void_p), ("harris_bytes", C.c_size_t), ("harris_offsets", C.c_void_p), ("harris_counts", C.c_void_p),
                 ("dog", C.c_void_p), ("dog_bytes", C.c_size_t), ("dog_offsets", C.c_void_p), ("dog_counts", C.c_void_p)]
+
+
+class Nn2(C.Structure):
+    _fields_ = [("index", C.c_int32), ("dist2", C.c_float), ("second_dist2", C.c_float)]
+
+
+class Match(C.Structure):
+    _fields_ = [("query", C.c_int32), ("train", C.c_int32), ("dist2", C.c_float)]
+
+
+class DescSets(C.Structure):
+    """vslam_desc_sets: n sets of descriptor rows behind device pointers (desc_sets() fills one from torch tensors)."""
+    _fields_ = [("desc", C.c_void_p), ("defined", C.c_void_p), ("points", C.c_void_p), ("counts", C.c_void_p), ("cap", C.c_uint32)]
+
+
+class MatchOut(C.Structure):
+    """vslam_match_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("nn", C.c_void_p), ("nn_bytes", C.c_size_t), ("matches", C.c_void_p), ("matches_bytes", C.c_size_t),
+                ("match_counts", C.c_void_p), ("match_counts_bytes", C.c_size_t), ("match_cap", C.c_uint32)]
 
 
 class PyramidInfo(C.Structure):
@@ -145,6 +166,8 @@ SIGNATURES = {
     "vslam_pack_points16_dev": (_I, [_P, _P, C.c_uint32, _P, _I, _P, _Z, _P]),
     "vslam_points16_expand": (None, [_P, _Z, _P]),
     "vslam_count_totals_dev": (_I, [_P, _P, _P, _I, _P]),
+    "vslam_match_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _I, _F, _I, C.POINTER(MatchOut)]),
+    "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -285,6 +308,27 @@ def batch_out_required(p: Params, n_frames: int) -> BatchOut:
     if rc:
         raise VslamError(rc, "vslam_batch_out_required")
     return z
+
+
+def desc_sets(desc, counts, defined=None, points=None) -> DescSets:
+    """vslam_desc_sets over CUDA tensors: desc f32 [n, cap, 128], counts int32 [n], defined uint8 [n, cap], points int32 [n, cap, 6] -
+    the descriptors / oriented_counts / descriptor_defined / oriented_points tensors of detect_batch, or slices of them along the
+    first dimension (desc[1:], counts[1:] ... are the train sets of consecutive-frame matching).  The tensors must outlive the call."""
+    import torch
+
+    if desc.dim() != 3 or desc.shape[2] != 128 or desc.dtype != torch.float32 or not desc.is_contiguous() or not desc.is_cuda:
+        raise ValueError("desc_sets: desc must be a contiguous float32 CUDA tensor [n, cap, 128]")
+    n, cap = desc.shape[0], desc.shape[1]
+    if counts.numel() < n or counts.dtype != torch.int32 or not counts.is_contiguous():
+        raise ValueError("desc_sets: counts must be int32 [n]")
+    if defined is not None and not (defined.dtype == torch.uint8 and defined.is_contiguous() and tuple(defined.shape) == (n, cap)):
+        raise ValueError("desc_sets: defined must be uint8 [n, cap]")
+    if points is not None and not (points.dtype == torch.int32 and points.is_contiguous() and tuple(points.shape) == (n, cap, 6)):
+        raise ValueError("desc_sets: points must be int32 [n, cap, 6]")
+    s = DescSets(desc.data_ptr(), defined.data_ptr() if defined is not None else None, points.data_ptr() if points is not None else None,
+                 counts.data_ptr(), cap)
+    s.n = n
+    return s
 
 
 def _u8(a):
@@ -603,6 +647,43 @@ class Context:
         n = (harris_counts if harris_counts is not None else dog_counts).numel()
         self._chk(lib().vslam_count_totals_dev(self._h, harris_counts.data_ptr() if harris_counts is not None else None,
                                                dog_counts.data_ptr() if dog_counts is not None else None, n, totals.data_ptr()), "vslam_count_totals_dev")
+
+    def match(self, query: DescSets, train: DescSets, n_pairs: int | None = None, ratio2: float = 0.64, same_octave: bool = False,
+              nn=None, matches=None, match_counts=None):
+        """vslam_match_dev: pair j matches set j of `query` against set j of `train` (desc_sets()); asynchronous on the context stream.
+        nn: int32 / float32 CUDA tensor of n_pairs * query.cap vslam_nn2 records (NN2_DTYPE), matches: n_pairs * match_cap vslam_match
+        records (MATCH_DTYPE; match_cap = its second dimension), match_counts: int32 [n_pairs].  ratio2 is the SQUARED ratio."""
+        n = min(query.n, train.n) if n_pairs is None else int(n_pairs)
+        mo = MatchOut()
+        mo.struct_size = C.sizeof(MatchOut)
+        for name, t in (("nn", nn), ("matches", matches), ("match_counts", match_counts)):
+            if t is not None:
+                if not (t.is_cuda and t.device.index == self.device and t.is_contiguous() and t.element_size() == 4):
+                    raise ValueError(f"match: {name} must be a contiguous 4-byte-element tensor on cuda:{self.device}")
+                setattr(mo, name, t.data_ptr())
+                setattr(mo, name + "_bytes", t.numel() * 4)
+        if matches is not None:
+            mo.match_cap = matches.shape[1]
+        self._chk(lib().vslam_match_dev(self._h, C.byref(query), C.byref(train), n, float(ratio2), int(bool(same_octave)), C.byref(mo)), "vslam_match_dev")
+
+    def match_host(self, q, t, ratio2: float = 0.64, same_octave: bool = False, q_defined=None, t_defined=None, q_points=None, t_points=None,
+                   match_cap: int | None = None):
+        """vslam_match_host: one pair of numpy descriptor arrays [n, 128] -> (nn [nq] NN2_DTYPE, matches MATCH_DTYPE, total accepted)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 128)
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in
+               ((q_defined, np.uint8), (q_points, POINT_DTYPE), (t_defined, np.uint8), (t_points, POINT_DTYPE))]
+        for a, rows in zip(opt, (len(q), len(q), len(t), len(t))):
+            if a is not None and a.size != rows:
+                raise ValueError("match_host: defined / points must have one entry per descriptor row")
+        ptr = [None if a is None else a.ctypes.data for a in opt]
+        cap = max(len(q), 1) if match_cap is None else int(match_cap)
+        nn = np.zeros(len(q), NN2_DTYPE)
+        matches = np.zeros(cap, MATCH_DTYPE)
+        total = C.c_size_t()
+        self._chk(lib().vslam_match_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), float(ratio2),
+                                         int(bool(same_octave)), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_host")
+        return nn, matches[: min(total.value, cap)], total.value
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -223,6 +223,33 @@ struct OrientBatchEntries {  // entry = one survivor of a frame: 36-bit mask of 
     }
 };
 
+struct MatchEntries {  // entry = 64 consecutive query rows of a pair: bits = accepted queries
+    static constexpr int WORDS = 1;
+    struct Info {
+        unsigned int first;
+    };
+    const unsigned long long* flags;
+    size_t fwords;
+    const vslam_nn2* nn;
+    unsigned int qcap;
+    vslam_match* out;
+    __device__ size_t count() const { return fwords; }
+    __device__ unsigned int load(int f, size_t e, unsigned long long (&w)[4]) const {
+        w[0] = flags[f * fwords + e];
+        return __popcll(w[0]);
+    }
+    __device__ Info info(int, size_t e) const { return Info{(unsigned int)(e * 64)}; }
+    __device__ void emit(int f, const Info& in, const unsigned long long (&w)[4], unsigned int k, size_t slot) const {
+        const unsigned int q = in.first + (unsigned int)select64(w[0], k);
+        const vslam_nn2 r = nn[(size_t)f * qcap + q];
+        vslam_match m;
+        m.query = (int)q;
+        m.train = r.index;
+        m.dist2 = r.dist2;
+        out[slot] = m;
+    }
+};
+
 // Block-wide exclusive scan for 256 threads; `total` = block sum.
 __device__ __forceinline__ unsigned int block_excl_scan_256(unsigned int v, unsigned int* wsum, unsigned int& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -30,6 +30,7 @@
 #include "kernels_extrema_dense.hip.h"
 #include "vslam_internal.h"
 #include "vslam_ctx.h"
+#include "vslam_launch.h"
 #include "vslam_mx.h"
 
 using namespace vslam;
@@ -51,23 +52,8 @@ static const char* const kKernelNames =
     "k_resize_linear2x\nk_blur_h_generic\nk_blur_v_generic\n"
     "k_dog5\nk_resize_nearest_half\nk_extrema\nk_pyr_octave\nk_pyr_octave_mx\n"
     "k_gauss_v_strip\nk_gauss_h_strip\nk_gauss_h_diff\nk_resize_linear2x_slide\nk_resize_nearest_half_v4\nk_extrema_w3\nk_extrema_dense\nk_localize_points\nk_orient_keypoints\nk_edge_response_windows\nk_level_gradients\nk_pack_rows\nk_edge_flags\nk_survivor_ranges\nk_orient_survivors\n"
-    "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals";
-
-
-// Launch on `stream` with `lds` bytes of dynamic LDS, bracketed for the timing hook as "name@tag".
-#define LAUNCH_ON(ctx, name, tag, stream, lds, kern, grid, block, ...)        \
-    do {                                                                      \
-        {                                                                     \
-            TimedScope ts_(ctx, name, tag, stream);                           \
-            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);  \
-        }                                                                     \
-        HIPCHK(ctx, hipGetLastError());                                       \
-    } while (0)
-// ... on the context stream, no dynamic LDS, tagged with the octave being enqueued.
-#define LAUNCH(ctx, name, kern, grid, block, ...) LAUNCH_ON(ctx, name, (ctx)->launch_tag, (ctx)->stream, 0, kern, grid, block, __VA_ARGS__)
-
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+    "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals\n"
+    "k_desc_norms\nk_match_nn2\nk_match_merge";
 
 
 // Runs `body` with the context's launch stream temporarily replaced (LAUNCH uses ctx->stream).
@@ -116,7 +102,7 @@ static void block_release(vslam_ctx* c, void* p, size_t cap) {
         (void)hipFree(p);
 }
 
-static int ws_reserve(vslam_ctx* c, size_t bytes) {
+int vslam::ws_reserve(vslam_ctx* c, size_t bytes) {
     if (bytes <= c->ws_cap) return VSLAM_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < vslam_ctx::kAux; ++i)
@@ -129,43 +115,6 @@ static int ws_reserve(vslam_ctx* c, size_t bytes) {
     c->ws_cap = want;
     return VSLAM_OK;
 }
-
-// The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
-// and commit() reserves the sum and sets every pointer: the size reserved cannot differ from the size handed out.
-// Buffers lie in the order of the add() calls, each on a 256-byte boundary.  No heap: the per-image entry points are
-// bound by launch latency, so a request list costs them nothing but a few stores.
-// (anonymous namespace, here and below: the member functions of these host-only types stay out of the library's dynamic symbols)
-namespace {
-class WsPlan {
-    struct Slot {
-        void* where;                   // the caller's T*
-        void (*set)(void*, char*);     // stores a T* there
-        size_t off;
-    };
-    static constexpr int kMaxSlots = 32;  // the most any entry point asks for is 18 (vslam_filter_keypoints)
-    Slot slots[kMaxSlots];
-    int n = 0;
-    size_t total = 0;
-
-  public:
-    WsPlan() = default;
-    WsPlan(const WsPlan&) = delete;  // (the slots point at the caller's variables)
-    WsPlan& operator=(const WsPlan&) = delete;
-    template <typename T>
-    void add(T*& p, size_t count) {
-        if (n < kMaxSlots) slots[n] = Slot{&p, [](void* w, char* q) { *static_cast<T**>(w) = reinterpret_cast<T*>(q); }, total};
-        ++n;
-        total += align_up(count * sizeof(T), 256);
-    }
-    // The pointers given to add() must still be where they were: structs that hold them are not moved or copied in between.
-    int commit(vslam_ctx* c) {
-        if (n > kMaxSlots) return fail(c, VSLAM_ERR_NOMEM, "workspace plan: more buffers than WsPlan::kMaxSlots");
-        TRY(ws_reserve(c, total));
-        for (int i = 0; i < n; ++i) slots[i].set(slots[i].where, c->ws + slots[i].off);
-        return VSLAM_OK;
-    }
-};
-}  // namespace
 
 // One-time device tables (tap matrices) are allocated and copied with blocking calls: inside a stream capture that would
 // invalidate the capture, so a call that still needs one says so instead (include/vslam.h: the warm-up call must run with
@@ -416,6 +365,13 @@ static int enqueue_compaction(vslam_ctx* c, const E& ent, size_t entries, int nf
     return VSLAM_OK;
 }
 static inline size_t compaction_ws_elems(size_t entries, int nf) { return (size_t)nf * ((entries + CMP_CHUNK - 1) / CMP_CHUNK) + 64; }
+
+size_t vslam::match_list_ws_elems(size_t fwords, int n_pairs) { return compaction_ws_elems(fwords, n_pairs); }
+int vslam::enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_nn2* nn, unsigned int qcap, int n_pairs,
+                              unsigned int* chunk_ws, vslam_match* matches, unsigned int match_cap, unsigned int* match_counts) {
+    const MatchEntries ent{flags, fwords, nn, qcap, matches};
+    return enqueue_compaction(c, ent, fwords, n_pairs, chunk_ws, matches ? match_cap : 0u, match_counts, 0);
+}
 
 // The table of the localization's quadratic term, filled by the same device function that the
 // kernels fall back to (so a lookup cannot differ from the computation).

@@ -1,0 +1,69 @@
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip) share to enqueue kernels: the launch macros
+// the timing hook sees, and the context's bump workspace with its per-call plan.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "vslam_ctx.h"
+
+// Launch on `stream` with `lds` bytes of dynamic LDS, bracketed for the timing hook as "name@tag".
+#define LAUNCH_ON(ctx, name, tag, stream, lds, kern, grid, block, ...)        \
+    do {                                                                      \
+        {                                                                     \
+            TimedScope ts_(ctx, name, tag, stream);                           \
+            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);  \
+        }                                                                     \
+        HIPCHK(ctx, hipGetLastError());                                       \
+    } while (0)
+// ... on the context stream, no dynamic LDS, tagged with the octave being enqueued.
+#define LAUNCH(ctx, name, kern, grid, block, ...) LAUNCH_ON(ctx, name, (ctx)->launch_tag, (ctx)->stream, 0, kern, grid, block, __VA_ARGS__)
+
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+namespace vslam {
+// Grows the context's workspace to `bytes` (vslam_hip.hip): waits for the context's streams first, never inside a launch sequence.
+int ws_reserve(vslam_ctx* c, size_t bytes);
+// The match list of vslam_match_dev: count -> scan -> scatter (kernels_compact.hip.h, MatchEntries) over the accepted-query
+// flag words of n_pairs pairs, fwords words each.  The compaction kernels are compiled in vslam_hip.hip, with the other lists'.
+// chunk_ws: scratch of match_list_ws_elems(fwords, n_pairs) u32; matches may be null (totals only).
+size_t match_list_ws_elems(size_t fwords, int n_pairs);
+int enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_nn2* nn, unsigned int qcap, int n_pairs,
+                       unsigned int* chunk_ws, vslam_match* matches, unsigned int match_cap, unsigned int* match_counts);
+}  // namespace vslam
+
+// The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
+// and commit() reserves the sum and sets every pointer: the size reserved cannot differ from the size handed out.
+// Buffers lie in the order of the add() calls, each on a 256-byte boundary.  No heap: the per-image entry points are
+// bound by launch latency, so a request list costs them nothing but a few stores.
+// (anonymous namespace, here and below: the member functions of these host-only types stay out of the library's dynamic symbols)
+namespace {
+class WsPlan {
+    struct Slot {
+        void* where;                   // the caller's T*
+        void (*set)(void*, char*);     // stores a T* there
+        size_t off;
+    };
+    static constexpr int kMaxSlots = 32;  // the most any entry point asks for is 18 (vslam_filter_keypoints)
+    Slot slots[kMaxSlots];
+    int n = 0;
+    size_t total = 0;
+
+  public:
+    WsPlan() = default;
+    WsPlan(const WsPlan&) = delete;  // (the slots point at the caller's variables)
+    WsPlan& operator=(const WsPlan&) = delete;
+    template <typename T>
+    void add(T*& p, size_t count) {
+        if (n < kMaxSlots) slots[n] = Slot{&p, [](void* w, char* q) { *static_cast<T**>(w) = reinterpret_cast<T*>(q); }, total};
+        ++n;
+        total += align_up(count * sizeof(T), 256);
+    }
+    // The pointers given to add() must still be where they were: structs that hold them are not moved or copied in between.
+    int commit(vslam_ctx* c) {
+        if (n > kMaxSlots) return fail(c, VSLAM_ERR_NOMEM, "workspace plan: more buffers than WsPlan::kMaxSlots");
+        TRY(vslam::ws_reserve(c, total));
+        for (int i = 0; i < n; ++i) slots[i].set(slots[i].where, c->ws + slots[i].off);
+        return VSLAM_OK;
+    }
+};
+}  // namespace

@@ -1,0 +1,69 @@
+// The step the reference's `DoG` executable stops short of (Diff_of_Gauss.cpp:687, "final step is graphing and comparing
+// two images with each other"): the DoG pipeline of DoG.cpp on two images - pyramid, initialKeypointDetection,
+// filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
+// second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.
+//   usage: Match [first.pgm second.pgm | WxH] [octaves, default 4]      (WxH: frames 0 and 1 of the synthetic stream)
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+
+#include "imgio.hpp"
+#include "vslam_cxx.hpp"
+
+using namespace cv;
+
+namespace {
+struct Described {
+    std::vector<std::vector<float>> descriptors;
+    std::vector<unsigned char> defined;
+    size_t n_defined = 0;
+};
+
+Described describe(Mat img, int numOctaves) {  // (the reference's constructor takes a non-const Mat&)
+    Described out;
+    GaussPyramid pyramid{img, numOctaves, 1.6};
+    for (int octave = 0; octave < pyramid.getNumOctaves(); ++octave) {
+        std::vector<SLAM::point> keypoints, reducedKeypoints;
+        initialKeypointDetection(keypoints, pyramid, octave, 3);
+        filterKeypoints(pyramid, octave, keypoints, reducedKeypoints);
+        std::vector<unsigned char> defined;
+        SIFT(reducedKeypoints, out.descriptors, pyramid, octave, &defined);
+        out.defined.insert(out.defined.end(), defined.begin(), defined.end());
+    }
+    for (unsigned char d : out.defined) out.n_defined += d != 0;
+    return out;
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+    try {
+        Mat first, second;
+        int w = 0, h = 0, next = 2;
+        if (argc < 2) {
+            first = imgio::synthetic(384, 512, 0), second = imgio::synthetic(384, 512, 1);
+        } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
+            first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
+        } else {
+            if (argc < 3) throw std::runtime_error("usage: Match [first.pgm second.pgm | WxH] [octaves]");
+            first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
+            next = 3;
+        }
+        const int numOctaves = argc > next ? std::atoi(argv[next]) : 4;
+        const auto t0 = std::chrono::steady_clock::now();
+        const Described q = describe(first, numOctaves), t = describe(second, numOctaves);
+        const vslam::Matches m = vslam::matchDescriptors(q.descriptors, t.descriptors, 0.8f, &q.defined, &t.defined);
+        const auto t1 = std::chrono::steady_clock::now();
+        size_t exact = 0, nearest = 0;
+        for (const vslam_nn2& r : m.nn) nearest += r.index >= 0;
+        for (const vslam_match& a : m.matches) exact += a.dist2 == 0.0f;
+        std::printf("{\"exe\": \"Match\", \"octaves\": %d, \"query\": {\"rows\": %d, \"cols\": %d, \"descriptors\": %zu, \"defined\": %zu}, "
+                    "\"train\": {\"rows\": %d, \"cols\": %d, \"descriptors\": %zu, \"defined\": %zu}, \"with_nearest\": %zu, \"accepted\": %zu, "
+                    "\"zero_distance\": %zu, \"ratio\": 0.8, \"ms\": %.3f}\n",
+                    numOctaves, first.rows, first.cols, q.descriptors.size(), q.n_defined, second.rows, second.cols, t.descriptors.size(), t.n_defined,
+                    nearest, m.matches.size(), exact, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "Match: %s\n", e.what());
+        return EXIT_FAILURE;
+    }
+}

@@ -440,3 +440,31 @@ void writeFeatureDescriptors(const std::string& file_name, const std::vector<std
     if (vslam_descriptor_file_write(file_name.c_str(), flat.data(), v.size()) != VSLAM_OK)
         throw vslam::Error(VSLAM_ERR_INVALID, "writeFeatureDescriptors: cannot write " + file_name);
 }
+
+// ---- matching (the step after SIFT; no reference counterpart beyond the comment at Diff_of_Gauss.cpp:687) ---------
+
+vslam::Matches vslam::matchDescriptors(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train, float ratio,
+                                       const std::vector<unsigned char>* query_defined, const std::vector<unsigned char>* train_defined) {
+    auto flatten = [](const std::vector<std::vector<float>>& v, const std::vector<unsigned char>* defined) {
+        require(!defined || defined->size() == v.size(), "matchDescriptors: one defined flag per descriptor");
+        std::vector<float> flat;
+        flat.reserve(128 * v.size());
+        for (const auto& d : v) {
+            require(d.size() == 128, "matchDescriptors: a descriptor is not 128 floats");
+            flat.insert(flat.end(), d.begin(), d.end());
+        }
+        return flat;
+    };
+    const std::vector<float> q = flatten(query, query_defined), t = flatten(train, train_defined);
+    vslam::Matches out;
+    out.nn.resize(query.size());
+    out.matches.resize(query.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_match_host(c, q.data(), query_defined ? query_defined->data() : nullptr, nullptr, query.size(), t.data(),
+                                  train_defined ? train_defined->data() : nullptr, nullptr, train.size(), ratio * ratio, 0,
+                                  out.nn.empty() ? nullptr : out.nn.data(), out.matches.empty() ? nullptr : out.matches.data(), out.matches.size(), &total),
+                 c, "matchDescriptors");
+    out.matches.resize(total);
+    return out;
+}

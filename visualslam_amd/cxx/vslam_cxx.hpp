@@ -175,3 +175,16 @@ void SIFT(std::vector<SLAM::point>& reducedKeypoints, std::vector<std::vector<fl
           GaussPyramid& pyramid, int octave, std::vector<unsigned char>* defined = nullptr);
 // featureDescriptors.dat exactly as Diff_of_Gauss.cpp:837-863 writes it (vslam_descriptor_file_write).
 void writeFeatureDescriptors(const std::string& file_name, const std::vector<std::vector<float>>& featureDescriptors_vec);
+
+// The step Diff_of_Gauss.cpp:687 leaves open ("final step is graphing and comparing two images with each other"): every
+// query descriptor's nearest and second-nearest train descriptor and Lowe's ratio test, exact, on the GPU (vslam_match_host;
+// the arithmetic is stated in include/vslam.h).  The two vectors are what SIFT() fills; `ratio` is squared once in f32.
+// *_defined: the flags SIFT() returns (null = all defined; undefined rows neither match nor are matched).
+namespace vslam {
+struct Matches {
+    std::vector<vslam_nn2> nn;         // one per query descriptor: {train index or -1, dist2, second_dist2}
+    std::vector<vslam_match> matches;  // the accepted queries, ascending query order
+};
+Matches matchDescriptors(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train, float ratio = 0.8f,
+                         const std::vector<unsigned char>* query_defined = nullptr, const std::vector<unsigned char>* train_defined = nullptr);
+}  // namespace vslam
