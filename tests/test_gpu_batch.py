@@ -707,6 +707,52 @@ def test_stream_tuner_never_blocks_the_host():
         ctx.close()
 
 
+def test_contexts_closed_in_mid_comparison_and_at_every_level_leave_results_alone():
+    # Every stream and event of a context has one owner, which vslam_ctx_destroy empties: (1) a context closed while the
+    # tuner is comparing (three calls: candidate pair 1 and two pairs of timing events exist, pair 2 does not) closes without
+    # error, and a fresh context then gives the same bytes; (2) so do contexts pinned to levels 0, 1 and 2, closed after one call.
+    import torch
+
+    capi.build()
+    frames = synth.frames_np(32, 120, 160, stream_id=5)
+    keys = ("harris_kps", "harris_counts", "dog_points", "dog_counts", "nms_mask", "extrema_bits")
+
+    def close_ok(ctx):
+        h, ctx._h = ctx._h, None
+        assert capi.lib().vslam_ctx_destroy(h) == 0
+        torch.cuda.synchronize()  # (work left behind or a handle destroyed twice would surface here as a HIP error)
+
+    def blob(ctx):
+        _, _, out = run_batch(ctx, torch, frames)
+        return b"".join(out[k].tobytes() for k in keys)
+
+    ctx = capi.Context(0, torch.cuda.current_stream().cuda_stream)
+    try:
+        ctx.set_side_stream_priority(True)
+        ctx.tune_side_streams(True)
+        got = [blob(ctx) for _ in range(3)]
+        assert ctx.side_stream_report() == (0, 1)  # in mid-comparison
+        close_ok(ctx)
+    finally:
+        ctx.close()
+    assert got[1] == got[0] and got[2] == got[0]
+    ctx = capi.Context(0, torch.cuda.current_stream().cuda_stream)
+    try:
+        assert blob(ctx) == got[0]
+        close_ok(ctx)
+    finally:
+        ctx.close()
+    for level in (0, 1, 2):
+        ctx = capi.Context(0, torch.cuda.current_stream().cuda_stream)
+        try:
+            ctx.pin_side_streams(level)
+            assert blob(ctx) == got[0], level
+            assert ctx.join_watch_report()[:2] == (level, True)
+            close_ok(ctx)
+        finally:
+            ctx.close()
+
+
 def test_join_watchdog_levels_give_the_same_results_and_the_watch_ends():
     # the library itself notices when its low-priority side streams are held up (the main stream's wait at
     # the end of a call exceeds 3 % of the call) and tries the next form - side streams at the main stream's priority (level 1),

@@ -1,5 +1,6 @@
 // The context of the C ABI and the pieces every translation unit of the library shares: error plumbing, the bench
-// timing hook's scope object, and the interface of the side-stream scheduling unit (vslam_sched.cpp).
+// timing hook's scope object, and the interface of the side-stream scheduling unit (vslam_sched.cpp; its decisions are
+// in vslam_sched_policy.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/vslam.h"
+#include "vslam_sched_policy.h"
 
 // Diagnostic environment switches (the reference paths of VSLAM_HDIFF and VSLAM_ORIENT_SCALAR) exist only in a build with
 // -DVSLAM_DIAGNOSTICS (lib/libvslam_diag.so, `make diag`): the shipped library never reads them.
@@ -23,66 +25,13 @@
 #define VSLAM_DIAG_ENV(name) (static_cast<const char*>(nullptr))
 #endif
 
-// Which pair of low-priority side streams the batched path runs on: see "side-stream placement" below.
-struct StreamTuner {
-    static constexpr int K = 3;                      // candidate pairs
-    static constexpr int M = K + 1;                  // measured calls: pair 0, 1, 2, 0
-    hipStream_t cand[K][2] = {};                     // cand[0] = the pair ensure_aux created
-    hipEvent_t t0[M] = {}, t1[M] = {};
-    int measured = 0;                                // calls measured so far
-    int measuring = -1;                              // slot being measured by the current call
-    bool enabled = false;                            // vslam_ctx_tune_side_streams (or VSLAM_STREAM_TUNER=1 when the context was created)
-    bool done = false;
-    int chosen = 0;
-    unsigned long long key = 0;                      // shape of the calls being compared (0: none yet)
-    int calls = 0, resets = 0;
-};
-
-// Side-stream priority and the join watchdog (round 5).
-// The batched path's two side streams (Harris chain; scans and lists) may run at the LOWEST stream priority, so that they
-// yield to the octave kernels, or at the main stream's.  Which is faster is decided by the hardware queue each stream
-// happens to land on (HIP multiplexes streams onto GPU_MAX_HW_QUEUES queues per priority level, default 4; DESIGN section
-// 5.4).  Same box, C++ host, device-resident, frames/s with 2 / 3 / 4 / 6 / 12 queues: yielding 14.1 k / 11.5 k / 13.4 k /
-// 14.0 k / 14.0 k, same priority 13.7 k / 13.7 k / 14.0 k / 13.7 k / 14.2 k - yielding wins 2-3 % on a lucky layout and
-// loses 18 % on an unlucky one (a low-priority queue behind the main queue's barrier packet crawls), same priority never
-// moves more than 3.5 %.  The default is therefore the SAME priority (level 1): a caller that embeds the library in a
-// process with streams of its own gets a sane schedule with HIP's default queue count, without setting an environment
-// variable or opting in to anything.  A host that owns its queue layout asks for yielding streams (level 0) with
-// vslam_ctx_set_side_stream_priority / VSLAM_SIDE_PRIORITY=low (Stream's host-fed mode, which also asks for 12 queues).
-//
-// The watchdog keeps either choice honest.  The first full-size batch calls of a context are bracketed by three events on
-// the main stream - start, "my own kernels are enqueued up to here" (just before the waits on the side streams' join
-// events) and end.  t(end) - t(own) is how long the main stream sat waiting for side work: 0.4 % of an 18 ms batch when
-// the side streams run freely, 5 % with yielding streams on four queues, 20 % when one of them is being starved.  A later
-// call reads the events once they are complete (hipEventQuery: nothing ever waits on the host).  Three measured calls with
-// a median lag above the level's limit (3 % at level 0, 10 % at level 1) start a TRIAL of the next level - same priority,
-// then no side streams at all (level 2) - and the trial is kept only if its fastest call beats the previous level's fastest
-// by 1 %; otherwise the context goes back.  Either way the watch ends after at most ten measured calls.  Off while a capture
-// is on, while the opt-in tuner is comparing pairs, and under VSLAM_JOIN_WATCH=0; vslam_ctx_pin_side_streams pins a level.
-// Results never depend on the level.
-struct JoinWatch {
-    static constexpr int RING = 4, NEED = 3;
-    hipEvent_t t0[RING] = {}, tm[RING] = {}, t1[RING] = {};
-    bool live[RING] = {};       // events of slot i are recorded and not yet read
-    int head = 0;               // next slot to record
-    int recording = -1;         // slot of the call being enqueued
-    int calls = 0;              // eligible calls at the current level (the first is not measured)
-    int n_meas = 0;             // measurements at the current level
-    float lag[NEED] = {}, best_total = 0.0f;
-    float level_best[3] = {0.0f, 0.0f, 0.0f};  // fastest measured call at each level tried
-    int level = 1;              // 0: low-priority (yielding) side streams, 1: the main stream's priority, 2: no side streams
-    int trial_from = -1;        // the level a running trial came from (-1: the current level is not a trial)
-    unsigned long long key = 0; // shape of the calls being measured (only calls of one shape are compared)
-    int restarts = 0;
-    bool done = false, disabled = false, pinned = false;
-    float last_lag_frac = -1.0f;
-    hipStream_t pair[2][2] = {};  // the side-stream pairs of levels 0 and 1 (both live until the context goes)
-};
-
 struct vslam_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // Every stream and event created for this context (own_stream / own_event in vslam_sched.cpp), the context's own main
+    // stream included: vslam_ctx_destroy destroys what is listed here and nothing else.  Every other handle below is borrowed.
+    vslam::Owned<hipStream_t> streams;
+    vslam::Owned<hipEvent_t> events;
     std::string err;
     // bump workspace in HBM, grown between calls only (never inside a launch sequence)
     char* ws = nullptr;
@@ -104,10 +53,12 @@ struct vslam_ctx {
     static constexpr int kAux = 3;
     hipStream_t aux[kAux] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kAux] = {nullptr, nullptr, nullptr}, ev_oct[VSLAM_MAX_OCTAVES] = {};
-    int prio_lo = 0;      // priority of the two side streams in use (0: the main stream's)
     int prio_dev_lo = 0;  // the device's lowest stream priority (0: it has no priority levels)
-    StreamTuner tuner;    // which pair of side streams the batched path runs on (see StreamTuner)
-    JoinWatch watch;      // steps the side streams down when their join lags (see JoinWatch)
+    vslam::PairSlots<hipStream_t> pairs;  // the side-stream pairs in existence; aux[0], aux[1] are one of them
+    vslam::StreamTuner tuner;  // which pair of side streams the batched path runs on (vslam_sched_policy.h)
+    hipEvent_t tuner_ev[vslam::StreamTuner::M][2] = {};  // start, end of each timed call
+    vslam::JoinWatch watch;  // steps the side streams down when their join lags (vslam_sched_policy.h)
+    hipEvent_t watch_ev[vslam::JoinWatch::RING][3] = {};  // start, own work enqueued, end of each measured call
     hipEvent_t ev_phase = nullptr;  // recorded by every vslam_detect_batch_dev call once its octave-0 kernels are enqueued (vslam_ctx_follow)
     bool phase_marked = false;
     hipEvent_t ev_up2 = nullptr;  // the second half of a batch has been upsampled (enqueue_dog)
@@ -161,17 +112,29 @@ static inline int bind_device(vslam_ctx* c) {
     return VSLAM_OK;
 }
 
-// ---- vslam_sched.cpp: side-stream placement, the join watchdog, the bench timing hook -----------------------------
+// ---- vslam_sched.cpp: the owner of the context's streams and events, the fork / join of a batch call, the timing hook
 namespace vslam {
-void sched_init_from_env(vslam_ctx* c);   // VSLAM_JOIN_WATCH, VSLAM_SIDE_PRIORITY, VSLAM_STREAM_TUNER (vslam_ctx_create)
-void sched_destroy(vslam_ctx* c);         // side streams, their events, the hook's events (vslam_ctx_destroy)
-int sched_ensure_aux(vslam_ctx* c);       // creates the side streams and the fork / join events on the first batch call
-// Before the fork of a batch call: read finished measurements, move between the levels, start this call's measurement.
-int sched_watch_before_call(vslam_ctx* c, unsigned long long key, bool eligible, bool capturing);
-// The opt-in tuner: picks the pair of (yielding) side streams this call uses / closes the call's measurement.
-int sched_tuner_before_call(vslam_ctx* c, unsigned long long key, bool eligible);
-int sched_tuner_after_call(vslam_ctx* c);
+void sched_init_from_env(vslam_ctx* c);  // VSLAM_JOIN_WATCH, VSLAM_SIDE_PRIORITY, VSLAM_STREAM_TUNER (vslam_ctx_create)
+int own_stream(vslam_ctx* c, int priority, hipStream_t* out);  // non-blocking; priority 0: the default one
+int own_event(vslam_ctx* c, unsigned flags, hipEvent_t* out);
+void sched_destroy(vslam_ctx* c);  // waits for every stream of the context, then destroys every handle it owns (vslam_ctx_destroy)
+int sched_mark_phase(vslam_ctx* c);  // records ev_phase on the current stream (vslam_ctx_follow)
 std::pair<hipEvent_t, hipEvent_t>* timing_slot(vslam_ctx* c);
+
+// The fork and join of one vslam_detect_batch_dev call.  begin: the side streams exist (created on the context's first
+// call), the watchdog and the tuner have had their say, and - unless the watchdog is at level 2 - aux[] wait for the main
+// stream.  end (the main stream's own work is enqueued): aux[] are joined back, the call's measurements are closed.  A call
+// that returns early in between leaves the scope with the fork open: the side streams are drained, so that they cannot run
+// into buffers the caller (or the next ws_reserve) reuses.
+struct BatchFork {
+    vslam_ctx* c;
+    bool side = false;  // the call has side streams
+    bool open = false;
+    // `eligible`: a full-size batch with both paths (what the tuner compares); `big`: one the watchdog measures too
+    int begin(unsigned long long key, bool eligible, bool big, bool capturing);
+    int end();
+    ~BatchFork();
+};
 }  // namespace vslam
 
 // Brackets the launches made inside its scope with HIP events on the context stream when the

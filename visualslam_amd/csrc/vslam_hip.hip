@@ -511,15 +511,6 @@ static int enqueue_pyr_octave_mx(vslam_ctx* c, double sigma0, int o, const OctPl
     return VSLAM_OK;
 }
 
-// vslam_ctx_follow: the point of a batch call, the end of octave 0, behind which a second context's batch may start (its
-// heavy octave-0 kernels then run beside this call's remaining, shorter kernels instead of beside its own octave 0).
-static int mark_phase(vslam_ctx* c) {
-    if (!c->ev_phase) HIPCHK(c, hipEventCreateWithFlags(&c->ev_phase, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_phase, c->stream));
-    c->phase_marked = true;
-    return VSLAM_OK;
-}
-
 // The octave whose kernels the held-back side work of a batch waits for (enqueue_dog): the last
 // LDS-tiled one for batches of 32 frames or more, -1 (no gate) otherwise.
 static int dog_side_gate(const std::vector<OctPlan>& plans, int nf) {
@@ -752,7 +743,7 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
                    dim3(256), io.oct + (size_t)3 * P, out.pframe, pitch, s.bases + s.base_off[o + 1], s.bases_frame, L.pitch[o + 1], rows,
                    L.rows[o + 1], L.cols[o + 1]);
         if (side) HIPCHK(c, hipEventRecord(c->ev_oct[o], c->stream));
-        if (o == 0) TRY(mark_phase(c));
+        if (o == 0) TRY(sched_mark_phase(c));
         if (run.after_octave) TRY(run.after_octave(o));  // octave o's kernels are enqueued and ev_oct[o] marks their end
         if (o < gate) continue;  // scan + compaction of this octave are enqueued behind octave `gate`
         // ... which is when the octaves held back until then get theirs, in order
@@ -856,12 +847,9 @@ int vslam_ctx_create(int device, void* stream, vslam_ctx** out) {
         c->stream = nullptr;  // the NULL stream itself: every HIP call below takes it as "stream 0"
     } else if (stream) {
         c->stream = (hipStream_t)stream;
-    } else {
-        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete c;
-            return VSLAM_ERR_HIP;
-        }
-        c->own_stream = true;
+    } else if (own_stream(c, 0, &c->stream) != VSLAM_OK) {
+        delete c;
+        return VSLAM_ERR_HIP;
     }
     {
         const char* e = std::getenv("VSLAM_MX");
@@ -896,19 +884,12 @@ int vslam_ctx_destroy(vslam_ctx* c) {
     if (!c) return VSLAM_ERR_INVALID;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (int i = 0; i < vslam_ctx::kAux; ++i)  // a failed batch call may have left side-stream work un-joined
-        if (c->aux[i]) (void)hipStreamSynchronize(c->aux[i]);
+    sched_destroy(c);  // every stream and event the context owns
     for (auto& kv : c->tables) (void)hipFree(kv.second);
     if (c->ws) (void)hipFree(c->ws);
     for (auto& b : c->block_cache) (void)hipFree(b.second);
     if (c->loc_lut) (void)hipFree(c->loc_lut);
     if (c->dump) (void)hipFree(c->dump);
-    sched_destroy(c);
-    for (hipEvent_t e : {c->ev_phase, c->ev_up2, c->ev_chunk, c->ev_pack, c->ev_list0, c->ev_edge, c->ev_or_fork, c->ev_or_join[0], c->ev_or_join[1]})
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->ev_oct)
-        if (e) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return VSLAM_OK;
 }
@@ -1826,36 +1807,14 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     // back); each alone reproduces the crash.  While a capture is on, both stay on the list stream; everything else forks
     // from and joins to the main (origin) stream.
     const bool capturing = stream_is_capturing(c);  // the nested forks stay out of a capture
-    hipStream_t sh = c->stream, sx = nullptr;  // Harris stream, extrema stream (nullptr = main)
-    // Any early return between the fork and the join must not leave the side streams running into
-    // buffers the caller (or the next ws_reserve) is about to reuse: drain them on the error path.
-    struct ForkGuard {
-        vslam_ctx* c;
-        bool armed = false;
-        ~ForkGuard() {
-            if (!armed) return;
-            for (int i = 0; i < vslam_ctx::kAux; ++i)
-                if (c->aux[i]) (void)hipStreamSynchronize(c->aux[i]);
-            (void)hipStreamSynchronize(c->stream);
-        }
-    } guard{c};
     // the shape of this call (the stream tuner and the join watchdog compare calls of one shape only)
     const unsigned long long call_key = ((unsigned long long)(unsigned)n_frames << 40) ^ ((unsigned long long)(unsigned)p.rows << 20) ^ (unsigned)p.cols ^
                                         ((unsigned long long)(p.localize + 2 * p.orient + 4 * p.extrema_dense + 8 * (out->descriptors != nullptr)) << 60) ^
                                         ((unsigned long long)(unsigned)p.n_octaves << 56) ^ ((unsigned long long)(c->mx ? 1 : 0) << 39);
-    TRY(sched_ensure_aux(c));
-    // (calls of a few megapixels are dominated by launch latencies: their lag says nothing about starvation)
-    TRY(sched_watch_before_call(c, call_key, dog && harris && n_frames >= 32 && (size_t)n_frames * N >= ((size_t)16 << 20), capturing));
-    const bool side_streams = c->watch.level != 2;  // the watchdog's last step: everything on the caller's stream
-    if (side_streams) {
-        // the side-stream pair of this call (StreamTuner): only full-size batches with both paths are compared
-        TRY(sched_tuner_before_call(c, call_key, dog && harris && n_frames >= 32));
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        for (int i = 0; i < vslam_ctx::kAux; ++i) HIPCHK(c, hipStreamWaitEvent(c->aux[i], c->ev_fork, 0));
-        sh = c->aux[0];
-        sx = c->aux[1];
-        guard.armed = true;
-    }
+    BatchFork fork{c};  // (an early return below drains the side streams)
+    TRY(fork.begin(call_key, dog && harris && n_frames >= 32, (size_t)n_frames * N >= ((size_t)16 << 20), capturing));
+    const bool side_streams = fork.side;
+    const hipStream_t sh = side_streams ? c->aux[0] : c->stream, sx = side_streams ? c->aux[1] : nullptr;  // Harris stream, extrema stream (nullptr = main)
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int nf = std::min(chunk, n_frames - f0);
         const uint8_t* fr = d_frames + (size_t)f0 * frame_stride;
@@ -1909,21 +1868,7 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
             }
         }
     }
-    if (c->watch.recording >= 0) HIPCHK(c, hipEventRecord(c->watch.tm[c->watch.recording], c->stream));  // the main stream's own work ends here
-    if (side_streams)  // join
-        for (int i = 0; i < vslam_ctx::kAux; ++i) {
-            HIPCHK(c, hipEventRecord(c->ev_join[i], c->aux[i]));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[i], 0));
-        }
-    if (c->watch.recording >= 0) {
-        HIPCHK(c, hipEventRecord(c->watch.t1[c->watch.recording], c->stream));
-        c->watch.live[c->watch.recording] = true;
-        c->watch.recording = -1;
-    }
-    if (!c->phase_marked) TRY(mark_phase(c));  // no DoG path in this call: its end is the mark
-    if (side_streams) TRY(sched_tuner_after_call(c));
-    guard.armed = false;
-    return VSLAM_OK;
+    return fork.end();
 }
 
 

@@ -1,18 +1,48 @@
-// Side-stream placement (the opt-in stream tuner), the join watchdog and the bench timing hook of the batched path:
-// host-side scheduling code only, no kernels.  Kept apart from the C ABI / launch plan (vslam_hip.hip).
+// The owner of a context's streams and events, the fork / join of a batch call (side-stream placement, the join watchdog:
+// the decisions themselves are in vslam_sched_policy.h) and the bench timing hook: host-side scheduling code only, no
+// kernels.  Kept apart from the C ABI / launch plan (vslam_hip.hip).
 #include "vslam_ctx.h"
 
 #include <algorithm>
 
 namespace vslam {
 
+// ---- the owner -------------------------------------------------------------------------------------------------------
+// Every stream and event of a context is created here and listed once (vslam_ctx::streams / events); teardown destroys
+// the lists, an early release takes the handle off its list first.  Nothing else creates or destroys a handle.
+int own_stream(vslam_ctx* c, int priority, hipStream_t* out) {
+    if (priority == 0 || hipStreamCreateWithPriority(out, hipStreamNonBlocking, priority) != hipSuccess) {
+        (void)hipGetLastError();  // priorities are a speed matter only
+        HIPCHK(c, hipStreamCreateWithFlags(out, hipStreamNonBlocking));
+    }
+    c->streams.add(*out);
+    return VSLAM_OK;
+}
+int own_event(vslam_ctx* c, unsigned flags, hipEvent_t* out) {
+    HIPCHK(c, flags ? hipEventCreateWithFlags(out, flags) : hipEventCreate(out));
+    c->events.add(*out);
+    return VSLAM_OK;
+}
+static void release(vslam_ctx* c, hipStream_t& st) {
+    if (st && c->streams.remove(st)) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
+    st = nullptr;
+}
+static void release(vslam_ctx* c, hipEvent_t& e) {
+    if (e && c->events.remove(e)) (void)hipEventDestroy(e);
+    e = nullptr;
+}
+void sched_destroy(vslam_ctx* c) {
+    for (hipStream_t st : c->streams.list) (void)hipStreamSynchronize(st);  // a failed batch call may have left side-stream work un-joined
+    for (hipEvent_t e : c->events.list) (void)hipEventDestroy(e);
+    for (hipStream_t st : c->streams.list) (void)hipStreamDestroy(st);
+}
+
 std::pair<hipEvent_t, hipEvent_t>* timing_slot(vslam_ctx* c) {
     if (c->timing_used == c->timing_ev.size()) {
         if (c->timing_ev.size() >= 65536) return nullptr;
-        hipEvent_t a, b;
-        if (hipEventCreate(&a) != hipSuccess) return nullptr;
-        if (hipEventCreate(&b) != hipSuccess) {
-            (void)hipEventDestroy(a);
+        hipEvent_t a = nullptr, b = nullptr;
+        if (own_event(c, 0, &a) != VSLAM_OK || own_event(c, 0, &b) != VSLAM_OK) {
+            release(c, a);
             return nullptr;
         }
         c->timing_ev.emplace_back(a, b);
@@ -20,210 +50,102 @@ std::pair<hipEvent_t, hipEvent_t>* timing_slot(vslam_ctx* c) {
     return &c->timing_ev[c->timing_used++];
 }
 
-// ---- side-stream placement ---------------------------------------------------------------------------------------
-// HIP binds every stream to one of GPU_MAX_HW_QUEUES hardware queues per priority level, and the placement is not ours to
-// choose.  Measured: depending on the queue a LOW-priority side stream lands on, the batch runs up
-// to 20 % slower (the same binary: 11.4 k frames/s with 3 queues per level, 14.2 k with 12) - on one bad queue the side
-// kernels crawl while the main stream's queue sits on the barrier that waits for them.  A host that wants the library to
-// look for a better pair OPTS IN (vslam_ctx_tune_side_streams; `Stream --tuner`): the 2nd to 5th full-size batch
-// call of the context then run on three candidate pairs of side streams (the first pair twice), each call bracketed by two
-// events on the main stream, and the first later call that finds all of them complete (hipEventQuery: the entry point stays
-// asynchronous, nothing waits on the host) adopts the fastest pair - the first one unless another is at least 3 % faster.
-// Only calls of one shape are compared (calls of another shape, small or odd calls run on the pair in use and do not
-// disturb the comparison; a caller whose full-size shape keeps changing ends it on the first pair after three restarts);
-// nothing is timed while the stream is being captured.  Results never depend on the streams a call runs on.
-static int tuner_pair_of(int slot) { return slot == StreamTuner::K ? 0 : slot; }
+// vslam_ctx_follow: the point of a batch call, the end of octave 0, behind which a second context's batch may start (its
+// heavy octave-0 kernels then run beside this call's remaining, shorter kernels instead of beside its own octave 0).
+int sched_mark_phase(vslam_ctx* c) {
+    if (!c->ev_phase) TRY(own_event(c, hipEventDisableTiming, &c->ev_phase));
+    HIPCHK(c, hipEventRecord(c->ev_phase, c->stream));
+    c->phase_marked = true;
+    return VSLAM_OK;
+}
 
-static int create_side_stream(vslam_ctx* c, int prio_lo, hipStream_t* out) {
-    if (prio_lo == 0 || hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio_lo) != hipSuccess) {
-        (void)hipGetLastError();  // priorities are a speed matter only
-        HIPCHK(c, hipStreamCreateWithFlags(out, hipStreamNonBlocking));
+// ---- carrying out what the policy (vslam_sched_policy.h) decides ----------------------------------------------------
+// The call runs on the pair in `slot`, created now if the slot is empty (while the other pairs exist: it binds to another queue).
+static int use_pair(vslam_ctx* c, int slot, int priority) {
+    for (int i = 0; i < 2; ++i) {
+        if (!c->pairs.h[slot][i]) TRY(own_stream(c, priority, &c->pairs.h[slot][i]));
+        c->aux[i] = c->pairs.h[slot][i];  // the pair being left is idle: every call joins its side streams back
     }
     return VSLAM_OK;
 }
 
 static void tuner_finish(vslam_ctx* c, int chosen) {
-    StreamTuner& t = c->tuner;
-    t.chosen = chosen;
-    t.done = true;
-    t.measuring = -1;
-    c->aux[0] = t.cand[chosen][0], c->aux[1] = t.cand[chosen][1];
-    // the watchdog's cached pair of this level must be the pair that survives (the other candidates are destroyed below)
-    if (c->watch.level <= 1 && t.cand[chosen][0]) c->watch.pair[c->watch.level][0] = t.cand[chosen][0], c->watch.pair[c->watch.level][1] = t.cand[chosen][1];
-    for (int k = 0; k < StreamTuner::K; ++k) {
-        if (k == chosen) continue;
-        for (hipStream_t& st : t.cand[k])
-            if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st), st = nullptr;
-    }
-    for (int m = 0; m < StreamTuner::M; ++m) {
-        if (t.t0[m]) (void)hipEventDestroy(t.t0[m]), t.t0[m] = nullptr;
-        if (t.t1[m]) (void)hipEventDestroy(t.t1[m]), t.t1[m] = nullptr;
-    }
+    c->tuner.finish(chosen);
+    c->pairs.keep(chosen, [c](hipStream_t& st) { release(c, st); });  // the losers are idle: every measured call has joined them back
+    (void)use_pair(c, kLevel0, 0);  // (live: nothing is created)
+    for (auto& pr : c->tuner_ev)
+        for (hipEvent_t& e : pr) release(c, e);
 }
 
 // Before the fork of a batch call (ensure_aux has run): picks the pair of side streams this call uses.  Never blocks.
-int sched_tuner_before_call(vslam_ctx* c, unsigned long long key, bool eligible) {
+static int tuner_before_call(vslam_ctx* c, unsigned long long key, bool eligible, bool capturing) {
     StreamTuner& t = c->tuner;
-    if (t.done || !t.enabled) return VSLAM_OK;
-    if (c->watch.level > 0) {  // the pairs it compares are yielding ones: at the main stream's priority (or without side
-        t.done = true;         // streams) there is nothing to compare, and the join watchdog must not wait for a verdict
-        return VSLAM_OK;
+    switch (t.before_call(c->watch.level, c->prio_dev_lo != 0, capturing, key, eligible)) {
+    case StreamTuner::kIdle: break;
+    case StreamTuner::kGiveUp: tuner_finish(c, 0); break;
+    case StreamTuner::kFirstPair: TRY(use_pair(c, kLevel0, c->prio_dev_lo)); break;
+    case StreamTuner::kMeasure: {
+        hipEvent_t* ev = c->tuner_ev[t.measured];
+        TRY(use_pair(c, c->pairs.of_candidate(StreamTuner::pair_of(t.measured)), c->prio_dev_lo));
+        for (int j = 0; j < 2; ++j)
+            if (!ev[j]) TRY(own_event(c, 0, &ev[j]));
+        HIPCHK(c, hipEventRecord(ev[0], c->stream));
+        t.started();
+        break;
     }
-    if (c->prio_lo == 0) {  // no priority levels: one pair is as good as another
-        t.done = true;
-        return VSLAM_OK;
-    }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess) (void)hipGetLastError();
-    if (cap != hipStreamCaptureStatusNone) return VSLAM_OK;  // a captured call records no timing events and runs on the pair in use
-    ++t.calls;
-    if (t.calls == 1 || !eligible) return VSLAM_OK;  // the first call pays one-time costs; small / odd calls are not what is being tuned
-    if (t.key == 0) t.key = key;
-    if (key != t.key) {  // another full-size shape: start over with it (the pairs created so far stay), but not for ever
-        if (++t.resets > 3) {
-            tuner_finish(c, 0);
-            return VSLAM_OK;
+    case StreamTuner::kDecide: {  // once the last measured call has finished - until then on the first pair
+        TRY(use_pair(c, kLevel0, c->prio_dev_lo));
+        const hipError_t q = hipEventQuery(c->tuner_ev[StreamTuner::M - 1][1]);
+        if (q == hipErrorNotReady) {
+            (void)hipGetLastError();
+            break;
         }
-        t.key = key;
-        t.measured = 0;
-        c->aux[0] = t.cand[0][0], c->aux[1] = t.cand[0][1];
-        return VSLAM_OK;
+        float ms[StreamTuner::M] = {};
+        bool ok = q == hipSuccess;
+        for (int m = 0; m < StreamTuner::M && ok; ++m) ok = hipEventElapsedTime(&ms[m], c->tuner_ev[m][0], c->tuner_ev[m][1]) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        tuner_finish(c, StreamTuner::choose(ok, ms));
+        break;
     }
-    if (t.measured < StreamTuner::M) {
-        const int m = t.measured, k = tuner_pair_of(m);
-        for (hipStream_t& st : t.cand[k])
-            if (!st) TRY(create_side_stream(c, c->prio_lo, &st));  // created while the other pairs exist: binds to another queue
-        if (!t.t0[m]) HIPCHK(c, hipEventCreate(&t.t0[m]));
-        if (!t.t1[m]) HIPCHK(c, hipEventCreate(&t.t1[m]));
-        c->aux[0] = t.cand[k][0], c->aux[1] = t.cand[k][1];
-        HIPCHK(c, hipEventRecord(t.t0[m], c->stream));
-        t.measuring = m;
-        return VSLAM_OK;
     }
-    // every candidate has been timed: decide once the last measured call has finished - until then on the first pair
-    c->aux[0] = t.cand[0][0], c->aux[1] = t.cand[0][1];
-    const hipError_t q = hipEventQuery(t.t1[StreamTuner::M - 1]);
-    if (q == hipErrorNotReady) {
-        (void)hipGetLastError();
-        return VSLAM_OK;
-    }
-    float ms[StreamTuner::M] = {};
-    bool ok = q == hipSuccess;
-    for (int m = 0; m < StreamTuner::M && ok; ++m) ok = hipEventElapsedTime(&ms[m], t.t0[m], t.t1[m]) == hipSuccess;
-    int best = 0;
-    if (ok) {
-        const float first = std::min(ms[0], ms[StreamTuner::K]);  // pair 0 was timed twice (the early calls run on cold clocks)
-        float best_ms = first;
-        for (int k = 1; k < StreamTuner::K; ++k)
-            if (ms[k] < 0.97f * first && ms[k] < best_ms) best = k, best_ms = ms[k];
-    } else {
-        (void)hipGetLastError();
-    }
-    tuner_finish(c, best);  // the discarded streams are idle (every measured call has joined them back): nothing to wait for
-    return VSLAM_OK;
-}
-
-int sched_tuner_after_call(vslam_ctx* c) {
-    StreamTuner& t = c->tuner;
-    if (t.measuring < 0) return VSLAM_OK;
-    HIPCHK(c, hipEventRecord(t.t1[t.measuring], c->stream));
-    t.measuring = -1;
-    ++t.measured;
     return VSLAM_OK;
 }
 
 // Before the fork of a batch call: reads finished measurements, moves between the levels, starts this call's measurement.
-static int watch_set_level(vslam_ctx* c, int level) {
+static int watch_before_call(vslam_ctx* c, unsigned long long key, bool eligible, bool capturing) {
     JoinWatch& w = c->watch;
-    for (bool& l : w.live) l = false;  // measurements in flight belong to the form being left
-    w.calls = w.n_meas = 0;
-    w.best_total = 0.0f;
-    w.level = level;
-    if (level <= 1) {
-        for (int i = 0; i < 2; ++i) {
-            if (!w.pair[level][i]) TRY(create_side_stream(c, level == 0 ? c->prio_dev_lo : 0, &w.pair[level][i]));
-            c->aux[i] = w.pair[level][i];  // the pair being left is idle: every call joins its side streams back
-        }
-        c->prio_lo = level == 0 ? c->prio_dev_lo : 0;
-    }
-    return VSLAM_OK;
-}
-
-int sched_watch_before_call(vslam_ctx* c, unsigned long long key, bool eligible, bool capturing) {
-    JoinWatch& w = c->watch;
-    w.recording = -1;
-    if (w.done || w.disabled || capturing || (c->tuner.enabled && !c->tuner.done)) return VSLAM_OK;
-    if (eligible && key != w.key) {  // calls of another shape: their times say nothing about the ones measured so far
-        for (bool& l : w.live) l = false;
-        w.calls = w.n_meas = 0;
-        w.best_total = 0.0f;
-        if (w.key != 0 && ++w.restarts > 3) {  // a caller whose shape keeps changing: stop watching (a running trial ends where it started)
-            if (w.trial_from >= 0) TRY(watch_set_level(c, w.trial_from));
-            w.trial_from = -1;
-            w.done = true;
-            return VSLAM_OK;
-        }
-        w.key = key;
-    }
-    if (w.level <= 1 && !w.pair[w.level][0]) w.pair[w.level][0] = c->aux[0], w.pair[w.level][1] = c->aux[1];
+    const int level = w.level;
+    const auto follow = [&]() -> int {  // the policy has moved to another level: its pair (levels 0 and 1) is the one in use now
+        if (w.level == level || w.level > 1) return VSLAM_OK;
+        return use_pair(c, c->pairs.of_level(w.level), w.level == 0 ? c->prio_dev_lo : 0);
+    };
+    if (!w.before_call(key, eligible, capturing, c->tuner.busy())) return follow();
     for (int i = 0; i < JoinWatch::RING; ++i) {
         if (!w.live[i]) continue;
-        const hipError_t q = hipEventQuery(w.t1[i]);
+        hipEvent_t* ev = c->watch_ev[i];
+        const hipError_t q = hipEventQuery(ev[2]);
         if (q == hipErrorNotReady) {
             (void)hipGetLastError();
             continue;
         }
-        w.live[i] = false;
         float total = 0.0f, lag = 0.0f;
-        if (q != hipSuccess || hipEventElapsedTime(&total, w.t0[i], w.t1[i]) != hipSuccess || hipEventElapsedTime(&lag, w.tm[i], w.t1[i]) != hipSuccess || !(total > 0.0f)) {
-            (void)hipGetLastError();
-            continue;
-        }
-        w.last_lag_frac = lag / total;
-        if (w.n_meas < JoinWatch::NEED) {
-            w.lag[w.n_meas++] = lag / total;
-            w.best_total = (w.best_total == 0.0f || total < w.best_total) ? total : w.best_total;
-        }
+        const bool ok = q == hipSuccess && hipEventElapsedTime(&total, ev[0], ev[2]) == hipSuccess && hipEventElapsedTime(&lag, ev[1], ev[2]) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        w.measured(i, ok, total, lag);
     }
-    if (w.n_meas >= JoinWatch::NEED) {
-        const float a = w.lag[0], b = w.lag[1], m = w.lag[2];
-        const float med = std::max(std::min(a, b), std::min(std::max(a, b), m));
-        w.level_best[w.level] = w.best_total;
-        bool keep = true;
-        if (w.trial_from >= 0 && !(w.best_total < 0.99f * w.level_best[w.trial_from])) {  // the trial did not pay: go back, stop
-            TRY(watch_set_level(c, w.trial_from));
-            w.trial_from = -1;
-            w.done = true;
-            keep = false;
-        }
-        if (keep) {
-            w.trial_from = -1;
-            const float limit = w.level == 0 ? 0.03f : 0.10f;
-            if (w.level < 2 && med > limit && (w.level == 1 || c->prio_dev_lo != 0)) {  // (level 0 without priority levels IS level 1)
-                const int from = w.level;
-                TRY(watch_set_level(c, from + 1));
-                w.trial_from = from;
-            } else
-                w.done = true;
-        }
-        if (w.done) return VSLAM_OK;
-    }
-    if (!eligible) return VSLAM_OK;
-    if (++w.calls == 1) return VSLAM_OK;  // the first call of a form pays one-time costs
-    const int slot = w.head;
-    if (w.live[slot]) return VSLAM_OK;  // the host is more than RING calls ahead: skip this one
-    if (!w.t0[slot]) {
-        HIPCHK(c, hipEventCreate(&w.t0[slot]));
-        HIPCHK(c, hipEventCreate(&w.tm[slot]));
-        HIPCHK(c, hipEventCreate(&w.t1[slot]));
-    }
-    HIPCHK(c, hipEventRecord(w.t0[slot], c->stream));
-    w.recording = slot;
-    w.head = (slot + 1) % JoinWatch::RING;
+    w.decide();
+    TRY(follow());
+    const int slot = w.start(eligible);
+    if (slot < 0) return VSLAM_OK;
+    for (hipEvent_t& e : c->watch_ev[slot])
+        if (!e) TRY(own_event(c, 0, &e));
+    HIPCHK(c, hipEventRecord(c->watch_ev[slot][0], c->stream));
     return VSLAM_OK;
 }
 
-int sched_ensure_aux(vslam_ctx* c) {
+// The side streams and the fork / join events, on the context's first batch call.  (Queue placement depends on the order
+// of creation, DESIGN section 5.4: everything is created here, in this order, whether the call will use it or not.)
+static int ensure_aux(vslam_ctx* c) {
     if (c->ev_fork) return VSLAM_OK;
     int prio_lo = 0, prio_hi = 0;
     if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) {  // numerically: lowest priority, highest priority
@@ -231,29 +153,60 @@ int sched_ensure_aux(vslam_ctx* c) {
         prio_lo = 0;
     }
     c->prio_dev_lo = prio_lo;
-    if (prio_lo == 0 && c->watch.level == 0) c->watch.level = 1;  // no priority levels on this device
-    c->prio_lo = c->watch.level >= 1 ? 0 : prio_lo;
+    c->watch.device(prio_lo != 0);
+    hipStream_t* pair = c->pairs.h[c->pairs.of_level(c->watch.level)];  // (a context pinned to level 2 never uses it)
     for (int i = 0; i < vslam_ctx::kAux; ++i) {
         // aux[0], aux[1] (Harris chain, scans and lists) yield to the octave kernels; aux[2] carries only the
         // second-half upsample, which the main stream WAITS for: at low priority it was starved for the whole
         // first-half octave kernel whenever its start slipped behind that kernel's (C++ host, 0.35 ms per step)
-        if (i == 2)
-            HIPCHK(c, hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
-        else
-            TRY(create_side_stream(c, c->prio_lo, &c->aux[i]));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
+        TRY(own_stream(c, i < 2 && c->watch.level == 0 ? prio_lo : 0, &c->aux[i]));
+        if (i < 2) pair[i] = c->aux[i];
+        TRY(own_event(c, hipEventDisableTiming, &c->ev_join[i]));
     }
-    c->tuner.cand[0][0] = c->aux[0], c->tuner.cand[0][1] = c->aux[1];
-    for (auto& e : c->ev_oct) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_up2, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_chunk, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_pack, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_list0, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_edge, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_or_fork, hipEventDisableTiming));
-    for (auto& e : c->ev_or_join) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    for (auto& e : c->ev_oct) TRY(own_event(c, hipEventDisableTiming, &e));
+    for (hipEvent_t* e : {&c->ev_up2, &c->ev_chunk, &c->ev_pack, &c->ev_list0, &c->ev_edge, &c->ev_or_fork, &c->ev_or_join[0], &c->ev_or_join[1], &c->ev_fork})
+        TRY(own_event(c, hipEventDisableTiming, e));
     return VSLAM_OK;
+}
+
+int BatchFork::begin(unsigned long long key, bool eligible, bool big, bool capturing) {
+    TRY(ensure_aux(c));
+    // (calls of a few megapixels are dominated by launch latencies: their lag says nothing about starvation)
+    TRY(watch_before_call(c, key, eligible && big, capturing));
+    side = c->watch.level != 2;  // the watchdog's last step: everything on the caller's stream
+    if (!side) return VSLAM_OK;
+    TRY(tuner_before_call(c, key, eligible, capturing));
+    HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+    for (hipStream_t st : c->aux) HIPCHK(c, hipStreamWaitEvent(st, c->ev_fork, 0));
+    open = true;
+    return VSLAM_OK;
+}
+
+int BatchFork::end() {
+    if (c->watch.recording >= 0) HIPCHK(c, hipEventRecord(c->watch_ev[c->watch.recording][1], c->stream));  // the main stream's own work ends here
+    if (side)
+        for (int i = 0; i < vslam_ctx::kAux; ++i) {
+            HIPCHK(c, hipEventRecord(c->ev_join[i], c->aux[i]));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join[i], 0));
+        }
+    if (c->watch.recording >= 0) {
+        HIPCHK(c, hipEventRecord(c->watch_ev[c->watch.recording][2], c->stream));
+        c->watch.recorded();
+    }
+    if (!c->phase_marked) TRY(sched_mark_phase(c));  // no DoG path in this call: its end is the mark
+    if (side && c->tuner.measuring >= 0) {
+        HIPCHK(c, hipEventRecord(c->tuner_ev[c->tuner.measuring][1], c->stream));
+        c->tuner.after_call();
+    }
+    open = false;
+    return VSLAM_OK;
+}
+
+BatchFork::~BatchFork() {
+    if (!open) return;
+    for (hipStream_t st : c->aux)
+        if (st) (void)hipStreamSynchronize(st);
+    (void)hipStreamSynchronize(c->stream);
 }
 
 void sched_init_from_env(vslam_ctx* c) {
@@ -262,25 +215,6 @@ void sched_init_from_env(vslam_ctx* c) {
     if (const char* sp = std::getenv("VSLAM_SIDE_PRIORITY")) c->watch.level = (sp[0] == 'l' || sp[0] == 'L') ? 0 : 1;  // low | main
     const char* t = std::getenv("VSLAM_STREAM_TUNER");
     if (t && t[0] == '1') (void)vslam_ctx_tune_side_streams(c, 1);
-}
-
-void sched_destroy(vslam_ctx* c) {
-    for (auto& ev : c->timing_ev) {
-        (void)hipEventDestroy(ev.first);
-        (void)hipEventDestroy(ev.second);
-    }
-    if (c->ev_fork && !c->tuner.done) tuner_finish(c, 0);  // candidate pairs of an unfinished comparison go first (aux = pair 0 again)
-    for (int i = 0; i < vslam_ctx::kAux; ++i) {
-        if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]);
-        if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (int i = 0; i < JoinWatch::RING; ++i)
-        for (hipEvent_t e : {c->watch.t0[i], c->watch.tm[i], c->watch.t1[i]})
-            if (e) (void)hipEventDestroy(e);
-    for (auto& pr : c->watch.pair)
-        for (hipStream_t st : pr)
-            if (st && st != c->aux[0] && st != c->aux[1]) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
 }
 
 }  // namespace vslam
@@ -319,7 +253,7 @@ int vslam_kernel_timing_read(vslam_ctx* c, int* launches, double* total_ms) {
 int vslam_ctx_side_stream_report(const vslam_ctx* c, int* pair, int* state) {
     if (!c) return VSLAM_ERR_INVALID;
     if (pair) *pair = c->tuner.chosen;
-    if (state) *state = c->tuner.done ? 2 : ((c->tuner.enabled && c->tuner.calls > 1) ? 1 : 0);
+    if (state) *state = c->tuner.state();
     return VSLAM_OK;
 }
 
