@@ -27,9 +27,6 @@
 
 namespace vslam {
 
-constexpr int HD_J = 16;   // outputs per lane and row
-constexpr int HD_PAD = 2;  // LDS columns of padding after every 16
-
 typedef float hd_f2 __attribute__((ext_vector_type(2)));
 
 template <class F, int... I>
@@ -57,20 +54,14 @@ __host__ __device__ constexpr int hd_coef(int e) {
     return hd_w<LV>(e + LV::n / 2);
 }
 
-// geometry of octave O: widest kernel and left halo (>= r + 2: the window may start one column early to stay 16-byte aligned)
+// geometry of octave O: widest kernel and left halo (hd_left_halo, vslam_octave_launch.h, with HD_J, HD_PAD and hd_pw)
 template <int O>
 struct HdGeom {
     static constexpr int nmax = dtaps::Lvl<O, 5>::n;  // widths grow with the level
     static constexpr int rmax = nmax / 2;
-    static constexpr int HL = (rmax + 2 + 15) & ~15;
+    static constexpr int HL = hd_left_halo(rmax);
     static_assert(dtaps::Lvl<O, 0>::n <= nmax && dtaps::Lvl<O, 4>::n <= nmax, "level 5 is the widest");
 };
-
-// float2 columns of one staged row pair: left halo + 16 per segment + right halo, padded; a multiple of 16 + HD_PAD
-__host__ __device__ inline int hd_pw(int cols, int HL, int rmax) {
-    const int ccount = HL + 16 * ((cols + HD_J - 1) / HD_J) + rmax;
-    return (ccount + 1 + 15) / 16 * (16 + HD_PAD);  // + 1: the last read of a window may take one column past the staged ones
-}
 
 // One level of one lane: acc[j] = {out(row 0), out(row 1)} of output x0 + j, exact integers (bias and rounding constant included).
 template <class LV, int HL>

@@ -16,10 +16,10 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_pyramid.hip.h"
+#include "vslam_octave_launch.h"
 
 namespace vslam {
 
-constexpr int STRIP_W = 64;        // columns per vertical-pass workgroup
 constexpr int STRIP_MAXN = 2047;   // widest kernel (taps, after zero-tail trimming)
 // Kernels up to 2047 taps (round 5; 245 before): the reference's second constructor gives a 1080p frame six octaves, and
 // octaves 4 and 5 (240 x 135, 120 x 68) have kernels of up to 489 and 977 taps - several times wider than the image (4K: a seventh octave, 1955 taps on 120 x 68), which
@@ -188,6 +188,7 @@ __global__ __launch_bounds__(256) void k_gauss_h_strip(const uint16_t* __restric
     // items per thread: two of 8 columns x 4 rows, or four of fewer rows (the row count per item is chosen on the host so that the
     // items fill whole waves: 960 columns x 16 rows are 480 items of 4 rows = 7.5 waves, but 960 items of 2 rows = 15)
     constexpr int NI = RI == 4 ? 2 : 4;
+    static_assert(NI * 256 == strip_item_capacity(RI), "the host's launch choice (vslam_octave_launch.h) counts on this many items per workgroup");
     uint32_t prev_e[NI][RI][2], prev_o[NI][RI][2];
     // this thread's (at most two) items and the plane offset of each item's first row: the same for every
     // level, so the division and the multiply are done once (a dozen instructions saved per level)

@@ -32,6 +32,7 @@
 #include "vslam_ctx.h"
 #include "vslam_launch.h"
 #include "vslam_mx.h"
+#include "vslam_octave_launch.h"
 
 using namespace vslam;
 
@@ -64,8 +65,7 @@ struct StreamSwap {
     ~StreamSwap() { c->stream = saved; }
 };
 
-// Raises a kernel's dynamic shared memory ceiling to the most any launch of it may ask for.
-static constexpr int kMaxDynLds = 150 * 1024;
+// Raises a kernel's dynamic shared memory ceiling to the most any launch of it may ask for (kMaxDynLds, vslam_octave_launch.h).
 static int raise_dyn_lds(vslam_ctx* c, const void* fn) {
     if (c->lds_raised.count(fn)) return VSLAM_OK;
     HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds));
@@ -185,7 +185,8 @@ struct OctPlan {
     double sg[6] = {};
     int ke[6] = {};                 // zero-trimmed widths the fast kernels run with
     std::vector<uint16_t> taps[6];  // trimmed taps
-    int sh = 0;                     // rows per horizontal strip workgroup
+    int nmax = 0;                   // widest of ke
+    int sh = 0;                     // rows per horizontal strip workgroup (strip_plan_sh)
     int hdiff = 0;                  // octave of diff_taps.gen.h with these taps: the difference-form horizontal pass (k_gauss_h_diff)
     int mx = 0;                     // matrix-core configuration that runs these widths (mx_config_for), 0 = none; used on the opt-in path only
 };
@@ -205,13 +206,9 @@ static bool matches_cfg(const int ks[6]) {
     return true;
 }
 
-// u16-pair columns of one staged row of the horizontal strip pass (left halo + ceil(cols/8) groups
-// + right halo of the widest kernel), a multiple of 4
-static int strip_pw(int cols, int nmax) { return ((cols + 7) / 2 + nmax / 2 + 12 + 3) & ~3; }
-
 static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
     OctPlan pl;
-    int nmax = 0;
+    int& nmax = pl.nmax;
     for (int l = 0; l < 6; ++l) {
         pl.sg[l] = sigma_at(sigma0, o, l);
         pl.ks[l] = gauss_ksize_u8(pl.sg[l]);
@@ -225,13 +222,10 @@ static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
     } else if (matches_cfg<PyrCfgOct1>(pl.ke)) {
         pl.path = OctPath::Tile1;
     } else if (nmax <= STRIP_MAXN) {
-        const int RM = (nmax / 2 + 3) & ~3;
-        const size_t v_lds = (size_t)((((rows + 3) & ~3) + 2 * RM + 16) / 4) * STRIP_W * 4;
-        pl.sh = cols <= 1024 ? 16 : cols <= 2048 ? 8 : cols <= 4096 ? 4 : 0;
-        const size_t pw = (size_t)strip_pw(cols, nmax);
-        if (pl.sh && v_lds <= 150 * 1024 && pl.sh * pw * 4 <= 150 * 1024) pl.path = OctPath::Strip;
+        pl.sh = strip_plan_sh(rows, cols, nmax);
+        if (pl.sh) pl.path = OctPath::Strip;
         // the default pyramid's octaves 2-3 (and any octave with the same taps): horizontal pass in difference form
-        if (pl.path == OctPath::Strip && (cols + HD_J - 1) / HD_J <= 256)
+        if (pl.path == OctPath::Strip && hdiff_fits(cols))
             pl.hdiff = hd_octave_matches<2>(pl.taps) ? 2 : hd_octave_matches<3>(pl.taps) ? 3 : 0;
     }
     if (pl.path != OctPath::Generic) pl.mx = mx_config_for(pl.ke);
@@ -245,30 +239,23 @@ static std::vector<OctPlan> plan_octaves(double sigma0, const vslam_batch_layout
     return plans;
 }
 
+// The two horizontal passes of a strip octave, launched as strip_launch() (vslam_octave_launch.h) chose.
 template <int SH, int RI>
-static int launch_h_strip(vslam_ctx* c, const uint16_t* h, size_t hframe, const OctIO& io, int pw, const StripTaps* taps) {
-    const size_t lds = (size_t)SH * pw * 4;
+static int launch_h_strip(vslam_ctx* c, const uint16_t* h, size_t hframe, const OctIO& io, const StripLaunch& sl, const StripTaps* taps) {
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_h_strip<SH, RI>)));
-    LAUNCH_ON(c, "k_gauss_h_strip", c->launch_tag, c->stream, lds, (k_gauss_h_strip<SH, RI>), dim3(1, (io.rows + SH - 1) / SH, io.nf), dim3(256), h,
-              hframe, io.oct, io.pframe, io.rows, io.cols, io.pitch, pw, taps, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
+    LAUNCH_ON(c, "k_gauss_h_strip", c->launch_tag, c->stream, sl.h_lds, (k_gauss_h_strip<SH, RI>), dim3(1, sl.h_grid_y, io.nf), dim3(256), h,
+              hframe, io.oct, io.pframe, io.rows, io.cols, io.pitch, sl.pw, taps, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
     return VSLAM_OK;
 }
 
 template <int O>
-static int launch_h_diff(vslam_ctx* c, const uint16_t* h, size_t hframe, const OctIO& io) {
-    using G = HdGeom<O>;
-    const int rows = io.rows, cols = io.cols;
-    const int ncs = (cols + HD_J - 1) / HD_J, pw = hd_pw(cols, G::HL, G::rmax);
-    // row pairs per workgroup: at most 256 items (one per thread), LDS below the limit, and >= 256 workgroups for small batches
-    int npairs = std::max(1, std::min(8, 256 / ncs));
-    while (npairs > 1 && ((size_t)npairs * pw * 8 > (size_t)kMaxDynLds || (long)((rows + 2 * npairs - 1) / (2 * npairs)) * io.nf < 256)) --npairs;
-    const size_t lds = (size_t)npairs * pw * 8;
+static int launch_h_diff(vslam_ctx* c, const uint16_t* h, size_t hframe, const OctIO& io, const StripLaunch& sl) {
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_h_diff<O>)));
     // the timing hook's "k_gauss_h_strip" is the coarse octaves' horizontal pass whichever kernel runs it (bench.py's
     // per-kernel figures, the dispatch tests); "k_gauss_h_diff" times this kernel alone
     TimedScope ts(c, "k_gauss_h_strip", c->launch_tag);
-    LAUNCH_ON(c, "k_gauss_h_diff", c->launch_tag, c->stream, lds, k_gauss_h_diff<O>, dim3(1, (rows + 2 * npairs - 1) / (2 * npairs), io.nf), dim3(256), h,
-              hframe, io.oct, io.pframe, rows, cols, io.pitch, npairs, pw, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
+    LAUNCH_ON(c, "k_gauss_h_diff", c->launch_tag, c->stream, sl.h_lds, k_gauss_h_diff<O>, dim3(1, sl.h_grid_y, io.nf), dim3(256), h,
+              hframe, io.oct, io.pframe, io.rows, io.cols, io.pitch, sl.npairs, sl.pw, io.next_base, io.nframe, io.nrows, io.ncols, io.npitch);
     return VSLAM_OK;
 }
 
@@ -282,56 +269,32 @@ static int enqueue_strip_octave(vslam_ctx* c, double sigma0, int o, const OctPla
         return VSLAM_OK;
     }, &taps));
     const int rows = io.rows, cols = io.cols, nf = io.nf;
-    int nmax = 0;
-    for (int l = 0; l < 6; ++l) nmax = std::max(nmax, pl.ke[l]);
-    const int RM = (nmax / 2 + 3) & ~3;
-    const int rhq = (((rows + 3) & ~3) + 2 * RM + 16) / 4;
-    const size_t v_lds = (size_t)rhq * STRIP_W * 4;
-    const size_t P = (size_t)rows * io.pitch;
-    TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_v_strip)));
-    // small batches: split the six levels over workgroups until the launch has >= 256 of them
-    const int strips = (cols + STRIP_W - 1) / STRIP_W;
-    const int want = (256 + strips * nf - 1) / (strips * nf);
-    const int lsplit = want >= 6 ? 6 : want >= 3 ? 3 : want >= 2 ? 2 : 1;
-    LAUNCH_ON(c, "k_gauss_v_strip", o, c->stream, v_lds, k_gauss_v_strip, dim3(strips, lsplit, nf), dim3(256), io.base, io.bframe, h, 6 * P, rows, cols,
-              io.pitch, RM, rhq, taps);
-    c->launch_tag = o;
     // Diagnostics build only: VSLAM_HDIFF=0 keeps the dot2 pass where the difference form would run (A/B runs, byte-equality test)
     static const bool hdiff_off = [] {
         const char* e = VSLAM_DIAG_ENV("VSLAM_HDIFF");
         return e && e[0] == '0';
     }();
-    if (pl.hdiff == 2 && !hdiff_off) return launch_h_diff<2>(c, h, 6 * P, io);
-    if (pl.hdiff == 3 && !hdiff_off) return launch_h_diff<3>(c, h, 6 * P, io);
-    const int pw = strip_pw(cols, nmax);
-    // small batches: shorter row strips, more workgroups
-    int sh = pl.sh;
-    while (sh > 4 && (long)((rows + sh - 1) / sh) * nf < 256) sh >>= 1;
-    // ... and, when even that leaves most threads without an item, one row per item
-    const bool fine = sh == 4 && (long)((rows + 3) / 4) * nf < 256 && ((cols + 7) / 8) * 4 <= 512;
-    if (fine) return launch_h_strip<4, 1>(c, h, 6 * P, io, pw, taps);
-    if (sh == 16) {
-        // rows per item (round 5): the items of a workgroup should fill whole waves.  960 columns x 16 rows are 480 items of 8
-        // columns x 4 rows = 7.5 waves (every eighth wave-instruction wasted: the kernel runs AT its VALU issue time), but 960
-        // items of 2 rows = 15 waves; 480 columns need 1 row per item.  Fewer rows per item amortise the scalar tap loads over
-        // fewer dots, so the smaller item must be at least 2 % fuller to be chosen.
-        const int ncg = (cols + 7) / 8;
-        auto waste = [&](int ri) {
-            const long items = (long)ncg * (16 / ri);
-            if (items > (ri == 4 ? 512 : 1024)) return 1e9;
-            return (double)((items + 63) / 64 * 64 - items) / (double)items;
-        };
-        int ri = 4;
-        for (int r : {2, 1})
-            if (waste(r) + 0.02 < waste(ri)) ri = r;
-        if (ri == 2) return launch_h_strip<16, 2>(c, h, 6 * P, io, pw, taps);
-        if (ri == 1) return launch_h_strip<16, 1>(c, h, 6 * P, io, pw, taps);
+    const int hd = hdiff_off ? 0 : pl.hdiff;
+    const StripLaunch sl = hd == 2   ? strip_launch(rows, cols, nf, pl.sh, true, pl.nmax, HdGeom<2>::HL, HdGeom<2>::rmax)
+                           : hd == 3 ? strip_launch(rows, cols, nf, pl.sh, true, pl.nmax, HdGeom<3>::HL, HdGeom<3>::rmax)
+                                     : strip_launch(rows, cols, nf, pl.sh, false, pl.nmax);
+    const StripVGeom vg = strip_v_geom(rows, pl.nmax);
+    const size_t P = (size_t)rows * io.pitch;
+    TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_gauss_v_strip)));
+    LAUNCH_ON(c, "k_gauss_v_strip", o, c->stream, sl.v_lds, k_gauss_v_strip, dim3((cols + STRIP_W - 1) / STRIP_W, sl.lsplit, nf), dim3(256), io.base, io.bframe,
+              h, 6 * P, rows, cols, io.pitch, vg.RM, vg.rhq, taps);
+    c->launch_tag = o;
+    if (sl.diff) return hd == 2 ? launch_h_diff<2>(c, h, 6 * P, io, sl) : launch_h_diff<3>(c, h, 6 * P, io, sl);
+    // the six instantiations strip_launch() chooses among (tests/test_octave_launch_cpu.py: no other pair ever comes back)
+    switch (sl.SH * 8 + sl.RI) {
+        case 16 * 8 + 4: return launch_h_strip<16, 4>(c, h, 6 * P, io, sl, taps);
+        case 16 * 8 + 2: return launch_h_strip<16, 2>(c, h, 6 * P, io, sl, taps);
+        case 16 * 8 + 1: return launch_h_strip<16, 1>(c, h, 6 * P, io, sl, taps);
+        case 8 * 8 + 4: return launch_h_strip<8, 4>(c, h, 6 * P, io, sl, taps);
+        case 4 * 8 + 4: return launch_h_strip<4, 4>(c, h, 6 * P, io, sl, taps);
+        case 4 * 8 + 1: return launch_h_strip<4, 1>(c, h, 6 * P, io, sl, taps);
     }
-    switch (sh) {
-        case 16: return launch_h_strip<16, 4>(c, h, 6 * P, io, pw, taps);
-        case 8: return launch_h_strip<8, 4>(c, h, 6 * P, io, pw, taps);
-        default: return launch_h_strip<4, 4>(c, h, 6 * P, io, pw, taps);
-    }
+    return fail(c, VSLAM_ERR_UNSUPPORTED, "strip kernels: no instantiation for the chosen strip shape");
 }
 
 
@@ -697,10 +660,7 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
                  fuse_next ? s.bases + s.base_off[o + 1] : nullptr, s.bases_frame, has_next ? L.rows[o + 1] : 0, has_next ? L.cols[o + 1] : 0,
                  has_next ? L.pitch[o + 1] : 0};
         if (o == 0 && up2_fused) io.base = frames, io.bframe = fframe;  // the kernel reads the source frames (mx_launch: up2_step)
-        // tile shape: the wide tile (256 x 32) when it needs no more tile area than the tall one (128 x 64).
-        // A 384 x 32 tile (1920 = 5 x 384) on 384-thread workgroups was measured in round 3: six waves per
-        // workgroup sit 2-2-1-1 on the four SIMDs and meet at every barrier: 21.3 vs 18.3 ms per step.
-        const int shape = (long)((cols + 255) / 256) * ((rows + 31) / 32) <= (long)((cols + 127) / 128) * ((rows + 63) / 64) ? 1 : 0;
+        const int shape = pyr_tile_wide(rows, cols) ? 1 : 0;  // the wide tile (256 x 32) or the tall one (128 x 64)
         // matrix path: the plain lattice scan (window 3, candidates + contrast list) runs inside the octave kernel
         // while the DoG rows are in LDS (kernels_pyramid_mx.hip.h); k_extrema_pack then replaces k_extrema_w3
         fused[o] = c->mx && s.sitemap && out.do_extrema && !p.localize && !p.extrema_dense && p.extrema_window == 3 && L.lat_rows[o] > 0 &&
