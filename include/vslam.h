@@ -590,6 +590,103 @@ int vslam_match_host(vslam_ctx* ctx, const float* query, const uint8_t* query_de
                      const float* train, const uint8_t* train_defined, const vslam_point* train_points, size_t nt, float ratio2,
                      int same_octave, vslam_nn2* nn, vslam_match* matches, size_t match_cap, size_t* n_matches);
 
+/* ---------------------------------------------------------------- two-view geometry
+ * The step after matching (the reference's README: "3. 3D Reconstruction - Epipolar Geometry"): the fundamental matrix of
+ * every pair, by RANSAC over the match list vslam_match_dev wrote and the point lists vslam_detect_batch_dev wrote, and the
+ * inlier subset of each list.  A fixed number of hypotheses, no adaptive stop, no final least-squares refit.  The arithmetic
+ * is fixed here so that a CPU can restate it bit for bit (tests/epiref.py).  Everything is IEEE f64; every + - * / sqrt is
+ * rounded on its own (no fused multiply-add); a sum of more than two terms runs left to right as written, (a + b) + c.
+ *
+ * Coordinates of a point p, exact:  x = (p.col - p.padding) * 2^(p.octave - 1),  y = (p.row - p.padding) * 2^(p.octave - 1)
+ * (octave 0 is the 2x upsampled image).  A record is TRUSTED iff query < query_cap, train < train_cap (as unsigned) and both
+ * points' octave is in 0 .. 31; a record that is not trusted is never read through, is never an inlier, and a sample that
+ * contains one is invalid.  m = n_matches = min(match_counts[j], match_cap) records are considered.
+ *
+ * Sampling, a counter hash without state.  mix(x) on uint32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+ * x ^= x >> 16.  Pair j, hypothesis h: base = mix(mix(seed + j) + h); draw t = 0, 1, ... gives r = mix(base + t) and the index
+ * (uint64(r) * m) >> 32, kept if it is not among the indices kept so far; the sample is the first 8 kept indices, in that
+ * order.  Fewer than 8 after 64 draws: invalid.  m < 8: every hypothesis is invalid.
+ *
+ * Model from the 8 records (x, y) = query, (x', y') = train - the normalised 8-point algorithm:
+ *  1. Per side: cx = (x0 + x1 + ... + x7) / 8, cy likewise; d = (r0 + r1 + ... + r7) / 8 with ri = sqrt(dx*dx + dy*dy),
+ *     dx = xi - cx, dy = yi - cy; d == 0: invalid; s = 1.4142135623730951 / d; normalised point ((xi - cx) * s, (yi - cy) * s).
+ *  2. Row i of the 8 x 9 matrix a, from the normalised (x, y), (x', y'): [x'*x, x'*y, x', y'*x, y'*y, y', x, y, 1].
+ *  3. Gauss-Jordan with full pivoting, steps k = 0 .. 7: the pivot is the entry of largest |a[r][c]| over rows r >= k and the
+ *     columns no earlier step chose, scanned r ascending, then c ascending, a later entry replacing the choice only when
+ *     strictly larger than it - which starts at 0: a zero or a NaN is never chosen; no choice, or an infinite pivot: invalid.
+ *     Rows k and r are swapped; every entry of row k is divided by the pivot; for every other row i, with g = a[i][c]:
+ *     a[i][c'] = a[i][c'] - g * a[k][c'] for all nine c'.  c_k = c.  With `free` the column no step chose:
+ *     f[free] = 1, f[c_k] = -a[k][free]; F = f row-major.
+ *  4. Rank 2.  S = F^T F, S[i][j] = (F[0][i]*F[0][j] + F[1][i]*F[1][j]) + F[2][i]*F[2][j]; V = identity.  Six sweeps over the
+ *     pairs (p, q) = (0,1), (0,2), (1,2), r the third index; a pair with S[p][q] == 0 is skipped:
+ *       theta = (S[q][q] - S[p][p]) / (2 * S[p][q]);  t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta*theta + 1));
+ *       c = 1 / sqrt(t*t + 1);  s = t * c;   then, all from the old values:
+ *       S[p][p] -= t * S[p][q];  S[q][q] += t * S[p][q];  S[r][p] = c*S[r][p] - s*S[r][q];  S[r][q] = s*S[r][p] + c*S[r][q];
+ *       S[p][q] = 0 (S stays symmetric);  for i = 0 .. 2:  V[i][p] = c*V[i][p] - s*V[i][q];  V[i][q] = s*V[i][p] + c*V[i][q].
+ *     v = column k of V, k the smallest S[k][k] (lowest k on ties).  g_i = (F[i][0]*v0 + F[i][1]*v1) + F[i][2]*v2;
+ *     F[i][j] = F[i][j] - g_i * v_j.
+ *  5. F <- Tt^T F Tq, T = [[s, 0, a], [0, s, b], [0, 0, 1]] with a = -(s * cx), b = -(s * cy) of its side:
+ *       G[i][0] = F[i][0]*sq;  G[i][1] = F[i][1]*sq;  G[i][2] = (F[i][0]*aq + F[i][1]*bq) + F[i][2];
+ *       H[0][j] = st*G[0][j];  H[1][j] = st*G[1][j];  H[2][j] = (at*G[0][j] + bt*G[1][j]) + G[2][j].
+ *  6. n = sqrt(H[0][0]^2 + H[0][1]^2 + ... + H[2][2]^2), row-major, left to right; n zero or not finite: invalid; F = H / n.
+ *
+ * Inlier test (Sampson, image pixels, no division): a_i = (F[i][0]*x + F[i][1]*y) + F[i][2]; b_j = (F[0][j]*x' + F[1][j]*y')
+ * + F[2][j]; e = (x'*a0 + y'*a1) + a2; the record is an inlier iff e*e < max_dist2 * (((a0*a0 + a1*a1) + b0*b0) + b1*b1).
+ * Selection: the valid hypothesis with the most inliers, the lowest h on ties.  Counts are integers, so the result does not
+ * depend on how the records are split over lanes and workgroups, nor on vslam_ctx_set_f32_fused / vslam_ctx_set_matrix_path. */
+typedef struct {
+    double F[9];      /* all zero when not valid */
+    uint32_t inliers;
+    int32_t valid;
+} vslam_epipolar_hyp; /* 80 bytes */
+typedef struct {
+    double F[9];        /* row-major; x_train^T F x_query = 0; Frobenius norm 1; all zero when best < 0 */
+    uint32_t n_matches; /* min(match_counts[j], match_cap): the records considered */
+    uint32_t n_inliers;
+    int32_t best;       /* winning hypothesis, -1: none */
+    uint32_t n_valid;   /* hypotheses that produced a model */
+} vslam_epipolar;       /* 88 bytes */
+typedef struct {
+    uint32_t n_hypotheses; /* 1 .. 65535 */
+    uint32_t seed;
+    double max_dist2;      /* squared Sampson distance in pixels^2, finite and positive */
+} vslam_epipolar_params;
+/* Like vslam_match_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;       /* = sizeof(vslam_epipolar_out) */
+    vslam_epipolar* models;   /* [n_pairs], required */
+    size_t models_bytes;
+    uint64_t* inlier_bits;    /* [n_pairs][(match_cap + 63) / 64] optional: bit i % 64 of word i / 64 = record i is an inlier of
+                               * the winner; the first (n_matches + 63) / 64 words of a pair are written, the rest untouched */
+    size_t inlier_bits_bytes;
+    vslam_match* inliers;     /* [n_pairs][inlier_cap] optional: the inlier records, list order kept */
+    size_t inliers_bytes;
+    uint32_t* inlier_counts;  /* [n_pairs], required with inliers: totals (may exceed inlier_cap) */
+    size_t inlier_counts_bytes;
+    uint32_t inlier_cap;
+    vslam_epipolar_hyp* hypotheses; /* [n_pairs][n_hypotheses] optional: every hypothesis with its count */
+    size_t hypotheses_bytes;
+} vslam_epipolar_out;
+/* Pair j reads matches[j * match_cap ..], match_counts[j], query_points[j * query_cap ..] and train_points[j * train_cap ..]
+ * (DEVICE pointers; consecutive frames: train_points = query_points advanced by one set, as for vslam_match_dev).
+ * Asynchronous on the context stream, never waits on the host (the counts are read on the device, the grids are sized from
+ * the capacities); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch - and before the context is looked
+ * at - for a null pointer, a wrong struct_size, an undersized buffer, inliers without inlier_counts or with inlier_cap == 0,
+ * match_cap / query_cap / train_cap == 0, n_pairs outside 0 .. 65535 (0 does nothing), n_hypotheses outside 1 .. 65535, a
+ * max_dist2 that is not finite or not positive; then VSLAM_ERR_HIP when there is no usable HIP device, as for
+ * vslam_match_dev.  Not for stream capture. */
+int vslam_epipolar_dev(vslam_ctx* ctx, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
+                       const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points, uint32_t train_cap,
+                       int n_pairs, const vslam_epipolar_params* params, const vslam_epipolar_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call).  model is required; inlier_bits
+ * [(n_matches + 63) / 64], (inliers [inlier_cap], n_inliers) and hypotheses [n_hypotheses] are each optional; *n_inliers is
+ * the total, which may exceed inlier_cap.  n_query / n_train are the capacities the indices are checked against.  Errors as
+ * for vslam_epipolar_dev. */
+int vslam_epipolar_host(vslam_ctx* ctx, const vslam_match* matches, size_t n_matches, const vslam_point* query_points, size_t n_query,
+                        const vslam_point* train_points, size_t n_train, const vslam_epipolar_params* params, vslam_epipolar* model,
+                        uint64_t* inlier_bits, vslam_match* inliers, size_t inlier_cap, size_t* n_inliers,
+                        vslam_epipolar_hyp* hypotheses);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

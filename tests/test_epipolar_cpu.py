@@ -1,0 +1,265 @@
+"""Two-view geometry without a GPU: the C ABI's new symbols, struct layouts and argument checks, the host sizing under the
+sanitizers, and the CPU restatement of the arithmetic itself (tests/epiref.py), which the GPU tests compare against byte for
+byte: hash and sampling known answers, the 8-point model on exact data, rank 2, quality on planted data, selection rules."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import epiref
+from visualslam_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "visualslam_amd", "csrc")
+INVALID, HIP = -1, -2
+
+
+@pytest.fixture(scope="module")
+def lib():
+    capi.build()
+    return capi.lib()
+
+
+def test_epipolar_symbols_are_exported_by_both_libraries(lib):
+    for path in (capi.LIB_PATH, capi.DIAG_LIB_PATH):
+        L = C.CDLL(path)
+        for name in ("vslam_epipolar_dev", "vslam_epipolar_host"):
+            assert hasattr(L, name), (path, name)
+            assert name in capi.SIGNATURES
+    names = lib.vslam_kernel_names().split(b"\n")
+    for k in (b"k_epi_coords", b"k_epi_models", b"k_epi_score", b"k_epi_select", b"k_epi_flags"):
+        assert k in names
+
+
+def test_epipolar_struct_layouts_match_a_c99_compile_of_the_header(tmp_path):
+    if not shutil.which("gcc"):
+        pytest.skip("no gcc")
+    structs = {"vslam_epipolar_hyp": capi.EpipolarHyp, "vslam_epipolar": capi.Epipolar, "vslam_epipolar_params": capi.EpipolarParams,
+               "vslam_epipolar_out": capi.EpipolarOut}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vslam.h"', "int main(void) {"]
+    for cname, ct in structs.items():
+        lines.append(f'  printf("{cname} %zu", sizeof({cname}));')
+        lines += [f'  printf(" %zu", offsetof({cname}, {f[0]}));' for f in ct._fields_]
+        lines.append('  printf("\\n");')
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "abi.c", tmp_path / "abi"
+    src.write_text("\n".join(lines) + "\n")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    rows = {l.split()[0]: [int(v) for v in l.split()[1:]] for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines()}
+    for cname, ct in structs.items():
+        assert rows[cname] == [C.sizeof(ct)] + [getattr(ct, f[0]).offset for f in ct._fields_], cname
+    assert rows["vslam_epipolar_hyp"][0] == 80 and rows["vslam_epipolar"][0] == 88
+    assert capi.EPIPOLAR_HYP_DTYPE.itemsize == 80 and capi.EPIPOLAR_DTYPE.itemsize == 88
+    for dt, ct in ((capi.EPIPOLAR_HYP_DTYPE, capi.EpipolarHyp), (capi.EPIPOLAR_DTYPE, capi.Epipolar)):
+        assert [dt.fields[f[0]][1] for f in ct._fields_] == [getattr(ct, f[0]).offset for f in ct._fields_]
+
+
+class Args:
+    """A valid vslam_epipolar_dev call over host arrays (nothing is launched without a GPU: the pointers are never followed)."""
+
+    def __init__(self, n_pairs=2, match_cap=100, cap=50, inlier_cap=10, H=16):
+        self.keep = [np.zeros((n_pairs, match_cap), capi.MATCH_DTYPE), np.zeros(n_pairs, np.uint32), np.zeros((n_pairs, cap), capi.POINT_DTYPE),
+                     np.zeros(n_pairs, capi.EPIPOLAR_DTYPE), np.zeros((n_pairs, (match_cap + 63) // 64), np.uint64),
+                     np.zeros((n_pairs, inlier_cap), capi.MATCH_DTYPE), np.zeros(n_pairs, np.uint32), np.zeros((n_pairs, H), capi.EPIPOLAR_HYP_DTYPE)]
+        m, mc, p, mod, bits, inl, ic, hyp = self.keep
+        self.matches, self.counts, self.qp, self.tp = m.ctypes.data, mc.ctypes.data, p.ctypes.data, p.ctypes.data
+        self.match_cap, self.query_cap, self.train_cap, self.n_pairs = match_cap, cap, cap, n_pairs
+        self.prm = capi.EpipolarParams(H, 1, 4.0)
+        self.out = capi.EpipolarOut(C.sizeof(capi.EpipolarOut), mod.ctypes.data, mod.nbytes, bits.ctypes.data, bits.nbytes, inl.ctypes.data, inl.nbytes,
+                                    ic.ctypes.data, ic.nbytes, inlier_cap, hyp.ctypes.data, hyp.nbytes)
+
+    def call(self, lib, prm="prm", out="out"):
+        ref = lambda x: None if x is None else C.byref(getattr(self, x))
+        return lib.vslam_epipolar_dev(None, self.matches, self.counts, self.match_cap, self.qp, self.query_cap, self.tp, self.train_cap, self.n_pairs,
+                                      ref(prm), ref(out))
+
+
+def test_epipolar_dev_rejects_bad_arguments_before_it_needs_a_gpu(lib):
+    import torch
+
+    gpu = torch.cuda.is_available()
+    # a valid call: no context can exist without a GPU, and the answer is the ABI's "no HIP device"; with one, a null context is invalid
+    assert Args().call(lib) == (INVALID if gpu else HIP)
+    assert Args().call(lib, prm=None) == INVALID and Args().call(lib, out=None) == INVALID
+
+    def bad(**change):
+        a = Args()
+        for k, v in change.items():
+            obj, field = k.split("__")
+            setattr(getattr(a, obj), field, v) if obj != "a" else setattr(a, field, v)
+        return a.call(lib)
+
+    for name in ("matches", "counts", "qp", "tp"):
+        assert bad(**{"a__" + name: None}) == INVALID, name
+    assert bad(out__struct_size=C.sizeof(capi.EpipolarOut) - 8) == INVALID
+    assert bad(out__models=None) == INVALID and bad(out__models_bytes=2 * 88 - 1) == INVALID
+    assert bad(out__inlier_bits_bytes=2 * 2 * 8 - 1) == INVALID
+    assert bad(out__inliers_bytes=2 * 10 * 12 - 1) == INVALID
+    assert bad(out__inlier_counts=None) == INVALID                      # inliers without inlier_counts
+    assert bad(out__inlier_cap=0) == INVALID                            # inliers with no capacity
+    assert bad(out__inlier_counts_bytes=7) == INVALID
+    assert bad(out__hypotheses_bytes=2 * 16 * 80 - 1) == INVALID
+    assert bad(a__n_pairs=-1) == INVALID and bad(a__n_pairs=65536) == INVALID
+    assert bad(prm__n_hypotheses=0) == INVALID and bad(prm__n_hypotheses=65536) == INVALID
+    for d in (0.0, -4.0, float("nan"), float("inf")):
+        assert bad(prm__max_dist2=d) == INVALID
+    assert bad(a__match_cap=0) == INVALID and bad(a__query_cap=0) == INVALID and bad(a__train_cap=0) == INVALID
+    if not gpu:  # the optional outputs may be absent, and no pairs is a valid call
+        assert bad(out__inlier_bits=None, out__inliers=None, out__inlier_counts=None, out__hypotheses=None) == HIP
+        assert bad(out__inliers=None, out__inlier_cap=0) == HIP and bad(a__n_pairs=0) == HIP
+
+
+def test_epipolar_host_rejects_bad_arguments_before_it_needs_a_gpu(lib):
+    import torch
+
+    m, qp, tp, _ = epiref.planted_scene(1, n=20)
+    model, inl, total = np.zeros(1, capi.EPIPOLAR_DTYPE), np.zeros(20, capi.MATCH_DTYPE), C.c_size_t()
+    good = capi.EpipolarParams(16, 1, 4.0)
+
+    def call(prm=good, mp=m.ctypes.data, q=qp.ctypes.data, nq=20, modelp=model.ctypes.data, inlp=inl.ctypes.data, cap=20, tot=C.byref(total)):
+        return lib.vslam_epipolar_host(None, mp, 20, q, nq, tp.ctypes.data, 20, None if prm is None else C.byref(prm), modelp, None, inlp, cap, tot, None)
+
+    assert call() == (INVALID if torch.cuda.is_available() else HIP)
+    assert call(prm=None) == INVALID and call(modelp=None) == INVALID and call(mp=None) == INVALID and call(q=None) == INVALID
+    assert call(prm=capi.EpipolarParams(0, 1, 4.0)) == INVALID and call(prm=capi.EpipolarParams(65536, 1, 4.0)) == INVALID
+    for d in (0.0, -1.0, float("nan"), float("inf")):
+        assert call(prm=capi.EpipolarParams(16, 1, d)) == INVALID
+    assert call(tot=None) == INVALID and call(cap=0) == INVALID       # inliers without the total / without a capacity
+    assert call(q=None, nq=0) == INVALID                              # match records without points
+    if not torch.cuda.is_available():
+        assert call(inlp=None, tot=None) == HIP
+
+
+def test_host_sizing_and_checks_are_clean_under_asan_and_ubsan(tmp_path):
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    exe = tmp_path / "plan_driver"
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-I", CSRC, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "epipolar_plan_driver.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True)
+    if r.returncode != 0 and ("asan" in r.stderr or "sanitize" in r.stderr):
+        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr[-2000:]
+    rows = {l.split()[0]: dict(x.split("=", 1) for x in l.split()[1:]) for l in out.stdout.splitlines()}
+    assert rows["plan"]["bad"] == "0" and int(rows["plan"]["checked"]) == 18 * 12 * 12 * 9, rows["plan"]
+    assert rows["args"]["bad"] == "0" and int(rows["args"]["checked"]) >= 30, rows["args"]
+    src = open(os.path.join(CSRC, "vslam_epipolar_plan.h")).read()  # the header under test is plain host code
+    assert "#include <hip" not in src and "__global__" not in src
+
+
+# ---- the restatement itself
+
+def test_hash_and_sampling_known_answers():
+    assert epiref.mix(1) == 0x688990C0 and epiref.mix(0xDEADBEEF) == 0xE628C683
+    assert epiref.sample(1, 0, 0, 300) == [42, 124, 239, 184, 4, 155, 166, 238]
+    assert epiref.sample(7, 3, 511, 1000) == [750, 606, 766, 401, 550, 803, 509, 847]
+    assert epiref.sample(1, 0, 0, 8) == [1, 3, 6, 4, 0, 2, 5, 7]
+    assert epiref.sample(1, 0, 7, 8) is None            # 64 draws without 8 distinct indices
+    assert all(epiref.sample(1, 0, h, 7) is None for h in range(64))
+    for m in (8, 9, 64, 1 << 20, (1 << 32) - 1):         # distinct, in range
+        for h in range(50):
+            s = epiref.sample(3, 5, h, m)
+            assert s is None or (len(set(s)) == 8 and max(s) < m)
+
+
+def residuals(F, xq, xt):
+    return np.array([abs(np.array([*t, 1.0]) @ F @ np.array([*q, 1.0])) for q, t in zip(xq, xt)])
+
+
+def test_model_from_8_exact_correspondences_and_rank_two():
+    worst_res, worst_sv, without = 0.0, 0.0, []
+    for seed in range(15):
+        xq, xt = epiref.two_cameras(np.random.default_rng(100 + seed), 8)
+        assert 100 < np.abs(xq).max() < 2000                       # coordinates of order 10^3
+        F = epiref.model_from_8(np.hstack([xq, xt]))
+        assert F is not None and abs(np.linalg.norm(F) - 1.0) <= 4e-16
+        worst_res = max(worst_res, residuals(F, xq, xt).max())
+        sv = np.linalg.svd(F, compute_uv=False)
+        worst_sv = max(worst_sv, sv[2] / sv[0])
+        lattice = np.rint(np.hstack([xq, xt]))                      # the same points on the pixel lattice: no exact F any more
+        sv = np.linalg.svd(epiref.model_from_8(lattice), compute_uv=False)
+        worst_sv = max(worst_sv, sv[2] / sv[0])
+        sv = np.linalg.svd(epiref.model_from_8(lattice, rank2=False), compute_uv=False)
+        without.append(sv[2] / sv[0])
+    print("model_from_8: worst |x'^T F x|", worst_res, "worst sigma3 / sigma1", worst_sv, "without step 4", min(without), max(without))
+    assert worst_res <= 1e-9      # f64 rounding through a well-conditioned solve is 1e-13-ish (measured: 1.3e-13)
+    assert worst_sv <= 1e-12      # measured: 2.3e-18
+    assert min(without) > 1e-10   # ... and step 4 is what makes it so (measured: 3.7e-9 .. 7.2e-6 on the lattice)
+
+
+def test_model_from_8_degenerate_inputs():
+    xq, xt = epiref.two_cameras(np.random.default_rng(5), 8)
+    pts = np.hstack([xq, xt])
+    same = pts.copy()
+    same[:, :2] = same[0, :2]                      # all query points coincide: d == 0
+    assert epiref.model_from_8(same) is None
+    same = pts.copy()
+    same[:, 2:] = same[3, 2:]
+    assert epiref.model_from_8(same) is None
+    nan = pts.copy()
+    nan[2] = np.nan                                # a record that is not trusted
+    assert epiref.model_from_8(nan) is None
+    line = pts.copy()
+    line[:, 1], line[:, 3] = line[:, 0], line[:, 2]  # both sets on a line: the elimination runs out of pivots
+    assert epiref.model_from_8(line) is None
+
+
+# (planted inliers, found among them, planted outliers accepted, n_inliers, best) of the restatement, H = 512, max_dist2 = 4
+PLANTED = {1: (222, 222, 0, 222, 60), 2: (218, 217, 2, 219, 142), 3: (222, 222, 0, 222, 392), 4: (210, 209, 1, 210, 207)}
+
+
+@pytest.mark.parametrize("seed", sorted(PLANTED))
+def test_restatement_finds_the_planted_geometry(seed):
+    m, qp, tp, planted = epiref.planted_scene(seed)
+    assert len(m) == 300 and set(qp["octave"]) == {0, 1, 2} and set(qp["padding"]) == {0, 1}
+    model, flags, hyps = epiref.ransac(m, qp, tp, 512, seed, 4.0)
+    got = (int(planted.sum()), int((flags & planted).sum()), int((flags & ~planted).sum()), int(model["n_inliers"][0]), int(model["best"][0]))
+    print("planted scene", seed, got)
+    assert got[1] >= 0.9 * got[0] and got[2] <= 0.1 * int((~planted).sum())
+    assert got == PLANTED[seed]
+    assert int(model["n_matches"][0]) == 300 and int(model["n_valid"][0]) == int(hyps["valid"].sum()) <= 512
+    assert int(flags.sum()) == got[3] == int(hyps["inliers"][got[4]]) and model["F"][0].tobytes() == hyps["F"][got[4]].tobytes()
+    # score() of the winner over the coordinate records is the same count and the same flags
+    n, f = epiref.score(model["F"][0], epiref.coords(m, qp, tp), 4.0)
+    assert n == got[3] and (f == flags).all()
+
+
+def test_restatement_selection_rules():
+    # exact correspondences at octave 1 (pitch 1) would need integer pixels; a pure translation gives them: every valid hypothesis
+    # has every record as an inlier, so the tie goes to the lowest valid h
+    rng = np.random.default_rng(9)
+    m, qp, tp, planted = epiref.planted_scene(9, n=64, outliers=0.0)
+    model, flags, hyps = epiref.ransac(m, qp, tp, 64, 9, 1e6)   # a bound so wide that every record is an inlier of every model
+    valid = np.flatnonzero(hyps["valid"])
+    assert len(valid) > 1 and (hyps["inliers"][valid] == 64).all()
+    assert int(model["best"][0]) == valid[0] and int(model["n_inliers"][0]) == 64 and flags.all()
+    assert (hyps["F"][hyps["valid"] == 0] == 0).all() and (hyps["inliers"][hyps["valid"] == 0] == 0).all()
+    # an all-coincident point set: no hypothesis is valid
+    qc = qp.copy()
+    qc[:] = qp[0]
+    model, flags, hyps = epiref.ransac(m, qc, tp, 64, 9, 4.0)
+    assert int(model["best"][0]) == -1 and (model["F"][0] == 0).all() and int(model["n_inliers"][0]) == 0 and int(model["n_valid"][0]) == 0
+    assert not flags.any() and int(model["n_matches"][0]) == 64
+    # seven records
+    model, flags, hyps = epiref.ransac(m[:7], qp, tp, 64, 9, 4.0)
+    assert int(model["best"][0]) == -1 and int(model["n_matches"][0]) == 7 and not flags.any() and not hyps["valid"].any()
+    # records that are not trusted are never inliers, however wide the bound, and a sample with one is invalid
+    bad = m.copy()
+    bad["query"][3], bad["train"][10], bad["query"][20] = 64, 1 << 30, -1
+    tq = qp.copy()
+    tq["octave"][int(m["query"][30])] = 32
+    model, flags, hyps = epiref.ransac(bad, tq, tp, 64, 9, 1e6)
+    assert not flags[[3, 10, 20, 30]].any() and int(flags.sum()) == 60 == int(model["n_inliers"][0])
+    for h in range(64):
+        s = epiref.sample(9, 0, h, 64)
+        if s is not None and {3, 10, 20, 30} & set(s):
+            assert hyps["valid"][h] == 0
+    assert rng is not None

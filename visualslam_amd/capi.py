@@ -30,6 +30,8 @@ POINT_DTYPE = np.dtype([(n, "<i4") for n in ("row", "col", "value", "padding", "
 KP_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("response", "<f4")], align=True)
 NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4")], align=True)  # vslam_nn2
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
+EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
+EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
 
 
 class VslamError(RuntimeError):
@@ -92,6 +94,25 @@ class MatchOut(C.Structure):
     """vslam_match_out: struct_size, then every pointer with the bytes behind it."""
     _fields_ = [("struct_size", C.c_size_t), ("nn", C.c_void_p), ("nn_bytes", C.c_size_t), ("matches", C.c_void_p), ("matches_bytes", C.c_size_t),
                 ("match_counts", C.c_void_p), ("match_counts_bytes", C.c_size_t), ("match_cap", C.c_uint32)]
+
+
+class EpipolarHyp(C.Structure):
+    _fields_ = [("F", C.c_double * 9), ("inliers", C.c_uint32), ("valid", C.c_int32)]
+
+
+class Epipolar(C.Structure):
+    _fields_ = [("F", C.c_double * 9), ("n_matches", C.c_uint32), ("n_inliers", C.c_uint32), ("best", C.c_int32), ("n_valid", C.c_uint32)]
+
+
+class EpipolarParams(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_uint32), ("seed", C.c_uint32), ("max_dist2", C.c_double)]
+
+
+class EpipolarOut(C.Structure):
+    """vslam_epipolar_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("inlier_bits", C.c_void_p),
+                ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t), ("inlier_counts", C.c_void_p),
+                ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t)]
 
 
 class PyramidInfo(C.Structure):
@@ -168,6 +189,8 @@ SIGNATURES = {
     "vslam_count_totals_dev": (_I, [_P, _P, _P, _I, _P]),
     "vslam_match_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _I, _F, _I, C.POINTER(MatchOut)]),
     "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
+    "vslam_epipolar_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(EpipolarParams), C.POINTER(EpipolarOut)]),
+    "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -684,6 +707,61 @@ class Context:
         self._chk(lib().vslam_match_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), float(ratio2),
                                          int(bool(same_octave)), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_host")
         return nn, matches[: min(total.value, cap)], total.value
+
+    def epipolar(self, matches, match_counts, query_points, train_points, n_pairs: int | None = None, n_hypotheses: int = 512, seed: int = 1,
+                 max_dist2: float = 4.0, models=None, inlier_bits=None, inliers=None, inlier_counts=None, hypotheses=None):
+        """vslam_epipolar_dev: the RANSAC fundamental matrix of every pair from the tensors match() and detect_batch() wrote;
+        asynchronous on the context stream.  matches [n, match_cap, 3] (MATCH_DTYPE records), match_counts int32 [n], query_points /
+        train_points int32 [n, cap, 6] (train_points = query_points[1:] for consecutive frames).  Outputs, CUDA tensors: models - any
+        contiguous tensor of n_pairs * 88 bytes (EPIPOLAR_DTYPE after .cpu().numpy().view), inlier_bits int64 [n, (match_cap + 63) // 64],
+        inliers [n, inlier_cap, 3] like matches, inlier_counts int32 [n], hypotheses n_pairs * n_hypotheses * 80 bytes
+        (EPIPOLAR_HYP_DTYPE).  max_dist2 is the SQUARED Sampson distance in pixels."""
+        n = min(matches.shape[0], query_points.shape[0], train_points.shape[0]) if n_pairs is None else int(n_pairs)
+        for name, t in (("matches", matches), ("match_counts", match_counts), ("query_points", query_points), ("train_points", train_points),
+                        ("models", models), ("inlier_bits", inlier_bits), ("inliers", inliers), ("inlier_counts", inlier_counts), ("hypotheses", hypotheses)):
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"epipolar: {name} must be a contiguous tensor on cuda:{self.device}")
+        if models is None:
+            raise ValueError("epipolar: models is required")
+        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12 or query_points.dim() != 3 or train_points.dim() != 3:
+            raise ValueError("epipolar: matches must be [n, match_cap, 3] 4-byte elements, the points [n, cap, 6]")
+        if query_points.shape[2] * query_points.element_size() != 24 or train_points.shape[2] * train_points.element_size() != 24:
+            raise ValueError("epipolar: points must be [n, cap, 6] int32")
+        if min(matches.shape[0], match_counts.numel(), query_points.shape[0], train_points.shape[0]) < n or match_counts.element_size() != 4:
+            raise ValueError("epipolar: fewer sets than pairs")
+        eo = EpipolarOut()
+        eo.struct_size = C.sizeof(EpipolarOut)
+        for name, t in (("models", models), ("inlier_bits", inlier_bits), ("inliers", inliers), ("inlier_counts", inlier_counts), ("hypotheses", hypotheses)):
+            if t is not None:
+                setattr(eo, name, t.data_ptr())
+                setattr(eo, name + "_bytes", t.numel() * t.element_size())
+        if inliers is not None:
+            eo.inlier_cap = inliers.shape[1]
+        prm = EpipolarParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2))
+        self._chk(lib().vslam_epipolar_dev(self._h, matches.data_ptr(), match_counts.data_ptr(), matches.shape[1], query_points.data_ptr(),
+                                           query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n, C.byref(prm), C.byref(eo)),
+                  "vslam_epipolar_dev")
+
+    def epipolar_host(self, matches, query_points, train_points, n_hypotheses: int = 512, seed: int = 1, max_dist2: float = 4.0,
+                      inlier_cap: int | None = None, want_bits: bool = True, want_inliers: bool = True, want_hypotheses: bool = False):
+        """vslam_epipolar_host: one pair of numpy arrays (MATCH_DTYPE, POINT_DTYPE, POINT_DTYPE) -> (model: one EPIPOLAR_DTYPE record,
+        inlier_bits uint64 [(m + 63) // 64] or None, inliers MATCH_DTYPE or None, total inliers or None, hypotheses or None)."""
+        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE).reshape(-1)
+        qp = np.ascontiguousarray(query_points, dtype=POINT_DTYPE).reshape(-1)
+        tp = np.ascontiguousarray(train_points, dtype=POINT_DTYPE).reshape(-1)
+        m = len(mt)
+        cap = max(m, 1) if inlier_cap is None else int(inlier_cap)
+        model = np.zeros(1, EPIPOLAR_DTYPE)
+        bits = np.zeros((m + 63) // 64, np.uint64) if want_bits else None
+        inl = np.zeros(cap, MATCH_DTYPE) if want_inliers else None
+        hyp = np.zeros(int(n_hypotheses), EPIPOLAR_HYP_DTYPE) if want_hypotheses else None
+        total = C.c_size_t()
+        prm = EpipolarParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2))
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        self._chk(lib().vslam_epipolar_host(self._h, ptr(mt), m, ptr(qp), len(qp), ptr(tp), len(tp), C.byref(prm), model.ctypes.data, ptr(bits),
+                                            None if inl is None else inl.ctypes.data, cap, C.byref(total) if want_inliers else None, ptr(hyp)),
+                  "vslam_epipolar_host")
+        return (model[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None, hyp)
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -250,6 +250,28 @@ struct MatchEntries {  // entry = 64 consecutive query rows of a pair: bits = ac
     }
 };
 
+struct EpipolarEntries {  // entry = 64 consecutive match records of a pair: bits = inliers of the winning hypothesis
+    static constexpr int WORDS = 1;
+    struct Info {
+        unsigned int first;
+    };
+    const unsigned long long* flags;  // only the words that hold a record below the pair's count are defined
+    size_t fwords;
+    const vslam_match* matches;
+    const unsigned int* counts;
+    unsigned int mcap;
+    vslam_match* out;
+    __device__ size_t count() const { return fwords; }
+    __device__ unsigned int load(int f, size_t e, unsigned long long (&w)[4]) const {
+        w[0] = e * 64 < min(counts[f], mcap) ? flags[f * fwords + e] : 0ull;
+        return __popcll(w[0]);
+    }
+    __device__ Info info(int, size_t e) const { return Info{(unsigned int)(e * 64)}; }
+    __device__ void emit(int f, const Info& in, const unsigned long long (&w)[4], unsigned int k, size_t slot) const {
+        out[slot] = matches[(size_t)f * mcap + in.first + (unsigned int)select64(w[0], k)];
+    }
+};
+
 // Block-wide exclusive scan for 256 threads; `total` = block sum.
 __device__ __forceinline__ unsigned int block_excl_scan_256(unsigned int v, unsigned int* wsum, unsigned int& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -1,0 +1,118 @@
+// Two-view geometry of the C ABI (include/vslam.h): argument checks and sizing (vslam_epipolar_plan.h), scratch and launches
+// of kernels_epipolar.hip.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/vslam.h"
+#include "kernels_epipolar.hip.h"
+#include "vslam_ctx.h"
+#include "vslam_epipolar_plan.h"
+#include "vslam_launch.h"
+
+using namespace vslam;
+
+extern "C" {
+
+int vslam_epipolar_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
+                       const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points, uint32_t train_cap, int n_pairs,
+                       const vslam_epipolar_params* prm, const vslam_epipolar_out* out) {
+    static_assert(sizeof(vslam_epipolar_hyp) == 80 && sizeof(vslam_epipolar) == 88 && sizeof(EpiXY) == 32, "record layouts");
+    if (const char* why = epipolar_check_args(matches, match_counts, match_cap, query_points, query_cap, train_points, train_cap, n_pairs, prm, out))
+        return fail(c, VSLAM_ERR_INVALID, why);
+    TRY(usable_ctx(c));
+    if (n_pairs == 0) return VSLAM_OK;
+
+    const unsigned int H = prm->n_hypotheses;
+    const EpipolarPlan pl = epipolar_plan(match_cap, n_pairs, H);
+    EpiXY* xy = nullptr;
+    vslam_epipolar_hyp* hyp_ws = nullptr;
+    unsigned long long* flags_ws = nullptr;
+    unsigned int* chunk_ws = nullptr;
+    const bool lists = out->inlier_bits || out->inlier_counts;
+    WsPlan ws;
+    ws.add(xy, pl.coords_elems);
+    if (!out->hypotheses) ws.add(hyp_ws, pl.hyp_elems);
+    if (lists && !out->inlier_bits) ws.add(flags_ws, pl.flag_words);
+    if (out->inlier_counts) ws.add(chunk_ws, match_list_ws_elems(pl.fwords, n_pairs));
+    TRY(ws.commit(c));
+    vslam_epipolar_hyp* hyp = out->hypotheses ? out->hypotheses : hyp_ws;
+    unsigned long long* flags = out->inlier_bits ? reinterpret_cast<unsigned long long*>(out->inlier_bits) : flags_ws;
+
+    LAUNCH(c, "k_epi_coords", k_epi_coords, dim3(pl.rec_blocks, n_pairs), dim3(256), matches, match_counts, match_cap, query_points, query_cap,
+           train_points, train_cap, xy);
+    LAUNCH(c, "k_epi_models", k_epi_models, dim3(pl.model_blocks, n_pairs), dim3(EPI_MODEL_WG), xy, match_counts, match_cap, H, prm->seed, hyp);
+    LAUNCH(c, "k_epi_score", k_epi_score, dim3(pl.score_blocks, pl.nsplit, n_pairs), dim3(EPI_SCORE_WG), xy, match_counts, match_cap, H,
+           prm->max_dist2, hyp);
+    LAUNCH(c, "k_epi_select", k_epi_select, dim3(n_pairs), dim3(256), hyp, match_counts, match_cap, H, out->models);
+    if (lists)
+        LAUNCH(c, "k_epi_flags", k_epi_flags, dim3(pl.rec_blocks, n_pairs), dim3(256), xy, match_counts, match_cap, out->models, prm->max_dist2,
+               flags, pl.fwords);
+    if (out->inlier_counts)
+        TRY(enqueue_inlier_list(c, flags, pl.fwords, matches, match_counts, match_cap, n_pairs, chunk_ws, out->inliers, out->inlier_cap,
+                                out->inlier_counts));
+    return VSLAM_OK;
+}
+
+int vslam_epipolar_host(vslam_ctx* c, const vslam_match* matches, size_t n_matches, const vslam_point* query_points, size_t n_query,
+                        const vslam_point* train_points, size_t n_train, const vslam_epipolar_params* prm, vslam_epipolar* model,
+                        uint64_t* inlier_bits, vslam_match* inliers, size_t inlier_cap, size_t* n_inliers, vslam_epipolar_hyp* hypotheses) {
+    ARGCHK(c, prm && model, "epipolar_host: null argument");
+    ARGCHK(c, prm->n_hypotheses >= 1 && prm->n_hypotheses <= 65535, "epipolar_host: 1 .. 65535 hypotheses");
+    ARGCHK(c, std::isfinite(prm->max_dist2) && prm->max_dist2 > 0.0, "epipolar_host: max_dist2 must be finite and positive");
+    ARGCHK(c, (matches || n_matches == 0) && (query_points || n_query == 0) && (train_points || n_train == 0), "epipolar_host: null input");
+    ARGCHK(c, n_matches < (1u << 31) && n_query < (1u << 31) && n_train < (1u << 31) && inlier_cap < (1u << 31), "epipolar_host: too many records");
+    ARGCHK(c, !inliers || (n_inliers && inlier_cap > 0), "epipolar_host: inliers needs n_inliers and an inlier_cap");
+    ARGCHK(c, n_matches == 0 || (n_query > 0 && n_train > 0), "epipolar_host: matches without points");
+    TRY(usable_ctx(c));
+
+    DevBufs dev;
+    vslam_match* d_matches = nullptr;
+    vslam_point *d_q = nullptr, *d_t = nullptr;
+    uint32_t* d_cnt = nullptr;
+    const uint32_t h_cnt = (uint32_t)n_matches;
+    TRY(dev.put(c, d_matches, matches, n_matches));
+    TRY(dev.put(c, d_q, query_points, n_query));
+    TRY(dev.put(c, d_t, train_points, n_train));
+    TRY(dev.put(c, d_cnt, &h_cnt, 1));
+    // a capacity of at least 1 on every side (records without points were refused above)
+    const uint32_t mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
+    const size_t fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
+    vslam_epipolar_out out{};
+    out.struct_size = sizeof(out);
+    TRY(dev.get(c, out.models, 1));
+    out.models_bytes = sizeof(vslam_epipolar);
+    if (inlier_bits) {
+        TRY(dev.get(c, out.inlier_bits, fwords));
+        out.inlier_bits_bytes = fwords * sizeof(uint64_t);
+    }
+    if (n_inliers) {
+        TRY(dev.get(c, out.inlier_counts, 1));
+        out.inlier_counts_bytes = sizeof(uint32_t);
+        if (inliers) {
+            TRY(dev.get(c, out.inliers, inlier_cap));
+            out.inliers_bytes = inlier_cap * sizeof(vslam_match);
+            out.inlier_cap = (uint32_t)inlier_cap;
+        }
+    }
+    if (hypotheses) {
+        TRY(dev.get(c, out.hypotheses, prm->n_hypotheses));
+        out.hypotheses_bytes = (size_t)prm->n_hypotheses * sizeof(vslam_epipolar_hyp);
+    }
+    TRY(vslam_epipolar_dev(c, d_matches, d_cnt, mcap, d_q, qcap, d_t, tcap, 1, prm, &out));
+    uint32_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(model, out.models, sizeof(vslam_epipolar), hipMemcpyDeviceToHost, c->stream));
+    if (inlier_bits && used_words) HIPCHK(c, hipMemcpyAsync(inlier_bits, out.inlier_bits, used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (hypotheses) HIPCHK(c, hipMemcpyAsync(hypotheses, out.hypotheses, out.hypotheses_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (n_inliers) HIPCHK(c, hipMemcpyAsync(&total, out.inlier_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_inliers) {
+        *n_inliers = total;
+        const size_t k = std::min<size_t>(total, inlier_cap);
+        if (inliers && k) HIPCHK(c, hipMemcpy(inliers, out.inliers, k * sizeof(vslam_match), hipMemcpyDeviceToHost));
+    }
+    return VSLAM_OK;
+}
+
+}  // extern "C"

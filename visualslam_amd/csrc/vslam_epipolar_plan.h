@@ -1,0 +1,75 @@
+// The host arithmetic of vslam_epipolar_dev (include/vslam.h, "two-view geometry") that needs no HIP: the argument checks in
+// the ABI's order, and the grids and scratch sizes, all from the capacities (the counts live on the device).  Stated once,
+// here, so that a host program can run it under the sanitizers with extreme capacities (tests/epipolar_plan_driver.cpp).
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/vslam.h"
+
+namespace vslam {
+
+constexpr unsigned int EPI_TILE = 256;      // match records a k_epi_score workgroup stages in LDS at a time (8 KiB)
+constexpr unsigned int EPI_SCORE_WG = 256;  // hypotheses (lanes) per k_epi_score workgroup
+constexpr unsigned int EPI_MODEL_WG = 64;   // hypotheses per k_epi_models workgroup: one wave, 72 f64 of LDS per lane
+constexpr unsigned int EPI_MAX_SPLIT = 64;  // workgroups that share the records of one (pair, hypothesis block)
+constexpr size_t EPI_WANT_WGS = 2048;       // 8 workgroups per compute unit
+
+// The message of the first failed check, in the order of vslam_match_dev's (null, struct_size, n_pairs, the parameters, the
+// inputs, the buffers); nullptr: the call is valid.
+inline const char* epipolar_check_args(const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap, const vslam_point* query_points,
+                                       uint32_t query_cap, const vslam_point* train_points, uint32_t train_cap, int n_pairs,
+                                       const vslam_epipolar_params* prm, const vslam_epipolar_out* out) {
+    if (!prm || !out) return "epipolar: null argument";
+    if (out->struct_size != sizeof(vslam_epipolar_out)) return "epipolar: out->struct_size is not sizeof(vslam_epipolar_out)";
+    if (n_pairs < 0 || n_pairs > 65535) return "epipolar: 0 .. 65535 pairs per call";
+    if (prm->n_hypotheses < 1 || prm->n_hypotheses > 65535) return "epipolar: 1 .. 65535 hypotheses";
+    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "epipolar: max_dist2 must be finite and positive";
+    if (!matches || !match_counts || !query_points || !train_points) return "epipolar: null input";
+    if (match_cap == 0 || query_cap == 0 || train_cap == 0) return "epipolar: a capacity is zero";
+    const size_t np = (size_t)n_pairs, fwords = ((size_t)match_cap + 63) / 64;
+    if (!out->models) return "epipolar: models is required";
+    if (out->models_bytes / sizeof(vslam_epipolar) < np) return "epipolar: models buffer too small";
+    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "epipolar: inlier_bits buffer too small";
+    if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "epipolar: inliers needs inlier_counts and an inlier_cap";
+    if (out->inliers && out->inliers_bytes / sizeof(vslam_match) < np * out->inlier_cap) return "epipolar: inliers buffer too small";
+    if (out->inlier_counts && out->inlier_counts_bytes / sizeof(uint32_t) < np) return "epipolar: inlier_counts buffer too small";
+    if (out->hypotheses && out->hypotheses_bytes / sizeof(vslam_epipolar_hyp) < np * prm->n_hypotheses) return "epipolar: hypotheses buffer too small";
+    return nullptr;
+}
+
+// Grids and scratch of one valid call with n_pairs >= 1.  Every grid dimension stays within HIP's limits (x < 2^31, y and z
+// <= 65535) and no size wraps: n_pairs < 2^16, the capacities < 2^32, a record <= 80 bytes.
+struct EpipolarPlan {
+    unsigned int fwords;                  // ballot words per pair
+    unsigned int rec_blocks;              // 256-record blocks per pair: grid.x of k_epi_coords and k_epi_flags
+    unsigned int model_blocks;            // grid.x of k_epi_models
+    unsigned int score_blocks;            // grid.x of k_epi_score: hypothesis blocks
+    unsigned int tiles;                   // record tiles per pair
+    unsigned int nsplit;                  // grid.y of k_epi_score: the tiles are dealt round robin to nsplit workgroups
+    size_t coords_elems;                  // scratch: {x, y, x', y'} f64 records
+    size_t hyp_elems;                     // scratch when the caller gives no hypotheses buffer
+    size_t flag_words;                    // scratch when the caller gives no inlier_bits buffer
+};
+
+inline EpipolarPlan epipolar_plan(uint32_t match_cap, int n_pairs, uint32_t n_hypotheses) {
+    EpipolarPlan p{};
+    const size_t np = (size_t)n_pairs;
+    p.fwords = (unsigned int)(((size_t)match_cap + 63) / 64);
+    p.rec_blocks = (unsigned int)(((size_t)match_cap + 255) / 256);
+    p.model_blocks = (n_hypotheses + EPI_MODEL_WG - 1) / EPI_MODEL_WG;
+    p.score_blocks = (n_hypotheses + EPI_SCORE_WG - 1) / EPI_SCORE_WG;
+    p.tiles = (unsigned int)(((size_t)match_cap + EPI_TILE - 1) / EPI_TILE);
+    const size_t wgs = np * p.score_blocks;
+    size_t split = (EPI_WANT_WGS + wgs - 1) / wgs;
+    if (split > EPI_MAX_SPLIT) split = EPI_MAX_SPLIT;
+    if (split > p.tiles) split = p.tiles;
+    p.nsplit = (unsigned int)(split < 1 ? 1 : split);
+    p.coords_elems = np * match_cap;
+    p.hyp_elems = np * n_hypotheses;
+    p.flag_words = np * p.fwords;
+    return p;
+}
+
+}  // namespace vslam

@@ -54,7 +54,8 @@ static const char* const kKernelNames =
     "k_dog5\nk_resize_nearest_half\nk_extrema\nk_pyr_octave\nk_pyr_octave_mx\n"
     "k_gauss_v_strip\nk_gauss_h_strip\nk_gauss_h_diff\nk_resize_linear2x_slide\nk_resize_nearest_half_v4\nk_extrema_w3\nk_extrema_dense\nk_localize_points\nk_orient_keypoints\nk_edge_response_windows\nk_level_gradients\nk_pack_rows\nk_edge_flags\nk_survivor_ranges\nk_orient_survivors\n"
     "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals\n"
-    "k_desc_norms\nk_match_nn2\nk_match_merge";
+    "k_desc_norms\nk_match_nn2\nk_match_merge\n"
+    "k_epi_coords\nk_epi_models\nk_epi_score\nk_epi_select\nk_epi_flags";
 
 
 // Runs `body` with the context's launch stream temporarily replaced (LAUNCH uses ctx->stream).
@@ -334,6 +335,13 @@ int vslam::enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, siz
                               unsigned int* chunk_ws, vslam_match* matches, unsigned int match_cap, unsigned int* match_counts) {
     const MatchEntries ent{flags, fwords, nn, qcap, matches};
     return enqueue_compaction(c, ent, fwords, n_pairs, chunk_ws, matches ? match_cap : 0u, match_counts, 0);
+}
+
+int vslam::enqueue_inlier_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_match* matches, const unsigned int* match_counts,
+                               unsigned int match_cap, int n_pairs, unsigned int* chunk_ws, vslam_match* inliers, unsigned int inlier_cap,
+                               unsigned int* inlier_counts) {
+    const EpipolarEntries ent{flags, fwords, matches, match_counts, match_cap, inliers};
+    return enqueue_compaction(c, ent, fwords, n_pairs, chunk_ws, inliers ? inlier_cap : 0u, inlier_counts, 0);
 }
 
 // The table of the localization's quadratic term, filled by the same device function that the

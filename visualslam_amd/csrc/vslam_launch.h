@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +29,11 @@ int ws_reserve(vslam_ctx* c, size_t bytes);
 size_t match_list_ws_elems(size_t fwords, int n_pairs);
 int enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_nn2* nn, unsigned int qcap, int n_pairs,
                        unsigned int* chunk_ws, vslam_match* matches, unsigned int match_cap, unsigned int* match_counts);
+// The inlier list of vslam_epipolar_dev, the same way (EpipolarEntries): the winner's ballot words over the match records of
+// n_pairs pairs -> the inlier records in list order.  chunk_ws as above; inliers may be null (totals only).
+int enqueue_inlier_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_match* matches, const unsigned int* match_counts,
+                        unsigned int match_cap, int n_pairs, unsigned int* chunk_ws, vslam_match* inliers, unsigned int inlier_cap,
+                        unsigned int* inlier_counts);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
@@ -63,6 +68,41 @@ class WsPlan {
         if (n > kMaxSlots) return fail(c, VSLAM_ERR_NOMEM, "workspace plan: more buffers than WsPlan::kMaxSlots");
         TRY(vslam::ws_reserve(c, total));
         for (int i = 0; i < n; ++i) slots[i].set(slots[i].where, c->ws + slots[i].off);
+        return VSLAM_OK;
+    }
+};
+}  // namespace
+
+// What the entry points that work from host memory through per-call device buffers share (vslam_match_host,
+// vslam_epipolar_host), and the answer of a device entry point whose caller has no HIP device.
+namespace {
+// No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
+// after the arguments, before the context is touched.
+inline int usable_ctx(vslam_ctx* c) {
+    if (c) return bind_device(c);
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VSLAM_ERR_HIP;
+    return VSLAM_ERR_INVALID;
+}
+
+// Device buffers of one host-memory call: freed when the call returns.
+struct DevBufs {
+    std::vector<void*> all;
+    ~DevBufs() {
+        for (void* p : all) (void)hipFree(p);
+    }
+    template <typename T>
+    int get(vslam_ctx* c, T*& p, size_t count) {
+        void* q = nullptr;
+        HIPCHK(c, hipMalloc(&q, (count ? count : 1) * sizeof(T)));
+        all.push_back(q);
+        p = static_cast<T*>(q);
+        return VSLAM_OK;
+    }
+    template <typename T>
+    int put(vslam_ctx* c, T*& p, const T* host, size_t count) {
+        TRY(get(c, p, count));
+        if (count) HIPCHK(c, hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
         return VSLAM_OK;
     }
 };

@@ -12,39 +12,6 @@
 
 using namespace vslam;
 
-namespace {
-// No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
-// after the arguments, before the context is touched.
-int usable_ctx(vslam_ctx* c) {
-    if (c) return bind_device(c);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return VSLAM_ERR_HIP;
-    return VSLAM_ERR_INVALID;
-}
-
-// Device buffers of one vslam_match_host call.
-struct DevBufs {
-    std::vector<void*> all;
-    ~DevBufs() {
-        for (void* p : all) (void)hipFree(p);
-    }
-    template <typename T>
-    int get(vslam_ctx* c, T*& p, size_t count) {
-        void* q = nullptr;
-        HIPCHK(c, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-        all.push_back(q);
-        p = static_cast<T*>(q);
-        return VSLAM_OK;
-    }
-    template <typename T>
-    int put(vslam_ctx* c, T*& p, const T* host, size_t count) {
-        TRY(get(c, p, count));
-        if (count) HIPCHK(c, hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
-        return VSLAM_OK;
-    }
-};
-}  // namespace
-
 extern "C" {
 
 int vslam_match_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_desc_sets* T, int n_pairs, float ratio2, int same_octave,

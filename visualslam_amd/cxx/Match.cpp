@@ -1,11 +1,15 @@
 // The step the reference's `DoG` executable stops short of (Diff_of_Gauss.cpp:687, "final step is graphing and comparing
 // two images with each other"): the DoG pipeline of DoG.cpp on two images - pyramid, initialKeypointDetection,
 // filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
-// second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.
-//   usage: Match [first.pgm second.pgm | WxH] [octaves, default 4]      (WxH: frames 0 and 1 of the synthetic stream)
+// second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --epipolar adds
+// the step after that: the RANSAC fundamental matrix of the accepted matches (vslam::fundamentalRansac: 512 hypotheses, seed 1,
+// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.
+//   usage: Match [--epipolar] [first.pgm second.pgm | WxH] [octaves, default 4]      (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 
 #include "imgio.hpp"
 #include "vslam_cxx.hpp"
@@ -16,6 +20,7 @@ namespace {
 struct Described {
     std::vector<std::vector<float>> descriptors;
     std::vector<unsigned char> defined;
+    std::vector<SLAM::point> points;  // the oriented keypoint of every descriptor
     size_t n_defined = 0;
 };
 
@@ -29,6 +34,7 @@ Described describe(Mat img, int numOctaves) {  // (the reference's constructor t
         std::vector<unsigned char> defined;
         SIFT(reducedKeypoints, out.descriptors, pyramid, octave, &defined);
         out.defined.insert(out.defined.end(), defined.begin(), defined.end());
+        out.points.insert(out.points.end(), reducedKeypoints.begin(), reducedKeypoints.end());
     }
     for (unsigned char d : out.defined) out.n_defined += d != 0;
     return out;
@@ -37,6 +43,8 @@ Described describe(Mat img, int numOctaves) {  // (the reference's constructor t
 
 int main(int argc, char** argv) {
     try {
+        const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
+        if (epipolar) --argc, ++argv;
         Mat first, second;
         int w = 0, h = 0, next = 2;
         if (argc < 2) {
@@ -44,7 +52,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -52,15 +60,28 @@ int main(int argc, char** argv) {
         const auto t0 = std::chrono::steady_clock::now();
         const Described q = describe(first, numOctaves), t = describe(second, numOctaves);
         const vslam::Matches m = vslam::matchDescriptors(q.descriptors, t.descriptors, 0.8f, &q.defined, &t.defined);
+        std::string extra;
+        if (epipolar) {
+            const vslam::Epipolar e = vslam::fundamentalRansac(m.matches, q.points, t.points);
+            char buf[512];
+            std::snprintf(buf, sizeof buf, ", \"epipolar\": {\"n_inliers\": %u, \"best\": %d, \"n_valid\": %u, \"hypotheses\": 512, \"max_dist2\": 4.0, \"F\": [", e.model.n_inliers,
+                          e.model.best, e.model.n_valid);
+            extra = buf;
+            for (int i = 0; i < 9; ++i) {
+                std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", e.model.F[i]);
+                extra += buf;
+            }
+            extra += "]}";
+        }
         const auto t1 = std::chrono::steady_clock::now();
         size_t exact = 0, nearest = 0;
         for (const vslam_nn2& r : m.nn) nearest += r.index >= 0;
         for (const vslam_match& a : m.matches) exact += a.dist2 == 0.0f;
         std::printf("{\"exe\": \"Match\", \"octaves\": %d, \"query\": {\"rows\": %d, \"cols\": %d, \"descriptors\": %zu, \"defined\": %zu}, "
                     "\"train\": {\"rows\": %d, \"cols\": %d, \"descriptors\": %zu, \"defined\": %zu}, \"with_nearest\": %zu, \"accepted\": %zu, "
-                    "\"zero_distance\": %zu, \"ratio\": 0.8, \"ms\": %.3f}\n",
+                    "\"zero_distance\": %zu, \"ratio\": 0.8, \"ms\": %.3f%s}\n",
                     numOctaves, first.rows, first.cols, q.descriptors.size(), q.n_defined, second.rows, second.cols, t.descriptors.size(), t.n_defined,
-                    nearest, m.matches.size(), exact, std::chrono::duration<double, std::milli>(t1 - t0).count());
+                    nearest, m.matches.size(), exact, std::chrono::duration<double, std::milli>(t1 - t0).count(), extra.c_str());
         return 0;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "Match: %s\n", e.what());

@@ -468,3 +468,21 @@ vslam::Matches vslam::matchDescriptors(const std::vector<std::vector<float>>& qu
     out.matches.resize(total);
     return out;
 }
+
+// ---- two-view geometry (the reference's README step 3; no reference code) ------------------------------------------
+
+vslam::Epipolar vslam::fundamentalRansac(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                                         const std::vector<SLAM::point>& trainPoints, const vslam_epipolar_params& params) {
+    static_assert(sizeof(SLAM::point) == sizeof(vslam_point), "SLAM::point is the ABI's point record");
+    vslam::Epipolar out{};
+    out.inliers.resize(matches.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_epipolar_host(c, matches.empty() ? nullptr : matches.data(), matches.size(),
+                                     reinterpret_cast<const vslam_point*>(queryPoints.data()), queryPoints.size(),
+                                     reinterpret_cast<const vslam_point*>(trainPoints.data()), trainPoints.size(), &params, &out.model, nullptr,
+                                     out.inliers.empty() ? nullptr : out.inliers.data(), out.inliers.size(), &total, nullptr),
+                 c, "fundamentalRansac");
+    out.inliers.resize(total);
+    return out;
+}

@@ -187,4 +187,15 @@ struct Matches {
 };
 Matches matchDescriptors(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train, float ratio = 0.8f,
                          const std::vector<unsigned char>* query_defined = nullptr, const std::vector<unsigned char>* train_defined = nullptr);
+
+// The step after matching (the reference's README, "3. 3D Reconstruction - Epipolar Geometry"): the fundamental matrix of the
+// pair by RANSAC over the accepted matches, and their inlier subset, on the GPU (vslam_epipolar_host; sampling, the 8-point
+// model and the Sampson test are stated in include/vslam.h).  `matches` is Matches::matches; the two point vectors are the
+// oriented keypoints SIFT() described, all octaves of an image in the order of its descriptors.
+struct Epipolar {
+    vslam_epipolar model;              // F row-major with x_train^T F x_query = 0 in image pixels; best = -1: none
+    std::vector<vslam_match> inliers;  // the matches the model accepts, list order kept
+};
+Epipolar fundamentalRansac(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                           const std::vector<SLAM::point>& trainPoints, const vslam_epipolar_params& params = {512, 1, 4.0});
 }  // namespace vslam
