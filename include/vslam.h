@@ -537,7 +537,10 @@ int vslam_count_totals_dev(vslam_ctx* ctx, const uint32_t* harris_counts, const 
  *   n(a)     = s(a, a)
  *   d2(a, b) = (n(a) + n(b)) - 2 s(a, b) in f32: the sum rounded, the doubling exact, the difference rounded.
  * d2 is a pure function of the two rows and is stored as computed, WITHOUT a clamp: d2(a, a) is exactly 0, but for two
- * nearly identical rows it can be slightly NEGATIVE.
+ * nearly identical rows it can be slightly NEGATIVE.  Rows may hold any f32 value - subnormals, infinities, NaN, either zero:
+ * the chains are IEEE (no flush to zero), and a distance of +inf or NaN never wins (a query row with no other distance gets
+ * {-1, +inf, +inf}).  -inf CAN occur - nearly identical rows whose norms are each about 2^127: n(a) + n(b) still rounds to a finite
+ * value, 2 s to +inf - and it wins and is accepted like any smaller value.
  * Selection for one query row over the train rows j = 0 .. nt-1 ascending: best = second = +inf, index = -1; if d2 < best
  * then second = best, best = d2, index = j; otherwise if d2 < second then second = d2.  Ties keep the lowest index, a NaN
  * distance never wins, and two equal minima give second_dist2 == dist2.  Skipped: a train row whose `defined` byte is 0,

@@ -279,6 +279,31 @@ def score(F, xy, max_dist2):
     return int(n), flags.astype(bool)
 
 
+def exact_inlier(F, xy, max_dist2):
+    """The Sampson predicate e^2 < max_dist2 * den of F over coordinate records xy [m, 4] in exact rational arithmetic (the
+    inputs are doubles, so fractions.Fraction loses nothing) - NOT the header's rounded operations but the inequality they
+    stand for.  -> (inlier bool [m], near bool [m], trusted bool [m]); `near`: the two sides differ by no more than
+    2^-40 * (T^2 + max_dist2 * den), T = |x' a0| + |y' a1| + |a2|, about 2^12 roundings of the quantities being compared, where
+    the rounded test may fall on either side.  Records with NaN coordinates are not trusted and are never inliers."""
+    from fractions import Fraction as Q
+
+    f = [Q(float(v)) for v in np.asarray(F, np.float64).reshape(9)]
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 4)
+    md, eps = Q(float(max_dist2)), Q(1, 2 ** 40)
+    inl, near, trusted = (np.zeros(len(xy), bool) for _ in range(3))
+    for i, rec in enumerate(xy):
+        if np.isnan(rec).any():
+            continue
+        x, y, u, v = (Q(float(c)) for c in rec)
+        a0, a1, a2 = f[0] * x + f[1] * y + f[2], f[3] * x + f[4] * y + f[5], f[6] * x + f[7] * y + f[8]
+        b0, b1 = f[0] * u + f[3] * v + f[6], f[1] * u + f[4] * v + f[7]
+        e = u * a0 + v * a1 + a2
+        rhs = md * (a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1)
+        T = abs(u * a0) + abs(v * a1) + abs(a2)
+        trusted[i], inl[i], near[i] = True, e * e < rhs, abs(e * e - rhs) <= eps * (T * T + rhs)
+    return inl, near, trusted
+
+
 def ransac(matches, query_points, train_points, n_hypotheses, seed, max_dist2, pair=0):
     """One pair -> (model [1] capi.EPIPOLAR_DTYPE, flags bool [m], hypotheses [H] capi.EPIPOLAR_HYP_DTYPE).  `pair`: the index j
     the pair has inside a batched call (it enters the sampling hash)."""

@@ -35,6 +35,11 @@ void ref_d2(const float* a, const float* b, float* out) {
     const float na = chain(a, a), nb = chain(b, b), sum = na + nb, twice = 2.0f * chain(a, b);
     *out = sum - twice;
 }
+/* d2 of every query row against every train row, out [nq][nt] */
+void ref_d2_all(const float* q, size_t nq, const float* t, size_t nt, float* out) {
+    for (size_t i = 0; i < nq; ++i)
+        for (size_t j = 0; j < nt; ++j) ref_d2(q + 128 * i, t + 128 * j, out + i * nt + j);
+}
 /* query rows q0 .. q1-1 against every train row */
 void ref_match(const float* q, const uint8_t* qdef, const int32_t* qoct, size_t q0, size_t q1, const float* qn,
                const float* t, const uint8_t* tdef, const int32_t* toct, size_t nt, const float* tn,
@@ -98,6 +103,35 @@ def d2(a, b):
     return out[0]
 
 
+def d2_all(q, t):
+    """[nq, nt] f32: the restatement's d2 of every query row against every train row."""
+    q, t = _rows(q), _rows(t)
+    out = np.zeros((len(q), len(t)), np.float32)
+    lib().ref_d2_all(C.c_void_p(q.ctypes.data), C.c_size_t(len(q)), C.c_void_p(t.ctypes.data), C.c_size_t(len(t)), C.c_void_p(out.ctypes.data))
+    return out
+
+
+def exact_d2(q, t):
+    """[nq, nt] f64: sum over k of (a_k - b_k)^2 of the f32 rows, formed in f64 - NOT the matcher's arithmetic but the quantity
+    it stands for.  A difference of two f32 and its square are exact or correctly rounded in f64, and the 128-term f64 sum is
+    accurate to about 1e-14 relative."""
+    q, t = _rows(q).astype(np.float64), _rows(t).astype(np.float64)
+    out = np.zeros((len(q), len(t)), np.float64)
+    for lo in range(0, len(q), 32):
+        d = q[lo:lo + 32, None, :] - t[None, :, :]
+        out[lo:lo + 32] = (d * d).sum(axis=2)
+    return out
+
+
+def d2_bound(q, t):
+    """[nq, nt] f64: B = 264 * 2^-24 * (|a|^2 + |b|^2), a bound on |d2 - exact_d2| that is derived, not measured.  With
+    u = 2^-24, a 128-term fmaf chain errs by at most gamma_128 ~ 128 u times sum |a_k b_k|; the three chains of d2 contribute at
+    most 128 u (n(a) + n(b) + 2 sum |a b|) <= 256 u (n(a) + n(b)), and the two remaining roundings (the sum, the difference)
+    fewer than 8 u more of the same quantity."""
+    q, t = _rows(q).astype(np.float64), _rows(t).astype(np.float64)
+    return 264.0 * 2.0 ** -24 * ((q * q).sum(axis=1)[:, None] + (t * t).sum(axis=1)[None, :])
+
+
 def match(q, t, ratio2=0.64, same_octave=False, q_defined=None, t_defined=None, q_octave=None, t_octave=None):
     """-> (nn [nq] capi.NN2_DTYPE, matches capi.MATCH_DTYPE in ascending query order)."""
     q, t = _rows(q), _rows(t)
@@ -135,3 +169,20 @@ def reference_like_descriptors(rng, n):
     h = h / h.max(axis=1, keepdims=True)
     h = np.minimum(h, np.float32(0.2))
     return (h / h.max(axis=1, keepdims=True)).astype(np.float32)
+
+
+def crafted(rng, n, base=None, signed=False):
+    """n rows like the reference's descriptors; with `base`, a quarter of them are exact copies of base rows (distance exactly 0)
+    and a quarter are copies with sigma = 0.02 noise.  signed: every entry gets a random sign (cancellation in every chain) and
+    the noisy copies keep theirs; otherwise all entries are non-negative."""
+    d = reference_like_descriptors(rng, n)
+    if signed:
+        d = d * rng.choice(np.float32([-1.0, 1.0]), (n, 128))
+    if base is not None and len(base) and n:
+        k = rng.integers(0, len(base), n)
+        noisy = base[k] + rng.normal(0, 0.02, (n, 128)).astype(np.float32)
+        noisy = (noisy if signed else np.abs(noisy)).astype(np.float32)
+        pick = rng.random(n)
+        d[pick < 0.25] = base[k][pick < 0.25]
+        d[(pick >= 0.25) & (pick < 0.5)] = noisy[(pick >= 0.25) & (pick < 0.5)]
+    return d

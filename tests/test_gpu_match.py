@@ -23,14 +23,7 @@ def env():
 
 def crafted(rng, n, base=None):
     """n rows like the reference's descriptors; with `base`, half of them are copies / near copies of base rows."""
-    d = matchref.reference_like_descriptors(rng, n)
-    if base is not None and len(base) and n:
-        k = rng.integers(0, len(base), n)
-        noisy = np.abs(base[k] + rng.normal(0, 0.02, (n, 128)).astype(np.float32)).astype(np.float32)
-        pick = rng.random(n)
-        d[pick < 0.25] = base[k][pick < 0.25]           # exact copies: distance exactly 0
-        d[(pick >= 0.25) & (pick < 0.5)] = noisy[(pick >= 0.25) & (pick < 0.5)]
-    return d
+    return matchref.crafted(rng, n, base)
 
 
 def sets_to_device(torch, sets, cap, with_points):
