@@ -34,11 +34,9 @@
 #include <type_traits>
 
 #include "kernels_generic.hip.h"
+#include "vslam_harris_launch.h"  // HS_VALID_LANES, HS_STRIP_W (240 output columns per wave strip) and the launch geometry
 
 namespace vslam {
-
-constexpr int HS_VALID_LANES = 60;
-constexpr int HS_STRIP_W = 4 * HS_VALID_LANES;  // 240 output columns per wave strip
 
 typedef short s2_t __attribute__((ext_vector_type(2)));
 

@@ -721,18 +721,16 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
     return VSLAM_OK;
 }
 
-// Words of keypoint-flag scratch per frame for the Harris chain: 4 ballot words per strip row.
-static size_t harris_flag_words(int rows, int cols) { return (size_t)rows * ((cols + HS_STRIP_W - 1) / HS_STRIP_W) * 4; }
-
 // Harris chain on nf device frames with dense rows: response (required buffer), optional mask /
 // nms2 / keypoint list, all from the single-pass wave-strip kernel - its aligned form when every
-// row and frame starts on a dword, the any-width form otherwise.
+// row and frame starts on a dword, the any-width form otherwise.  Strips, segments, grid and the
+// flag words per frame (harris_flag_words) are vslam_harris_launch.h's.
 static int enqueue_harris(vslam_ctx* c, const uint8_t* frames, size_t fframe, int rows, int cols, int nf, float k,
                           float* resp, uint8_t* mask, float* nms2, unsigned long long* hflags, vslam_kp* kps,
                           unsigned int cap, unsigned int* counts, unsigned int* chunk_ws) {
     const size_t N = (size_t)rows * cols;
     if (N >= ((size_t)1 << 31)) return fail(c, VSLAM_ERR_UNSUPPORTED, "Harris: images of 2^31 pixels or more are not supported (32-bit row offsets)");
-    const bool aligned = cols % 4 == 0 && fframe % 4 == 0;
+    const HarrisLaunch g = harris_launch(rows, cols, nf, fframe);
     HarrisStripArgs a;
     a.img = frames;
     a.frame = fframe;
@@ -743,19 +741,15 @@ static int enqueue_harris(vslam_ctx* c, const uint8_t* frames, size_t fframe, in
     a.mask = mask;
     a.nms2 = nms2;
     a.flags = hflags;
-    a.nstrips = (cols + HS_STRIP_W - 1) / HS_STRIP_W;
-    a.fframe = (size_t)rows * a.nstrips * 4;
+    a.nstrips = g.nstrips;
+    a.fframe = g.flag_words;
+    a.seg = g.seg;
     if (!c->dump) HIPCHK(c, hipMalloc((void**)&c->dump, 256));
     a.dump = c->dump;
-    // enough waves to fill the chip several times over, long enough strips to amortise the
-    // 9-row pipeline fill
-    const long want_seg = std::max<long>(1, 12288 / ((long)a.nstrips * nf));
-    a.seg = (int)std::min<long>(rows, std::max<long>(16, (rows + want_seg - 1) / want_seg));
-    const int nseg = (rows + a.seg - 1) / a.seg;
-    if (aligned)
-        LAUNCH(c, "k_harris_strip", k_harris_strip<false>, dim3((a.nstrips * nseg + 3) / 4, 1, nf), dim3(256), a);
+    if (g.aligned)
+        LAUNCH(c, "k_harris_strip", k_harris_strip<false>, dim3(g.grid_x, 1, nf), dim3(64 * HS_WAVES), a);
     else
-        LAUNCH(c, "k_harris_strip", k_harris_strip<true>, dim3((a.nstrips * nseg + 3) / 4, 1, nf), dim3(256), a);
+        LAUNCH(c, "k_harris_strip", k_harris_strip<true>, dim3(g.grid_x, 1, nf), dim3(64 * HS_WAVES), a);
     if (hflags && kps && counts) {
         HarrisStripEntries ent{hflags, a.fframe, rows, cols, a.nstrips, resp, N, kps};
         TRY(enqueue_compaction(c, ent, (size_t)rows * a.nstrips, nf, chunk_ws, cap, counts, 0));
