@@ -690,6 +690,92 @@ int vslam_epipolar_host(vslam_ctx* ctx, const vslam_match* matches, size_t n_mat
                         uint64_t* inlier_bits, vslam_match* inliers, size_t inlier_cap, size_t* n_inliers,
                         vslam_epipolar_hyp* hypotheses);
 
+/* ---------------------------------------------------------------- relative pose and triangulation
+ * The step after the fundamental matrix: the camera motion of every pair and the 3-D point of every match record, from the
+ * `models` buffer vslam_epipolar_dev wrote (only F and best are read), a match list (any list; the intended one is the
+ * inliers / inlier_counts / inlier_cap of vslam_epipolar_dev) and the point lists.  One pinhole camera for both frames, no
+ * skew, no distortion.  Convention: x_train ~ R * x_query + t with |t| = 1 (the scale of a two-view reconstruction is free);
+ * a point X is in the QUERY camera's frame.  No degeneracy handling: a planar scene or a pure rotation gets whatever the
+ * decomposition gives.  Records are trusted, and their coordinates (x, y) = query, (x', y') = train computed, exactly as in
+ * the two-view geometry section; m = min(match_counts[j], match_cap) records are considered.  The arithmetic is fixed here so
+ * that a CPU can restate it bit for bit (tests/poseref.py): IEEE f64, every + - * / sqrt rounded on its own, sums left to
+ * right as written.  Matrices are row-major, M[i][j] = M[3*i + j].
+ *
+ *  1. Essential matrix E = K^T F K, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]:
+ *       G[i][0] = F[i][0]*fx;  G[i][1] = F[i][1]*fy;  G[i][2] = (F[i][0]*cx + F[i][1]*cy) + F[i][2];
+ *       E[0][j] = fx*G[0][j];  E[1][j] = fy*G[1][j];  E[2][j] = (cx*G[0][j] + cy*G[1][j]) + G[2][j];
+ *     then E = E / n, n the Frobenius norm as in step 6 of the two-view model (row-major, left to right); n zero or not
+ *     finite: the pair is INVALID.  A pair with models[j].best < 0 is invalid.
+ *  2. Right singular vectors: S = E^T E and the six Jacobi sweeps of step 4 of the two-view model, verbatim, give S and V.
+ *     k = the index of the smallest S[k][k] (lowest on ties), p < q the other two indices;  v1 = V[:, p], v2 = V[:, q],
+ *     v3 = v1 x v2, the cross product being (a x b)_0 = a1*b2 - a2*b1, (a x b)_1 = a2*b0 - a0*b2, (a x b)_2 = a0*b1 - a1*b0.
+ *  3. Left singular vectors: w1_i = (E[i][0]*v1_0 + E[i][1]*v1_1) + E[i][2]*v1_2;  n = sqrt((w1_0*w1_0 + w1_1*w1_1) + w1_2*w1_2);
+ *     n zero or not finite: invalid;  u1_i = w1_i / n.  w2 likewise from v2;  d = (u1_0*w2_0 + u1_1*w2_1) + u1_2*w2_2;
+ *     w2_i = w2_i - d*u1_i;  u2 = w2 / |w2| with the same norm and the same rule;  u3 = u1 x u2.
+ *  4. Candidates:  Ra[i][j] = (u2_i*v1_j - u1_i*v2_j) + u3_i*v3_j;   Rb[i][j] = (u1_i*v2_j - u2_i*v1_j) + u3_i*v3_j;
+ *     c = 0: (Ra, u3), 1: (Ra, -u3), 2: (Rb, u3), 3: (Rb, -u3).
+ *  5. Cheirality of one record under (R, t):  q = ((x - cx)/fx, (y - cy)/fy, 1),  b = ((x' - cx)/fx, (y' - cy)/fy, 1);
+ *     a_i = (R[i][0]*q0 + R[i][1]*q1) + R[i][2];   aa = (a0*a0 + a1*a1) + a2*a2, and bb = b.b, ab = a.b, at = a.t, bt = b.t of
+ *     the same shape;  det = aa*bb - ab*ab;  n1 = ab*bt - bb*at;  n2 = aa*bt - ab*at.  The record is IN FRONT (of both
+ *     cameras) iff det > 0 && n1 > 0 && n2 > 0; a record with NaN coordinates is not.  front[c] = the number of such records,
+ *     an integer: no order of summation matters.  (Negating t negates n1 and n2 exactly.)
+ *  6. Selection: the candidate with the largest front, the lowest c on ties; every count 0, or an invalid pair: best = -1
+ *     and R, t all zero.  valid: steps 1 - 3 produced candidates (an invalid pair's candidates are all zero).
+ *  7. The point of record i under the winner, the midpoint of the two rays' closest points:  l1 = n1/det;  l2 = n2/det;
+ *     c_i = l2*b_i - t_i;   P_j = (R[0][j]*c0 + R[1][j]*c1) + R[2][j]*c2;   X_j = 0.5 * (l1*q_j + P_j).   X is written as
+ *     computed for every considered record: NaN for one that is not trusted, whatever IEEE gives when det == 0 - except
+ *     that every NaN is written as the quiet NaN 0x7ff8000000000000 (IEEE fixes neither the sign nor the payload of a NaN).
+ * The result depends neither on how the records are split over lanes and workgroups nor on vslam_ctx_set_f32_fused /
+ * vslam_ctx_set_matrix_path. */
+typedef struct {
+    double fx, fy, cx, cy; /* all finite, fx and fy positive */
+} vslam_pose_params;
+typedef struct {
+    double R[9];
+    double t[3];
+    uint32_t front; /* records in front of both cameras under this candidate */
+    int32_t valid;
+} vslam_pose_cand; /* 104 bytes */
+typedef struct {
+    double R[9];        /* the winner; all zero when best < 0 */
+    double t[3];
+    uint32_t n_matches; /* min(match_counts[j], match_cap): the records considered */
+    uint32_t n_front;   /* the winner's count, 0 when best < 0 */
+    int32_t best;       /* winning candidate 0 .. 3, -1: none */
+    int32_t valid;      /* steps 1 - 3 produced candidates */
+} vslam_pose;           /* 112 bytes */
+/* Like vslam_epipolar_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;          /* = sizeof(vslam_pose_out) */
+    vslam_pose* poses;           /* [n_pairs], required */
+    size_t poses_bytes;
+    vslam_pose_cand* candidates; /* [n_pairs][4] optional */
+    size_t candidates_bytes;
+    double* points;              /* [n_pairs][match_cap][3] optional: X of record i; rows i < n_matches of a pair with best >= 0
+                                  * are written, every other row is left untouched */
+    size_t points_bytes;
+    uint64_t* front_bits;        /* [n_pairs][(match_cap + 63) / 64] optional: bit i % 64 of word i / 64 = record i is in front
+                                  * under the winner; the first (n_matches + 63) / 64 words of a pair are written (all zero when
+                                  * best < 0), the rest untouched */
+    size_t front_bits_bytes;
+} vslam_pose_out;
+/* Pair j reads models[j] and the lists as vslam_epipolar_dev does (DEVICE pointers).  Asynchronous on the context stream,
+ * never waits on the host (the counts are read on the device, the grids are sized from the capacities); scratch belongs to
+ * the context.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null pointer, a wrong
+ * struct_size, an undersized buffer, match_cap / query_cap / train_cap == 0, n_pairs outside 0 .. 65535 (0 does nothing), an
+ * intrinsic that is not finite, fx or fy not positive; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for
+ * stream capture. */
+int vslam_pose_dev(vslam_ctx* ctx, const vslam_epipolar* models, const vslam_match* matches, const uint32_t* match_counts,
+                   uint32_t match_cap, const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points,
+                   uint32_t train_cap, int n_pairs, const vslam_pose_params* params, const vslam_pose_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call).  model and pose are required;
+ * candidates [4], points [n_matches][3] and front_bits [(n_matches + 63) / 64] are each optional (NULL).  n_query / n_train are
+ * the capacities the indices are checked against.  Errors as for vslam_pose_dev. */
+int vslam_pose_host(vslam_ctx* ctx, const vslam_epipolar* model, const vslam_match* matches, size_t n_matches,
+                    const vslam_point* query_points, size_t n_query, const vslam_point* train_points, size_t n_train,
+                    const vslam_pose_params* params, vslam_pose* pose, vslam_pose_cand* candidates, double* points,
+                    uint64_t* front_bits);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

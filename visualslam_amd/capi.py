@@ -32,6 +32,8 @@ NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4"
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
+POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
+POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
 
 
 class VslamError(RuntimeError):
@@ -115,6 +117,26 @@ class EpipolarOut(C.Structure):
                 ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t)]
 
 
+class PoseParams(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class PoseCand(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("front", C.c_uint32), ("valid", C.c_int32)]
+
+
+class Pose(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("n_matches", C.c_uint32), ("n_front", C.c_uint32), ("best", C.c_int32),
+                ("valid", C.c_int32)]
+
+
+class PoseOut(C.Structure):
+    """vslam_pose_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("poses", C.c_void_p), ("poses_bytes", C.c_size_t), ("candidates", C.c_void_p),
+                ("candidates_bytes", C.c_size_t), ("points", C.c_void_p), ("points_bytes", C.c_size_t), ("front_bits", C.c_void_p),
+                ("front_bits_bytes", C.c_size_t)]
+
+
 class PyramidInfo(C.Structure):
     _fields_ = [
         ("n_octaves", C.c_int), ("n_levels", C.c_int), ("n_dogs", C.c_int), ("sigma0", C.c_double),
@@ -191,6 +213,8 @@ SIGNATURES = {
     "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_epipolar_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(EpipolarParams), C.POINTER(EpipolarOut)]),
     "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
+    "vslam_pose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(PoseParams), C.POINTER(PoseOut)]),
+    "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -762,6 +786,59 @@ class Context:
                                             None if inl is None else inl.ctypes.data, cap, C.byref(total) if want_inliers else None, ptr(hyp)),
                   "vslam_epipolar_host")
         return (model[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None, hyp)
+
+    def pose(self, models, matches, match_counts, query_points, train_points, intrinsics, n_pairs: int | None = None, poses=None, candidates=None,
+             points=None, front_bits=None):
+        """vslam_pose_dev: the camera motion of every pair (x_train ~ R x_query + t, |t| = 1) and the 3-D point of every match
+        record, from the models tensor epipolar() wrote and a match list - the intended one is epipolar()'s inliers / inlier_counts;
+        asynchronous on the context stream.  intrinsics = (fx, fy, cx, cy).  Outputs, CUDA tensors: poses - any contiguous tensor of
+        n_pairs * 112 bytes (POSE_DTYPE after .cpu().numpy().view), candidates n_pairs * 4 * 104 bytes (POSE_CAND_DTYPE), points
+        float64 [n, match_cap, 3] (query-camera frame), front_bits int64 [n, (match_cap + 63) // 64]."""
+        n = min(matches.shape[0], query_points.shape[0], train_points.shape[0]) if n_pairs is None else int(n_pairs)
+        for name, t in (("models", models), ("matches", matches), ("match_counts", match_counts), ("query_points", query_points),
+                        ("train_points", train_points), ("poses", poses), ("candidates", candidates), ("points", points), ("front_bits", front_bits)):
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"pose: {name} must be a contiguous tensor on cuda:{self.device}")
+        if poses is None:
+            raise ValueError("pose: poses is required")
+        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12 or query_points.dim() != 3 or train_points.dim() != 3:
+            raise ValueError("pose: matches must be [n, match_cap, 3] 4-byte elements, the points [n, cap, 6]")
+        if query_points.shape[2] * query_points.element_size() != 24 or train_points.shape[2] * train_points.element_size() != 24:
+            raise ValueError("pose: points must be [n, cap, 6] int32")
+        if min(matches.shape[0], match_counts.numel(), query_points.shape[0], train_points.shape[0]) < n or match_counts.element_size() != 4:
+            raise ValueError("pose: fewer sets than pairs")
+        if models.numel() * models.element_size() < n * 88:
+            raise ValueError("pose: models must hold n_pairs * 88 bytes")
+        po = PoseOut()
+        po.struct_size = C.sizeof(PoseOut)
+        for name, t in (("poses", poses), ("candidates", candidates), ("points", points), ("front_bits", front_bits)):
+            if t is not None:
+                setattr(po, name, t.data_ptr())
+                setattr(po, name + "_bytes", t.numel() * t.element_size())
+        prm = PoseParams(*(float(v) for v in intrinsics))
+        self._chk(lib().vslam_pose_dev(self._h, models.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), matches.shape[1],
+                                       query_points.data_ptr(), query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n,
+                                       C.byref(prm), C.byref(po)), "vslam_pose_dev")
+
+    def pose_host(self, model, matches, query_points, train_points, intrinsics, want_candidates: bool = True, want_points: bool = True,
+                  want_bits: bool = True):
+        """vslam_pose_host: one pair of numpy arrays (one EPIPOLAR_DTYPE record, MATCH_DTYPE, POINT_DTYPE, POINT_DTYPE) -> (pose: one
+        POSE_DTYPE record, candidates [4] POSE_CAND_DTYPE or None, points float64 [m, 3] or None - None too when there is no winner -,
+        front_bits uint64 [(m + 63) // 64] or None)."""
+        mod = np.ascontiguousarray(model, dtype=EPIPOLAR_DTYPE).reshape(-1)[:1]
+        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE).reshape(-1)
+        qp = np.ascontiguousarray(query_points, dtype=POINT_DTYPE).reshape(-1)
+        tp = np.ascontiguousarray(train_points, dtype=POINT_DTYPE).reshape(-1)
+        m = len(mt)
+        pose = np.zeros(1, POSE_DTYPE)
+        cand = np.zeros(4, POSE_CAND_DTYPE) if want_candidates else None
+        pts = np.zeros((max(m, 1), 3), np.float64) if want_points else None
+        bits = np.zeros((m + 63) // 64, np.uint64) if want_bits else None
+        prm = PoseParams(*(float(v) for v in intrinsics))
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        self._chk(lib().vslam_pose_host(self._h, mod.ctypes.data, ptr(mt), m, ptr(qp), len(qp), ptr(tp), len(tp), C.byref(prm), pose.ctypes.data,
+                                        ptr(cand), ptr(pts), ptr(bits)), "vslam_pose_host")
+        return pose[0], cand, (pts[:m] if want_points and int(pose["best"][0]) >= 0 else None), bits
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -15,10 +15,6 @@
 
 namespace vslam {
 
-struct __attribute__((aligned(16))) EpiXY {  // one record: query (x, y), train (u, v)
-    double x, y, u, v;
-};
-
 __device__ __forceinline__ unsigned int epi_mix(unsigned int x) {
     x ^= x >> 16;
     x *= 0x7feb352du;

@@ -1,0 +1,277 @@
+// Relative pose and triangulation (include/vslam.h, "relative pose and triangulation"): from the fundamental matrix of every
+// pair and a match list to (R, t) and the 3-D point of every record.
+//   k_pose_candidates : one lane per pair: E = K^T F K, its singular vectors by the Jacobi sweeps of the two-view model, the
+//                       four (R, t) candidates (steps 1 - 4); everything in registers, statically indexed
+//   k_pose_vote       : the hot path, one lane per match record: the cheirality test under both rotations - the sign of t
+//                       flips n1 and n2 exactly, so two evaluations give all four votes; ballot + popcount per wave, one
+//                       integer atomicAdd per wave and candidate
+//   k_pose_select     : one lane per pair: the candidate with the most records in front, lowest index on ties
+//   k_pose_points     : one lane per record: the midpoint of the two rays under the winner, and the wave's ballot word
+// The {x, y, x', y'} records come from k_epi_coords (vslam::enqueue_epi_coords).  The arithmetic is the header's, operation
+// for operation: every + - * / sqrt of f64 is an IEEE operation of its own (the library is built with -ffp-contract=off; f64
+// division and sqrt are correctly rounded on gfx950), sums run left to right.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/vslam.h"
+#include "vslam_epipolar_plan.h"
+#include "vslam_pose_plan.h"
+
+namespace vslam {
+
+__device__ __forceinline__ bool pose_finite_nonzero(double n) { return n != 0.0 && n < __longlong_as_double(0x7ff0000000000000ll); }
+
+// One Jacobi rotation of the pair (P, Q) of the symmetric 3 x 3 S (step 4 of the two-view model): app, aqq, apq its block,
+// arp, arq the third index's two entries.  P and Q are compile-time, so V never leaves the registers.
+template <int P, int Q>
+__device__ __forceinline__ void pose_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double (&V)[3][3]) {
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    const double napp = app - t * apq, naqq = aqq + t * apq;
+    const double narp = c * arp - s * arq, narq = s * arp + c * arq;
+    app = napp, aqq = naqq, apq = 0.0, arp = narp, arq = narq;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double vp = c * V[i][P] - s * V[i][Q], vq = s * V[i][P] + c * V[i][Q];
+        V[i][P] = vp, V[i][Q] = vq;
+    }
+}
+
+__device__ __forceinline__ void pose_cross(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// w = E v, then u = w / |w|; false: the norm is zero or not finite.  `u1`: w is first made orthogonal to it (step 3's w2).
+__device__ __forceinline__ bool pose_left_vector(const double (&E)[9], const double (&v)[3], const double* u1, double (&u)[3]) {
+    double w[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w[i] = (E[3 * i] * v[0] + E[3 * i + 1] * v[1]) + E[3 * i + 2] * v[2];
+    if (u1) {
+        const double d = (u1[0] * w[0] + u1[1] * w[1]) + u1[2] * w[2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) w[i] = w[i] - d * u1[i];
+    }
+    const double n = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+    if (!pose_finite_nonzero(n)) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u[i] = w[i] / n;
+    return true;
+}
+
+// grid = (pair blocks of 64), one lane per pair.
+__global__ __launch_bounds__(POSE_PAIR_WG) void k_pose_candidates(const vslam_epipolar* __restrict__ models, vslam_pose_params K, int n_pairs,
+                                                                   vslam_pose_cand* __restrict__ cand) {
+    const int j = blockIdx.x * POSE_PAIR_WG + threadIdx.x;
+    if (j >= n_pairs) return;
+    double Ra[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, Rb[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, u3[3] = {0, 0, 0};
+    bool ok = false;
+    do {
+        if (models[j].best < 0) break;
+        // 1. E = K^T F K, Frobenius norm 1
+        double G[9], E[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double f0 = models[j].F[3 * i], f1 = models[j].F[3 * i + 1], f2 = models[j].F[3 * i + 2];
+            G[3 * i] = f0 * K.fx;
+            G[3 * i + 1] = f1 * K.fy;
+            G[3 * i + 2] = (f0 * K.cx + f1 * K.cy) + f2;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            E[c] = K.fx * G[c];
+            E[3 + c] = K.fy * G[3 + c];
+            E[6 + c] = (K.cx * G[c] + K.cy * G[3 + c]) + G[6 + c];
+        }
+        double n2 = E[0] * E[0];
+#pragma unroll
+        for (int i = 1; i < 9; ++i) n2 = n2 + E[i] * E[i];
+        const double nrm = sqrt(n2);
+        if (!pose_finite_nonzero(nrm)) break;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) E[i] = E[i] / nrm;
+        // 2. right singular vectors: cyclic Jacobi on S = E^T E
+        double S00 = (E[0] * E[0] + E[3] * E[3]) + E[6] * E[6], S01 = (E[0] * E[1] + E[3] * E[4]) + E[6] * E[7],
+               S02 = (E[0] * E[2] + E[3] * E[5]) + E[6] * E[8], S11 = (E[1] * E[1] + E[4] * E[4]) + E[7] * E[7],
+               S12 = (E[1] * E[2] + E[4] * E[5]) + E[7] * E[8], S22 = (E[2] * E[2] + E[5] * E[5]) + E[8] * E[8];
+        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+#pragma unroll
+        for (int sweep = 0; sweep < 6; ++sweep) {
+            pose_rotate<0, 1>(S00, S11, S01, S02, S12, V);
+            pose_rotate<0, 2>(S00, S22, S02, S01, S12, V);
+            pose_rotate<1, 2>(S11, S22, S12, S01, S02, V);
+        }
+        int k = 0;
+        double smin = S00;
+        if (S11 < smin) k = 1, smin = S11;
+        if (S22 < smin) k = 2, smin = S22;
+        // (p, q) = (1, 2), (0, 2), (0, 1) for k = 0, 1, 2: selects, not indexed reads
+        double v1[3], v2[3], v3[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            v1[i] = k == 0 ? V[i][1] : V[i][0];
+            v2[i] = k == 2 ? V[i][1] : V[i][2];
+        }
+        pose_cross(v1, v2, v3);
+        // 3. left singular vectors
+        double u1[3], u2[3];
+        if (!pose_left_vector(E, v1, nullptr, u1)) break;
+        if (!pose_left_vector(E, v2, u1, u2)) break;
+        pose_cross(u1, u2, u3);
+        // 4. the two rotations
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                Ra[3 * i + c] = (u2[i] * v1[c] - u1[i] * v2[c]) + u3[i] * v3[c];
+                Rb[3 * i + c] = (u1[i] * v2[c] - u2[i] * v1[c]) + u3[i] * v3[c];
+            }
+        ok = true;
+    } while (false);
+    if (!ok) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Ra[i] = Rb[i] = 0.0;
+        u3[0] = u3[1] = u3[2] = 0.0;
+    }
+    vslam_pose_cand* out = cand + (size_t)j * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) out[c].R[i] = c < 2 ? Ra[i] : Rb[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) out[c].t[i] = (c & 1) && ok ? -u3[i] : u3[i];
+        out[c].front = 0;
+        out[c].valid = ok ? 1 : 0;
+    }
+}
+
+// The two rays of one record (step 5): q = (q0, q1, 1), b = (b0, b1, 1).
+struct PoseRays {
+    double q0, q1, b0, b1;
+};
+__device__ __forceinline__ PoseRays pose_rays(const EpiXY& p, const vslam_pose_params& K) {
+    return PoseRays{(p.x - K.cx) / K.fx, (p.y - K.cy) / K.fy, (p.u - K.cx) / K.fx, (p.v - K.cy) / K.fy};
+}
+
+// det, n1, n2 of one record under (R, t) (step 5; the third component of q and b is 1, and x * 1 is x).
+__device__ __forceinline__ void pose_solve(const double (&R)[9], const double (&t)[3], const PoseRays& r, double& det, double& n1, double& n2) {
+    const double a0 = (R[0] * r.q0 + R[1] * r.q1) + R[2], a1 = (R[3] * r.q0 + R[4] * r.q1) + R[5], a2 = (R[6] * r.q0 + R[7] * r.q1) + R[8];
+    const double aa = (a0 * a0 + a1 * a1) + a2 * a2;
+    const double bb = (r.b0 * r.b0 + r.b1 * r.b1) + 1.0;
+    const double ab = (a0 * r.b0 + a1 * r.b1) + a2;
+    const double at = (a0 * t[0] + a1 * t[1]) + a2 * t[2];
+    const double bt = (r.b0 * t[0] + r.b1 * t[1]) + t[2];
+    det = aa * bb - ab * ab;
+    n1 = ab * bt - bb * at;
+    n2 = aa * bt - ab * at;
+}
+
+__device__ __forceinline__ unsigned int pose_count(const unsigned int* __restrict__ counts, int j, unsigned int cap) { return min(counts[j], cap); }
+
+// grid = (record blocks of 256, pairs).  The pair's candidates are read through addresses that are the same in every lane.
+// `cand` is read (R, t, valid) and written (front, by atomicAdd) here, so it is neither const nor restrict.
+__global__ __launch_bounds__(POSE_REC_WG) void k_pose_vote(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts,
+                                                            unsigned int mcap, vslam_pose_params K, vslam_pose_cand* cand) {
+    const int j = blockIdx.y;
+    const unsigned int m = pose_count(counts, j, mcap);
+    const size_t i = (size_t)blockIdx.x * POSE_REC_WG + threadIdx.x;  // (64 bits: the last block of a capacity near 2^32 runs past it)
+    if ((i & ~(size_t)63) >= m) return;                               // wave-uniform: the wave holds no record
+    vslam_pose_cand* cj = cand + (size_t)j * 4;
+    if (!cj[0].valid) return;  // block-uniform: every count stays 0
+    double Ra[9], Rb[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Ra[k] = cj[0].R[k], Rb[k] = cj[2].R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = cj[0].t[k];
+    bool f0 = false, f1 = false, f2 = false, f3 = false;
+    if (i < m) {
+        const PoseRays r = pose_rays(xy[(size_t)j * mcap + i], K);
+        double det, n1, n2;
+        pose_solve(Ra, t, r, det, n1, n2);
+        f0 = det > 0.0 && n1 > 0.0 && n2 > 0.0;
+        f1 = det > 0.0 && n1 < 0.0 && n2 < 0.0;  // under -t: -n1 > 0 && -n2 > 0
+        pose_solve(Rb, t, r, det, n1, n2);
+        f2 = det > 0.0 && n1 > 0.0 && n2 > 0.0;
+        f3 = det > 0.0 && n1 < 0.0 && n2 < 0.0;
+    }
+    const unsigned int c0 = __popcll(__ballot(f0)), c1 = __popcll(__ballot(f1)), c2 = __popcll(__ballot(f2)), c3 = __popcll(__ballot(f3));
+    if ((threadIdx.x & 63) == 0) {
+        if (c0) atomicAdd(&cj[0].front, c0);
+        if (c1) atomicAdd(&cj[1].front, c1);
+        if (c2) atomicAdd(&cj[2].front, c2);
+        if (c3) atomicAdd(&cj[3].front, c3);
+    }
+}
+
+// grid = (pair blocks of 64), one lane per pair.
+__global__ __launch_bounds__(POSE_PAIR_WG) void k_pose_select(const vslam_pose_cand* __restrict__ cand, const unsigned int* __restrict__ counts,
+                                                               unsigned int mcap, int n_pairs, vslam_pose* __restrict__ poses) {
+    const int j = blockIdx.x * POSE_PAIR_WG + threadIdx.x;
+    if (j >= n_pairs) return;
+    const vslam_pose_cand* cj = cand + (size_t)j * 4;
+    int best = -1;
+    unsigned int most = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (cj[c].front > most) most = cj[c].front, best = c;  // strictly more: the lowest c on ties, and a count of 0 never wins
+    const int valid = cj[0].valid;
+    if (!valid) best = -1;
+    vslam_pose out;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out.R[i] = best < 0 ? 0.0 : cj[best].R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) out.t[i] = best < 0 ? 0.0 : cj[best].t[i];
+    out.n_matches = pose_count(counts, j, mcap);
+    out.n_front = best < 0 ? 0u : most;
+    out.best = best;
+    out.valid = valid;
+    poses[j] = out;
+}
+
+// A NaN leaves as the quiet NaN 0x7ff8000000000000: IEEE fixes neither the sign nor the payload of a NaN an operation makes.
+__device__ __forceinline__ double pose_canonical(double x) { return x == x ? x : __longlong_as_double(0x7ff8000000000000ll); }
+
+// grid = (record blocks of 256, pairs): X of every record below the count (points may be null), and bit i % 64 of word i / 64
+// = record i is in front under the winner (bits may be null).  Without a winner the words are zero and no point is written.
+__global__ __launch_bounds__(POSE_REC_WG) void k_pose_points(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts,
+                                                              unsigned int mcap, const vslam_pose* __restrict__ poses, vslam_pose_params K,
+                                                              double* __restrict__ points, unsigned long long* __restrict__ bits, unsigned int fwords) {
+    const int j = blockIdx.y;
+    const unsigned int m = pose_count(counts, j, mcap);
+    const size_t i = (size_t)blockIdx.x * POSE_REC_WG + threadIdx.x;
+    if ((i & ~(size_t)63) >= m) return;  // wave-uniform: the wave's word holds no record
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    if (poses[j].best < 0) {  // block-uniform
+        if (bits && lane0) bits[(size_t)j * fwords + (i >> 6)] = 0ull;
+        return;
+    }
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = poses[j].R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = poses[j].t[k];
+    bool in = false;
+    if (i < m) {
+        const PoseRays r = pose_rays(xy[(size_t)j * mcap + i], K);
+        double det, n1, n2;
+        pose_solve(R, t, r, det, n1, n2);
+        in = det > 0.0 && n1 > 0.0 && n2 > 0.0;
+        if (points) {
+            const double l1 = n1 / det, l2 = n2 / det;
+            const double c0 = l2 * r.b0 - t[0], c1 = l2 * r.b1 - t[1], c2 = l2 - t[2];
+            const double P0 = (R[0] * c0 + R[3] * c1) + R[6] * c2, P1 = (R[1] * c0 + R[4] * c1) + R[7] * c2, P2 = (R[2] * c0 + R[5] * c1) + R[8] * c2;
+            double* X = points + ((size_t)j * mcap + i) * 3;
+            X[0] = pose_canonical(0.5 * (l1 * r.q0 + P0));
+            X[1] = pose_canonical(0.5 * (l1 * r.q1 + P1));
+            X[2] = pose_canonical(0.5 * (l1 + P2));
+        }
+    }
+    const unsigned long long w = __ballot(in);
+    if (bits && lane0) bits[(size_t)j * fwords + (i >> 6)] = w;
+}
+
+}  // namespace vslam

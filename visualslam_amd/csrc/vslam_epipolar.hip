@@ -13,6 +13,15 @@
 
 using namespace vslam;
 
+int vslam::enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
+                              const vslam_point* query_points, unsigned int query_cap, const vslam_point* train_points, unsigned int train_cap,
+                              int n_pairs, EpiXY* xy) {
+    const unsigned int rec_blocks = (unsigned int)(((size_t)match_cap + 255) / 256);
+    LAUNCH(c, "k_epi_coords", k_epi_coords, dim3(rec_blocks, n_pairs), dim3(256), matches, match_counts, match_cap, query_points, query_cap,
+           train_points, train_cap, xy);
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_epipolar_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
@@ -40,8 +49,7 @@ int vslam_epipolar_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t*
     vslam_epipolar_hyp* hyp = out->hypotheses ? out->hypotheses : hyp_ws;
     unsigned long long* flags = out->inlier_bits ? reinterpret_cast<unsigned long long*>(out->inlier_bits) : flags_ws;
 
-    LAUNCH(c, "k_epi_coords", k_epi_coords, dim3(pl.rec_blocks, n_pairs), dim3(256), matches, match_counts, match_cap, query_points, query_cap,
-           train_points, train_cap, xy);
+    TRY(enqueue_epi_coords(c, matches, match_counts, match_cap, query_points, query_cap, train_points, train_cap, n_pairs, xy));
     LAUNCH(c, "k_epi_models", k_epi_models, dim3(pl.model_blocks, n_pairs), dim3(EPI_MODEL_WG), xy, match_counts, match_cap, H, prm->seed, hyp);
     LAUNCH(c, "k_epi_score", k_epi_score, dim3(pl.score_blocks, pl.nsplit, n_pairs), dim3(EPI_SCORE_WG), xy, match_counts, match_cap, H,
            prm->max_dist2, hyp);

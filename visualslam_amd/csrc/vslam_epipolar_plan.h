@@ -10,6 +10,10 @@
 
 namespace vslam {
 
+struct __attribute__((aligned(16))) EpiXY {  // one record of the coordinate scratch: query (x, y), train (u, v); NaN: not trusted
+    double x, y, u, v;
+};
+
 constexpr unsigned int EPI_TILE = 256;      // match records a k_epi_score workgroup stages in LDS at a time (8 KiB)
 constexpr unsigned int EPI_SCORE_WG = 256;  // hypotheses (lanes) per k_epi_score workgroup
 constexpr unsigned int EPI_MODEL_WG = 64;   // hypotheses per k_epi_models workgroup: one wave, 72 f64 of LDS per lane

@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_pose.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +34,12 @@ int enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, size_t fwo
 int enqueue_inlier_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_match* matches, const unsigned int* match_counts,
                         unsigned int match_cap, int n_pairs, unsigned int* chunk_ws, vslam_match* inliers, unsigned int inlier_cap,
                         unsigned int* inlier_counts);
+// The {x, y, x', y'} scratch of the two-view entry points (k_epi_coords, compiled in vslam_epipolar.hip; vslam_pose_dev reads
+// the same records): one EpiXY per match record below each pair's count, xy [n_pairs][match_cap].
+struct EpiXY;
+int enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
+                       const vslam_point* query_points, unsigned int query_cap, const vslam_point* train_points, unsigned int train_cap,
+                       int n_pairs, EpiXY* xy);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
@@ -74,7 +80,7 @@ class WsPlan {
 }  // namespace
 
 // What the entry points that work from host memory through per-call device buffers share (vslam_match_host,
-// vslam_epipolar_host), and the answer of a device entry point whose caller has no HIP device.
+// vslam_epipolar_host, vslam_pose_host), and the answer of a device entry point whose caller has no HIP device.
 namespace {
 // No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
 // after the arguments, before the context is touched.

@@ -3,8 +3,11 @@
 // filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
 // second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --epipolar adds
 // the step after that: the RANSAC fundamental matrix of the accepted matches (vslam::fundamentalRansac: 512 hypotheses, seed 1,
-// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.
-//   usage: Match [--epipolar] [first.pgm second.pgm | WxH] [octaves, default 4]      (WxH: frames 0 and 1 of the synthetic stream)
+// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --pose fx,fy,cx,cy (after --epipolar)
+// adds the step after that: the camera motion from the inlier matches (vslam::relativePose) as a "pose" object with R, t, the
+// winning candidate and the number of inliers in front of both cameras.
+//   usage: Match [--epipolar [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+//          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +48,13 @@ int main(int argc, char** argv) {
     try {
         const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
         if (epipolar) --argc, ++argv;
+        vslam_pose_params camera{};
+        const bool pose = epipolar && argc > 2 && std::strcmp(argv[1], "--pose") == 0;
+        if (pose) {
+            if (std::sscanf(argv[2], "%lf,%lf,%lf,%lf", &camera.fx, &camera.fy, &camera.cx, &camera.cy) != 4)
+                throw std::runtime_error("--pose takes fx,fy,cx,cy");
+            argc -= 2, argv += 2;
+        }
         Mat first, second;
         int w = 0, h = 0, next = 2;
         if (argc < 2) {
@@ -52,7 +62,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -72,6 +82,22 @@ int main(int argc, char** argv) {
                 extra += buf;
             }
             extra += "]}";
+            if (pose) {
+                const vslam::Pose p = vslam::relativePose(e.model, e.inliers, q.points, t.points, camera);
+                std::snprintf(buf, sizeof buf, ", \"pose\": {\"n_matches\": %u, \"n_front\": %u, \"best\": %d, \"valid\": %d, \"R\": [", p.pose.n_matches,
+                              p.pose.n_front, p.pose.best, p.pose.valid);
+                extra += buf;
+                for (int i = 0; i < 9; ++i) {
+                    std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", p.pose.R[i]);
+                    extra += buf;
+                }
+                extra += "], \"t\": [";
+                for (int i = 0; i < 3; ++i) {
+                    std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", p.pose.t[i]);
+                    extra += buf;
+                }
+                extra += "]}";
+            }
         }
         const auto t1 = std::chrono::steady_clock::now();
         size_t exact = 0, nearest = 0;

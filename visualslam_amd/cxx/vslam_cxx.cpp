@@ -486,3 +486,18 @@ vslam::Epipolar vslam::fundamentalRansac(const std::vector<vslam_match>& matches
     out.inliers.resize(total);
     return out;
 }
+
+vslam::Pose vslam::relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                                const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera) {
+    vslam::Pose out{};
+    out.points.resize(matches.size() * 3);
+    out.frontBits.resize((matches.size() + 63) / 64);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_pose_host(c, &model, matches.empty() ? nullptr : matches.data(), matches.size(),
+                                 reinterpret_cast<const vslam_point*>(queryPoints.data()), queryPoints.size(),
+                                 reinterpret_cast<const vslam_point*>(trainPoints.data()), trainPoints.size(), &camera, &out.pose, out.candidates,
+                                 out.points.empty() ? nullptr : out.points.data(), out.frontBits.empty() ? nullptr : out.frontBits.data()),
+                 c, "relativePose");
+    if (out.pose.best < 0) out.points.clear();
+    return out;
+}

@@ -198,4 +198,17 @@ struct Epipolar {
 };
 Epipolar fundamentalRansac(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                            const std::vector<SLAM::point>& trainPoints, const vslam_epipolar_params& params = {512, 1, 4.0});
+
+// The step after that: the camera motion of the pair (x_train ~ R x_query + t, |t| = 1) and the 3-D point of every record of
+// `matches` - the intended list is Epipolar::inliers - from the model fundamentalRansac found, on the GPU (vslam_pose_host;
+// the decomposition, the cheirality vote and the triangulation are stated in include/vslam.h).  One pinhole camera
+// {fx, fy, cx, cy} for both frames.
+struct Pose {
+    vslam_pose pose;                 // R row-major, t, the winner's count; best = -1: none
+    vslam_pose_cand candidates[4];   // the four (R, t) with their counts
+    std::vector<double> points;      // [matches][3], query-camera frame; empty when best < 0
+    std::vector<uint64_t> frontBits; // bit i % 64 of word i / 64: record i is in front of both cameras under the winner
+};
+Pose relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                  const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera);
 }  // namespace vslam
