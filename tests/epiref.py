@@ -13,8 +13,57 @@ import numpy as np
 
 from visualslam_amd import capi
 
-_SRC = r"""
+# The 3 x 3 pieces that the relative-pose restatement (tests/poseref.py) needs too: both C sources begin with this fragment.
+GEOM3_SRC = r"""
 #include <math.h>
+/* S = M^T M; six sweeps of cyclic Jacobi with the eigenvectors accumulated in V: d [3] = diag S, V [3][3] */
+void ref_gram_jacobi(const double* M, double* d, double* Vout) {
+    double S[3][3], (*V)[3] = (double (*)[3])Vout;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { V[i][j] = i == j; S[i][j] = (M[i] * M[j] + M[3 + i] * M[3 + j]) + M[6 + i] * M[6 + j]; }
+    static const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2}, R[3] = {2, 1, 0};
+    for (int sweep = 0; sweep < 6; ++sweep)
+        for (int e = 0; e < 3; ++e) {
+            const int p = P[e], q = Q[e], r = R[e];
+            const double apq = S[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (S[q][q] - S[p][p]) / (2.0 * apq);
+            const double den = fabs(theta) + sqrt(theta * theta + 1.0);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+            const double app = S[p][p] - t * apq, aqq = S[q][q] + t * apq;
+            const double arp = c * S[r][p] - s * S[r][q], arq = s * S[r][p] + c * S[r][q];
+            S[p][p] = app; S[q][q] = aqq; S[p][q] = S[q][p] = 0.0;
+            S[r][p] = S[p][r] = arp; S[r][q] = S[q][r] = arq;
+            for (int i = 0; i < 3; ++i) {
+                const double vp = c * V[i][p] - s * V[i][q], vq = s * V[i][p] + c * V[i][q];
+                V[i][p] = vp; V[i][q] = vq;
+            }
+        }
+    for (int i = 0; i < 3; ++i) d[i] = S[i][i];
+}
+
+/* H = L^T F R; L, R = {sx, sy, ax, ay} stand for [[sx, 0, ax], [0, sy, ay], [0, 0, 1]] */
+void ref_lt_f_r(const double* L, const double* F, const double* R, double* H) {
+    double G[9];
+    for (int i = 0; i < 3; ++i) {
+        G[3 * i] = F[3 * i] * R[0]; G[3 * i + 1] = F[3 * i + 1] * R[1];
+        G[3 * i + 2] = (F[3 * i] * R[2] + F[3 * i + 1] * R[3]) + F[3 * i + 2];
+    }
+    for (int j = 0; j < 3; ++j) {
+        H[j] = L[0] * G[j]; H[3 + j] = L[1] * G[3 + j];
+        H[6 + j] = (L[2] * G[j] + L[3] * G[3 + j]) + G[6 + j];
+    }
+}
+
+double ref_frobenius(const double* M) {
+    double n2 = M[0] * M[0];
+    for (int i = 1; i < 9; ++i) n2 = n2 + M[i] * M[i];
+    return sqrt(n2);
+}
+"""
+
+_SRC = GEOM3_SRC + r"""
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -120,52 +169,22 @@ int ref_model_from_8(const double* pts, double* F, int rank2) {
     f[fr] = 1.0;
     for (int k = 0; k < 8; ++k) f[pc[k]] = -a[k][fr];
     if (rank2) {
-        /* S = F^T F, upper triangle; cyclic Jacobi with the eigenvectors accumulated in V */
-        double S[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        for (int i = 0; i < 3; ++i)
-            for (int j = i; j < 3; ++j) S[i][j] = S[j][i] = (f[i] * f[j] + f[3 + i] * f[3 + j]) + f[6 + i] * f[6 + j];
-        static const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2}, R[3] = {2, 1, 0};
-        for (int sweep = 0; sweep < 6; ++sweep)
-            for (int e = 0; e < 3; ++e) {
-                const int p = P[e], q = Q[e], r = R[e];
-                const double apq = S[p][q];
-                if (apq == 0.0) continue;
-                const double theta = (S[q][q] - S[p][p]) / (2.0 * apq);
-                const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                const double app = S[p][p] - t * apq, aqq = S[q][q] + t * apq;
-                const double arp = c * S[r][p] - s * S[r][q], arq = s * S[r][p] + c * S[r][q];
-                S[p][p] = app; S[q][q] = aqq; S[p][q] = S[q][p] = 0.0;
-                S[r][p] = S[p][r] = arp; S[r][q] = S[q][r] = arq;
-                for (int i = 0; i < 3; ++i) {
-                    const double vp = c * V[i][p] - s * V[i][q], vq = s * V[i][p] + c * V[i][q];
-                    V[i][p] = vp; V[i][q] = vq;
-                }
-            }
+        double S[3], V[9];
+        ref_gram_jacobi(f, S, V);
         int k = 0;
-        if (S[1][1] < S[k][k]) k = 1;
-        if (S[2][2] < S[k][k]) k = 2;
-        const double v0 = V[0][k], v1 = V[1][k], v2 = V[2][k];
+        if (S[1] < S[k]) k = 1;
+        if (S[2] < S[k]) k = 2;
+        const double v0 = V[k], v1 = V[3 + k], v2 = V[6 + k];
         for (int i = 0; i < 3; ++i) {
             const double g = (f[3 * i] * v0 + f[3 * i + 1] * v1) + f[3 * i + 2] * v2;
             f[3 * i] = f[3 * i] - g * v0; f[3 * i + 1] = f[3 * i + 1] - g * v1; f[3 * i + 2] = f[3 * i + 2] - g * v2;
         }
     }
     /* F <- Tt^T F Tq, T = [[s, 0, -(s cx)], [0, s, -(s cy)], [0, 0, 1]] */
-    const double aq = -(sq * cqx), bq = -(sq * cqy), at = -(st * ctx), bt = -(st * cty);
-    double G[9], H[9];
-    for (int i = 0; i < 3; ++i) {
-        G[3 * i] = f[3 * i] * sq; G[3 * i + 1] = f[3 * i + 1] * sq;
-        G[3 * i + 2] = (f[3 * i] * aq + f[3 * i + 1] * bq) + f[3 * i + 2];
-    }
-    for (int j = 0; j < 3; ++j) {
-        H[j] = st * G[j]; H[3 + j] = st * G[3 + j];
-        H[6 + j] = (at * G[j] + bt * G[3 + j]) + G[6 + j];
-    }
-    double n2 = H[0] * H[0];
-    for (int i = 1; i < 9; ++i) n2 = n2 + H[i] * H[i];
-    const double n = sqrt(n2);
+    const double Tq[4] = {sq, sq, -(sq * cqx), -(sq * cqy)}, Tt[4] = {st, st, -(st * ctx), -(st * cty)};
+    double H[9];
+    ref_lt_f_r(Tt, f, Tq, H);
+    const double n = ref_frobenius(H);
     if (n == 0.0 || !(n < INFINITY)) return 0;
     for (int i = 0; i < 9; ++i) F[i] = H[i] / n;
     return 1;
@@ -222,17 +241,23 @@ void ref_ransac(const match* mt, uint32_t m, const point* qp, uint32_t qcap, con
 _lib = None
 
 
+def compile_c(name, text):
+    """-> the C source `text` as a ctypes library, built the way every restatement is."""
+    d = tempfile.mkdtemp(prefix=name + "_")
+    src, so = os.path.join(d, name + ".c"), os.path.join(d, name + ".so")
+    with open(src, "w") as f:
+        f.write(text)
+    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", so, "-lm"], check=True, capture_output=True)
+    return C.CDLL(so)
+
+
 def lib():
     global _lib
     if _lib is None:
-        d = tempfile.mkdtemp(prefix="epiref_")
-        src, so = os.path.join(d, "epiref.c"), os.path.join(d, "epiref.so")
-        with open(src, "w") as f:
-            f.write(_SRC)
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", so, "-lm"], check=True, capture_output=True)
-        L = C.CDLL(so)
+        L = compile_c("epiref", _SRC)
         L.ref_mix.restype = C.c_uint32
         L.ref_score.restype = C.c_uint32
+        L.ref_frobenius.restype = C.c_double
         _lib = L
     return _lib
 

@@ -6,17 +6,13 @@ candidate is voted on by itself (the library derives the -t votes from the signs
 tests/epiref.py.  This is the checker, not the product: the library has no CPU path.
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import epiref
 from visualslam_amd import capi
 
-_SRC = r"""
-#include <math.h>
+_SRC = epiref.GEOM3_SRC + r"""
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -35,52 +31,20 @@ static double norm3(const double* w) { return sqrt((w[0] * w[0] + w[1] * w[1]) +
 
 /* steps 1 - 4: F [9] and K = {fx, fy, cx, cy} -> out [4]; returns valid.  Invalid: everything zero. */
 int ref_candidates(const double* F, int32_t best, const double* K, cand* out) {
-    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
     memset(out, 0, 4 * sizeof(cand));
     if (best < 0) return 0;
-    double G[9], E[9];
-    for (int i = 0; i < 3; ++i) {
-        G[3 * i] = F[3 * i] * fx; G[3 * i + 1] = F[3 * i + 1] * fy;
-        G[3 * i + 2] = (F[3 * i] * cx + F[3 * i + 1] * cy) + F[3 * i + 2];
-    }
-    for (int j = 0; j < 3; ++j) {
-        E[j] = fx * G[j]; E[3 + j] = fy * G[3 + j];
-        E[6 + j] = (cx * G[j] + cy * G[3 + j]) + G[6 + j];
-    }
-    double n2 = E[0] * E[0];
-    for (int i = 1; i < 9; ++i) n2 = n2 + E[i] * E[i];
-    const double n = sqrt(n2);
+    double E[9], S[3], V[9];
+    ref_lt_f_r(K, F, K, E);
+    const double n = ref_frobenius(E);
     if (!usable(n)) return 0;
     for (int i = 0; i < 9; ++i) E[i] = E[i] / n;
-    /* S = E^T E; cyclic Jacobi with the eigenvectors accumulated in V (tests/epiref.py, step 4) */
-    double S[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i; j < 3; ++j) S[i][j] = S[j][i] = (E[i] * E[j] + E[3 + i] * E[3 + j]) + E[6 + i] * E[6 + j];
-    static const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2}, R3[3] = {2, 1, 0};
-    for (int sweep = 0; sweep < 6; ++sweep)
-        for (int e = 0; e < 3; ++e) {
-            const int p = P[e], q = Q[e], r = R3[e];
-            const double apq = S[p][q];
-            if (apq == 0.0) continue;
-            const double theta = (S[q][q] - S[p][p]) / (2.0 * apq);
-            const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-            const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-            const double app = S[p][p] - t * apq, aqq = S[q][q] + t * apq;
-            const double arp = c * S[r][p] - s * S[r][q], arq = s * S[r][p] + c * S[r][q];
-            S[p][p] = app; S[q][q] = aqq; S[p][q] = S[q][p] = 0.0;
-            S[r][p] = S[p][r] = arp; S[r][q] = S[q][r] = arq;
-            for (int i = 0; i < 3; ++i) {
-                const double vp = c * V[i][p] - s * V[i][q], vq = s * V[i][p] + c * V[i][q];
-                V[i][p] = vp; V[i][q] = vq;
-            }
-        }
+    ref_gram_jacobi(E, S, V);
     int k = 0;
-    if (S[1][1] < S[k][k]) k = 1;
-    if (S[2][2] < S[k][k]) k = 2;
+    if (S[1] < S[k]) k = 1;
+    if (S[2] < S[k]) k = 2;
     const int p = k == 0 ? 1 : 0, q = k == 2 ? 1 : 2;
     double v1[3], v2[3], v3[3], w[3], u1[3], u2[3], u3[3];
-    for (int i = 0; i < 3; ++i) { v1[i] = V[i][p]; v2[i] = V[i][q]; }
+    for (int i = 0; i < 3; ++i) { v1[i] = V[3 * i + p]; v2[i] = V[3 * i + q]; }
     cross(v1, v2, v3);
     for (int i = 0; i < 3; ++i) w[i] = (E[3 * i] * v1[0] + E[3 * i + 1] * v1[1]) + E[3 * i + 2] * v1[2];
     double nw = norm3(w);
@@ -182,12 +146,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        d = tempfile.mkdtemp(prefix="poseref_")
-        src, so = os.path.join(d, "poseref.c"), os.path.join(d, "poseref.so")
-        with open(src, "w") as f:
-            f.write(_SRC)
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", so, "-lm"], check=True, capture_output=True)
-        L = C.CDLL(so)
+        L = epiref.compile_c("poseref", _SRC)
         L.ref_vote.restype = C.c_uint32
         _lib = L
     return _lib
@@ -198,8 +157,7 @@ def _p(a):
 
 
 def _k(K):
-    K = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
-    return K
+    return np.ascontiguousarray(K, dtype=np.float64).reshape(4)
 
 
 def candidates(F, K, best=0):

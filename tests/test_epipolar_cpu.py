@@ -155,6 +155,49 @@ def test_host_sizing_and_checks_are_clean_under_asan_and_ubsan(tmp_path):
     assert "#include <hip" not in src and "__global__" not in src
 
 
+def test_shared_device_helpers_on_the_cpu_equal_the_restatement_bit_for_bit(tmp_path):
+    """kernels_geom3.hip.h, the text the two-view kernels compile, built by g++ as a program of its own under ASan and UBSan:
+    Gram + Jacobi (diagonal and V, sweeps rolled and unrolled), L^T F R and the Frobenius norm must print the bit patterns of
+    the exported restatement functions of tests/epiref.py."""
+    cxx = shutil.which("g++")
+    if not cxx:
+        pytest.skip("no g++")
+    exe = tmp_path / "geom3_driver"
+    r = subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                        os.path.join(ROOT, "tests", "geom3_driver.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    if r.returncode != 0 and ("asan" in r.stderr or "sanitize" in r.stderr):
+        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
+    assert r.returncode == 0, r.stderr[-2000:]
+    rng = np.random.default_rng(20)
+    full = [np.eye(3), np.outer([1.0, 2.0, 3.0], [4.0, -5.0, 6.0]),               # identity; rank 1
+            np.array([[2.0, 0, 1], [0, 3, 1], [0, 0, 1]])]                          # S01 == 0 exactly: the apq == 0 skip
+    full += [rng.standard_normal((3, 3)) * 10.0 ** rng.uniform(-150, 150) for _ in range(200)]
+    inf, nan = float("inf"), float("nan")
+    norm_only = [np.zeros((3, 3)), *(np.array([[1.0, 2, 3], row, [4, 5, 6]]) for row in ([inf] * 3, [-inf] * 3, [inf, -inf, inf], [nan] * 3))]
+    recs = [("A", np.concatenate([m.reshape(9), rng.uniform(0.1, 2000, 2), rng.normal(0, 1000, 2), rng.uniform(0.1, 2000, 2), rng.normal(0, 1000, 2)]))
+            for m in full] + [("N", np.concatenate([m.reshape(9), np.ones(8)])) for m in norm_only]
+    hexes = lambda a: " ".join("%016x" % v for v in np.ascontiguousarray(a, dtype=np.float64).reshape(-1).view(np.uint64))
+    (tmp_path / "in.txt").write_text("".join(f"{kind} {hexes(v)}\n" for kind, v in recs))
+    out = subprocess.run([str(exe), str(tmp_path / "in.txt")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-2000:]  # clean under both sanitizers
+
+    L, ptr, want = epiref.lib(), lambda a: C.c_void_p(a.ctypes.data), []
+    for kind, v in recs:
+        M = np.ascontiguousarray(v[:9])
+        if kind == "A":
+            d, V, P = np.zeros(3), np.zeros(9), np.zeros(9)
+            L.ref_gram_jacobi(ptr(M), ptr(d), ptr(V))
+            L.ref_lt_f_r(ptr(np.ascontiguousarray(v[9:13])), ptr(M), ptr(np.ascontiguousarray(v[13:17])), ptr(P))
+            want += [f"J1 {hexes(d)} {hexes(V)}", f"J6 {hexes(d)} {hexes(V)}", f"P {hexes(P)}"]
+        n = L.ref_frobenius(ptr(M))
+        want.append(f"N {hexes(n)} {int(n != 0.0 and n < inf)}")
+    got = out.stdout.splitlines()
+    assert len(got) == len(want) == 3 * 203 + 208
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (i, g, w)
+    assert [l.split()[2] for l in got[-5:]] == ["0", "0", "0", "0", "0"] and got[3].split()[2] == "1"  # zero, inf, inf, inf, NaN norms; identity
+
+
 # ---- the restatement itself
 
 def test_hash_and_sampling_known_answers():

@@ -392,6 +392,25 @@ def _f32(a):
     return a
 
 
+def _fill_out(out, tensors):
+    """A vslam_*_out struct from its output tensors by field name: struct_size, pointers, byte sizes."""
+    out.struct_size = C.sizeof(out)
+    for name, t in tensors.items():
+        if t is not None:
+            setattr(out, name, t.data_ptr())
+            setattr(out, name + "_bytes", t.numel() * t.element_size())
+    return out
+
+
+def _host_lists(matches, query_points, train_points):
+    """The three lists of one host pair as flat record arrays."""
+    return tuple(np.ascontiguousarray(a, dtype=dt).reshape(-1) for a, dt in ((matches, MATCH_DTYPE), (query_points, POINT_DTYPE), (train_points, POINT_DTYPE)))
+
+
+def _ptr(a):
+    return None if a is None or a.size == 0 else a.ctypes.data
+
+
 STREAM_LEGACY = 1  # VSLAM_STREAM_LEGACY == hipStreamLegacy: the device's NULL stream
 
 
@@ -701,14 +720,11 @@ class Context:
         nn: int32 / float32 CUDA tensor of n_pairs * query.cap vslam_nn2 records (NN2_DTYPE), matches: n_pairs * match_cap vslam_match
         records (MATCH_DTYPE; match_cap = its second dimension), match_counts: int32 [n_pairs].  ratio2 is the SQUARED ratio."""
         n = min(query.n, train.n) if n_pairs is None else int(n_pairs)
-        mo = MatchOut()
-        mo.struct_size = C.sizeof(MatchOut)
-        for name, t in (("nn", nn), ("matches", matches), ("match_counts", match_counts)):
-            if t is not None:
-                if not (t.is_cuda and t.device.index == self.device and t.is_contiguous() and t.element_size() == 4):
-                    raise ValueError(f"match: {name} must be a contiguous 4-byte-element tensor on cuda:{self.device}")
-                setattr(mo, name, t.data_ptr())
-                setattr(mo, name + "_bytes", t.numel() * 4)
+        outs = dict(nn=nn, matches=matches, match_counts=match_counts)
+        for name, t in outs.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous() and t.element_size() == 4):
+                raise ValueError(f"match: {name} must be a contiguous 4-byte-element tensor on cuda:{self.device}")
+        mo = _fill_out(MatchOut(), outs)
         if matches is not None:
             mo.match_cap = matches.shape[1]
         self._chk(lib().vslam_match_dev(self._h, C.byref(query), C.byref(train), n, float(ratio2), int(bool(same_octave)), C.byref(mo)), "vslam_match_dev")
@@ -732,6 +748,23 @@ class Context:
                                          int(bool(same_octave)), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_host")
         return nn, matches[: min(total.value, cap)], total.value
 
+    def _two_view_lists(self, stage, n_pairs, required, tensors):
+        """The checks epipolar() and pose() share over their tensors (by argument name, in the order they are reported) -> the number of pairs."""
+        matches, match_counts, query_points, train_points = (tensors[k] for k in ("matches", "match_counts", "query_points", "train_points"))
+        n = min(matches.shape[0], query_points.shape[0], train_points.shape[0]) if n_pairs is None else int(n_pairs)
+        for name, t in tensors.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"{stage}: {name} must be a contiguous tensor on cuda:{self.device}")
+        if tensors[required] is None:
+            raise ValueError(f"{stage}: {required} is required")
+        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12 or query_points.dim() != 3 or train_points.dim() != 3:
+            raise ValueError(f"{stage}: matches must be [n, match_cap, 3] 4-byte elements, the points [n, cap, 6]")
+        if query_points.shape[2] * query_points.element_size() != 24 or train_points.shape[2] * train_points.element_size() != 24:
+            raise ValueError(f"{stage}: points must be [n, cap, 6] int32")
+        if min(matches.shape[0], match_counts.numel(), query_points.shape[0], train_points.shape[0]) < n or match_counts.element_size() != 4:
+            raise ValueError(f"{stage}: fewer sets than pairs")
+        return n
+
     def epipolar(self, matches, match_counts, query_points, train_points, n_pairs: int | None = None, n_hypotheses: int = 512, seed: int = 1,
                  max_dist2: float = 4.0, models=None, inlier_bits=None, inliers=None, inlier_counts=None, hypotheses=None):
         """vslam_epipolar_dev: the RANSAC fundamental matrix of every pair from the tensors match() and detect_batch() wrote;
@@ -740,25 +773,9 @@ class Context:
         contiguous tensor of n_pairs * 88 bytes (EPIPOLAR_DTYPE after .cpu().numpy().view), inlier_bits int64 [n, (match_cap + 63) // 64],
         inliers [n, inlier_cap, 3] like matches, inlier_counts int32 [n], hypotheses n_pairs * n_hypotheses * 80 bytes
         (EPIPOLAR_HYP_DTYPE).  max_dist2 is the SQUARED Sampson distance in pixels."""
-        n = min(matches.shape[0], query_points.shape[0], train_points.shape[0]) if n_pairs is None else int(n_pairs)
-        for name, t in (("matches", matches), ("match_counts", match_counts), ("query_points", query_points), ("train_points", train_points),
-                        ("models", models), ("inlier_bits", inlier_bits), ("inliers", inliers), ("inlier_counts", inlier_counts), ("hypotheses", hypotheses)):
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"epipolar: {name} must be a contiguous tensor on cuda:{self.device}")
-        if models is None:
-            raise ValueError("epipolar: models is required")
-        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12 or query_points.dim() != 3 or train_points.dim() != 3:
-            raise ValueError("epipolar: matches must be [n, match_cap, 3] 4-byte elements, the points [n, cap, 6]")
-        if query_points.shape[2] * query_points.element_size() != 24 or train_points.shape[2] * train_points.element_size() != 24:
-            raise ValueError("epipolar: points must be [n, cap, 6] int32")
-        if min(matches.shape[0], match_counts.numel(), query_points.shape[0], train_points.shape[0]) < n or match_counts.element_size() != 4:
-            raise ValueError("epipolar: fewer sets than pairs")
-        eo = EpipolarOut()
-        eo.struct_size = C.sizeof(EpipolarOut)
-        for name, t in (("models", models), ("inlier_bits", inlier_bits), ("inliers", inliers), ("inlier_counts", inlier_counts), ("hypotheses", hypotheses)):
-            if t is not None:
-                setattr(eo, name, t.data_ptr())
-                setattr(eo, name + "_bytes", t.numel() * t.element_size())
+        outs = dict(models=models, inlier_bits=inlier_bits, inliers=inliers, inlier_counts=inlier_counts, hypotheses=hypotheses)
+        n = self._two_view_lists("epipolar", n_pairs, "models", dict(matches=matches, match_counts=match_counts, query_points=query_points, train_points=train_points, **outs))
+        eo = _fill_out(EpipolarOut(), outs)
         if inliers is not None:
             eo.inlier_cap = inliers.shape[1]
         prm = EpipolarParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2))
@@ -770,9 +787,7 @@ class Context:
                       inlier_cap: int | None = None, want_bits: bool = True, want_inliers: bool = True, want_hypotheses: bool = False):
         """vslam_epipolar_host: one pair of numpy arrays (MATCH_DTYPE, POINT_DTYPE, POINT_DTYPE) -> (model: one EPIPOLAR_DTYPE record,
         inlier_bits uint64 [(m + 63) // 64] or None, inliers MATCH_DTYPE or None, total inliers or None, hypotheses or None)."""
-        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE).reshape(-1)
-        qp = np.ascontiguousarray(query_points, dtype=POINT_DTYPE).reshape(-1)
-        tp = np.ascontiguousarray(train_points, dtype=POINT_DTYPE).reshape(-1)
+        mt, qp, tp = _host_lists(matches, query_points, train_points)
         m = len(mt)
         cap = max(m, 1) if inlier_cap is None else int(inlier_cap)
         model = np.zeros(1, EPIPOLAR_DTYPE)
@@ -781,9 +796,8 @@ class Context:
         hyp = np.zeros(int(n_hypotheses), EPIPOLAR_HYP_DTYPE) if want_hypotheses else None
         total = C.c_size_t()
         prm = EpipolarParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2))
-        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
-        self._chk(lib().vslam_epipolar_host(self._h, ptr(mt), m, ptr(qp), len(qp), ptr(tp), len(tp), C.byref(prm), model.ctypes.data, ptr(bits),
-                                            None if inl is None else inl.ctypes.data, cap, C.byref(total) if want_inliers else None, ptr(hyp)),
+        self._chk(lib().vslam_epipolar_host(self._h, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp), C.byref(prm), model.ctypes.data, _ptr(bits),
+                                            None if inl is None else inl.ctypes.data, cap, C.byref(total) if want_inliers else None, _ptr(hyp)),
                   "vslam_epipolar_host")
         return (model[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None, hyp)
 
@@ -794,27 +808,11 @@ class Context:
         asynchronous on the context stream.  intrinsics = (fx, fy, cx, cy).  Outputs, CUDA tensors: poses - any contiguous tensor of
         n_pairs * 112 bytes (POSE_DTYPE after .cpu().numpy().view), candidates n_pairs * 4 * 104 bytes (POSE_CAND_DTYPE), points
         float64 [n, match_cap, 3] (query-camera frame), front_bits int64 [n, (match_cap + 63) // 64]."""
-        n = min(matches.shape[0], query_points.shape[0], train_points.shape[0]) if n_pairs is None else int(n_pairs)
-        for name, t in (("models", models), ("matches", matches), ("match_counts", match_counts), ("query_points", query_points),
-                        ("train_points", train_points), ("poses", poses), ("candidates", candidates), ("points", points), ("front_bits", front_bits)):
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"pose: {name} must be a contiguous tensor on cuda:{self.device}")
-        if poses is None:
-            raise ValueError("pose: poses is required")
-        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12 or query_points.dim() != 3 or train_points.dim() != 3:
-            raise ValueError("pose: matches must be [n, match_cap, 3] 4-byte elements, the points [n, cap, 6]")
-        if query_points.shape[2] * query_points.element_size() != 24 or train_points.shape[2] * train_points.element_size() != 24:
-            raise ValueError("pose: points must be [n, cap, 6] int32")
-        if min(matches.shape[0], match_counts.numel(), query_points.shape[0], train_points.shape[0]) < n or match_counts.element_size() != 4:
-            raise ValueError("pose: fewer sets than pairs")
+        outs = dict(poses=poses, candidates=candidates, points=points, front_bits=front_bits)
+        n = self._two_view_lists("pose", n_pairs, "poses", dict(models=models, matches=matches, match_counts=match_counts, query_points=query_points, train_points=train_points, **outs))
         if models.numel() * models.element_size() < n * 88:
             raise ValueError("pose: models must hold n_pairs * 88 bytes")
-        po = PoseOut()
-        po.struct_size = C.sizeof(PoseOut)
-        for name, t in (("poses", poses), ("candidates", candidates), ("points", points), ("front_bits", front_bits)):
-            if t is not None:
-                setattr(po, name, t.data_ptr())
-                setattr(po, name + "_bytes", t.numel() * t.element_size())
+        po = _fill_out(PoseOut(), outs)
         prm = PoseParams(*(float(v) for v in intrinsics))
         self._chk(lib().vslam_pose_dev(self._h, models.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), matches.shape[1],
                                        query_points.data_ptr(), query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n,
@@ -826,18 +824,15 @@ class Context:
         POSE_DTYPE record, candidates [4] POSE_CAND_DTYPE or None, points float64 [m, 3] or None - None too when there is no winner -,
         front_bits uint64 [(m + 63) // 64] or None)."""
         mod = np.ascontiguousarray(model, dtype=EPIPOLAR_DTYPE).reshape(-1)[:1]
-        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE).reshape(-1)
-        qp = np.ascontiguousarray(query_points, dtype=POINT_DTYPE).reshape(-1)
-        tp = np.ascontiguousarray(train_points, dtype=POINT_DTYPE).reshape(-1)
+        mt, qp, tp = _host_lists(matches, query_points, train_points)
         m = len(mt)
         pose = np.zeros(1, POSE_DTYPE)
         cand = np.zeros(4, POSE_CAND_DTYPE) if want_candidates else None
         pts = np.zeros((max(m, 1), 3), np.float64) if want_points else None
         bits = np.zeros((m + 63) // 64, np.uint64) if want_bits else None
         prm = PoseParams(*(float(v) for v in intrinsics))
-        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
-        self._chk(lib().vslam_pose_host(self._h, mod.ctypes.data, ptr(mt), m, ptr(qp), len(qp), ptr(tp), len(tp), C.byref(prm), pose.ctypes.data,
-                                        ptr(cand), ptr(pts), ptr(bits)), "vslam_pose_host")
+        self._chk(lib().vslam_pose_host(self._h, mod.ctypes.data, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp), C.byref(prm), pose.ctypes.data,
+                                        _ptr(cand), _ptr(pts), _ptr(bits)), "vslam_pose_host")
         return pose[0], cand, (pts[:m] if want_points and int(pose["best"][0]) >= 0 else None), bits
 
     def kernel_timing_enable(self, name: str | None):

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
+#include "kernels_geom3.hip.h"
 #include "vslam_epipolar_plan.h"
 
 namespace vslam {
@@ -24,15 +25,13 @@ __device__ __forceinline__ unsigned int epi_mix(unsigned int x) {
     return x;
 }
 
-__device__ __forceinline__ unsigned int epi_count(const unsigned int* __restrict__ counts, int j, unsigned int cap) { return min(counts[j], cap); }
-
 // grid = (record blocks, pairs)
 __global__ __launch_bounds__(256) void k_epi_coords(const vslam_match* __restrict__ matches, const unsigned int* __restrict__ counts,
                                                      unsigned int mcap, const vslam_point* __restrict__ qpts, unsigned int qcap,
                                                      const vslam_point* __restrict__ tpts, unsigned int tcap, EpiXY* __restrict__ xy) {
     const int j = blockIdx.y;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // (64 bits: the last block of a capacity near 2^32 runs past it)
-    if (i >= epi_count(counts, j, mcap)) return;
+    if (i >= g3_count(counts, j, mcap)) return;
     const vslam_match m = matches[(size_t)j * mcap + i];
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     EpiXY r{nan, nan, nan, nan};
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(EPI_MODEL_WG) void k_epi_models(const EpiXY* __rest
     vslam_epipolar_hyp* out = hyp + (size_t)j * H + h;
     double F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool ok = false;
-    const unsigned int m = epi_count(counts, j, mcap);
+    const unsigned int m = g3_count(counts, j, mcap);
     do {
         if (m < 8) break;
         // the sample
@@ -177,35 +176,12 @@ __global__ __launch_bounds__(EPI_MODEL_WG) void k_epi_models(const EpiXY* __rest
         double f[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) f[i] = a[i][l];
-        // 4. rank 2: cyclic Jacobi on S = F^T F (statically indexed: the three pairs are unrolled)
-        double S00 = (f[0] * f[0] + f[3] * f[3]) + f[6] * f[6], S01 = (f[0] * f[1] + f[3] * f[4]) + f[6] * f[7],
-               S02 = (f[0] * f[2] + f[3] * f[5]) + f[6] * f[8], S11 = (f[1] * f[1] + f[4] * f[4]) + f[7] * f[7],
-               S12 = (f[1] * f[2] + f[4] * f[5]) + f[7] * f[8], S22 = (f[2] * f[2] + f[5] * f[5]) + f[8] * f[8];
-        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        // rotates the pair (p, q): app, aqq, apq its block, arp, arq the third index's two entries
-        auto rotate = [&](double& app, double& aqq, double& apq, double& arp, double& arq, int p, int q) {
-            if (apq == 0.0) return;
-            const double theta = (aqq - app) / (2.0 * apq);
-            const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-            const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-            const double napp = app - t * apq, naqq = aqq + t * apq;
-            const double narp = c * arp - s * arq, narq = s * arp + c * arq;
-            app = napp, aqq = naqq, apq = 0.0, arp = narp, arq = narq;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double vp = c * V[i][p] - s * V[i][q], vq = s * V[i][p] + c * V[i][q];
-                V[i][p] = vp, V[i][q] = vq;
-            }
-        };
-        for (int sweep = 0; sweep < 6; ++sweep) {
-            rotate(S00, S11, S01, S02, S12, 0, 1);
-            rotate(S00, S22, S02, S01, S12, 0, 2);
-            rotate(S11, S22, S12, S01, S02, 1, 2);
-        }
-        double v0 = V[0][0], v1 = V[1][0], v2 = V[2][0], smin = S00;
-        if (S11 < smin) v0 = V[0][1], v1 = V[1][1], v2 = V[2][1], smin = S11;
-        if (S22 < smin) v0 = V[0][2], v1 = V[1][2], v2 = V[2][2], smin = S22;
+        // 4. rank 2: the singular vector of the smallest singular value is projected out
+        double S[3], V[3][3];
+        g3_gram_jacobi<1>(f, S, V);
+        double v0 = V[0][0], v1 = V[1][0], v2 = V[2][0], smin = S[0];
+        if (S[1] < smin) v0 = V[0][1], v1 = V[1][1], v2 = V[2][1], smin = S[1];
+        if (S[2] < smin) v0 = V[0][2], v1 = V[1][2], v2 = V[2][2], smin = S[2];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const double g = (f[3 * i] * v0 + f[3 * i + 1] * v1) + f[3 * i + 2] * v2;
@@ -214,26 +190,11 @@ __global__ __launch_bounds__(EPI_MODEL_WG) void k_epi_models(const EpiXY* __rest
             f[3 * i + 2] = f[3 * i + 2] - g * v2;
         }
         // 5. undo the normalisation
-        const double aq = -(sq * cqx), bq = -(sq * cqy), at = -(st * ctx), bt = -(st * cty);
-        double G[9], Hm[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            G[3 * i] = f[3 * i] * sq;
-            G[3 * i + 1] = f[3 * i + 1] * sq;
-            G[3 * i + 2] = (f[3 * i] * aq + f[3 * i + 1] * bq) + f[3 * i + 2];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            Hm[c] = st * G[c];
-            Hm[3 + c] = st * G[3 + c];
-            Hm[6 + c] = (at * G[c] + bt * G[3 + c]) + G[6 + c];
-        }
+        double Hm[9];
+        g3_lt_f_r(G3Affine{st, st, -(st * ctx), -(st * cty)}, f, G3Affine{sq, sq, -(sq * cqx), -(sq * cqy)}, Hm);
         // 6. Frobenius norm 1
-        double n2 = Hm[0] * Hm[0];
-#pragma unroll
-        for (int i = 1; i < 9; ++i) n2 = n2 + Hm[i] * Hm[i];
-        const double nrm = sqrt(n2);
-        if (nrm == 0.0 || !(nrm < __longlong_as_double(0x7ff0000000000000ll))) break;
+        const double nrm = g3_frobenius(Hm);
+        if (!g3_finite_nonzero(nrm)) break;
 #pragma unroll
         for (int i = 0; i < 9; ++i) F[i] = Hm[i] / nrm;
         ok = true;
@@ -261,7 +222,7 @@ __global__ __launch_bounds__(EPI_SCORE_WG) void k_epi_score(const EpiXY* __restr
                                                              vslam_epipolar_hyp* __restrict__ hyp) {
     __shared__ EpiXY tile[EPI_TILE];
     const int j = blockIdx.z;
-    const unsigned int m = epi_count(counts, j, mcap);
+    const unsigned int m = g3_count(counts, j, mcap);
     const unsigned int h = blockIdx.x * EPI_SCORE_WG + threadIdx.x;
     vslam_epipolar_hyp* mine = hyp + (size_t)j * H + min(h, H - 1);
     double F[9];
@@ -310,7 +271,7 @@ __global__ __launch_bounds__(256) void k_epi_select(const vslam_epipolar_hyp* __
     if (threadIdx.x == 0) {
         key = max(max(skey[0], skey[1]), max(skey[2], skey[3]));
         vslam_epipolar out;
-        out.n_matches = epi_count(counts, j, mcap);
+        out.n_matches = g3_count(counts, j, mcap);
         out.n_valid = sval[0] + sval[1] + sval[2] + sval[3];
         if (key) {
             const unsigned int best = 65535u - (unsigned int)(key & 0xffffull);
@@ -334,16 +295,16 @@ __global__ __launch_bounds__(256) void k_epi_flags(const EpiXY* __restrict__ xy,
                                                     const vslam_epipolar* __restrict__ models, double max_dist2,
                                                     unsigned long long* __restrict__ flags, unsigned int fwords) {
     const int j = blockIdx.y;
-    const unsigned int m = epi_count(counts, j, mcap);
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if ((i & ~(size_t)63) >= m) return;  // wave-uniform: the wave's word holds no record
+    const unsigned int m = g3_count(counts, j, mcap);
+    const size_t i = g3_record(blockIdx.x, 256, threadIdx.x);
+    if (!g3_wave_has_record(i, m)) return;
     double F[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) F[k] = models[j].F[k];
     bool in = false;
     if (i < m) in = epi_inlier(F, xy[(size_t)j * mcap + i], max_dist2);
     const unsigned long long w = __ballot(in);
-    if ((threadIdx.x & 63) == 0) flags[(size_t)j * fwords + (i >> 6)] = w;
+    g3_store_word(flags, j, fwords, i, g3_first_lane(threadIdx.x), w);
 }
 
 }  // namespace vslam

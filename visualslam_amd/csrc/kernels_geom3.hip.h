@@ -1,0 +1,95 @@
+// The 3 x 3 f64 arithmetic and the record walk that the two-view stages share (kernels_epipolar.hip.h, kernels_pose.hip.h),
+// each stated once.  Of include/vslam.h this states "two-view geometry" steps 4 (the Jacobi sweeps on F^T F), 5 (the
+// normalisation undone: a product L^T F R) and 6 (Frobenius norm, finite and non-zero), and "relative pose and triangulation"
+// steps 1 (E = K^T F K: the same product and norm) and 2 (the same sweeps on E^T E).  Every + - * / sqrt is an IEEE operation
+// of its own and sums run left to right: the order written here is the ABI's.  Plain C++ - G3 is __host__ __device__ under
+// hipcc and nothing elsewhere - so a host compiler runs the same text (tests/geom3_driver.cpp, against tests/epiref.py).
+// The callers differ in one thing, on purpose: k_pose_candidates unrolls the six sweeps fully (UNROLL = 6), k_epi_models
+// does not (UNROLL = 1) - it stands at 257 VGPRs, 80 bytes of scratch and 55296 bytes of LDS, and that budget must not grow.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#ifdef __HIPCC__
+#define G3 __host__ __device__
+#else
+#define G3
+#endif
+
+namespace vslam {
+
+G3 inline bool g3_finite_nonzero(double n) { return n != 0.0 && n < __builtin_huge_val(); }
+
+// One Jacobi rotation of the pair (P, Q) of a symmetric 3 x 3 S: app, aqq, apq its block, arp, arq the third index's two
+// entries.  P and Q are compile-time, so V never leaves the registers.
+template <int P, int Q>
+G3 inline void g3_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double (&V)[3][3]) {
+    if (apq == 0.0) return;
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    const double napp = app - t * apq, naqq = aqq + t * apq;
+    const double narp = c * arp - s * arq, narq = s * arp + c * arq;
+    app = napp, aqq = naqq, apq = 0.0, arp = narp, arq = narq;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double vp = c * V[i][P] - s * V[i][Q], vq = s * V[i][P] + c * V[i][Q];
+        V[i][P] = vp, V[i][Q] = vq;
+    }
+}
+
+// S = M^T M of the row-major M, six cyclic sweeps (0, 1), (0, 2), (1, 2): d = the diagonal left, V = the rotations accumulated.
+template <int UNROLL>
+G3 inline void g3_gram_jacobi(const double (&M)[9], double (&d)[3], double (&V)[3][3]) {
+    double S00 = (M[0] * M[0] + M[3] * M[3]) + M[6] * M[6], S01 = (M[0] * M[1] + M[3] * M[4]) + M[6] * M[7],
+           S02 = (M[0] * M[2] + M[3] * M[5]) + M[6] * M[8], S11 = (M[1] * M[1] + M[4] * M[4]) + M[7] * M[7],
+           S12 = (M[1] * M[2] + M[4] * M[5]) + M[7] * M[8], S22 = (M[2] * M[2] + M[5] * M[5]) + M[8] * M[8];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) V[i / 3][i % 3] = i / 3 == i % 3 ? 1.0 : 0.0;
+#pragma unroll UNROLL
+    for (int sweep = 0; sweep < 6; ++sweep) {
+        g3_rotate<0, 1>(S00, S11, S01, S02, S12, V);
+        g3_rotate<0, 2>(S00, S22, S02, S01, S12, V);
+        g3_rotate<1, 2>(S11, S22, S12, S01, S02, V);
+    }
+    d[0] = S00, d[1] = S11, d[2] = S22;
+}
+
+struct G3Affine {  // the matrix [[sx, 0, ax], [0, sy, ay], [0, 0, 1]]: a normalisation, or the intrinsics
+    double sx, sy, ax, ay;
+};
+// out = L^T F R, the right factor first.
+G3 inline void g3_lt_f_r(const G3Affine& L, const double (&F)[9], const G3Affine& R, double (&out)[9]) {
+    double G[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        G[3 * i] = F[3 * i] * R.sx, G[3 * i + 1] = F[3 * i + 1] * R.sy;
+        G[3 * i + 2] = (F[3 * i] * R.ax + F[3 * i + 1] * R.ay) + F[3 * i + 2];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        out[c] = L.sx * G[c], out[3 + c] = L.sy * G[3 + c];
+        out[6 + c] = (L.ax * G[c] + L.ay * G[3 + c]) + G[6 + c];
+    }
+}
+
+// The Frobenius norm, the squares summed left to right.
+G3 inline double g3_frobenius(const double (&M)[9]) {
+    double n2 = M[0] * M[0];
+#pragma unroll
+    for (int i = 1; i < 9; ++i) n2 = n2 + M[i] * M[i];
+    return sqrt(n2);
+}
+
+// The record walk.  Pair j has min(count, capacity) records; lane `lane` of workgroup `block` has record i, 64 bits (the last
+// block of a capacity near 2^32 runs past it); a wave none of whose records lies below m leaves (wave-uniform); lane 0 of a
+// wave speaks for it and stores its ballot word, word i / 64 of pair j.
+G3 inline unsigned int g3_count(const unsigned int* __restrict__ counts, int j, unsigned int cap) { return counts[j] < cap ? counts[j] : cap; }
+G3 inline size_t g3_record(unsigned int block, unsigned int wg, unsigned int lane) { return (size_t)block * wg + lane; }
+G3 inline bool g3_wave_has_record(size_t i, unsigned int m) { return (i & ~(size_t)63) < m; }
+G3 inline bool g3_first_lane(unsigned int lane) { return (lane & 63) == 0; }
+G3 inline void g3_store_word(unsigned long long* words, size_t j, unsigned int fwords, size_t i, bool store, unsigned long long w) {
+    if (store) words[j * fwords + (i >> 6)] = w;
+}
+
+}  // namespace vslam

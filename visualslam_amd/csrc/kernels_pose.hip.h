@@ -8,37 +8,15 @@
 //   k_pose_select     : one lane per pair: the candidate with the most records in front, lowest index on ties
 //   k_pose_points     : one lane per record: the midpoint of the two rays under the winner, and the wave's ballot word
 // The {x, y, x', y'} records come from k_epi_coords (vslam::enqueue_epi_coords).  The arithmetic is the header's, operation
-// for operation: every + - * / sqrt of f64 is an IEEE operation of its own (the library is built with -ffp-contract=off; f64
-// division and sqrt are correctly rounded on gfx950), sums run left to right.
+// for operation, under the rules of kernels_epipolar.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
-#include "vslam_epipolar_plan.h"
+#include "kernels_geom3.hip.h"
 #include "vslam_pose_plan.h"
 
 namespace vslam {
-
-__device__ __forceinline__ bool pose_finite_nonzero(double n) { return n != 0.0 && n < __longlong_as_double(0x7ff0000000000000ll); }
-
-// One Jacobi rotation of the pair (P, Q) of the symmetric 3 x 3 S (step 4 of the two-view model): app, aqq, apq its block,
-// arp, arq the third index's two entries.  P and Q are compile-time, so V never leaves the registers.
-template <int P, int Q>
-__device__ __forceinline__ void pose_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double (&V)[3][3]) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    const double napp = app - t * apq, naqq = aqq + t * apq;
-    const double narp = c * arp - s * arq, narq = s * arp + c * arq;
-    app = napp, aqq = naqq, apq = 0.0, arp = narp, arq = narq;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double vp = c * V[i][P] - s * V[i][Q], vq = s * V[i][P] + c * V[i][Q];
-        V[i][P] = vp, V[i][Q] = vq;
-    }
-}
 
 __device__ __forceinline__ void pose_cross(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
     o[0] = a[1] * b[2] - a[2] * b[1];
@@ -57,7 +35,7 @@ __device__ __forceinline__ bool pose_left_vector(const double (&E)[9], const dou
         for (int i = 0; i < 3; ++i) w[i] = w[i] - d * u1[i];
     }
     const double n = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
-    if (!pose_finite_nonzero(n)) return false;
+    if (!g3_finite_nonzero(n)) return false;
 #pragma unroll
     for (int i = 0; i < 3; ++i) u[i] = w[i] / n;
     return true;
@@ -73,42 +51,20 @@ __global__ __launch_bounds__(POSE_PAIR_WG) void k_pose_candidates(const vslam_ep
     do {
         if (models[j].best < 0) break;
         // 1. E = K^T F K, Frobenius norm 1
-        double G[9], E[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double f0 = models[j].F[3 * i], f1 = models[j].F[3 * i + 1], f2 = models[j].F[3 * i + 2];
-            G[3 * i] = f0 * K.fx;
-            G[3 * i + 1] = f1 * K.fy;
-            G[3 * i + 2] = (f0 * K.cx + f1 * K.cy) + f2;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            E[c] = K.fx * G[c];
-            E[3 + c] = K.fy * G[3 + c];
-            E[6 + c] = (K.cx * G[c] + K.cy * G[3 + c]) + G[6 + c];
-        }
-        double n2 = E[0] * E[0];
-#pragma unroll
-        for (int i = 1; i < 9; ++i) n2 = n2 + E[i] * E[i];
-        const double nrm = sqrt(n2);
-        if (!pose_finite_nonzero(nrm)) break;
+        double E[9];
+        const G3Affine Km{K.fx, K.fy, K.cx, K.cy};
+        g3_lt_f_r(Km, models[j].F, Km, E);
+        const double nrm = g3_frobenius(E);
+        if (!g3_finite_nonzero(nrm)) break;
 #pragma unroll
         for (int i = 0; i < 9; ++i) E[i] = E[i] / nrm;
         // 2. right singular vectors: cyclic Jacobi on S = E^T E
-        double S00 = (E[0] * E[0] + E[3] * E[3]) + E[6] * E[6], S01 = (E[0] * E[1] + E[3] * E[4]) + E[6] * E[7],
-               S02 = (E[0] * E[2] + E[3] * E[5]) + E[6] * E[8], S11 = (E[1] * E[1] + E[4] * E[4]) + E[7] * E[7],
-               S12 = (E[1] * E[2] + E[4] * E[5]) + E[7] * E[8], S22 = (E[2] * E[2] + E[5] * E[5]) + E[8] * E[8];
-        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-#pragma unroll
-        for (int sweep = 0; sweep < 6; ++sweep) {
-            pose_rotate<0, 1>(S00, S11, S01, S02, S12, V);
-            pose_rotate<0, 2>(S00, S22, S02, S01, S12, V);
-            pose_rotate<1, 2>(S11, S22, S12, S01, S02, V);
-        }
+        double S[3], V[3][3];
+        g3_gram_jacobi<6>(E, S, V);
         int k = 0;
-        double smin = S00;
-        if (S11 < smin) k = 1, smin = S11;
-        if (S22 < smin) k = 2, smin = S22;
+        double smin = S[0];
+        if (S[1] < smin) k = 1, smin = S[1];
+        if (S[2] < smin) k = 2, smin = S[2];
         // (p, q) = (1, 2), (0, 2), (0, 1) for k = 0, 1, 2: selects, not indexed reads
         double v1[3], v2[3], v3[3];
 #pragma unroll
@@ -170,16 +126,14 @@ __device__ __forceinline__ void pose_solve(const double (&R)[9], const double (&
     n2 = aa * bt - ab * at;
 }
 
-__device__ __forceinline__ unsigned int pose_count(const unsigned int* __restrict__ counts, int j, unsigned int cap) { return min(counts[j], cap); }
-
 // grid = (record blocks of 256, pairs).  The pair's candidates are read through addresses that are the same in every lane.
 // `cand` is read (R, t, valid) and written (front, by atomicAdd) here, so it is neither const nor restrict.
 __global__ __launch_bounds__(POSE_REC_WG) void k_pose_vote(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts,
                                                             unsigned int mcap, vslam_pose_params K, vslam_pose_cand* cand) {
     const int j = blockIdx.y;
-    const unsigned int m = pose_count(counts, j, mcap);
-    const size_t i = (size_t)blockIdx.x * POSE_REC_WG + threadIdx.x;  // (64 bits: the last block of a capacity near 2^32 runs past it)
-    if ((i & ~(size_t)63) >= m) return;                               // wave-uniform: the wave holds no record
+    const unsigned int m = g3_count(counts, j, mcap);
+    const size_t i = g3_record(blockIdx.x, POSE_REC_WG, threadIdx.x);
+    if (!g3_wave_has_record(i, m)) return;
     vslam_pose_cand* cj = cand + (size_t)j * 4;
     if (!cj[0].valid) return;  // block-uniform: every count stays 0
     double Ra[9], Rb[9], t[3];
@@ -199,7 +153,7 @@ __global__ __launch_bounds__(POSE_REC_WG) void k_pose_vote(const EpiXY* __restri
         f3 = det > 0.0 && n1 < 0.0 && n2 < 0.0;
     }
     const unsigned int c0 = __popcll(__ballot(f0)), c1 = __popcll(__ballot(f1)), c2 = __popcll(__ballot(f2)), c3 = __popcll(__ballot(f3));
-    if ((threadIdx.x & 63) == 0) {
+    if (g3_first_lane(threadIdx.x)) {
         if (c0) atomicAdd(&cj[0].front, c0);
         if (c1) atomicAdd(&cj[1].front, c1);
         if (c2) atomicAdd(&cj[2].front, c2);
@@ -225,7 +179,7 @@ __global__ __launch_bounds__(POSE_PAIR_WG) void k_pose_select(const vslam_pose_c
     for (int i = 0; i < 9; ++i) out.R[i] = best < 0 ? 0.0 : cj[best].R[i];
 #pragma unroll
     for (int i = 0; i < 3; ++i) out.t[i] = best < 0 ? 0.0 : cj[best].t[i];
-    out.n_matches = pose_count(counts, j, mcap);
+    out.n_matches = g3_count(counts, j, mcap);
     out.n_front = best < 0 ? 0u : most;
     out.best = best;
     out.valid = valid;
@@ -241,12 +195,12 @@ __global__ __launch_bounds__(POSE_REC_WG) void k_pose_points(const EpiXY* __rest
                                                               unsigned int mcap, const vslam_pose* __restrict__ poses, vslam_pose_params K,
                                                               double* __restrict__ points, unsigned long long* __restrict__ bits, unsigned int fwords) {
     const int j = blockIdx.y;
-    const unsigned int m = pose_count(counts, j, mcap);
-    const size_t i = (size_t)blockIdx.x * POSE_REC_WG + threadIdx.x;
-    if ((i & ~(size_t)63) >= m) return;  // wave-uniform: the wave's word holds no record
-    const bool lane0 = (threadIdx.x & 63) == 0;
+    const unsigned int m = g3_count(counts, j, mcap);
+    const size_t i = g3_record(blockIdx.x, POSE_REC_WG, threadIdx.x);
+    if (!g3_wave_has_record(i, m)) return;
+    const bool lane0 = g3_first_lane(threadIdx.x);
     if (poses[j].best < 0) {  // block-uniform
-        if (bits && lane0) bits[(size_t)j * fwords + (i >> 6)] = 0ull;
+        g3_store_word(bits, j, fwords, i, bits && lane0, 0ull);
         return;
     }
     double R[9], t[3];
@@ -271,7 +225,7 @@ __global__ __launch_bounds__(POSE_REC_WG) void k_pose_points(const EpiXY* __rest
         }
     }
     const unsigned long long w = __ballot(in);
-    if (bits && lane0) bits[(size_t)j * fwords + (i >> 6)] = w;
+    g3_store_word(bits, j, fwords, i, bits && lane0, w);
 }
 
 }  // namespace vslam

@@ -16,9 +16,8 @@ using namespace vslam;
 int vslam::enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
                               const vslam_point* query_points, unsigned int query_cap, const vslam_point* train_points, unsigned int train_cap,
                               int n_pairs, EpiXY* xy) {
-    const unsigned int rec_blocks = (unsigned int)(((size_t)match_cap + 255) / 256);
-    LAUNCH(c, "k_epi_coords", k_epi_coords, dim3(rec_blocks, n_pairs), dim3(256), matches, match_counts, match_cap, query_points, query_cap,
-           train_points, train_cap, xy);
+    LAUNCH(c, "k_epi_coords", k_epi_coords, dim3(twoview_plan(match_cap, n_pairs).rec_blocks, n_pairs), dim3(TWOVIEW_REC_WG), matches, match_counts,
+           match_cap, query_points, query_cap, train_points, train_cap, xy);
     return VSLAM_OK;
 }
 
@@ -29,7 +28,7 @@ int vslam_epipolar_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t*
                        const vslam_epipolar_params* prm, const vslam_epipolar_out* out) {
     static_assert(sizeof(vslam_epipolar_hyp) == 80 && sizeof(vslam_epipolar) == 88 && sizeof(EpiXY) == 32, "record layouts");
     if (const char* why = epipolar_check_args(matches, match_counts, match_cap, query_points, query_cap, train_points, train_cap, n_pairs, prm, out))
-        return fail(c, VSLAM_ERR_INVALID, why);
+        return fail(c, VSLAM_ERR_INVALID, std::string("epipolar: ") + why);
     TRY(usable_ctx(c));
     if (n_pairs == 0) return VSLAM_OK;
 
@@ -69,31 +68,19 @@ int vslam_epipolar_host(vslam_ctx* c, const vslam_match* matches, size_t n_match
     ARGCHK(c, prm && model, "epipolar_host: null argument");
     ARGCHK(c, prm->n_hypotheses >= 1 && prm->n_hypotheses <= 65535, "epipolar_host: 1 .. 65535 hypotheses");
     ARGCHK(c, std::isfinite(prm->max_dist2) && prm->max_dist2 > 0.0, "epipolar_host: max_dist2 must be finite and positive");
-    ARGCHK(c, (matches || n_matches == 0) && (query_points || n_query == 0) && (train_points || n_train == 0), "epipolar_host: null input");
-    ARGCHK(c, n_matches < (1u << 31) && n_query < (1u << 31) && n_train < (1u << 31) && inlier_cap < (1u << 31), "epipolar_host: too many records");
-    ARGCHK(c, !inliers || (n_inliers && inlier_cap > 0), "epipolar_host: inliers needs n_inliers and an inlier_cap");
-    ARGCHK(c, n_matches == 0 || (n_query > 0 && n_train > 0), "epipolar_host: matches without points");
+    HostPair in{matches, query_points, train_points, n_matches, n_query, n_train};
+    TRY(in.check(c, "epipolar_host", inlier_cap, !inliers || (n_inliers && inlier_cap > 0) ? nullptr : "inliers needs n_inliers and an inlier_cap"));
     TRY(usable_ctx(c));
 
     DevBufs dev;
-    vslam_match* d_matches = nullptr;
-    vslam_point *d_q = nullptr, *d_t = nullptr;
-    uint32_t* d_cnt = nullptr;
-    const uint32_t h_cnt = (uint32_t)n_matches;
-    TRY(dev.put(c, d_matches, matches, n_matches));
-    TRY(dev.put(c, d_q, query_points, n_query));
-    TRY(dev.put(c, d_t, train_points, n_train));
-    TRY(dev.put(c, d_cnt, &h_cnt, 1));
-    // a capacity of at least 1 on every side (records without points were refused above)
-    const uint32_t mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
-    const size_t fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
+    TRY(in.upload(c, dev));
     vslam_epipolar_out out{};
     out.struct_size = sizeof(out);
     TRY(dev.get(c, out.models, 1));
     out.models_bytes = sizeof(vslam_epipolar);
     if (inlier_bits) {
-        TRY(dev.get(c, out.inlier_bits, fwords));
-        out.inlier_bits_bytes = fwords * sizeof(uint64_t);
+        TRY(dev.get(c, out.inlier_bits, in.fwords));
+        out.inlier_bits_bytes = in.fwords * sizeof(uint64_t);
     }
     if (n_inliers) {
         TRY(dev.get(c, out.inlier_counts, 1));
@@ -108,10 +95,10 @@ int vslam_epipolar_host(vslam_ctx* c, const vslam_match* matches, size_t n_match
         TRY(dev.get(c, out.hypotheses, prm->n_hypotheses));
         out.hypotheses_bytes = (size_t)prm->n_hypotheses * sizeof(vslam_epipolar_hyp);
     }
-    TRY(vslam_epipolar_dev(c, d_matches, d_cnt, mcap, d_q, qcap, d_t, tcap, 1, prm, &out));
+    TRY(vslam_epipolar_dev(c, in.d_matches, in.d_cnt, in.mcap, in.d_q, in.qcap, in.d_t, in.tcap, 1, prm, &out));
     uint32_t total = 0;
     HIPCHK(c, hipMemcpyAsync(model, out.models, sizeof(vslam_epipolar), hipMemcpyDeviceToHost, c->stream));
-    if (inlier_bits && used_words) HIPCHK(c, hipMemcpyAsync(inlier_bits, out.inlier_bits, used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (inlier_bits && in.used_words) HIPCHK(c, hipMemcpyAsync(inlier_bits, out.inlier_bits, in.used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (hypotheses) HIPCHK(c, hipMemcpyAsync(hypotheses, out.hypotheses, out.hypotheses_bytes, hipMemcpyDeviceToHost, c->stream));
     if (n_inliers) HIPCHK(c, hipMemcpyAsync(&total, out.inlier_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -20,48 +20,59 @@ constexpr unsigned int EPI_MODEL_WG = 64;   // hypotheses per k_epi_models workg
 constexpr unsigned int EPI_MAX_SPLIT = 64;  // workgroups that share the records of one (pair, hypothesis block)
 constexpr size_t EPI_WANT_WGS = 2048;       // 8 workgroups per compute unit
 
-// The message of the first failed check, in the order of vslam_match_dev's (null, struct_size, n_pairs, the parameters, the
-// inputs, the buffers); nullptr: the call is valid.
+// What vslam_pose_plan.h shares with this header: the sizes that follow from the match capacity alone, and the checks of the
+// pair count and of the input lists (`inputs`: every input pointer of the stage is there).
+constexpr unsigned int TWOVIEW_REC_WG = 256;  // match records (lanes) per workgroup of the kernels that walk the records
+struct TwoViewPlan {
+    unsigned int fwords, rec_blocks;  // per pair: ballot words, and TWOVIEW_REC_WG-record blocks (grid.x of the kernels that walk the records)
+    size_t coords_elems;              // scratch: {x, y, x', y'} f64 records
+};
+inline size_t twoview_fwords(size_t match_cap) { return (match_cap + 63) / 64; }
+inline TwoViewPlan twoview_plan(uint32_t match_cap, int n_pairs) {
+    return {(unsigned int)twoview_fwords(match_cap), (unsigned int)(((size_t)match_cap + TWOVIEW_REC_WG - 1) / TWOVIEW_REC_WG), (size_t)n_pairs * match_cap};
+}
+inline const char* twoview_check_pairs(int n_pairs) { return n_pairs < 0 || n_pairs > 65535 ? "0 .. 65535 pairs per call" : nullptr; }
+inline const char* twoview_check_inputs(bool inputs, uint32_t match_cap, uint32_t query_cap, uint32_t train_cap) {
+    return !inputs ? "null input" : match_cap == 0 || query_cap == 0 || train_cap == 0 ? "a capacity is zero" : nullptr;
+}
+
+// The message of the first failed check - the entry point puts its stage in front ("epipolar: ") -, in the order of vslam_match_dev's
+// (null, struct_size, n_pairs, the parameters, the inputs, the buffers); nullptr: the call is valid.
 inline const char* epipolar_check_args(const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap, const vslam_point* query_points,
                                        uint32_t query_cap, const vslam_point* train_points, uint32_t train_cap, int n_pairs,
                                        const vslam_epipolar_params* prm, const vslam_epipolar_out* out) {
-    if (!prm || !out) return "epipolar: null argument";
-    if (out->struct_size != sizeof(vslam_epipolar_out)) return "epipolar: out->struct_size is not sizeof(vslam_epipolar_out)";
-    if (n_pairs < 0 || n_pairs > 65535) return "epipolar: 0 .. 65535 pairs per call";
-    if (prm->n_hypotheses < 1 || prm->n_hypotheses > 65535) return "epipolar: 1 .. 65535 hypotheses";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "epipolar: max_dist2 must be finite and positive";
-    if (!matches || !match_counts || !query_points || !train_points) return "epipolar: null input";
-    if (match_cap == 0 || query_cap == 0 || train_cap == 0) return "epipolar: a capacity is zero";
-    const size_t np = (size_t)n_pairs, fwords = ((size_t)match_cap + 63) / 64;
-    if (!out->models) return "epipolar: models is required";
-    if (out->models_bytes / sizeof(vslam_epipolar) < np) return "epipolar: models buffer too small";
-    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "epipolar: inlier_bits buffer too small";
-    if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "epipolar: inliers needs inlier_counts and an inlier_cap";
-    if (out->inliers && out->inliers_bytes / sizeof(vslam_match) < np * out->inlier_cap) return "epipolar: inliers buffer too small";
-    if (out->inlier_counts && out->inlier_counts_bytes / sizeof(uint32_t) < np) return "epipolar: inlier_counts buffer too small";
-    if (out->hypotheses && out->hypotheses_bytes / sizeof(vslam_epipolar_hyp) < np * prm->n_hypotheses) return "epipolar: hypotheses buffer too small";
+    if (!prm || !out) return "null argument";
+    if (out->struct_size != sizeof(vslam_epipolar_out)) return "out->struct_size is not sizeof(vslam_epipolar_out)";
+    if (const char* why = twoview_check_pairs(n_pairs)) return why;
+    if (prm->n_hypotheses < 1 || prm->n_hypotheses > 65535) return "1 .. 65535 hypotheses";
+    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
+    if (const char* why = twoview_check_inputs(matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
+    const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
+    if (!out->models) return "models is required";
+    if (out->models_bytes / sizeof(vslam_epipolar) < np) return "models buffer too small";
+    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "inlier_bits buffer too small";
+    if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "inliers needs inlier_counts and an inlier_cap";
+    if (out->inliers && out->inliers_bytes / sizeof(vslam_match) < np * out->inlier_cap) return "inliers buffer too small";
+    if (out->inlier_counts && out->inlier_counts_bytes / sizeof(uint32_t) < np) return "inlier_counts buffer too small";
+    if (out->hypotheses && out->hypotheses_bytes / sizeof(vslam_epipolar_hyp) < np * prm->n_hypotheses) return "hypotheses buffer too small";
     return nullptr;
 }
 
 // Grids and scratch of one valid call with n_pairs >= 1.  Every grid dimension stays within HIP's limits (x < 2^31, y and z
 // <= 65535) and no size wraps: n_pairs < 2^16, the capacities < 2^32, a record <= 80 bytes.
-struct EpipolarPlan {
-    unsigned int fwords;                  // ballot words per pair
-    unsigned int rec_blocks;              // 256-record blocks per pair: grid.x of k_epi_coords and k_epi_flags
+struct EpipolarPlan : TwoViewPlan {       // (rec_blocks: grid.x of k_epi_coords and k_epi_flags)
     unsigned int model_blocks;            // grid.x of k_epi_models
     unsigned int score_blocks;            // grid.x of k_epi_score: hypothesis blocks
     unsigned int tiles;                   // record tiles per pair
     unsigned int nsplit;                  // grid.y of k_epi_score: the tiles are dealt round robin to nsplit workgroups
-    size_t coords_elems;                  // scratch: {x, y, x', y'} f64 records
     size_t hyp_elems;                     // scratch when the caller gives no hypotheses buffer
     size_t flag_words;                    // scratch when the caller gives no inlier_bits buffer
 };
 
 inline EpipolarPlan epipolar_plan(uint32_t match_cap, int n_pairs, uint32_t n_hypotheses) {
     EpipolarPlan p{};
+    static_cast<TwoViewPlan&>(p) = twoview_plan(match_cap, n_pairs);
     const size_t np = (size_t)n_pairs;
-    p.fwords = (unsigned int)(((size_t)match_cap + 63) / 64);
-    p.rec_blocks = (unsigned int)(((size_t)match_cap + 255) / 256);
     p.model_blocks = (n_hypotheses + EPI_MODEL_WG - 1) / EPI_MODEL_WG;
     p.score_blocks = (n_hypotheses + EPI_SCORE_WG - 1) / EPI_SCORE_WG;
     p.tiles = (unsigned int)(((size_t)match_cap + EPI_TILE - 1) / EPI_TILE);
@@ -70,7 +81,6 @@ inline EpipolarPlan epipolar_plan(uint32_t match_cap, int n_pairs, uint32_t n_hy
     if (split > EPI_MAX_SPLIT) split = EPI_MAX_SPLIT;
     if (split > p.tiles) split = p.tiles;
     p.nsplit = (unsigned int)(split < 1 ? 1 : split);
-    p.coords_elems = np * match_cap;
     p.hyp_elems = np * n_hypotheses;
     p.flag_words = np * p.fwords;
     return p;

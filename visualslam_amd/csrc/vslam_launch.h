@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "vslam_ctx.h"
 
 // Launch on `stream` with `lds` bytes of dynamic LDS, bracketed for the timing hook as "name@tag".
@@ -109,6 +111,37 @@ struct DevBufs {
     int put(vslam_ctx* c, T*& p, const T* host, size_t count) {
         TRY(get(c, p, count));
         if (count) HIPCHK(c, hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        return VSLAM_OK;
+    }
+};
+
+// One host pair of the two-view entry points (vslam_epipolar_host, vslam_pose_host): the checks they share, in the ABI's
+// order, and the device copies of the three lists and of the count.
+struct HostPair {
+    const vslam_match* matches;
+    const vslam_point *query_points, *train_points;
+    size_t n_matches, n_query, n_train;
+    vslam_match* d_matches = nullptr;
+    vslam_point *d_q = nullptr, *d_t = nullptr;
+    uint32_t *d_cnt = nullptr, h_cnt = 0, mcap = 0, qcap = 0, tcap = 0;  // a capacity of at least 1 on every side
+    size_t fwords = 0, used_words = 0;                                    // ballot words of the capacity, and those that hold a record
+
+    // `more`: a further record count of the stage's; `own`: what a check of the stage's own, due before the last one here, found
+    int check(vslam_ctx* c, const char* stage, size_t more = 0, const char* own = nullptr) const {
+        ARGCHK(c, (matches || n_matches == 0) && (query_points || n_query == 0) && (train_points || n_train == 0), std::string(stage) + ": null input");
+        ARGCHK(c, n_matches < (1u << 31) && n_query < (1u << 31) && n_train < (1u << 31) && more < (1u << 31), std::string(stage) + ": too many records");
+        ARGCHK(c, !own, std::string(stage) + ": " + own);
+        ARGCHK(c, n_matches == 0 || (n_query > 0 && n_train > 0), std::string(stage) + ": matches without points");
+        return VSLAM_OK;
+    }
+    int upload(vslam_ctx* c, DevBufs& dev) {  // (records without points were refused by check())
+        h_cnt = (uint32_t)n_matches;
+        TRY(dev.put(c, d_matches, matches, n_matches));
+        TRY(dev.put(c, d_q, query_points, n_query));
+        TRY(dev.put(c, d_t, train_points, n_train));
+        TRY(dev.put(c, d_cnt, &h_cnt, 1));
+        mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
+        fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
         return VSLAM_OK;
     }
 };

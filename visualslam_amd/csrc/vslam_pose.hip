@@ -20,7 +20,7 @@ int vslam_pose_dev(vslam_ctx* c, const vslam_epipolar* models, const vslam_match
                    const vslam_pose_params* prm, const vslam_pose_out* out) {
     static_assert(sizeof(vslam_pose_cand) == 104 && sizeof(vslam_pose) == 112 && sizeof(EpiXY) == 32, "record layouts");
     if (const char* why = pose_check_args(models, matches, match_counts, match_cap, query_points, query_cap, train_points, train_cap, n_pairs, prm, out))
-        return fail(c, VSLAM_ERR_INVALID, why);
+        return fail(c, VSLAM_ERR_INVALID, std::string("pose: ") + why);
     TRY(usable_ctx(c));
     if (n_pairs == 0) return VSLAM_OK;
 
@@ -49,25 +49,14 @@ int vslam_pose_host(vslam_ctx* c, const vslam_epipolar* model, const vslam_match
     ARGCHK(c, prm && model && pose, "pose_host: null argument");
     ARGCHK(c, std::isfinite(prm->fx) && std::isfinite(prm->fy) && std::isfinite(prm->cx) && std::isfinite(prm->cy), "pose_host: the intrinsics must be finite");
     ARGCHK(c, prm->fx > 0.0 && prm->fy > 0.0, "pose_host: fx and fy must be positive");
-    ARGCHK(c, (matches || n_matches == 0) && (query_points || n_query == 0) && (train_points || n_train == 0), "pose_host: null input");
-    ARGCHK(c, n_matches < (1u << 31) && n_query < (1u << 31) && n_train < (1u << 31), "pose_host: too many records");
-    ARGCHK(c, n_matches == 0 || (n_query > 0 && n_train > 0), "pose_host: matches without points");
+    HostPair in{matches, query_points, train_points, n_matches, n_query, n_train};
+    TRY(in.check(c, "pose_host"));
     TRY(usable_ctx(c));
 
     DevBufs dev;
     vslam_epipolar* d_model = nullptr;
-    vslam_match* d_matches = nullptr;
-    vslam_point *d_q = nullptr, *d_t = nullptr;
-    uint32_t* d_cnt = nullptr;
-    const uint32_t h_cnt = (uint32_t)n_matches;
     TRY(dev.put(c, d_model, model, 1));
-    TRY(dev.put(c, d_matches, matches, n_matches));
-    TRY(dev.put(c, d_q, query_points, n_query));
-    TRY(dev.put(c, d_t, train_points, n_train));
-    TRY(dev.put(c, d_cnt, &h_cnt, 1));
-    // a capacity of at least 1 on every side (records without points were refused above)
-    const uint32_t mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
-    const size_t fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
+    TRY(in.upload(c, dev));
     vslam_pose_out out{};
     out.struct_size = sizeof(out);
     TRY(dev.get(c, out.poses, 1));
@@ -77,17 +66,17 @@ int vslam_pose_host(vslam_ctx* c, const vslam_epipolar* model, const vslam_match
         out.candidates_bytes = 4 * sizeof(vslam_pose_cand);
     }
     if (points) {
-        TRY(dev.get(c, out.points, (size_t)mcap * 3));
-        out.points_bytes = (size_t)mcap * 3 * sizeof(double);
+        TRY(dev.get(c, out.points, (size_t)in.mcap * 3));
+        out.points_bytes = (size_t)in.mcap * 3 * sizeof(double);
     }
     if (front_bits) {
-        TRY(dev.get(c, out.front_bits, fwords));
-        out.front_bits_bytes = fwords * sizeof(uint64_t);
+        TRY(dev.get(c, out.front_bits, in.fwords));
+        out.front_bits_bytes = in.fwords * sizeof(uint64_t);
     }
-    TRY(vslam_pose_dev(c, d_model, d_matches, d_cnt, mcap, d_q, qcap, d_t, tcap, 1, prm, &out));
+    TRY(vslam_pose_dev(c, d_model, in.d_matches, in.d_cnt, in.mcap, in.d_q, in.qcap, in.d_t, in.tcap, 1, prm, &out));
     HIPCHK(c, hipMemcpyAsync(pose, out.poses, sizeof(vslam_pose), hipMemcpyDeviceToHost, c->stream));
     if (candidates) HIPCHK(c, hipMemcpyAsync(candidates, out.candidates, 4 * sizeof(vslam_pose_cand), hipMemcpyDeviceToHost, c->stream));
-    if (front_bits && used_words) HIPCHK(c, hipMemcpyAsync(front_bits, out.front_bits, used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (front_bits && in.used_words) HIPCHK(c, hipMemcpyAsync(front_bits, out.front_bits, in.used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // the point rows of a pair without a winner are not written: the caller's stay as they are
     if (points && n_matches && pose->best >= 0) HIPCHK(c, hipMemcpy(points, out.points, n_matches * 3 * sizeof(double), hipMemcpyDeviceToHost));
