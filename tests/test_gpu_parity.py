@@ -317,6 +317,43 @@ def test_filter_keypoints_bit_exact(ctx, shape, n_oct, kind):
     got.close()
 
 
+def test_per_image_calls_share_the_cached_taps_of_two_pyramids(ctx):
+    # The per-image filterKeypoints / SIFT read their blur taps from the context's table cache, keyed by (sigma, tap count):
+    # two pyramids with different sigma0 live on one context, and the calls go 1.6 (its tables are made), 1.3 (its tables
+    # are made beside them), 1.6 again (its tables are found among both pyramids').
+    img = frame((135, 240))
+    sigmas = (1.6, 1.3)
+    want = {s: oracle.Pyramid(img, 2, s) for s in sigmas}
+    got = {s: ctx.pyramid(img, 2, s) for s in sigmas}
+    ref = {}  # per (sigma0, octave): the oracle's answers, computed once
+    for s in sigmas:
+        for o in range(2):
+            r, c = want[s].sizes[o]
+            extra = np.zeros(12, capi.POINT_DTYPE)  # the hand-placed keypoints of test_filter_keypoints_bit_exact: all six levels
+            for i, (y, x) in enumerate([(0, 0), (r, c), (0, c), (r, 0), (1, 1), (r - 1, c - 1), (r // 2, 0), (0, c // 2), (r // 2, c // 2), (1, c), (r, 1), (2, 3)]):
+                extra[i] = (y, x, 50, 1, o, i % 6)
+            kp = want[s].keypoints(o, 3)
+            oriented = want[s].filter_keypoints(o, kp)
+            ref[s, o] = (kp, oriented, extra, want[s].filter_keypoints(o, extra)) + tuple(want[s].sift_descriptors(o, oriented))
+    # the test cannot pass empty: the oracle alone gives these counts at octave 0 (octave 1 of so small a noise frame has no
+    # keypoints: there only the hand-placed ones run)
+    assert (len(ref[1.6, 0][1]), int(ref[1.6, 0][5].sum())) == (494, 314)
+    assert (len(ref[1.3, 0][1]), int(ref[1.3, 0][5].sum())) == (1017, 577)
+    for s in (1.6, 1.3, 1.6):
+        for o in range(2):
+            kp, oriented, extra, wextra, wd, wok = ref[s, o]
+            g, n = got[s].filter_keypoints(o, kp)
+            assert n == len(oriented) and same(g, oriented), (s, o)
+            g, n = got[s].filter_keypoints(o, extra)
+            assert n == len(wextra) and same(g, wextra), ("extra", s, o)
+            gd, gok = got[s].sift_descriptors(o, oriented)
+            assert (gok == wok).all(), (s, o)
+            assert np.array_equal(gd, wd, equal_nan=True), (s, o)  # bit-exact apart from the NaN payload of 0 / 0
+    for s in sigmas:
+        got[s].close()
+        want[s].close()
+
+
 def test_edge_response_windows(ctx):
     rng = np.random.default_rng(5)
     gx = rng.integers(-255, 256, (5000, 4)).astype(np.float32)

@@ -285,6 +285,27 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     return a;
 }
 
+// orientationHistogram's bin of an angle in degrees (Diff_of_Gauss.cpp:114, :126): BINS = 36 in filterKeypoints (:352), 8 in SIFT (:631)
+template <int BINS>
+__device__ __forceinline__ int hist_bin(float deg) {
+    const float reductionCoeff = (float)BINS / 360.0f;  // :114
+    const int index = (int)(deg * reductionCoeff);      // :126
+    return min(max(index, 0), BINS - 1);
+}
+
+// cv::magnitude of one gradient: integer components, so the sum of squares is exact and the result is the correctly rounded
+// f32 square root (6 operations; tools/sqrt_check.hip) - the bare v_sqrt_f32 is not
+__device__ __forceinline__ float gradient_magnitude(float gx, float gy) {
+    const float xx = gx * gx, yy = gy * gy;
+    return sqrt_rn_small_nr(xx + yy);
+}
+
+// Plane `level` of octave o in frame f's pyramid block (g: OrientBatchGeom, kernels_orient_batch.hip.h, or SiftBatchGeom, kernels_sift.hip.h)
+template <class Geom>
+__device__ __forceinline__ const uint8_t* level_plane(const uint8_t* __restrict__ pyr, int f, size_t pframe, const Geom& g, int o, int level) {
+    return pyr + f * pframe + g.oct_off[o] + (size_t)level * g.rows[o] * g.pitch[o];
+}
+
 template <bool FMA>
 __global__ __launch_bounds__(256) void k_level_gradients(const uint8_t* __restrict__ g, int gpitch, int rows, int cols,
                                                           float* __restrict__ gx, float* __restrict__ gy,
@@ -297,10 +318,7 @@ __global__ __launch_bounds__(256) void k_level_gradients(const uint8_t* __restri
     const size_t o = (size_t)r * cols + c;
     if (gx) gx[o] = x;
     if (gy) gy[o] = y;
-    if (mag) {
-        const float xx = x * x, yy = y * y;
-        mag[o] = sqrt_rn_small_nr(xx + yy);  // IEEE-correct f32 square root (the bare v_sqrt_f32 is not)
-    }
+    if (mag) mag[o] = gradient_magnitude(x, y);
     if (orient) orient[o] = fast_atan2_deg<FMA>(y, x);
 }
 

@@ -11,10 +11,15 @@
 // s += k(c+i)*(S(+i) + S(-i)); histogram: row-major += per bin), so the result is the oracle's
 // bit for bit.  Peaks leave as a 36-bit mask per keypoint; kernels_compact.hip.h turns the masks
 // into the ordered SLAM::point list.
+//
+// The steps the three orientation kernels share - this one, k_orient_survivors (kernels_orient_batch.hip.h) and
+// k_orient_survivors_pk (kernels_orient_pk.hip.h) - are stated here once: the edge test, the gradient of a staged u8 patch,
+// magnitude_at, the symmetric column pass, the bin masks of a wave and the histogram / peak mask of a window.  The bin of an
+// angle, the magnitude of a gradient and the address of a level's plane, which SIFT needs too, stand in kernels_aux.hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kernels_generic.hip.h"
+#include "kernels_aux.hip.h"
 
 namespace vslam {
 
@@ -52,19 +57,80 @@ __device__ __forceinline__ float edge_response_u8(const uint8_t* __restrict__ G,
     return (tr * tr) / det;                                                               // :107
 }
 
-// Lane B of the wave receives the 64-bit mask of the lanes whose bin is B, for B = 0 .. OR_BINS - 1: one compare into VCC
-// and two v_writelane with an immediate lane select per bin (this compiler has no builtin for v_writelane; the wait
-// states between the compare and the reads of VCC are written out because the hazard recogniser does not look inside
-// inline asm).
-template <int B>
-__device__ __forceinline__ void bin_masks_to_lanes(int mybin, unsigned int& lo, unsigned int& hi) {
-    if constexpr (B < OR_BINS) {
-        asm volatile("v_cmp_eq_u32_e32 vcc, %2, %3\n\ts_nop 3\n\tv_writelane_b32 %0, vcc_lo, %2\n\tv_writelane_b32 %1, vcc_hi, %2"
-                     : "+v"(lo), "+v"(hi)
-                     : "n"(B), "v"(mybin)
-                     : "vcc");
-        bin_masks_to_lanes<B + 1>(mybin, lo, hi);
+// filterKeypoints' edge rejection (:331-335): the keypoint stays iff its response is below ((r + 1)^2) / r, r = 10
+__device__ __forceinline__ bool passes_edge_test(const uint8_t* __restrict__ G, int gpitch, int rows, int cols, int y, int x, int pad) {
+    const float r = 10.0f, threshold = ((r + 1.0f) * (r + 1.0f)) / r;  // :331-332
+    return edge_response_u8(G, gpitch, rows, cols, y, x, pad) < threshold;  // :335
+}
+
+// Sobel (ksize 1) gradient of an interior pixel from a staged u8 patch: c0 = the pixel's byte, pb = bytes per patch row
+__device__ __forceinline__ void patch_gradient(const uint8_t* c0, int pb, float& gx, float& gy) {
+    gx = (float)((int)c0[1] - (int)c0[-1]), gy = (float)((int)c0[pb] - (int)c0[-pb]);
+}
+
+// cv::magnitude of the level's Sobel gradients at one pixel (processGradients, GaussPyramid.cpp:65-104)
+__device__ __forceinline__ float magnitude_at(const uint8_t* __restrict__ G, int gpitch, int rows, int cols, int r, int c) {
+    float x, y;
+    gradient_at(G, gpitch, rows, cols, r, c, x, y);
+    return gradient_magnitude(x, y);
+}
+
+// Symmetric column pass of window pixel (i, j) over the row-filtered strip rb[16 + 2R][16], taps kl[2R + 1]:
+// s = k[R] * S(0); s += k[R + t] * (S(+t) + S(-t))
+template <bool FMA>
+__device__ __forceinline__ float column_pass_sym(const float* kl, const float* rb, int R, int i, int j) {
+    float s0 = kl[R] * rb[(i + R) * OR_WIN + j];
+#pragma unroll 4
+    for (int t = 1; t <= R; ++t) s0 = mad_f32<FMA>(kl[R + t], rb[(i + R + t) * OR_WIN + j] + rb[(i + R - t) * OR_WIN + j], s0);
+    return s0;
+}
+
+// Lane B of the wave gets the 64-bit mask of the lanes whose bin is B (bins 0..63) from the six ballots of the bin
+// index's bit planes: mask = AND_k (plane_k XOR (bit k of B ? 0 : ~0)).  12 + 22 instructions for the wave.
+// nsel[k] = the lane's own (bit k of lane ? 0 : ~0), formed once per kernel (bin_plane_selectors).
+__device__ __forceinline__ void bin_plane_selectors(int lane, unsigned int (&nsel)[6]) {
+#pragma unroll
+    for (int b = 0; b < 6; ++b) nsel[b] = ((lane >> b) & 1) ? 0u : ~0u;
+}
+__device__ __forceinline__ void bin_masks_from_planes(int mybin, const unsigned int (&nsel)[6], unsigned int& lo, unsigned int& hi) {
+    lo = hi = ~0u;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const unsigned long long plane = __ballot((mybin >> k) & 1);
+        lo &= (unsigned int)plane ^ nsel[k];
+        hi &= (unsigned int)(plane >> 32) ^ nsel[k];
     }
+}
+
+// A 256-thread workgroup's bin masks, binmask[bin][wave]: every wave ballots its 64 pixels (thread = window pixel, bin_of = its
+// histogram bin) and the bin's lane stores the wave's mask
+__device__ __forceinline__ void store_bin_masks(unsigned long long (*binmask)[4], int bin_of, const unsigned int (&nsel)[6]) {
+    unsigned int mlo, mhi;
+    bin_masks_from_planes(bin_of, nsel, mlo, mhi);
+    if ((threadIdx.x & 63) < OR_BINS) binmask[threadIdx.x & 63][threadIdx.x >> 6] = ((unsigned long long)mhi << 32) | mlo;
+}
+
+// Histogram and peaks of one window (:112-133, :352-366), by ONE wave, lane = bin: a bin's magnitudes are added in pixel order
+// (binmask[4 bin + w] = the pixels 64 w .. 64 w + 63 that fall into the bin; ascending bit = ascending pixel index), the 36 sums
+// sit in lanes 0..35, so the maximum and the peak test need no pass through LDS.  Returns the 36-bit mask of the peaks.
+__device__ __forceinline__ unsigned long long peak_mask(const unsigned long long* binmask, const float* mw, int lane) {
+    float h = 0.0f;
+    if (lane < OR_BINS) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            unsigned long long m = binmask[lane * 4 + w];
+            while (m) {
+                h += mw[64 * w + __builtin_ctzll(m)];
+                m &= m - 1;
+            }
+        }
+    }
+    float mx = lane < OR_BINS ? h : 0.0f;  // sums of non-negative weights: 0 is neutral, and bin 0 is among them
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    const float peakThreshold = mx * 0.8f;                 // :358
+    const bool peak = lane < OR_BINS && h > peakThreshold;  // :362
+    return __ballot(peak);
 }
 
 // grid = (keypoints), 256 threads, dynamic LDS = orient_lds_bytes(max R).  FMA: the filter's multiply-adds fused (mad_f32).
@@ -78,11 +144,7 @@ __global__ __launch_bounds__(256) void k_orient_keypoints(const vslam_point* __r
     const int q = blockIdx.x;
     const vslam_point kp = kps[q];
     const int x = kp.col, y = kp.row, level = kp.level;
-    if (threadIdx.x == 0) {
-        const float r = 10.0f, threshold = ((r + 1.0f) * (r + 1.0f)) / r;  // :331-332
-        const float response = edge_response_u8(lv.gauss[level], gpitch, rows, cols, y, x, kp.padding);
-        keep_s = response < threshold;  // :335
-    }
+    if (threadIdx.x == 0) keep_s = passes_edge_test(lv.gauss[level], gpitch, rows, cols, y, x, kp.padding);
     __syncthreads();
     if (!keep_s) {
         if (threadIdx.x == 0) masks[q] = 0ull;
@@ -111,44 +173,17 @@ __global__ __launch_bounds__(256) void k_orient_keypoints(const vslam_point* __r
         rb[it] = s0;
     }
     __syncthreads();
-    int bin_of;
+    unsigned int nsel[6];
+    bin_plane_selectors(threadIdx.x & 63, nsel);
     {
         const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
-        float s0 = kl[R] * rb[(i + R) * OR_WIN + j];
-#pragma unroll 4
-        for (int t = 1; t <= R; ++t) s0 = mad_f32<FMA>(kl[R + t], rb[(i + R + t) * OR_WIN + j] + rb[(i + R - t) * OR_WIN + j], s0);
-        mw[threadIdx.x] = s0;
-        const float reductionCoeff = (float)OR_BINS / 360.0f;  // :114
+        mw[threadIdx.x] = column_pass_sym<FMA>(kl, rb, R, i, j);
         const float o = lv.orient[level][(size_t)clampi(y + i - OR_PAD, 0, rows - 1) * cols + clampi(x + j - OR_PAD, 0, cols - 1)];
-        const int index = (int)(o * reductionCoeff);  // :126; fastAtan2 on integer gradients stays below 359.8
-        bin_of = min(max(index, 0), OR_BINS - 1);
-    }
-    // histogram (:112-133): a bin's magnitudes in pixel order.  Every wave ballots its 64 pixels bin by bin, the bin's
-    // lane then adds only its own pixels (ascending bit = ascending pixel index) - as in k_orient_survivors
-    {
-        unsigned int mlo = 0, mhi = 0;
-        bin_masks_to_lanes<0>(bin_of, mlo, mhi);
-        if ((threadIdx.x & 63) < OR_BINS) binmask[threadIdx.x & 63][threadIdx.x >> 6] = ((unsigned long long)mhi << 32) | mlo;
+        store_bin_masks(binmask, hist_bin<OR_BINS>(o), nsel);  // fastAtan2 on integer gradients stays below 359.8
     }
     __syncthreads();
     if (threadIdx.x < 64) {
-        float h = 0.0f;
-        if (threadIdx.x < OR_BINS) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                unsigned long long m = binmask[threadIdx.x][w];
-                while (m) {
-                    h += mw[64 * w + __builtin_ctzll(m)];
-                    m &= m - 1;
-                }
-            }
-        }
-        float mx = threadIdx.x < OR_BINS ? h : 0.0f;  // sums of non-negative weights: 0 is neutral
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        const float peakThreshold = mx * 0.8f;                          // :358
-        const bool peak = threadIdx.x < OR_BINS && h > peakThreshold;  // :362
-        const unsigned long long m = __ballot(peak);
+        const unsigned long long m = peak_mask(&binmask[0][0], mw, threadIdx.x);
         if (threadIdx.x == 0) masks[q] = m;
     }
 }

@@ -11,7 +11,7 @@
 //                         whole detection - so the (16+2R)^2 magnitude region the window's blur
 //                         reaches is formed in LDS from the Gaussian level (same f32 arithmetic:
 //                         exact integer gradients, correctly rounded sqrt), then row pass, symmetric
-//                         column pass, histogram and peak mask exactly as in the per-image kernel.
+//                         column pass, histogram and peak mask through the per-image kernel's own functions.
 //                         Regions that do not fit the LDS (the 300-tap kernels of octave 3, where
 //                         survivors are rare) take the magnitudes tap by tap instead.
 // The masks are compacted into SLAM::point{row, col, angle, 0, octave, level} records in list
@@ -49,9 +49,7 @@ __global__ __launch_bounds__(256) void k_edge_flags(const vslam_point* __restric
     if (i >= begin && i < end) {
         const vslam_point kp = pts[(size_t)f * cap + i];
         const int o = kp.octave;
-        const uint8_t* G = pyr + f * pframe + g.oct_off[o] + (size_t)kp.level * g.rows[o] * g.pitch[o];
-        const float r = 10.0f, threshold = ((r + 1.0f) * (r + 1.0f)) / r;  // :331-332
-        keep = edge_response_u8(G, g.pitch[o], g.rows[o], g.cols[o], kp.row, kp.col, kp.padding) < threshold;  // :335
+        keep = passes_edge_test(level_plane(pyr, f, pframe, g, o, kp.level), g.pitch[o], g.rows[o], g.cols[o], kp.row, kp.col, kp.padding);
     }
     const unsigned long long w = __ballot(keep);
     const unsigned int word = i >> 6;
@@ -65,14 +63,6 @@ __global__ __launch_bounds__(256) void k_edge_flags(const vslam_point* __restric
             *dst = w;
         }
     }
-}
-
-// cv::magnitude of the level's Sobel gradients at one pixel (processGradients, GaussPyramid.cpp:65-104)
-__device__ __forceinline__ float magnitude_at(const uint8_t* __restrict__ G, int gpitch, int rows, int cols, int r, int c) {
-    float x, y;
-    gradient_at(G, gpitch, rows, cols, r, c, x, y);
-    const float xx = x * x, yy = y * y;
-    return sqrt_rn_small_nr(xx + yy);  // correctly rounded f32 square root (6 operations; tools/sqrt_check.hip)
 }
 
 // The survivor list of a frame is in list order, i.e. octave by octave and, inside an octave, level by level
@@ -126,12 +116,14 @@ __global__ __launch_bounds__(256) void k_orient_survivors(const vslam_point* __r
     // the next survivor's record is fetched while the current one is processed (two dependent loads: index, record)
     vslam_point kp_next{};
     if (k_begin + blockIdx.x < k_end) kp_next = pts[(size_t)f * cap + surv[(size_t)f * scap + k_begin + blockIdx.x]];
+    unsigned int nsel[6];
+    bin_plane_selectors(threadIdx.x & 63, nsel);
     for (unsigned int k = k_begin + blockIdx.x; k < k_end; k += gridDim.x) {
         const vslam_point kp = kp_next;
         if (k + gridDim.x < k_end) kp_next = pts[(size_t)f * cap + surv[(size_t)f * scap + k + gridDim.x]];
         const int o = oct, level = kp.level, x = kp.col, y = kp.row;
         const int rows = g.rows[o], cols = g.cols[o], gpitch = g.pitch[o];
-        const uint8_t* __restrict__ G = pyr + f * pframe + g.oct_off[o] + (size_t)level * rows * gpitch;
+        const uint8_t* __restrict__ G = level_plane(pyr, f, pframe, g, o, level);
         const int kn = g.kn[o][level], R = kn >> 1;
         const float* __restrict__ kt = g.kern[o][level];
         const int prows = rows + 2 * OR_PAD, pcols = cols + 2 * OR_PAD;
@@ -176,10 +168,9 @@ __global__ __launch_bounds__(256) void k_orient_survivors(const vslam_point* __r
             int rr = (int)threadIdx.x / span, cc = (int)threadIdx.x - rr * span;
             int off = (rr + 1) * pb + (cc + 1);  // the region pixel inside the patch
             for (int it = threadIdx.x; it < span * span; it += 256) {
-                const uint8_t* c0 = Pb + off;
-                const float gx = (float)((int)c0[1] - (int)c0[-1]), gy = (float)((int)c0[pb] - (int)c0[-pb]);
-                const float xx = gx * gx, yy = gy * gy;
-                M[it] = sqrt_rn_small_nr(xx + yy);
+                float gx, gy;
+                patch_gradient(Pb + off, pb, gx, gy);
+                M[it] = gradient_magnitude(gx, gy);
                 cc += dr;
                 const bool wrap = cc >= span;
                 cc -= wrap ? span : 0;
@@ -211,53 +202,23 @@ __global__ __launch_bounds__(256) void k_orient_survivors(const vslam_point* __r
             }
         }
         __syncthreads();
-        int bin_of;
         {
             const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
-            float s0 = kl[R] * rb[(i + R) * OR_WIN + j];
-#pragma unroll 4
-            for (int t = 1; t <= R; ++t) s0 = mad_f32<FMA>(kl[R + t], rb[(i + R + t) * OR_WIN + j] + rb[(i + R - t) * OR_WIN + j], s0);
-            mw[threadIdx.x] = s0;
+            mw[threadIdx.x] = column_pass_sym<FMA>(kl, rb, R, i, j);
             float gx, gy;
-            if (patch) {  // interior survivor: the window's pixels and their Sobel neighbours are in the staged patch
-                const uint8_t* c0 = reinterpret_cast<const uint8_t*>(Pw) + (px0 & 3) + (i + R + 1) * (4 * pdw) + (j + R + 1);
-                gx = (float)((int)c0[1] - (int)c0[-1]), gy = (float)((int)c0[4 * pdw] - (int)c0[-4 * pdw]);
-            } else {
+            if (patch)  // interior survivor: the window's pixels and their Sobel neighbours are in the staged patch
+                patch_gradient(reinterpret_cast<const uint8_t*>(Pw) + (px0 & 3) + (i + R + 1) * (4 * pdw) + (j + R + 1), 4 * pdw, gx, gy);
+            else
                 gradient_at(G, gpitch, rows, cols, clampi(y + i - OR_PAD, 0, rows - 1), clampi(x + j - OR_PAD, 0, cols - 1), gx, gy);
-            }
-            const float reductionCoeff = (float)OR_BINS / 360.0f;            // :114
-            const int index = (int)(fast_atan2_deg(gy, gx) * reductionCoeff);  // :126
-            bin_of = min(max(index, 0), OR_BINS - 1);
-        }
-        // The histogram (:112-133) adds a bin's magnitudes in pixel order; a lane per bin walking all 256 pixels
-        // (round 2) kept one wave busy for 256 dependent iterations while three waited.  Each wave now ballots
-        // its 64 pixels bin by bin (ascending pixel index inside a mask = the reference's order), and the bin's
-        // lane adds only its own pixels: a handful instead of 256.
-        {
-            unsigned int mlo = 0, mhi = 0;
-            bin_masks_to_lanes<0>(bin_of, mlo, mhi);
-            if ((threadIdx.x & 63) < OR_BINS) binmask[threadIdx.x & 63][threadIdx.x >> 6] = ((unsigned long long)mhi << 32) | mlo;
+            // The histogram (:112-133) adds a bin's magnitudes in pixel order; a lane per bin walking all 256 pixels
+            // (round 2) kept one wave busy for 256 dependent iterations while three waited.  Each wave now ballots
+            // its 64 pixels bin by bin (ascending pixel index inside a mask = the reference's order), and the bin's
+            // lane adds only its own pixels: a handful instead of 256.
+            store_bin_masks(binmask, hist_bin<OR_BINS>(fast_atan2_deg(gy, gx)), nsel);
         }
         __syncthreads();
         if (threadIdx.x < 64) {
-            float h = 0.0f;
-            if (threadIdx.x < OR_BINS) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    unsigned long long m = binmask[threadIdx.x][w];
-                    while (m) {
-                        h += mw[64 * w + __builtin_ctzll(m)];
-                        m &= m - 1;
-                    }
-                }
-            }
-            // the 36 sums sit in lanes 0..35 of this wave: maximum and peak test without another pass through LDS
-            float mx = threadIdx.x < OR_BINS ? h : 0.0f;  // sums of non-negative weights: 0 is neutral, and bin 0 is among them
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            const float peakThreshold = mx * 0.8f;                          // :358
-            const bool peak = threadIdx.x < OR_BINS && h > peakThreshold;  // :362
-            const unsigned long long m = __ballot(peak);
+            const unsigned long long m = peak_mask(&binmask[0][0], mw, threadIdx.x);
             if (threadIdx.x == 0) masks[(size_t)f * scap + k] = m;
         }
     }

@@ -24,6 +24,9 @@
 //
 // Survivors whose region or its Sobel neighbours touch the image border (a strip of R + 9 pixels) take their magnitudes
 // and window gradients pixel by pixel from the image with the reference's border rules, then the same passes.
+//
+// The bin of an angle, the gradient of a patch pixel, the bin masks (bin_masks_from_planes) and the histogram / peak mask are
+// the functions of kernels_orient.hip.h and kernels_aux.hip.h that the other two orientation kernels call; the packed passes are this file's own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -78,20 +81,6 @@ __device__ __forceinline__ vslam_f2 pk_cross_diff(vslam_f2 x, vslam_f2 y) {
 }
 __device__ __forceinline__ float ubyte_f32(uint32_t w, int b) { return (float)((w >> (8 * b)) & 0xffu); }
 
-// Lane B of the wave gets the 64-bit mask of the lanes whose bin is B (bins 0..63) from the six ballots of the bin
-// index's bit planes: mask = AND_k (plane_k XOR (bit k of B ? 0 : ~0)).  12 + 22 instructions for the wave, where a
-// compare and two v_writelane per bin (bin_masks_to_lanes, kernels_orient.hip.h) took 108.  nsel[k] = the lane's own
-// (bit k of lane ? 0 : ~0), formed once per kernel.
-__device__ __forceinline__ void bin_masks_from_planes(int mybin, const unsigned int (&nsel)[6], unsigned int& lo, unsigned int& hi) {
-    lo = hi = ~0u;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const unsigned long long plane = __ballot((mybin >> k) & 1);
-        lo &= (unsigned int)plane ^ nsel[k];
-        hi &= (unsigned int)(plane >> 32) ^ nsel[k];
-    }
-}
-
 // Device layout of the padded taps of one (octave, level) (written by get_orient_taps, vslam_hip.hip):
 //   [0, n)            the taps themselves (k_orient_survivors, SIFT)
 //   row  = A .. :     0 0 0 k[0] .. k[n-1] 0 0 ..    A = (n + 3) & ~3, length NR = ((n + 6) & ~3) + 8
@@ -140,11 +129,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
                        k_end = ranges[(size_t)f * OR_RANGE_STRIDE + OR_LEVEL_RANGES + 4 * oct + level];
     const int rows = g.rows[o], cols = g.cols[o], gpitch = g.pitch[o];
     const int prows = rows + 2 * OR_PAD, pcols = cols + 2 * OR_PAD;
-    const uint8_t* __restrict__ G = pyr + f * pframe + g.oct_off[o] + (size_t)level * rows * gpitch;
+    const uint8_t* __restrict__ G = level_plane(pyr, f, pframe, g, o, level);
     const float* __restrict__ kt = g.kern[o][level];
     unsigned int nsel[6];
-#pragma unroll
-    for (int b = 0; b < 6; ++b) nsel[b] = ((lane >> b) & 1) ? 0u : ~0u;
+    bin_plane_selectors(lane, nsel);
     // The patch of a survivor is fetched one survivor ahead, into registers of wave 1 (lane = patch row): its load round
     // trip - a good part of a survivor's whole time - runs beside the previous survivor's passes.  So the records are
     // fetched two ahead.
@@ -196,23 +184,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             }
             if (k + gridDim.x < k_end) fetch_patch(geo_of(rec0));
         } else if (has_prev) {
-            float h = 0.0f;
-            if (lane < OR_BINS) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    unsigned long long m = binmask[lane * 4 + w];
-                    while (m) {
-                        h += mw[64 * w + __builtin_ctzll(m)];
-                        m &= m - 1;
-                    }
-                }
-            }
-            float mx = lane < OR_BINS ? h : 0.0f;  // sums of non-negative weights: 0 is neutral
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            const float peakThreshold = mx * 0.8f;                 // :358
-            const bool peak = lane < OR_BINS && h > peakThreshold;  // :362
-            const unsigned long long m = __ballot(peak);
+            const unsigned long long m = peak_mask(binmask, mw, lane);
             if (lane == 0) masks[(size_t)f * scap + k_prev] = m;
         }
         if (!have) break;
@@ -261,15 +233,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
             for (int half = 0; half < 2; ++half) {
                 const int p = tid + 128 * half, i = p >> 4, j = p & 15;
                 float gx, gy;
-                if (interior) {
-                    const uint8_t* c0 = Pb + (i + R + 1) * pb + (j + R + 1);
-                    gx = (float)((int)c0[1] - (int)c0[-1]), gy = (float)((int)c0[pb] - (int)c0[-pb]);
-                } else {
+                if (interior)
+                    patch_gradient(Pb + (i + R + 1) * pb + (j + R + 1), pb, gx, gy);
+                else
                     gradient_at(G, gpitch, rows, cols, clampi(y + i - OR_PAD, 0, rows - 1), clampi(x + j - OR_PAD, 0, cols - 1), gx, gy);
-                }
-                const float reductionCoeff = (float)OR_BINS / 360.0f;            // :114
-                const int index = (int)(fast_atan2_deg(gy, gx) * reductionCoeff);  // :126
-                const int bin_of = min(max(index, 0), OR_BINS - 1);
+                const int bin_of = hist_bin<OR_BINS>(fast_atan2_deg(gy, gx));
                 unsigned int mlo, mhi;
                 bin_masks_from_planes(bin_of, nsel, mlo, mhi);
                 if (lane < OR_BINS) binmask[lane * 4 + wave + 2 * half] = ((unsigned long long)mhi << 32) | mlo;  // pixels 64 (wave + 2 half) ..

@@ -92,8 +92,7 @@ __device__ __forceinline__ void sift_one_keypoint(SiftShared& sh, const vslam_po
             const int r = clampi(prow - SIFT_PAD, 0, rows - 1), c = clampi(pcol - SIFT_PAD, 0, cols - 1);  // padOctave(20): replicate
             float gx, gy;
             gradient_at(G, gpitch, rows, cols, r, c, gx, gy);
-            const float xx = gx * gx, yy = gy * gy;
-            mval = sqrt_rn_small_nr(xx + yy);            // cv::magnitude, correctly rounded (kernels_generic.hip.h)
+            mval = gradient_magnitude(gx, gy);           // cv::magnitude, correctly rounded (kernels_aux.hip.h)
             sh.mag[t] = mval;
             o = fast_atan2_deg(gy, gx);                  // cv::phase(..., true)
             if ((kn >> 1) <= SIFT_EXT_R) {
@@ -123,11 +122,7 @@ __device__ __forceinline__ void sift_one_keypoint(SiftShared& sh, const vslam_po
         __syncthreads();
         return;
     }
-    {
-        const float reductionCoeff = (float)8 / 360.0f;  // :114 with size = 8 (:631)
-        const int index = (int)(o * reductionCoeff);     // :126
-        sh.bin[t] = (uint8_t)min(max(index, 0), 7);
-    }
+    sh.bin[t] = (uint8_t)hist_bin<8>(o);  // size = 8 (:631)
     const int R = kn >> 1;
     if (R <= SIFT_EXT_R) {
         // The ROI is 16 wide and the kernels 25 ... 77 taps: the reflect-101 extension of a row is the triangle wave of
@@ -288,7 +283,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const vslam_point kp = kp_next;
         if (q + gridDim.x < n) kp_next = oriented[(size_t)f * cap + q + gridDim.x];
         const int o = __builtin_amdgcn_readfirstlane(kp.octave), level = __builtin_amdgcn_readfirstlane(kp.level);  // one record per workgroup: scalar
-        const uint8_t* G = pyr + f * pframe + g.oct_off[o] + (size_t)level * g.rows[o] * g.pitch[o];
+        const uint8_t* G = level_plane(pyr, f, pframe, g, o, level);
         const unsigned int b = (unsigned int)__builtin_amdgcn_readfirstlane(kp.value) / 10u;
         sift_one_keypoint<FMA>(sh, kp, g.cs36[b < 36u ? b : 0u], G, g.pitch[o], g.rows[o], g.cols[o], g.kern[o][level], g.kn[o][level],
                           desc + ((size_t)f * cap + q) * SIFT_DESC, defined ? defined + (size_t)f * cap + q : nullptr);

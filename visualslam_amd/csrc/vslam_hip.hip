@@ -792,6 +792,75 @@ static int read_list(vslam_ctx* c, const unsigned int* d_count, const R* d_list,
     return VSLAM_OK;
 }
 
+// ---------------------------------------------------------------- what filterKeypoints and SIFT share, per image and batched
+
+// Device copy of getGaussianKernel(n, sigma, CV_32F) for the blur of filterKeypoints and SIFT (sigma = 1.5 * sigma(o, l)), cached
+// per context by (sigma, n): the per-image entry points and the batched path read the same tables.  `what`: the caller's
+// prefix in error texts.
+static int get_orient_taps(vslam_ctx* c, double sigma, const char* what, const float** out, int* n_out) {
+    const int n = gauss_ksize_f32(sigma);
+    if (n <= 0 || n > (1 << 20)) return fail(c, VSLAM_ERR_INVALID, std::string(what) + ": bad blur kernel");  // before n sizes the table
+    *n_out = n;
+    return get_table(c, kTableOrient, sigma, n, what, 4 * (size_t)orient_taps_pk_floats(n), [&](void* host) -> int {
+        std::vector<float> k;
+        if (!gauss_kernel_f32(n, sigma, k)) return fail(c, VSLAM_ERR_INVALID, std::string(what) + ": bad blur kernel");
+        float* t = static_cast<float*>(host);
+        std::copy(k.begin(), k.end(), t);
+        // behind the taps: the zero-padded row / column forms k_orient_survivors_pk reads through scalar loads
+        for (int i = 0; i < n; ++i) t[(size_t)orient_taps_row_off(n) + 3 + i] = t[(size_t)i];
+        for (int i = 1; i <= n / 2; ++i) t[(size_t)orient_taps_col_off(n) + i - 1] = t[(size_t)(n / 2 + i)];
+        return VSLAM_OK;
+    }, out);
+}
+
+// What the per-image filterKeypoints and SIFT share: the keypoints' range checks (coordinates may leave the octave by
+// `margin`; what the reference would throw on - vector::at(level), a Rect outside the padded Mat - or could not have
+// produced is an error here), and for every level a keypoint uses its Gaussian plane and the cached taps of
+// sigma = 1.5 * sigma(octave, level) (Diff_of_Gauss.cpp:346, :616).  Levels no keypoint uses stay null / 0.
+struct KeypointLevels {
+    bool used[VSLAM_NUM_LEVELS] = {};
+    const uint8_t* gauss[VSLAM_NUM_LEVELS] = {};
+    const float* kern[VSLAM_NUM_LEVELS] = {};
+    int kn[VSLAM_NUM_LEVELS] = {};
+    template <class Levels>  // OrientLevels, SiftLevels
+    void fill(Levels& lv) const {
+        for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) lv.gauss[l] = gauss[l], lv.kern[l] = kern[l], lv.kn[l] = kn[l];
+    }
+};
+static int keypoint_levels(vslam_ctx* c, const vslam_pyramid* py, int octave, const vslam_point* kps, size_t n, int margin, const char* what,
+                           KeypointLevels& kl) {
+    const int rows = py->layout.rows[octave], cols = py->layout.cols[octave], pitch = py->layout.pitch[octave];
+    for (size_t i = 0; i < n; ++i) {
+        const vslam_point& k = kps[i];
+        if (k.level < 0 || k.level >= VSLAM_NUM_LEVELS || k.octave != octave || k.col < -margin || k.row < -margin || k.col > cols + margin ||
+            k.row > rows + margin)
+            return fail(c, VSLAM_ERR_RANGE, std::string(what) + ": keypoint outside the octave's data");
+        kl.used[k.level] = true;
+    }
+    for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
+        if (!kl.used[l]) continue;
+        kl.gauss[l] = py->d_block + py->layout.octave_offset[octave] + (size_t)l * rows * pitch;
+        TRY(get_orient_taps(c, 1.5 * py->info.sigma[octave][l], what, &kl.kern[l], &kl.kn[l]));
+    }
+    return VSLAM_OK;
+}
+
+// What OrientBatchGeom and SiftBatchGeom share, from (p, L): every octave's rows / cols / pitch / oct_off and, for the levels
+// initialKeypointDetection produces (1 .. 3, Diff_of_Gauss.cpp:264), the taps of sigma = 1.5 * sigma(o, l) (:346, :616).
+// Every other field is zeroed.
+template <class Geom>
+static int fill_batch_geom(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, Geom& g) {
+    std::memset(&g, 0, sizeof(g));
+    for (int o = 0; o < L.n_octaves; ++o) {
+        g.rows[o] = L.rows[o];
+        g.cols[o] = L.cols[o];
+        g.pitch[o] = L.pitch[o];
+        g.oct_off[o] = L.octave_offset[o];
+        for (int l = 1; l <= 3; ++l) TRY(get_orient_taps(c, 1.5 * sigma_at(p.sigma0, o, l), "filterKeypoints", &g.kern[o][l], &g.kn[o][l]));
+    }
+    return VSLAM_OK;
+}
+
 
 extern "C" {
 
@@ -1211,10 +1280,7 @@ int vslam_pyramid_get_gradients(const vslam_pyramid* py, int octave, int level, 
         if (!host[i]) dev[i] = nullptr;
     const int pitch = py->layout.pitch[octave];
     const uint8_t* g = py->d_block + py->layout.octave_offset[octave] + (size_t)level * rows * pitch;
-    if (c->f32_fused)
-        LAUNCH(c, "k_level_gradients", k_level_gradients<true>, grid_rows(cols, rows), dim3(256), g, pitch, rows, cols, dev[0], dev[1], dev[2], dev[3]);
-    else
-        LAUNCH(c, "k_level_gradients", k_level_gradients<false>, grid_rows(cols, rows), dim3(256), g, pitch, rows, cols, dev[0], dev[1], dev[2], dev[3]);
+    LAUNCH(c, "k_level_gradients", F32_KERNEL(c, k_level_gradients), grid_rows(cols, rows), dim3(256), g, pitch, rows, cols, dev[0], dev[1], dev[2], dev[3]);
     for (int i = 0; i < 4; ++i)
         if (host[i]) TRY(d2h(c, host[i], dst_step, dev[i], 4 * (size_t)cols, 4 * (size_t)cols, rows));
     return vslam_ctx_sync(c);
@@ -1326,55 +1392,35 @@ int vslam_filter_keypoints(vslam_ctx* c, const vslam_pyramid* py, int octave, co
     if (n == 0) return VSLAM_OK;
     const int rows = py->layout.rows[octave], cols = py->layout.cols[octave], pitch = py->layout.pitch[octave];
     const size_t P = (size_t)rows * cols;  // dense f32 scratch images
-    // what the reference would throw on (vector::at, Rect outside the padded Mat) is an error here
-    bool used[VSLAM_NUM_LEVELS] = {};
-    for (size_t i = 0; i < n; ++i) {
-        const vslam_point& k = kps[i];
-        if (k.level < 0 || k.level >= VSLAM_NUM_LEVELS || k.col < 0 || k.row < 0 || k.col > cols || k.row > rows || k.octave != octave)
-            return fail(c, VSLAM_ERR_RANGE, "filterKeypoints: keypoint outside the octave's data");
-        used[k.level] = true;
-    }
-    std::vector<float> taps[VSLAM_NUM_LEVELS];
+    KeypointLevels kl;
+    TRY(keypoint_levels(c, py, octave, kps, n, 0, "filterKeypoints", kl));
     int max_r = 0;
-    size_t tap_elems = 0;
-    for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
-        if (!used[l]) continue;
-        const double sigma = 1.5 * py->info.sigma[octave][l];  // Diff_of_Gauss.cpp:346
-        if (!gauss_kernel_f32(gauss_ksize_f32(sigma), sigma, taps[l])) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");
-        max_r = std::max(max_r, (int)taps[l].size() / 2);
-        tap_elems += align_up(taps[l].size(), 64);
-    }
+    for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) max_r = std::max(max_r, kl.kn[l] / 2);
     const size_t lds = orient_lds_bytes(max_r);
     if (lds > 150 * 1024) return fail(c, VSLAM_ERR_UNSUPPORTED, "filterKeypoints: blur kernel too wide for the LDS strip");
     const unsigned int ocap = (unsigned int)std::min<size_t>(cap, 0x7fffffff);
     vslam_point *d_kps, *d_out;
     unsigned long long* d_masks;
     unsigned int *d_n, *d_cws;
-    float *d_taps, *d_mag[VSLAM_NUM_LEVELS], *d_ori[VSLAM_NUM_LEVELS];
+    float *d_mag[VSLAM_NUM_LEVELS], *d_ori[VSLAM_NUM_LEVELS];
     WsPlan ws;
-    ws.add(d_kps, n), ws.add(d_masks, n), ws.add(d_out, ocap), ws.add(d_n, 1), ws.add(d_cws, compaction_ws_elems(n, 1)), ws.add(d_taps, tap_elems);
+    ws.add(d_kps, n), ws.add(d_masks, n), ws.add(d_out, ocap), ws.add(d_n, 1), ws.add(d_cws, compaction_ws_elems(n, 1));
     for (int l = 0; l < VSLAM_NUM_LEVELS; ++l)
-        if (used[l]) ws.add(d_mag[l], P), ws.add(d_ori[l], P);
+        if (kl.used[l]) ws.add(d_mag[l], P), ws.add(d_ori[l], P);
     TRY(ws.commit(c));
     OrientLevels lv{};
+    kl.fill(lv);
     HIPCHK(c, hipMemcpyAsync(d_kps, kps, sizeof(vslam_point) * n, hipMemcpyHostToDevice, c->stream));
-    size_t toff = 0;
     for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
-        if (!used[l]) continue;
-        const uint8_t* g = py->d_block + py->layout.octave_offset[octave] + (size_t)l * rows * pitch;
+        if (!kl.used[l]) continue;
         // processGradients for the level (GaussPyramid.cpp:65-104): magnitude and orientation only
         // (the orientation image is only BINNED here: no bin depends on the arctangent's variant, kernels_aux.hip.h)
-        LAUNCH(c, "k_level_gradients", k_level_gradients<false>, grid_rows(cols, rows), dim3(256), g, pitch, rows, cols, (float*)nullptr,
+        LAUNCH(c, "k_level_gradients", k_level_gradients<false>, grid_rows(cols, rows), dim3(256), kl.gauss[l], pitch, rows, cols, (float*)nullptr,
                (float*)nullptr, d_mag[l], d_ori[l]);
-        HIPCHK(c, hipMemcpyAsync(d_taps + toff, taps[l].data(), 4 * taps[l].size(), hipMemcpyHostToDevice, c->stream));
-        lv.gauss[l] = g;
         lv.mag[l] = d_mag[l];
         lv.orient[l] = d_ori[l];
-        lv.kern[l] = d_taps + toff;
-        lv.kn[l] = (int)taps[l].size();
-        toff += align_up(taps[l].size(), 64);
     }
-    const auto k_orient = c->f32_fused ? k_orient_keypoints<true> : k_orient_keypoints<false>;
+    const auto k_orient = F32_KERNEL(c, k_orient_keypoints);
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(k_orient)));
     LAUNCH_ON(c, "k_orient_keypoints", -1, c->stream, lds, k_orient, dim3((unsigned)n), dim3(256), d_kps, (int)n, lv, pitch, rows, cols, d_masks);
     OrientEntries ent{d_masks, d_kps, n, d_out};
@@ -1390,48 +1436,22 @@ int vslam_sift_descriptors(vslam_ctx* c, const vslam_pyramid* py, int octave, co
     ARGCHK(c, n <= 0x7fffffff / 128, "SIFT: too many keypoints");
     if (n == 0) return VSLAM_OK;
     const int rows = py->layout.rows[octave], cols = py->layout.cols[octave], pitch = py->layout.pitch[octave];
-    bool used[VSLAM_NUM_LEVELS] = {};
+    KeypointLevels kl;
+    TRY(keypoint_levels(c, py, octave, kps, n, SIFT_PAD, "SIFT", kl));
     std::vector<float2> cs(n);
-    for (size_t i = 0; i < n; ++i) {
-        const vslam_point& k = kps[i];
-        // what the reference would throw on (vector::at(level)) or could not have produced is an error here
-        if (k.level < 0 || k.level >= VSLAM_NUM_LEVELS || k.octave != octave || k.col < -SIFT_PAD || k.row < -SIFT_PAD ||
-            k.col > cols + SIFT_PAD || k.row > rows + SIFT_PAD)
-            return fail(c, VSLAM_ERR_RANGE, "SIFT: keypoint outside the octave's data");
-        used[k.level] = true;
-        vslam_cos_sin_deg((float)k.value, &cs[i].x, &cs[i].y);  // keypoint.value holds the angle in degrees (:594)
-    }
-    std::vector<float> taps[VSLAM_NUM_LEVELS];
-    size_t tap_elems = 0;
-    for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
-        if (!used[l]) continue;
-        const double sigma = 1.5 * py->info.sigma[octave][l];  // Diff_of_Gauss.cpp:616
-        if (!gauss_kernel_f32(gauss_ksize_f32(sigma), sigma, taps[l])) return fail(c, VSLAM_ERR_INVALID, "SIFT: bad blur kernel");
-        tap_elems += align_up(taps[l].size(), 64);
-    }
+    for (size_t i = 0; i < n; ++i) vslam_cos_sin_deg((float)kps[i].value, &cs[i].x, &cs[i].y);  // keypoint.value holds the angle in degrees (:594)
     vslam_point* d_kps;
     float2* d_cs;
-    float *d_desc, *d_taps;
+    float* d_desc;
     uint8_t* d_def;
     WsPlan ws;
-    ws.add(d_kps, n), ws.add(d_cs, n), ws.add(d_desc, 128 * n), ws.add(d_def, n), ws.add(d_taps, tap_elems);
+    ws.add(d_kps, n), ws.add(d_cs, n), ws.add(d_desc, 128 * n), ws.add(d_def, n);
     TRY(ws.commit(c));
     HIPCHK(c, hipMemcpyAsync(d_kps, kps, sizeof(vslam_point) * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_cs, cs.data(), sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
     SiftLevels lv{};
-    size_t toff = 0;
-    for (int l = 0; l < VSLAM_NUM_LEVELS; ++l) {
-        if (!used[l]) continue;
-        HIPCHK(c, hipMemcpyAsync(d_taps + toff, taps[l].data(), 4 * taps[l].size(), hipMemcpyHostToDevice, c->stream));
-        lv.gauss[l] = py->d_block + py->layout.octave_offset[octave] + (size_t)l * rows * pitch;
-        lv.kern[l] = d_taps + toff;
-        lv.kn[l] = (int)taps[l].size();
-        toff += align_up(taps[l].size(), 64);
-    }
-    if (c->f32_fused)
-        LAUNCH(c, "k_sift_descriptors", k_sift_descriptors<true>, dim3((unsigned)n), dim3(256), d_kps, d_cs, (int)n, lv, pitch, rows, cols, d_desc, d_def);
-    else
-        LAUNCH(c, "k_sift_descriptors", k_sift_descriptors<false>, dim3((unsigned)n), dim3(256), d_kps, d_cs, (int)n, lv, pitch, rows, cols, d_desc, d_def);
+    kl.fill(lv);
+    LAUNCH(c, "k_sift_descriptors", F32_KERNEL(c, k_sift_descriptors), dim3((unsigned)n), dim3(256), d_kps, d_cs, (int)n, lv, pitch, rows, cols, d_desc, d_def);
     std::vector<uint8_t> h_def(n);
     HIPCHK(c, hipMemcpyAsync(desc, d_desc, sizeof(float) * 128 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_def.data(), d_def, n, hipMemcpyDeviceToHost, c->stream));
@@ -1478,23 +1498,6 @@ int vslam_structure_matrix_windows(vslam_ctx* c, const float* gx_windows, const 
 
 // ------------------------------------------------------------- device-resident batched path
 
-// Device copy of getGaussianKernel(n, sigma, CV_32F) for the orientation blur, cached per context.
-static int get_orient_taps(vslam_ctx* c, double sigma, const float** out, int* n_out) {
-    const int n = gauss_ksize_f32(sigma);
-    if (n <= 0 || n > (1 << 20)) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");  // before n sizes the table
-    *n_out = n;
-    return get_table(c, kTableOrient, sigma, n, "filterKeypoints", 4 * (size_t)orient_taps_pk_floats(n), [&](void* host) -> int {
-        std::vector<float> k;
-        if (!gauss_kernel_f32(n, sigma, k)) return fail(c, VSLAM_ERR_INVALID, "filterKeypoints: bad blur kernel");
-        float* t = static_cast<float*>(host);
-        std::copy(k.begin(), k.end(), t);
-        // behind the taps: the zero-padded row / column forms k_orient_survivors_pk reads through scalar loads
-        for (int i = 0; i < n; ++i) t[(size_t)orient_taps_row_off(n) + 3 + i] = t[(size_t)i];
-        for (int i = 1; i <= n / 2; ++i) t[(size_t)orient_taps_col_off(n) + i - 1] = t[(size_t)(n / 2 + i)];
-        return VSLAM_OK;
-    }, out);
-}
-
 struct OrientScratch {
     unsigned long long* flags = nullptr;  // [nf][fwords] edge-test ballots
     unsigned int* surv = nullptr;         // [nf][scap] surviving record indices
@@ -1527,17 +1530,12 @@ struct OrientPlan {
 };
 static int make_orient_plan(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, OrientPlan& pl) {
     OrientBatchGeom& g = pl.g;
-    std::memset(&g, 0, sizeof(g));
+    TRY(fill_batch_geom(c, p, L, g));
     g.n_oct = L.n_octaves;
     constexpr int kBigLds = 36 * 1024;  // floats: 144 KB
     for (int o = 0; o < L.n_octaves; ++o) {
-        g.rows[o] = L.rows[o];
-        g.cols[o] = L.cols[o];
-        g.pitch[o] = L.pitch[o];
-        g.oct_off[o] = L.octave_offset[o];
         int worst = 0, strip = 0;
-        for (int l = 1; l <= 3; ++l) {  // the levels initialKeypointDetection produces (Diff_of_Gauss.cpp:264)
-            TRY(get_orient_taps(c, 1.5 * sigma_at(p.sigma0, o, l), &g.kern[o][l], &g.kn[o][l]));  // :346
+        for (int l = 1; l <= 3; ++l) {
             const int span = OR_WIN + 2 * (g.kn[o][l] / 2);
             // maps + taps + strip + region + the u8 patch of interior survivors (k_orient_survivors)
             worst = std::max(worst, 3 * span + span * OR_WIN + span * span + (span + 2) * ((span + 8) >> 2));
@@ -1587,7 +1585,7 @@ static int enqueue_orient_batch(vslam_ctx* c, const vslam_params& p, const vslam
     SurvivorEntries se{s.flags, fw, s.surv};
     TRY(enqueue_compaction(c, se, fw, nf, s.cws, (unsigned int)scap, s.scounts, 0));
     LAUNCH(c, "k_survivor_ranges", k_survivor_ranges, dim3(nf), dim3(128), points, p.dog_cap, s.surv, s.scounts, (unsigned int)scap, L.n_octaves, s.ranges);
-    const auto k_surv = c->f32_fused ? k_orient_survivors<true> : k_orient_survivors<false>;
+    const auto k_surv = F32_KERNEL(c, k_orient_survivors);
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(k_surv)));
     const int gwg = (int)std::min<long>(1024, std::max<long>(16, 8192 / nf));
     // The launches below are independent (each takes its own survivors, each writes its own mask words) and every one ends
@@ -1646,23 +1644,12 @@ static int enqueue_orient_batch(vslam_ctx* c, const vslam_params& p, const vslam
 static int enqueue_sift_batch(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, int nf, const uint8_t* pyr, size_t pframe,
                               const vslam_point* oriented, const unsigned int* ocounts, float* desc, uint8_t* defined) {
     SiftBatchGeom g;
-    std::memset(&g, 0, sizeof(g));
-    for (int o = 0; o < L.n_octaves; ++o) {
-        g.rows[o] = L.rows[o];
-        g.cols[o] = L.cols[o];
-        g.pitch[o] = L.pitch[o];
-        g.oct_off[o] = L.octave_offset[o];
-        for (int l = 1; l <= 3; ++l)  // the levels initialKeypointDetection produces; same taps as the orientation blur
-            TRY(get_orient_taps(c, 1.5 * sigma_at(p.sigma0, o, l), &g.kern[o][l], &g.kn[o][l]));  // Diff_of_Gauss.cpp:616
-    }
+    TRY(fill_batch_geom(c, p, L, g));  // same taps as the orientation blur
     for (int b = 0; b < 36; ++b) vslam_cos_sin_deg((float)(10 * b), &g.cs36[b].x, &g.cs36[b].y);  // host libm, like the reference
     // 8 x 32 workgroups per frame at 256 frames (~120 points each on a dense frame): with 32 the launch ended on a tail of
     // half-empty CUs (11.3 ms per 256-frame step against 10.1)
     const int gwg = 8 * (int)std::min<long>(1024, std::max<long>(16, 8192 / nf));
-    if (c->f32_fused)
-        LAUNCH(c, "k_sift_descriptors", k_sift_descriptors_batch<true>, dim3(gwg, nf), dim3(256), oriented, ocounts, p.oriented_cap, pyr, pframe, g, desc, defined);
-    else
-        LAUNCH(c, "k_sift_descriptors", k_sift_descriptors_batch<false>, dim3(gwg, nf), dim3(256), oriented, ocounts, p.oriented_cap, pyr, pframe, g, desc, defined);
+    LAUNCH(c, "k_sift_descriptors", F32_KERNEL(c, k_sift_descriptors_batch), dim3(gwg, nf), dim3(256), oriented, ocounts, p.oriented_cap, pyr, pframe, g, desc, defined);
     return VSLAM_OK;
 }
 

@@ -18,6 +18,8 @@
     } while (0)
 // ... on the context stream, no dynamic LDS, tagged with the octave being enqueued.
 #define LAUNCH(ctx, name, kern, grid, block, ...) LAUNCH_ON(ctx, name, (ctx)->launch_tag, (ctx)->stream, 0, kern, grid, block, __VA_ARGS__)
+// The instantiation of a `template <bool FMA>` kernel (mad_f32, kernels_aux.hip.h) that the context's f32_fused setting asks for.
+#define F32_KERNEL(ctx, kern) ((ctx)->f32_fused ? kern<true> : kern<false>)
 
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -56,7 +58,7 @@ class WsPlan {
         void (*set)(void*, char*);     // stores a T* there
         size_t off;
     };
-    static constexpr int kMaxSlots = 32;  // the most any entry point asks for is 18 (vslam_filter_keypoints)
+    static constexpr int kMaxSlots = 32;  // the most any entry point asks for is 17 (vslam_filter_keypoints)
     Slot slots[kMaxSlots];
     int n = 0;
     size_t total = 0;
