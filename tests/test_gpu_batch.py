@@ -60,6 +60,32 @@ def run_batch(ctx, torch, frames_np, with_nms2=True, **pkw):
     return p, L, {k: (v.cpu().numpy() if v is not None else None) for k, v in o.items()}
 
 
+def check_oriented_frame(p, out, f, want, all_pts, n_oct):
+    """The oriented-point and descriptor outputs of frame f against the oracle pyramid `want`; all_pts[o] = the oracle's
+    keypoint list of octave o.  out[k][f] = frame f's slice of output k (tests/test_gpu_orient_steady.py brings back only the
+    frames it checks)."""
+    # filterKeypoints per octave, concatenated in octave order (SURVEY section 8f row 3)
+    wo =np.concatenate([want.filter_keypoints(o, all_pts[o]) for o in range(n_oct)])
+    # survivors of the edge test = keypoints with at least one oriented point (every survivor has a peak)
+    n_surv = len({(int(q["octave"]), int(q["level"]), int(q["row"]), int(q["col"])) for q in wo})
+    assert out["oriented_survivors"][f] == n_surv, (f, int(out["oriented_survivors"][f]), n_surv)
+    assert n_surv <= p.oriented_cap, "check_frame compares whole lists: raise oriented_cap"
+    assert out["oriented_counts"][f] == len(wo), (f, int(out["oriented_counts"][f]), len(wo))
+    mo = min(len(wo), p.oriented_cap)
+    goo = out["oriented_points"][f][:mo].copy().view(capi.POINT_DTYPE).reshape(-1)
+    assert goo.tobytes() == wo[:mo].tobytes()
+    # SIFT() on the oriented points, octave by octave (SURVEY section 8f row 4), in the batched path
+    wd, wk = [], []
+    for o in range(n_oct):
+        d, k = want.sift_descriptors(o, wo[wo["octave"] == o])
+        wd.append(d)
+        wk.append(k)
+    wd, wk = np.concatenate(wd), np.concatenate(wk)
+    assert (out["descriptor_defined"][f][:mo] == wk[:mo]).all()
+    assert np.array_equal(out["descriptors"][f][:mo], wd[:mo], equal_nan=True)
+    assert (out["descriptors"][f][mo:] == 7.0).all() and (out["descriptor_defined"][f][mo:] == 9).all()  # rows beyond the list untouched
+
+
 def check_frame(p, L, out, f, img, n_oct):
     R = oracle.harris_response(img)
     assert out["response"][f].tobytes() == R.tobytes()
@@ -99,26 +125,8 @@ def check_frame(p, L, out, f, img, n_oct):
     m = min(len(allp), p.dog_cap)
     got = out["dog_points"][f][:m].copy().view(capi.POINT_DTYPE).reshape(-1)
     assert got.tobytes() == allp[:m].tobytes()
-    if p.orient:  # filterKeypoints per octave, concatenated in octave order
-        wo = np.concatenate([want.filter_keypoints(o, all_pts[o]) for o in range(n_oct)])
-        # survivors of the edge test = keypoints with at least one oriented point (every survivor has a peak)
-        n_surv = len({(int(q["octave"]), int(q["level"]), int(q["row"]), int(q["col"])) for q in wo})
-        assert out["oriented_survivors"][f] == n_surv, (f, int(out["oriented_survivors"][f]), n_surv)
-        assert n_surv <= p.oriented_cap, "check_frame compares whole lists: raise oriented_cap"
-        assert out["oriented_counts"][f] == len(wo), (f, int(out["oriented_counts"][f]), len(wo))
-        mo = min(len(wo), p.oriented_cap)
-        goo = out["oriented_points"][f][:mo].copy().view(capi.POINT_DTYPE).reshape(-1)
-        assert goo.tobytes() == wo[:mo].tobytes()
-        # SIFT() on the oriented points, octave by octave, in the batched path
-        wd, wk = [], []
-        for o in range(n_oct):
-            d, k = want.sift_descriptors(o, wo[wo["octave"] == o])
-            wd.append(d)
-            wk.append(k)
-        wd, wk = np.concatenate(wd), np.concatenate(wk)
-        assert (out["descriptor_defined"][f][:mo] == wk[:mo]).all()
-        assert np.array_equal(out["descriptors"][f][:mo], wd[:mo], equal_nan=True)
-        assert (out["descriptors"][f][mo:] == 7.0).all() and (out["descriptor_defined"][f][mo:] == 9).all()  # rows beyond the list untouched
+    if p.orient:
+        check_oriented_frame(p, out, f, want, all_pts, n_oct)
     want.close()
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
+from tests.orientcensus import block_noise
 from visualslam_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -281,12 +282,14 @@ def test_feature_point_localization_bit_exact(ctx):
     assert len(k0) == 0 and len(v0) == 0
 
 
-@pytest.mark.parametrize("shape,n_oct,kind", [((96, 160), 3, "noise"), ((75, 131), 2, "noise"), ((48, 64), 3, "checker"), ((135, 240), 4, "noise"), ((20, 24), 2, "noise")])
+@pytest.mark.parametrize("shape,n_oct,kind", [((96, 160), 3, "noise"), ((75, 131), 2, "noise"), ((48, 64), 3, "checker"), ((135, 240), 4, "noise"), ((20, 24), 2, "noise"),
+                                                ((512, 512), 4, "block")])
 def test_filter_keypoints_bit_exact(ctx, shape, n_oct, kind):
     # edge rejection + blurred-magnitude orientation histogram; the list
     # (positions, angles, order) must equal the oracle's.  Small images make the 1.5*sigma blur
-    # kernels wider than the padded image (multiple reflections).
-    img = frame(shape, kind, 6)
+    # kernels wider than the padded image (multiple reflections).  "block": noise enlarged block-wise in bands of 4, 16, 32 and
+    # 64 pixels - the one content here whose octaves 1, 2 and 3 all have keypoints that survive the edge test.
+    img = block_noise(*shape, (4, 16, 32, 64), stream_id=1) if kind == "block" else frame(shape, kind, 6)
     want, got = oracle.Pyramid(img, n_oct, 1.6), ctx.pyramid(img, n_oct, 1.6)
     total = 0
     for o in range(n_oct):
@@ -297,6 +300,7 @@ def test_filter_keypoints_bit_exact(ctx, shape, n_oct, kind):
         g2, n2 = got.filter_keypoints(o, kp, cap=3)
         assert n2 == len(w) and same(g2, w[:3])
         total += n
+        assert n >= 20 or kind != "block", (o, n)
         # synthetic keypoints at the corners / edges of the padded coordinate range, all six levels
         r, c = want.sizes[o]
         extra = np.zeros(12, capi.POINT_DTYPE)

@@ -52,10 +52,12 @@ def test_sift_descriptors_on_synthetic_frames(ctx, shape, kind):
 
 def test_sift_every_angle_and_the_level_edges(ctx):
     # hand-made oriented keypoints: all 36 histogram angles, positions at the corners of the padded
-    # coordinate range, every level the pipeline can produce
+    # coordinate range, every level the pipeline can produce, all four octaves: 25 ... 79 taps filter explicitly extended rows
+    # (octaves 0 and 1), 99 ... 309 taps come through the LDS tap table (octaves 2 and 3, down to a 38 x 38 level)
     img = synth.frame_np(150, 150, kind="noise")
-    want, got = oracle.Pyramid(img, 2, 1.6), ctx.pyramid(img, 2, 1.6)
-    for o in range(2):
+    want, got = oracle.Pyramid(img, 4, 1.6), ctx.pyramid(img, 4, 1.6)
+    assert [max(oracle.gauss_ksize_f32(1.5 * want.sigmas[o][l]) for l in (1, 2, 3)) // 2 > 47 for o in range(4)] == [False, False, True, True]
+    for o in range(4):
         r, c = want.sizes[o]
         kps = []
         for a in range(0, 360, 10):
@@ -88,3 +90,19 @@ def test_sift_undefined_without_flags_is_an_error(ctx):
         got.sift_descriptors(0, bad)
     got.close()
     want.close()
+
+
+def test_a_pyramid_left_open_is_closed_with_its_context():
+    # A test that fails between ctx.pyramid() and close() leaves the pyramid to the collector, which reaches it after the
+    # module's context is gone; vslam_pyramid_destroy returns the pyramid's blocks to its context, so the order matters.
+    # Context.close() closes the pyramids still open on it first, and a later close() of such a pyramid does nothing.
+    capi.build()
+    c = capi.Context(0)
+    img = synth.frame_np(64, 64, kind="noise")
+    a, b = c.pyramid(img, 2, 1.6), c.pyramid(img, 2, 1.6)
+    a.close()
+    assert a._h is None and b._h is not None
+    c.close()
+    assert b._h is None and c._h is None
+    b.close()
+    del a, b

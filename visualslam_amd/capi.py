@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -434,9 +435,14 @@ class Context:
             raise VslamError(rc, "vslam_ctx_create", "no usable HIP device" if rc == -2 else "")
         self._h = h
         self.device = device
+        self._pyramids = weakref.WeakSet()  # the live Pyramid objects built on this context
 
     def close(self):
         if getattr(self, "_h", None):
+            # a vslam_pyramid hands its device blocks back to its context when it is destroyed: one that outlived the context
+            # (a caller's exception skipped its close(), the collector gets to it later) would write into freed host memory
+            for py in list(self._pyramids):
+                py.close()
             lib().vslam_ctx_destroy(self._h)
             self._h = None
 
@@ -853,6 +859,7 @@ class Pyramid:
         h = C.c_void_p()
         ctx._chk(lib().vslam_pyramid_build_u8(ctx._h, img.ctypes.data, *img.shape, img.strides[0], n_octaves, float(sigma0), C.byref(h)), "vslam_pyramid_build_u8")
         self._h = h
+        ctx._pyramids.add(self)
         info = PyramidInfo()
         lib().vslam_pyramid_get_info(h, C.byref(info))
         self.n_octaves = info.n_octaves
