@@ -140,16 +140,19 @@ def test_batch_small_frames_all_outputs(env, path):
         check_frame(p, L, out, f, frames[f], 3)
 
 
-@pytest.mark.parametrize("mode", ["candidates", "localized", "oriented"])
+@pytest.mark.parametrize("mode", ["candidates", "localized", "oriented", "oriented-260"])
 def test_batch_larger_than_one_chunk(env, mode):
     # more frames than one whole-batch launch takes (256): the second chunk reuses the scratch, the
-    # events and the auxiliary streams of the first; frames on both sides of the seam against the oracle
+    # events and the auxiliary streams of the first; frames on both sides of the seam against the oracle.
+    # 260 frames: the second chunk (4 frames) has another plan than the first (csrc/vslam_batch_plan.h) - eager scans and
+    # the Harris chain at once where the first was gated, no second-half upsample
     ctx, torch = env
-    frames = synth.frames_np(300, 40, 56, stream_id=13)
+    n = 260 if mode == "oriented-260" else 300
+    frames = synth.frames_np(n, 40, 56, stream_id=13)
     frames[256] = synth.frame_np(40, 56, kind="noise")
-    kw = dict(localize=int(mode != "candidates"), orient=int(mode == "oriented"))
+    kw = dict(localize=int(mode != "candidates"), orient=int(mode.startswith("oriented")))
     p, L, out = run_batch(ctx, torch, frames, n_octaves=2, harris_cap=1024, dog_cap=2048, **kw)
-    for f in (0, 1, 254, 255, 256, 257, 299):
+    for f in (0, 255, 256, 257, 259) if n == 260 else (0, 1, 254, 255, 256, 257, 299):
         check_frame(p, L, out, f, frames[f], 2)
     # every frame of the first chunk also appears, identically, nowhere else: spot-check that no
     # frame of chunk 2 picked up results of chunk 1
@@ -212,7 +215,7 @@ def test_two_full_chunks_of_256_frames(env, lists, path):
 
 @pytest.mark.parametrize("mode", ["candidates", "localized", "oriented"])
 def test_batch_of_40_frames_takes_the_gated_launch_order(env, mode):
-    # from 32 frames on the side streams are ordered differently (vslam_hip.hip, enqueue_dog): the Harris
+    # from 32 frames on the side streams are ordered differently (csrc/vslam_batch_plan.h): the Harris
     # chain and the localizing scan wait for the last LDS-tiled octave kernel, the plain scan does not.
     # Same results, every list mode, frames with different content
     ctx, torch = env

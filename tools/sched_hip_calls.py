@@ -8,8 +8,12 @@ on the order of creation).
   python tools/sched_hip_calls.py compare OUT/parent_hip_api_trace.csv OUT/new_hip_api_trace.csv
 
 run: seven 32 x 120 x 160 batch calls on a context with yielding side streams and the tuner on, then two 64 x 270 x 480 calls
-with localize = 1, orient = 1 on a default context; each context is closed.  compare: the calls named in CALLS, in trace
-order (function names are compared; handles are not numbered).  Runs of consecutive destroys - a
+with localize = 1, orient = 1 on a default context; then, for the plan of a chunk (csrc/vslam_batch_plan.h): a 300-frame and a
+260-frame 40 x 56 call with localize = 1, orient = 1 (two chunks: both orientation forks, a second chunk with the plan of the
+first and one with another), a 320-frame 40 x 56 call (the second chunk's second half waits for ev_chunk), a 300-frame
+96 x 160 call on the matrix path in candidates mode (the ev_pack wait of a later chunk) and one single-image Pyramid; each context is closed.  compare: the calls named in CALLS plus
+every kernel launch and asynchronous copy (is_enqueue), in trace order - so the interleaving of launches with records and
+waits is compared too (function names are compared; handles are not numbered).  Runs of consecutive destroys - a
 context's teardown, the tuner's losing pairs - are compared as counts: their internal order is free.
 """
 import collections
@@ -19,6 +23,12 @@ import sys
 
 CALLS = ("hipStreamCreateWithPriority", "hipStreamCreateWithFlags", "hipEventCreate", "hipEventCreateWithFlags", "hipEventRecord",
          "hipStreamWaitEvent", "hipEventQuery", "hipEventElapsedTime", "hipEventDestroy", "hipStreamDestroy")
+
+
+def is_enqueue(f):
+    """Kernel launches and asynchronous copies, under whatever name the trace gives them (hipLaunchKernel, hipModuleLaunchKernel,
+    hipExtLaunchKernel, ...; hipMemcpyAsync, hipMemcpy2DAsync, hipMemcpyDtoDAsync, ...)."""
+    return "LaunchKernel" in f or (f.startswith("hipMemcpy") and f.endswith("Async"))
 
 
 def run():
@@ -53,12 +63,21 @@ def run():
     ctx.close()
     ctx = capi.Context(0, torch.cuda.current_stream().cuda_stream)
     b = calls(ctx, 64, 270, 480, 2, localize=1, orient=1)
+    small = dict(n_octaves=2, harris_cap=1024, dog_cap=2048, localize=1, orient=1)
+    c3 = calls(ctx, 300, 40, 56, 1, **small)
+    c4 = calls(ctx, 260, 40, 56, 1, **small)
+    c6 = calls(ctx, 320, 40, 56, 1, n_octaves=2, harris_cap=1024, dog_cap=2048)  # a second chunk of 64 frames: upsampled in halves
+    ctx.set_matrix_path(True)
+    c5 = calls(ctx, 300, 96, 160, 1, n_octaves=3)
+    ctx.set_matrix_path(False)
+    py = capi.Pyramid(ctx, synth.frame_np(120, 160, kind="noise"), 3)
+    py.close()
     ctx.close()
-    print("library", capi.LIB_PATH, "dog points", a, b)
+    print("library", capi.LIB_PATH, "dog points", a, b, c3, c4, c6, c5)
 
 
 def sequence(path):
-    rows = [r for r in csv.DictReader(open(path)) if r["Function"] in CALLS]
+    rows = [r for r in csv.DictReader(open(path)) if r["Function"] in CALLS or is_enqueue(r["Function"])]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     seq = []
     for r in rows:
@@ -78,10 +97,10 @@ def compare(pa, pb):
         c = collections.Counter()
         for x in s:
             c.update(x if isinstance(x, collections.Counter) else [x])
-        print(name, len(s), "entries;", ", ".join(f"{k} {c[k]}" for k in CALLS))
+        print(name, len(s), "entries;", ", ".join(f"{k} {c[k]}" for k in (*CALLS, *sorted(k for k in c if is_enqueue(k)))))
     plain = lambda s: [x for x in s if not isinstance(x, collections.Counter)]
     same = plain(a) == plain(b)
-    print("create / record / wait / query calls, in order:", "identical" if same else "DIFFERENT")
+    print("create / record / wait / query calls, kernel launches and asynchronous copies, in order:", "identical" if same else "DIFFERENT")
     if not same:
         for i, (x, y) in enumerate(zip(plain(a), plain(b))):
             if x != y:

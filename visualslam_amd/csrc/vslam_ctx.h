@@ -67,7 +67,6 @@ struct vslam_ctx {
     // (the one scratch of the DoG path written on the main stream and read on a side stream: the next chunk's octave
     // kernels wait for this before they overwrite it)
     hipEvent_t ev_pack = nullptr;
-    bool pack_pending = false;
     hipEvent_t ev_list0 = nullptr, ev_edge = nullptr;  // octave 0's part of the DoG list is written / its edge test is done
     hipEvent_t ev_or_fork = nullptr, ev_or_join[2] = {nullptr, nullptr};  // the orientation launches spread over the idle side streams (enqueue_orient_batch)
     // recycled pyramid blocks: a GaussPyramid per image would otherwise pay hipMalloc + hipFree of

@@ -8,7 +8,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <functional>
 #include <map>
 #include <string>
 #include <set>
@@ -28,6 +27,7 @@
 #include "kernels_compact.hip.h"
 #include "kernels_sift.hip.h"
 #include "kernels_extrema_dense.hip.h"
+#include "vslam_batch_plan.h"
 #include "vslam_internal.h"
 #include "vslam_ctx.h"
 #include "vslam_launch.h"
@@ -483,16 +483,6 @@ static int enqueue_pyr_octave_mx(vslam_ctx* c, double sigma0, int o, const OctPl
     return VSLAM_OK;
 }
 
-// The octave whose kernels the held-back side work of a batch waits for (enqueue_dog): the last
-// LDS-tiled one for batches of 32 frames or more, -1 (no gate) otherwise.
-static int dog_side_gate(const std::vector<OctPlan>& plans, int nf) {
-    int gate = -1;
-    if (nf >= 32)
-        for (int o = 0; o < (int)plans.size(); ++o)
-            if (plans[o].path == OctPath::Tile0 || plans[o].path == OctPath::Tile1) gate = o;
-    return gate;
-}
-
 // Geometry of the dense 3x3x3 scan (kernels_extrema_dense.hip.h) for octave o of nf frames.
 static DenseGeom dense_geom(const vslam_batch_layout& L, int o, int min_contrast, int nf) {
     DenseGeom g;
@@ -520,145 +510,135 @@ struct DogOut {
     unsigned int* counts = nullptr;
 };
 
-// How a batched call runs enqueue_dog beside its other work; the defaults put everything on the context's stream.
-struct DogRun {
-    // `side`: stream for the extrema scans and the list compaction (they only read what the
-    // octave kernels wrote); ordered after the octave kernels by events.  nullptr = same stream.
-    hipStream_t side = nullptr;
-    hipStream_t up = nullptr;                 // stream for the second half's upsample of a large batch (with `side`)
-    std::function<int(int)> after_list;       // called with o once octave o's points are in the lists, on the stream they are written on
-    std::function<int(int)> after_octave;     // called with o once octave o's kernels are enqueued and ev_oct[o] marks their end
-    bool later_chunk = false;                 // not the first chunk of its call: the scratch still has readers from the chunk before
-    bool bases_are_scratch = false;           // nobody reads the octave bases after the call
-};
-}  // namespace
+// A lane of the plan as a stream.  (Lane::Main is the context's current stream: ask for it outside a StreamSwap.)
+static inline hipStream_t lane_stream(const vslam_ctx* c, Lane l) { return l == Lane::Main ? c->stream : c->aux[(int)l - 1]; }
 
-// The lattice scan of octave o and the compaction of its points into the frames' lists; on the side stream both wait for
-// ev_oct[o_done], the octave whose kernels were enqueued last.  `fused`: the octave kernel has left the site / seam maps.
-static int enqueue_octave_scan(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const ExtGeom& g, const DogScratch& s,
-                               const MxScan* fused, int o, int o_done, int nf, const DogOut& out, const DogRun& run) {
-    uint8_t* const pyr = out.pyr;
-    const size_t pframe = out.pframe;
-    unsigned long long* const bits = out.bits;
-    const hipStream_t side = run.side;
-    if (out.do_extrema && L.lat_rows[o] > 0 && L.lat_cols[o] > 0) {
-        hipStream_t es = c->stream;
-        if (side) {
-            HIPCHK(c, hipStreamWaitEvent(side, c->ev_oct[o_done], 0));
-            es = side;
-        }
-        if (p.extrema_dense) {
-            // extension: the dense 3x3x3 test on every pixel (kernels_extrema_dense.hip.h); the layout's
-            // lattice of this mode is the image itself
-            const DenseGeom dg = dense_geom(L, o, p.min_contrast, nf);
-            hipLaunchKernelGGL(k_extrema_dense, dim3(((dg.cols + 3) / 4 + 255) / 256, (dg.rows + dg.seg - 1) / dg.seg, nf), dim3(256), 0, es,
-                               pyr, pframe, dg, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o], L.bits_frame_words);
-        } else if (fused) {
-            {
-                TimedScope ts(c, "k_extrema_pack", o, es);
-                HIPCHK(c, mx_launch_pack(es, *fused, L.rows[o], L.lat_words[o], nf, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o],
-                                         L.bits_frame_words, kMxStripRows));
-            }
-            // the lattice rows whose windows straddle a strip's first image row (3a a multiple of the strip's rows, a power of two:
-            // a = 32, 64, ...) are not in the site map: the plain scan kernel runs on exactly those rows
-            const int sr = kMxStripRows;
-            const int n_straddle = (L.lat_rows[o] - 1) / sr;
-            TimedScope ts(c, "k_extrema_w3", o, es);
-            if (n_straddle > 0)
-                hipLaunchKernelGGL(k_extrema_w3<false>, dim3((L.lat_words[o] + 3) / 4, n_straddle, nf), dim3(256), 0, es, pyr, pframe, g, o, bits, s.lflags,
-                                   L.bits_frame_words, sr, sr);
-            if (es != c->stream) {  // the maps' reader is on another stream than their writer: mark its end for the next chunk
-                HIPCHK(c, hipEventRecord(c->ev_pack, es));
-                c->pack_pending = true;
-            }
-        } else if (p.extrema_window == 3) {
-            const dim3 eg((L.lat_words[o] + 3) / 4, L.lat_rows[o], nf);
-            if (p.localize)
-                LAUNCH_ON(c, "k_extrema_w3", o, es, 0, k_extrema_w3<true>, eg, dim3(256), pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
-            else
-                LAUNCH_ON(c, "k_extrema_w3", o, es, 0, k_extrema_w3<false>, eg, dim3(256), pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
-        } else
-            hipLaunchKernelGGL(k_extrema, dim3((L.lat_cols[o] + 255) / 256, L.lat_rows[o], nf * 3), dim3(256), 0, es, pyr,
-                               pframe, g, o, bits, s.lflags, L.bits_frame_words);
-        HIPCHK(c, hipGetLastError());
+// What the plan of a chunk takes from the layout, the octave plans and the parameters; the caller adds nf, the outputs asked
+// for (harris, do_extrema, lists) and the state of the call (bases_are_scratch, side, capturing, later_chunk).
+static BatchPlanIn batch_plan_input(const vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const std::vector<OctPlan>& plans, size_t fstep) {
+    BatchPlanIn in;
+    in.n_octaves = L.n_octaves;
+    for (int o = 0; o < L.n_octaves; ++o) {
+        in.tiled[o] = plans[o].path == OctPath::Tile0 || plans[o].path == OctPath::Tile1;
+        in.lattice[o] = L.lat_rows[o] > 0 && L.lat_cols[o] > 0;
+        in.scan_ok[o] = mx_scan_supported(plans[o].mx);
     }
-    // compact this octave's points right away (appending to the frame's list): on the side
-    // stream it overlaps the next octave's kernels instead of forming a serial tail
-    if (out.do_extrema && out.points && out.counts) {
-        StreamSwap sw(c, side ? side : c->stream);
-        const size_t entries = (size_t)3 * L.lat_rows[o] * L.lat_words[o];
-        if (p.extrema_dense) {
-            DenseDogEntries ent{s.lflags + L.bits_offset[o], L.bits_frame_words, pyr, pframe, dense_geom(L, o, p.min_contrast, nf), o, out.points};
-            TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, out.counts, o > 0 ? 1 : 0));
-        } else {
-            DogEntries ent{s.lflags, L.bits_frame_words, pyr, pframe, g, o, o + 1, out.points};
-            TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, out.counts, o > 0 ? 1 : 0));
-        }
-        if (run.after_list) TRY(run.after_list(o));  // on the stream the list is written on, behind octave o's records
-    }
-    return VSLAM_OK;
+    in.up2_ok = L.n_octaves > 0 && L.rows[0] == 2 * p.rows && L.cols[0] == 2 * p.cols && fstep <= 0x7fffffff && mx_up2_supported(plans[0].mx);
+    in.dog = L.n_octaves > 0;
+    in.localize = p.localize, in.orient = p.orient, in.extrema_dense = p.extrema_dense, in.extrema_window = p.extrema_window;
+    in.mx = c->mx;
+    return in;
 }
 
-// createPyramid (GaussPyramid.cpp:106-131) + initialKeypointDetection (Diff_of_Gauss.cpp:254)
-// for nf frames; `plans`: plan_octaves() of the same (sigma0, layout), as given to dog_scratch_plan.
-static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const std::vector<OctPlan>& plans, const uint8_t* frames,
-                       size_t fstep, size_t fframe, int nf, DogScratch& s, const DogOut& out, const DogRun& run = DogRun()) {
-    const hipStream_t side = run.side, up = run.up;
-    // Where the side work runs decides how much of the VALU-issue-bound octave kernels it costs
-    // (gate = dog_side_gate(): the last LDS-tiled octave, -1 = none; 256 x 1080p, same box):
-    //  * the Harris chain (VALU-heavy) always waits for that octave's kernel - the caller enqueues it
-    //    from after_octave(gate), behind ev_oct[gate] - and runs beside the coarse-octave strip
-    //    kernels, which are short of waves: k_pyr_octave 7.46 -> 6.06 ms per launch, +1.4 % frames/s;
-    //  * the plain extrema scan (HBM-heavy, ~90 VALU instructions per thread) starts as soon as its
-    //    octave is written, i.e. octave 0's scan runs beside octave 1's kernel: +2..3 % frames/s
-    //    over holding it back as well (the tail after the tiled octaves is as VALU-bound as they are,
-    //    so the scan's memory time is what gets hidden);
-    //  * the scan with FeaturePointLocalization inside (params.localize, ~8x the instructions) is
-    //    held back like the Harris chain: +0.5 % in the localize / orient / describe modes.
-    // Small batches keep the eager order: there the chain's latency matters, not the issue slots.
-    const int gate = (side && p.localize) ? dog_side_gate(plans, nf) : -1;
-    ExtGeom g;
-    if (p.localize) TRY(ensure_loc_lut(c));
-    fill_geom(c, p, L, g);
-    // Large batches go through the upsample and octave 0 in two halves: the second half is upsampled
-    // on the side stream (idle until octave 0 is done) while the first half's octave-0 kernel runs, so
-    // only half of the bandwidth-bound upsample is exposed in front of the VALU-bound octave kernels.
-    // The second half goes to a stream of its own (`up`): on `side` it would queue behind the previous
-    // chunk's whole list chain.  It overwrites bases the previous chunk's octave kernels (main stream)
-    // read, and nothing else orders it behind them - with pyramid-only outputs there is not even a scan
-    // waiting on ev_oct - so it waits for ev_chunk, recorded at the end of every chunk's main-stream work.
-    // (quarters and eighths were measured again in round 3 with the side upsample at normal priority: 21.41 /
-    // 21.44 ms against 21.29 for halves in the same configuration - no gain)
-    // Matrix path, batched entry (the octave bases are scratch nobody reads afterwards): octave 0's kernel forms its base from
-    // the frame while it stages a tile (kernels_pyramid_mx.hip.h: mx_stage_tile_up2) - no upsample kernel, no base in HBM.
-    const bool up2_fused = c->mx && run.bases_are_scratch && L.n_octaves > 0 && L.rows[0] == 2 * p.rows && L.cols[0] == 2 * p.cols && fstep <= 0x7fffffff &&
-                           mx_up2_supported(plans[0].mx);
-    const int nf_a = (!up2_fused && side && up && nf >= 64) ? nf / 2 : nf;
-    if (!up2_fused)
-        LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3(((p.cols + 3) / 4 + 255) / 256, (p.rows + 15) / 16, nf_a), dim3(256),
-               frames, fstep, fframe, s.bases + s.base_off[0], s.bases_frame, L.pitch[0], p.rows, p.cols, 16);
-    if (nf_a < nf) {
-        if (run.later_chunk) HIPCHK(c, hipStreamWaitEvent(up, c->ev_chunk, 0));
-        StreamSwap sw(c, up);
-        LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3(((p.cols + 3) / 4 + 255) / 256, (p.rows + 15) / 16, nf - nf_a), dim3(256),
-               frames + (size_t)nf_a * fframe, fstep, fframe, s.bases + s.base_off[0] + (size_t)nf_a * s.bases_frame, s.bases_frame, L.pitch[0],
-               p.rows, p.cols, 16);
-        HIPCHK(c, hipEventRecord(c->ev_up2, c->stream));
+// One chunk of the DoG path, as the steps of enqueue_dog share it.  `plan` (vslam_batch_plan.h) says on which lane and when
+// every piece goes; the steps decide nothing of that themselves.
+struct DogChunk {
+    const vslam_params& p;
+    const vslam_batch_layout& L;
+    const std::vector<OctPlan>& plans;  // plan_octaves() of the same (sigma0, layout), as given to dog_scratch_plan
+    const uint8_t* frames;
+    size_t fstep, fframe;
+    int nf;
+    DogScratch& s;
+    DogOut out;
+    BatchPlan plan;
+    ExtGeom g{};
+    MxScan scan[VSLAM_MAX_OCTAVES] = {};  // of the octaves whose lattice scan runs inside the octave kernel (plan.fused[o])
+
+    // First: octave 0's bases, and what a later chunk owes the readers of the chunk before.
+    int begin(vslam_ctx* c) {
+        const int nf_a = plan.nf_a;
+        if (p.localize) TRY(ensure_loc_lut(c));
+        fill_geom(c, p, L, g);
+        // (the halves of a large batch and octave 0's fused upsample: vslam_batch_plan.h)
+        if (!plan.up2_fused)
+            LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3(((p.cols + 3) / 4 + 255) / 256, (p.rows + 15) / 16, nf_a), dim3(256),
+                   frames, fstep, fframe, s.bases + s.base_off[0], s.bases_frame, L.pitch[0], p.rows, p.cols, 16);
+        if (nf_a < nf) {
+            const hipStream_t up = lane_stream(c, plan.up_lane);
+            if (plan.up_waits_chunk) HIPCHK(c, hipStreamWaitEvent(up, c->ev_chunk, 0));
+            StreamSwap sw(c, up);
+            LAUNCH(c, "k_resize_linear2x_slide", k_resize_linear2x_slide, dim3(((p.cols + 3) / 4 + 255) / 256, (p.rows + 15) / 16, nf - nf_a), dim3(256),
+                   frames + (size_t)nf_a * fframe, fstep, fframe, s.bases + s.base_off[0] + (size_t)nf_a * s.bases_frame, s.bases_frame, L.pitch[0],
+                   p.rows, p.cols, 16);
+            HIPCHK(c, hipEventRecord(c->ev_up2, c->stream));
+        }
+        // a later chunk reuses the site / seam maps: its octave kernels (main stream) must not overwrite them while the previous
+        // chunk's k_extrema_pack launches (side stream, low priority, possibly on a slow hardware queue) are still reading
+        if (plan.wait_pack) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pack, 0));
+        // matrix path: the plain lattice scan (window 3, candidates + contrast list) runs inside the octave kernel
+        // while the DoG rows are in LDS (kernels_pyramid_mx.hip.h); k_extrema_pack then replaces k_extrema_w3
+        for (int o = 0; o < L.n_octaves; ++o)
+            if (plan.fused[o])
+                scan[o] = MxScan{s.sitemap + s.site_off[o], s.site_frame, L.lat_rows[o], L.lat_cols[o], s.site_pitch[o], p.min_contrast,
+                                   s.colmap + s.col_off[o], s.col_frame, mx_seams(L.cols[o])};
+        return VSLAM_OK;
     }
-    bool fused[VSLAM_MAX_OCTAVES] = {};
-    // a later chunk reuses the site / seam maps: its octave kernels (main stream) must not overwrite them while the previous
-    // chunk's k_extrema_pack launches (side stream, low priority, possibly on a slow hardware queue) are still reading
-    if (run.later_chunk && c->pack_pending) {
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_pack, 0));
-        c->pack_pending = false;
+
+    // (scan_octave stands in front of octave on purpose: kernels are emitted in the order of their first use, and with the
+    // octave kernels in front of k_extrema_w3 the localize modes measured 0.4 % slower - profiles/batch_plan_ab.txt)
+    // Once per octave, when the plan says (after[o]): the lattice scan of octave o (initialKeypointDetection, Diff_of_Gauss.cpp:254) and the compaction
+    // of its points into the frames' lists; on the list lane both wait for ev_oct[o_done], the octave whose kernels were enqueued last.
+    int scan_octave(vslam_ctx* c, int o, int o_done) {
+        uint8_t* const pyr = out.pyr;
+        const size_t pframe = out.pframe;
+        unsigned long long* const bits = out.bits;
+        const bool on_side = plan.scan_lane != Lane::Main;
+        const hipStream_t es = lane_stream(c, plan.scan_lane);
+        if (out.do_extrema && L.lat_rows[o] > 0 && L.lat_cols[o] > 0) {
+            if (on_side) HIPCHK(c, hipStreamWaitEvent(es, c->ev_oct[o_done], 0));
+            if (p.extrema_dense) {
+                // extension: the dense 3x3x3 test on every pixel (kernels_extrema_dense.hip.h); the layout's
+                // lattice of this mode is the image itself
+                const DenseGeom dg = dense_geom(L, o, p.min_contrast, nf);
+                hipLaunchKernelGGL(k_extrema_dense, dim3(((dg.cols + 3) / 4 + 255) / 256, (dg.rows + dg.seg - 1) / dg.seg, nf), dim3(256), 0, es,
+                                   pyr, pframe, dg, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o], L.bits_frame_words);
+            } else if (plan.fused[o]) {  // the octave kernel has left the site / seam maps
+                {
+                    TimedScope ts(c, "k_extrema_pack", o, es);
+                    HIPCHK(c, mx_launch_pack(es, scan[o], L.rows[o], L.lat_words[o], nf, bits ? bits + L.bits_offset[o] : nullptr, s.lflags + L.bits_offset[o],
+                                             L.bits_frame_words, kMxStripRows));
+                }
+                // the lattice rows whose windows straddle a strip's first image row (3a a multiple of the strip's rows, a power of two:
+                // a = 32, 64, ...) are not in the site map: the plain scan kernel runs on exactly those rows
+                const int sr = kMxStripRows;
+                const int n_straddle = (L.lat_rows[o] - 1) / sr;
+                TimedScope ts(c, "k_extrema_w3", o, es);
+                if (n_straddle > 0)
+                    hipLaunchKernelGGL(k_extrema_w3<false>, dim3((L.lat_words[o] + 3) / 4, n_straddle, nf), dim3(256), 0, es, pyr, pframe, g, o, bits, s.lflags,
+                                       L.bits_frame_words, sr, sr);
+                // the maps' reader is on another stream than their writer: mark its end for the next chunk (plan.wait_pack)
+                if (on_side) HIPCHK(c, hipEventRecord(c->ev_pack, es));
+            } else if (p.extrema_window == 3) {
+                const dim3 eg((L.lat_words[o] + 3) / 4, L.lat_rows[o], nf);
+                if (p.localize)
+                    LAUNCH_ON(c, "k_extrema_w3", o, es, 0, k_extrema_w3<true>, eg, dim3(256), pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
+                else
+                    LAUNCH_ON(c, "k_extrema_w3", o, es, 0, k_extrema_w3<false>, eg, dim3(256), pyr, pframe, g, o, bits, s.lflags, L.bits_frame_words, 0, 1);
+            } else
+                hipLaunchKernelGGL(k_extrema, dim3((L.lat_cols[o] + 255) / 256, L.lat_rows[o], nf * 3), dim3(256), 0, es, pyr,
+                                   pframe, g, o, bits, s.lflags, L.bits_frame_words);
+            HIPCHK(c, hipGetLastError());
+        }
+        // compact this octave's points right away (appending to the frame's list): on the side
+        // stream it overlaps the next octave's kernels instead of forming a serial tail
+        if (out.do_extrema && out.points && out.counts) {
+            StreamSwap sw(c, es);
+            const size_t entries = (size_t)3 * L.lat_rows[o] * L.lat_words[o];
+            if (p.extrema_dense) {
+                DenseDogEntries ent{s.lflags + L.bits_offset[o], L.bits_frame_words, pyr, pframe, dense_geom(L, o, p.min_contrast, nf), o, out.points};
+                TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, out.counts, o > 0 ? 1 : 0));
+            } else {
+                DogEntries ent{s.lflags, L.bits_frame_words, pyr, pframe, g, o, o + 1, out.points};
+                TRY(enqueue_compaction(c, ent, entries, nf, s.cws, p.dog_cap, out.counts, o > 0 ? 1 : 0));
+            }
+        }
+        return VSLAM_OK;
     }
-    MxScan scan[VSLAM_MAX_OCTAVES] = {};  // of the octaves whose lattice scan runs inside the octave kernel (fused[o])
-    struct TagReset {
-        vslam_ctx* c;
-        ~TagReset() { c->launch_tag = -1; }
-    } tag_reset{c};
-    for (int o = 0; o < L.n_octaves; ++o) {
-        c->launch_tag = o;  // the timing hook's "name@o" (TimedScope) for every launch of this octave
+
+    // Once per octave: the kernels of octave o (createPyramid, GaussPyramid.cpp:106-131) and the event that marks their end.
+    int octave(vslam_ctx* c, int o) {
+        const int nf_a = plan.nf_a;
         const int rows = L.rows[o], cols = L.cols[o], pitch = L.pitch[o];
         const size_t P = (size_t)rows * pitch;
         const OctPlan& pl = plans[o];
@@ -668,22 +648,17 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
         OctIO io{s.bases + s.base_off[o], s.bases_frame, out.pyr + L.octave_offset[o], out.pframe, rows, cols, pitch, nf,
                  fuse_next ? s.bases + s.base_off[o + 1] : nullptr, s.bases_frame, has_next ? L.rows[o + 1] : 0, has_next ? L.cols[o + 1] : 0,
                  has_next ? L.pitch[o + 1] : 0};
-        if (o == 0 && up2_fused) io.base = frames, io.bframe = fframe;  // the kernel reads the source frames (mx_launch: up2_step)
+        const bool up2 = o == 0 && plan.up2_fused;
+        if (up2) io.base = frames, io.bframe = fframe;  // the kernel reads the source frames (mx_launch: up2_step)
         const int shape = pyr_tile_wide(rows, cols) ? 1 : 0;  // the wide tile (256 x 32) or the tall one (128 x 64)
-        // matrix path: the plain lattice scan (window 3, candidates + contrast list) runs inside the octave kernel
-        // while the DoG rows are in LDS (kernels_pyramid_mx.hip.h); k_extrema_pack then replaces k_extrema_w3
-        fused[o] = c->mx && s.sitemap && out.do_extrema && !p.localize && !p.extrema_dense && p.extrema_window == 3 && L.lat_rows[o] > 0 &&
-                   L.lat_cols[o] > 0 && mx_scan_supported(pl.mx);
-        if (fused[o])
-            scan[o] = MxScan{s.sitemap + s.site_off[o], s.site_frame, L.lat_rows[o], L.lat_cols[o], s.site_pitch[o], p.min_contrast,
-                             s.colmap + s.col_off[o], s.col_frame, mx_seams(cols)};
+        const bool fused = plan.fused[o];
         // frames [f_lo, f_lo + n) of this octave through the LDS-tiled kernel
         auto tiled = [&](int f_lo, int n) -> int {
             const OctIO part = io.frames(f_lo, n);
             if (c->mx && pl.mx) {
                 MxScan sc = scan[o];
-                if (fused[o]) sc.sitemap += (size_t)f_lo * s.site_frame, sc.colmap += (size_t)f_lo * s.col_frame;
-                return enqueue_pyr_octave_mx(c, p.sigma0, o, pl, part, fused[o] ? &sc : nullptr, o == 0 && up2_fused ? (int)fstep : 0);
+                if (fused) sc.sitemap += (size_t)f_lo * s.site_frame, sc.colmap += (size_t)f_lo * s.col_frame;
+                return enqueue_pyr_octave_mx(c, p.sigma0, o, pl, part, fused ? &sc : nullptr, up2 ? (int)fstep : 0);
             }
             if (pl.path == OctPath::Tile0)
                 return shape == 1 ? enqueue_pyr_octave<PyrCfgOct0W>(c, p.sigma0, o, pl, part) : enqueue_pyr_octave<PyrCfgOct0>(c, p.sigma0, o, pl, part);
@@ -711,16 +686,32 @@ static int enqueue_dog(vslam_ctx* c, const vslam_params& p, const vslam_batch_la
             LAUNCH(c, "k_resize_nearest_half_v4", k_resize_nearest_half_v4, dim3((L.cols[o + 1] / 4 + 256) / 256, L.rows[o + 1], nf),
                    dim3(256), io.oct + (size_t)3 * P, out.pframe, pitch, s.bases + s.base_off[o + 1], s.bases_frame, L.pitch[o + 1], rows,
                    L.rows[o + 1], L.cols[o + 1]);
-        if (side) HIPCHK(c, hipEventRecord(c->ev_oct[o], c->stream));
+        if (plan.ev_oct) HIPCHK(c, hipEventRecord(c->ev_oct[o], c->stream));
         if (o == 0) TRY(sched_mark_phase(c));
-        if (run.after_octave) TRY(run.after_octave(o));  // octave o's kernels are enqueued and ev_oct[o] marks their end
-        if (o < gate) continue;  // scan + compaction of this octave are enqueued behind octave `gate`
-        // ... which is when the octaves held back until then get theirs, in order
-        for (int oo = (o == gate ? 0 : o); oo <= o; ++oo) TRY(enqueue_octave_scan(c, p, L, g, s, fused[oo] ? &scan[oo] : nullptr, oo, o, nf, out, run));
+        return VSLAM_OK;
     }
-    if (side && up) HIPCHK(c, hipEventRecord(c->ev_chunk, c->stream));
-    return VSLAM_OK;
-}
+};
+
+// The Harris chain of one chunk (enqueue_harris's arguments).
+struct HarrisChunk {
+    const uint8_t* frames;
+    size_t fframe;
+    int rows, cols, nf;
+    float k, *resp;
+    uint8_t* mask;
+    float* nms2;
+    unsigned long long* hflags;
+    vslam_kp* kps;
+    unsigned int cap, *counts, *cws;
+};
+}  // namespace
+
+
+struct OrientPlan;
+struct OrientScratch;
+// One chunk of the DoG path with what the plan interleaves with it (defined with the batched path below): the Harris chain
+// `hc` at the gate, and the early edge test of the orientation stage (`opl`, `os`) behind octave 0's list.
+static int enqueue_dog(vslam_ctx* c, DogChunk& d, const HarrisChunk* hc = nullptr, const OrientPlan* opl = nullptr, OrientScratch* os = nullptr);
 
 // Harris chain on nf device frames with dense rows: response (required buffer), optional mask /
 // nms2 / keypoint list, all from the single-pass wave-strip kernel - its aligned form when every
@@ -1196,7 +1187,9 @@ int vslam_pyramid_build_u8(vslam_ctx* c, const uint8_t* img, int rows, int cols,
     int rc = ws.commit(c);
     if (rc) return cleanup(rc);
     if ((rc = h2d(c, d_img, cols, img, step, cols, rows))) return cleanup(rc);
-    if ((rc = enqueue_dog(c, p, L, plans, d_img, cols, N, 1, s, DogOut{py->d_block, L.pyramid_frame_bytes}))) return cleanup(rc);
+    // the batched path's chunk with everything on the context's stream: no side lanes, no Harris chain, no lists
+    DogChunk d{p, L, plans, d_img, (size_t)cols, N, 1, s, DogOut{py->d_block, L.pyramid_frame_bytes}, batch_plan(batch_plan_input(c, p, L, plans, cols))};
+    if ((rc = enqueue_dog(c, d))) return cleanup(rc);
     if (hipMemcpyAsync(py->d_bases, s.bases, sum_p, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
         return cleanup(fail(c, VSLAM_ERR_HIP, "device copy failed (bases)"));
     if ((rc = vslam_ctx_sync(c))) return cleanup(rc);
@@ -1506,8 +1499,6 @@ struct OrientScratch {
     unsigned int* cws = nullptr;          // compaction scratch
     unsigned int* obegin = nullptr;       // [nf] list length after octave 0 (the early edge-test launch covers [0, obegin))
     unsigned int* ranges = nullptr;       // [nf][OR_RANGE_STRIDE] first survivor of each octave, of each (octave, level) (k_survivor_ranges)
-    bool early_done = false;              // the early launch has been enqueued for this chunk
-    bool early_forked = false;            // ... on another stream: ev_edge marks its end
     size_t fwords = 0;
 };
 static void orient_scratch_plan(WsPlan& ws, const vslam_params& p, int nf, OrientScratch& s) {
@@ -1551,11 +1542,11 @@ static int make_orient_plan(vslam_ctx* c, const vslam_params& p, const vslam_bat
 // The edge test (Diff_of_Gauss.cpp:331-335) for the records octave 0 has appended.  Called on the stream
 // the list is written on, right behind that octave's compaction (`counts` is then the list length after
 // octave 0); the kernel itself goes to `other` (the Harris chain's stream, idle by then) so that it runs
-// beside the next octaves' scans instead of between them.
+// beside the next octaves' scans instead of between them - when the plan forks it (BatchPlan::early_edge_forked).
 static int enqueue_edge_flags_early(vslam_ctx* c, const vslam_params& p, const OrientPlan& pl, int nf, const uint8_t* pyr, size_t pframe,
-                                    const vslam_point* points, const unsigned int* counts, OrientScratch& s, hipStream_t other) {
+                                    const vslam_point* points, const unsigned int* counts, const OrientScratch& s, bool fork) {
+    const hipStream_t other = lane_stream(c, Lane::Harris);
     HIPCHK(c, hipMemcpyAsync(s.obegin, counts, sizeof(unsigned int) * (size_t)nf, hipMemcpyDeviceToDevice, c->stream));
-    const bool fork = other && other != c->stream;
     if (fork) {
         HIPCHK(c, hipEventRecord(c->ev_list0, c->stream));
         HIPCHK(c, hipStreamWaitEvent(other, c->ev_list0, 0));
@@ -1566,22 +1557,21 @@ static int enqueue_edge_flags_early(vslam_ctx* c, const vslam_params& p, const O
                (const unsigned int*)s.obegin, p.dog_cap, pyr, pframe, pl.g, s.flags, s.fwords);
         if (fork) HIPCHK(c, hipEventRecord(c->ev_edge, c->stream));
     }
-    s.early_done = true;
-    s.early_forked = fork;
     return VSLAM_OK;
 }
 
 // filterKeypoints for the keypoint lists of nf frames (kernels_orient_batch.hip.h), on the
-// context's current stream; the lists must be complete on that stream.
+// context's current stream; the lists must be complete on that stream.  `plan`: whether the early edge test has run for
+// this chunk and on which lane, and whether the per-octave launches spread over the idle side lanes.
 static int enqueue_orient_batch(vslam_ctx* c, const vslam_params& p, const vslam_batch_layout& L, const OrientPlan& pl, int nf, const uint8_t* pyr,
-                                size_t pframe, const vslam_point* points, const unsigned int* counts, OrientScratch& s,
-                                vslam_point* oriented, unsigned int* oriented_counts, hipStream_t side_a = nullptr, hipStream_t side_b = nullptr) {
+                                size_t pframe, const vslam_point* points, const unsigned int* counts, const OrientScratch& s,
+                                vslam_point* oriented, unsigned int* oriented_counts, const BatchPlan& plan) {
     const OrientBatchGeom& g = pl.g;
     const size_t scap = p.oriented_cap;
     const size_t fw = s.fwords;
-    if (s.early_done && s.early_forked) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_edge, 0));  // the two launches share a flag word
+    if (plan.early_edge_forked) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_edge, 0));  // the two launches share a flag word
     LAUNCH(c, "k_edge_flags", k_edge_flags, dim3((unsigned)((fw * 64 + 255) / 256), nf), dim3(256), points,
-           (const unsigned int*)(s.early_done ? s.obegin : nullptr), counts, p.dog_cap, pyr, pframe, g, s.flags, fw);
+           (const unsigned int*)(plan.early_edge ? s.obegin : nullptr), counts, p.dog_cap, pyr, pframe, g, s.flags, fw);
     SurvivorEntries se{s.flags, fw, s.surv};
     TRY(enqueue_compaction(c, se, fw, nf, s.cws, (unsigned int)scap, s.scounts, 0));
     LAUNCH(c, "k_survivor_ranges", k_survivor_ranges, dim3(nf), dim3(128), points, p.dog_cap, s.surv, s.scounts, (unsigned int)scap, L.n_octaves, s.ranges);
@@ -1591,7 +1581,8 @@ static int enqueue_orient_batch(vslam_ctx* c, const vslam_params& p, const vslam
     // The launches below are independent (each takes its own survivors, each writes its own mask words) and every one ends
     // on a tail of half-empty CUs: with two idle side streams at hand (the Harris chain's and the upsample's: both are
     // done long before the list is) they go out round-robin over three streams and share the chip.
-    const bool spread = side_a && side_b && side_a != c->stream && side_b != c->stream && side_a != side_b;
+    const bool spread = plan.spread;
+    const hipStream_t side_a = lane_stream(c, Lane::Harris), side_b = lane_stream(c, Lane::Up);
     hipStream_t lanes[3] = {c->stream, spread ? side_a : c->stream, spread ? side_b : c->stream};
     if (spread) {
         HIPCHK(c, hipEventRecord(c->ev_or_fork, c->stream));
@@ -1650,6 +1641,41 @@ static int enqueue_sift_batch(vslam_ctx* c, const vslam_params& p, const vslam_b
     // half-empty CUs (11.3 ms per 256-frame step against 10.1)
     const int gwg = 8 * (int)std::min<long>(1024, std::max<long>(16, 8192 / nf));
     LAUNCH(c, "k_sift_descriptors", F32_KERNEL(c, k_sift_descriptors_batch), dim3(gwg, nf), dim3(256), oriented, ocounts, p.oriented_cap, pyr, pframe, g, desc, defined);
+    return VSLAM_OK;
+}
+
+static int enqueue_harris_on(vslam_ctx* c, hipStream_t st, const HarrisChunk& h) {
+    StreamSwap sw(c, st);
+    return enqueue_harris(c, h.frames, h.fframe, h.rows, h.cols, h.nf, h.k, h.resp, h.mask, h.nms2, h.hflags, h.kps, h.cap, h.counts, h.cws);
+}
+
+// createPyramid (GaussPyramid.cpp:106-131) + initialKeypointDetection (Diff_of_Gauss.cpp:254) for the frames of one chunk,
+// with the chunk's other work enqueued where d.plan puts it: the one loop of the batched path and of vslam_pyramid_build_u8.
+static int enqueue_dog(vslam_ctx* c, DogChunk& d, const HarrisChunk* hc, const OrientPlan* opl, OrientScratch* os) {
+    // (why the gate octave and which work is held back behind it: vslam_batch_plan.h)
+    const BatchPlan& pl = d.plan;
+    const int n_oct = d.L.n_octaves;
+    TRY(d.begin(c));
+    struct TagReset {
+        vslam_ctx* c;
+        ~TagReset() { c->launch_tag = -1; }
+    } tag_reset{c};
+    for (int o = 0, oo = 0; o < n_oct; ++o) {
+        c->launch_tag = o;  // the timing hook's "name@o" (TimedScope) for every launch enqueued at this octave
+        TRY(d.octave(c, o));
+        if (hc && o == pl.harris_after) {
+            HIPCHK(c, hipStreamWaitEvent(lane_stream(c, pl.harris_lane), c->ev_oct[o], 0));
+            TRY(enqueue_harris_on(c, lane_stream(c, pl.harris_lane), *hc));
+        }
+        for (; oo < n_oct && pl.after[oo] == o; ++oo) {  // the scans due now, the held-back ones in order
+            TRY(d.scan_octave(c, oo, o));
+            if (oo == 0 && pl.early_edge) {  // on the stream the list is written on, behind octave 0's records
+                StreamSwap sw(c, lane_stream(c, pl.scan_lane));
+                TRY(enqueue_edge_flags_early(c, d.p, *opl, d.nf, d.out.pyr, d.out.pframe, d.out.points, d.out.counts, *os, pl.early_edge_forked));
+            }
+        }
+    }
+    if (pl.ev_chunk) HIPCHK(c, hipEventRecord(c->ev_chunk, c->stream));
     return VSLAM_OK;
 }
 
@@ -1721,15 +1747,21 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
     // Whole-batch launches: every kernel sees all frames (grid.z = frames), so even the coarse
     // octaves fill the chip.  Scratch: octave bases (+ u16 row sums of the non-tiled octaves).
     const int chunk = std::min(n_frames, 256);
-    const bool want_sitemap = dog && c->mx && !p.localize && !p.extrema_dense && p.extrema_window == 3;
     const std::vector<OctPlan> plans = plan_octaves(p.sigma0, L);
+    // the plan of a chunk (vslam_batch_plan.h): what does not change over the call here, the rest per chunk below
+    BatchPlanIn pin = batch_plan_input(c, p, L, plans, p.cols);
+    pin.nf = chunk;
+    pin.harris = harris;
+    pin.lists = out->dog_points && out->dog_counts;
+    pin.do_extrema = out->extrema_bits || pin.lists;
+    pin.bases_are_scratch = true;
     DogScratch s;
     OrientScratch os;
     float* resp_ws = nullptr;
     unsigned long long* hflags = nullptr;
     unsigned int* hcws = nullptr;
     WsPlan ws;
-    if (dog) dog_scratch_plan(ws, L, plans, chunk, s, want_sitemap);
+    if (dog) dog_scratch_plan(ws, L, plans, chunk, s, batch_plan(pin).sitemap);
     if (orient) orient_scratch_plan(ws, p, chunk, os);
     if (harris) {
         if (!out->response) ws.add(resp_ws, (size_t)chunk * N);
@@ -1737,80 +1769,42 @@ int vslam_detect_batch_dev(vslam_ctx* c, const vslam_params* pp, const uint8_t* 
         ws.add(hcws, compaction_ws_elems(harris_flag_words(p.rows, p.cols), chunk));
     }
     c->phase_marked = false;
-    c->pack_pending = false;  // the previous call joined its side streams back
     TRY(ws.commit(c));
     OrientPlan opl;
     if (orient) TRY(make_orient_plan(c, p, L, opl));
     // Fork: the Harris chain and the extrema/compaction chain run on the context's auxiliary streams beside the octave
     // kernels.  Measured on MI355X: +2.8 % (11.2k vs 10.9k frames/s) -- small, because every kernel of the batch is
     // VALU-issue-bound rather than HBM-bound; per-kernel durations grow accordingly when kernels share the chip.
-    // Under stream capture (hipGraph) no two SIDE streams of the call may wait on each other's events.  The topology is legal
-    // (fork from the origin stream, cross edges between the forked streams, all joined back) and every event is recorded on
-    // a stream that is already part of the capture; but this HIP runtime (ROCm 7.2's libamdhip64.so.7 and the copy torch 2.10
-    // bundles alike) never returns from hipStreamEndCapture then: a function that calls itself for every entry of a
-    // per-stream vector (the shape of hip::Stream::EndCapture over parallelCaptureStreams_) recurses 174,000 frames deep and
-    // the process dies of stack exhaustion - no HIP status is ever seen.  It was reproduced through this library and without
-    // it (profiles/r05_graph_try.json, profiles/r05_capture_cycle_repro.txt): two side streams that wait on each other's
-    // events are harmless by themselves and fatal as soon as each also waits on an origin-stream event again in between -
-    // which this library's side streams do on every octave's event.  The orientation stage has two such pairs - the early
-    // edge test (list stream -> Harris stream -> back) and the spread launches (list stream -> two idle side streams ->
-    // back); each alone reproduces the crash.  While a capture is on, both stay on the list stream; everything else forks
-    // from and joins to the main (origin) stream.
-    const bool capturing = stream_is_capturing(c);  // the nested forks stay out of a capture
+    // (the capture rule - no fork from one side stream to another while a capture is on - is batch_plan()'s)
+    pin.capturing = stream_is_capturing(c);
     // the shape of this call (the stream tuner and the join watchdog compare calls of one shape only)
     const unsigned long long call_key = ((unsigned long long)(unsigned)n_frames << 40) ^ ((unsigned long long)(unsigned)p.rows << 20) ^ (unsigned)p.cols ^
                                         ((unsigned long long)(p.localize + 2 * p.orient + 4 * p.extrema_dense + 8 * (out->descriptors != nullptr)) << 60) ^
                                         ((unsigned long long)(unsigned)p.n_octaves << 56) ^ ((unsigned long long)(c->mx ? 1 : 0) << 39);
     BatchFork fork{c};  // (an early return below drains the side streams)
-    TRY(fork.begin(call_key, dog && harris && n_frames >= 32, (size_t)n_frames * N >= ((size_t)16 << 20), capturing));
-    const bool side_streams = fork.side;
-    const hipStream_t sh = side_streams ? c->aux[0] : c->stream, sx = side_streams ? c->aux[1] : nullptr;  // Harris stream, extrema stream (nullptr = main)
+    TRY(fork.begin(call_key, dog && harris && n_frames >= 32, (size_t)n_frames * N >= ((size_t)16 << 20), pin.capturing));
+    pin.side = fork.side;
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int nf = std::min(chunk, n_frames - f0);
         const uint8_t* fr = d_frames + (size_t)f0 * frame_stride;
         const vslam_batch_out co = chunk_out(*out, p, L, f0);
-        auto do_harris = [&]() -> int {
-            StreamSwap sw(c, sh);
-            TRY(enqueue_harris(c, fr, frame_stride, p.rows, p.cols, nf, p.harris_k, co.response ? co.response : resp_ws, co.nms_mask, co.nms2,
-                               want_kps ? hflags : nullptr, want_kps ? co.harris_kps : nullptr, p.harris_cap, want_kps ? co.harris_counts : nullptr, hcws));
-            return VSLAM_OK;
-        };
+        pin.nf = nf;
+        pin.later_chunk = f0 > 0;
+        const BatchPlan plan = batch_plan(pin);
         // The Harris chain: without the DoG path or the side streams it is simply enqueued here.  With
         // them it goes to its own stream - at once for small batches, behind the last LDS-tiled octave
-        // kernel for large ones (enqueue_dog explains the gate) - and is enqueued from inside enqueue_dog,
-        // right after that octave's event, so that nothing enqueued on its stream later can get in front of it.
-        // (matrix path: starting the Harris chain at once, or behind octave 0 / 2 / 3 instead of 1, moved the step by less than
-        // +-1.5 % - 14.54 .. 14.90 ms on one box - so the gate stays where the default path has it)
-        const int harris_gate = (dog && side_streams) ? dog_side_gate(plans, nf) : -1;
-        if (harris && harris_gate < 0) TRY(do_harris());
+        // kernel for large ones (vslam_batch_plan.h explains the gate; enqueue_dog enqueues it there).
+        const HarrisChunk hc{fr, frame_stride, p.rows, p.cols, nf, p.harris_k, co.response ? co.response : resp_ws, co.nms_mask, co.nms2,
+                             want_kps ? hflags : nullptr, want_kps ? co.harris_kps : nullptr, p.harris_cap, want_kps ? co.harris_counts : nullptr, hcws};
+        if (harris && plan.harris_after < 0) TRY(enqueue_harris_on(c, lane_stream(c, plan.harris_lane), hc));
         if (dog) {
             const size_t pframe = L.pyramid_frame_bytes;
-            os.early_done = os.early_forked = false;
-            DogRun run;
-            run.side = sx;
-            run.up = side_streams ? c->aux[2] : nullptr;
-            run.later_chunk = f0 > 0;
-            run.bases_are_scratch = true;
-            // filterKeypoints' edge test for octave 0's records as soon as that octave's part of the list exists
-            run.after_list = [&](int o) -> int {
-                if (orient && o == 0 && L.n_octaves > 1)
-                    return enqueue_edge_flags_early(c, p, opl, nf, co.pyramid, pframe, co.dog_points, co.dog_counts, os, (side_streams && !capturing) ? sh : nullptr);
-                return VSLAM_OK;
-            };
-            run.after_octave = [&](int o) -> int {
-                if (harris && o == harris_gate) {
-                    HIPCHK(c, hipStreamWaitEvent(sh, c->ev_oct[o], 0));
-                    return do_harris();
-                }
-                return VSLAM_OK;
-            };
-            const bool ext = out->extrema_bits || (out->dog_points && out->dog_counts);
-            TRY(enqueue_dog(c, p, L, plans, fr, p.cols, frame_stride, nf, s,
-                            DogOut{co.pyramid, pframe, (unsigned long long*)co.extrema_bits, ext, co.dog_points, co.dog_counts}, run));
+            DogChunk d{p, L, plans, fr, (size_t)p.cols, frame_stride, nf, s,
+                       DogOut{co.pyramid, pframe, (unsigned long long*)co.extrema_bits, pin.do_extrema, co.dog_points, co.dog_counts}, plan};
+            TRY(enqueue_dog(c, d, harris ? &hc : nullptr, orient ? &opl : nullptr, &os));
             if (orient) {  // filterKeypoints behind the list, on the stream that produced it
-                StreamSwap sw(c, sx ? sx : c->stream);
-                TRY(enqueue_orient_batch(c, p, L, opl, nf, co.pyramid, pframe, co.dog_points, co.dog_counts, os, co.oriented_points, co.oriented_counts,
-                                         (side_streams && !capturing) ? sh : nullptr, (side_streams && !capturing) ? c->aux[2] : nullptr));
+                StreamSwap sw(c, lane_stream(c, plan.scan_lane));
+                TRY(enqueue_orient_batch(c, p, L, opl, nf, co.pyramid, pframe, co.dog_points, co.dog_counts, os, co.oriented_points, co.oriented_counts, plan));
                 if (co.oriented_survivors)
                     HIPCHK(c, hipMemcpyAsync(co.oriented_survivors, os.scounts, sizeof(unsigned int) * (size_t)nf, hipMemcpyDeviceToDevice, c->stream));
                 if (co.descriptors)
