@@ -776,6 +776,85 @@ int vslam_pose_host(vslam_ctx* ctx, const vslam_epipolar* model, const vslam_mat
                     const vslam_pose_params* params, vslam_pose* pose, vslam_pose_cand* candidates, double* points,
                     uint64_t* front_bits);
 
+/* ---------------------------------------------------------------- trajectory: pair poses chained into one world frame
+ * The step after the relative pose.  vslam_pose_dev leaves every pair with |t| = 1 and its points in its own query camera's
+ * frame and unit; this step recovers the scale of pair j relative to pair j - 1 from the points both pairs triangulated and
+ * chains the poses into one frame of coordinates.  The inputs are exactly what vslam_pose_dev read and wrote for n_pairs
+ * CONSECUTIVE pairs (pair j: query frame j, train frame j + 1): poses [n_pairs], matches [n_pairs][match_cap], match_counts,
+ * points [n_pairs][match_cap][3], front_bits [n_pairs][(match_cap + 63) / 64], and point_cap, the capacity of the frames' point
+ * lists: pair j's train indices and pair j + 1's query indices address the same set.  The point lists themselves are not
+ * read - the link is made by index.  The arithmetic is fixed here so that a CPU can restate it bit for bit
+ * (tests/chainref.py): IEEE f64, every + - * / sqrt rounded on its own, sums left to right as written, matrices row-major.
+ *
+ * m_j = min(match_counts[j], match_cap).  Record i of pair j is LIVE iff i < m_j, poses[j].best >= 0, bit i of the pair's
+ * front_bits is set, and query < point_cap and train < point_cap (as unsigned).  A record that is not live is never read
+ * through.
+ *
+ *  1. Link.  For pair j >= 1 and point index k < point_cap, prev_j[k] is the LOWEST i such that record i of pair j - 1 is live
+ *     and its train == k.  A live record b of pair j with query == q is linked to a = prev_j[q] if that exists.  Pair 0 has
+ *     no links.
+ *  2. Ratio of a linked record, with (R, t) = poses[j - 1], X = points[j - 1][a], Z = points[j][b]:
+ *       Y_i = ((R[i][0]*X0 + R[i][1]*X1) + R[i][2]*X2) + t_i;   dY = sqrt((Y0*Y0 + Y1*Y1) + Y2*Y2), dZ likewise from Z;
+ *       r = dY / dZ.   The ratio is USABLE iff r > 0 && r < +inf (a NaN fails both).
+ *  3. Median.  n_links[j] = the number of usable ratios of pair j (n_links[0] = 0); ratio[j] = the usable ratio of 0-based
+ *     rank (n_links[j] - 1) >> 1 in ascending order - the lower median -, 0.0 when n_links[j] == 0.  A value of the multiset:
+ *     no arithmetic, so neither the record order nor the split over workgroups plays a part.
+ *  4. Walk, sequential over j = 0 .. n_pairs - 1.  valid_j = poses[j].best >= 0;  linked_j = j >= 1 && valid_{j-1} && valid_j
+ *     && n_links[j] >= min_links.  Not linked - a segment starts: segment = j, scale = 1, W = I, w = 0.  Linked, with
+ *     (R, t, s) = (poses[j - 1].R, poses[j - 1].t, scale_{j-1}):  segment_j = segment_{j-1};  scale_j = scale_{j-1} * ratio[j];
+ *       W_j[i][k] = (R[i][0]*W[0][k] + R[i][1]*W[1][k]) + R[i][2]*W[2][k]   (W = W_{j-1});
+ *       w_j[i] = ((R[i][0]*w0 + R[i][1]*w1) + R[i][2]*w2) + s*t_i           (w = w_{j-1}).
+ *     Convention: x_camera_j = W_j x_world + w_j; the world is the query camera of the segment's first pair, in that pair's
+ *     unit.  The query camera's centre: C_i = -((W[0][i]*w0 + W[1][i]*w1) + W[2][i]*w2) (the negation is exact: -0.0 at a
+ *     segment start).  Ct: the same expression for the train camera (R_j W_j, R_j w_j + scale_j t_j), formed by the two
+ *     product rules above with (R, t, s) = (poses[j].R, poses[j].t, scale_j).  An invalid pair gets W = I, w = C = Ct = 0,
+ *     scale = 1, segment = j, linked = 0, valid = 0.  ratio and n_links are those of step 3 whether the pair is linked or not.
+ *  5. Map.  For a valid pair j and every i < m_j: record i live: c_k = scale_j*X_k - w_k, X = points[j][i];
+ *     M_i = (W[0][i]*c0 + W[1][i]*c1) + W[2][i]*c2, the point in world coordinates; not live: the quiet NaN three times.  Rows
+ *     past m_j, and all rows of an invalid pair, are left untouched.
+ * Every NaN in a double output of this section is written as 0x7ff8000000000000.
+ *
+ * Scratch (the context's): the link table, (n_pairs - 1) * point_cap * 4 bytes - 67 MB at 255 x 65536 -, and the ratio keys,
+ * (n_pairs - 1) * match_cap * 8 bytes - 134 MB at 255 x 65536; an allocation that fails is VSLAM_ERR_NOMEM. */
+typedef struct {
+    uint32_t min_links; /* >= 1: the usable ratios a pair needs to be chained to the pair before it */
+} vslam_chain_params;
+typedef struct {
+    double W[9], w[3]; /* x_camera_j = W x_world + w (the query camera of pair j) */
+    double C[3], Ct[3]; /* centres of the query and the train camera in the world */
+    double scale;      /* pair j's unit of length in the segment's: world length = scale * pair length */
+    double ratio;      /* step 3 */
+    uint32_t n_links;  /* step 3 */
+    int32_t segment;   /* the pair the segment started at */
+    int32_t linked;
+    int32_t valid;
+} vslam_chain; /* 176 bytes */
+/* Like vslam_pose_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size; /* = sizeof(vslam_chain_out) */
+    vslam_chain* chain; /* [n_pairs], required: the walk's records */
+    size_t chain_bytes;
+    double* map;        /* [n_pairs][match_cap][3] optional: step 5 */
+    size_t map_bytes;
+    int32_t* links;     /* [n_pairs][match_cap] optional: for i < m_j the linked a, or -1; the rest untouched */
+    size_t links_bytes;
+    double* ratios;     /* [n_pairs][match_cap] optional: for i < m_j r as computed when linked, the quiet NaN otherwise */
+    size_t ratios_bytes;
+} vslam_chain_out;
+/* DEVICE pointers, all required.  Asynchronous on the context stream, never waits on the host (the counts are read on the
+ * device, the grids are sized from the capacities).  VSLAM_ERR_INVALID before any launch - and before the context is looked
+ * at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing; 1 is one segment with no links),
+ * min_links == 0, match_cap or point_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.
+ * Not for stream capture. */
+int vslam_chain_dev(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                    uint32_t match_cap, const double* points, const uint64_t* front_bits, uint32_t point_cap, int n_pairs,
+                    const vslam_chain_params* params, const vslam_chain_out* out);
+/* The same call over HOST arrays, all n_pairs pairs at once, synchronous (a convenience path: device buffers per call).  The
+ * rows the device call leaves untouched keep the caller's bytes.  Errors as for vslam_chain_dev. */
+int vslam_chain_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                     uint32_t match_cap, const double* points, const uint64_t* front_bits, uint32_t point_cap, int n_pairs,
+                     const vslam_chain_params* params, const vslam_chain_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

@@ -35,6 +35,8 @@ EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid",
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
+CHAIN_DTYPE = np.dtype([("W", "<f8", (9,)), ("w", "<f8", (3,)), ("C", "<f8", (3,)), ("Ct", "<f8", (3,)), ("scale", "<f8"), ("ratio", "<f8"), ("n_links", "<u4"),
+                        ("segment", "<i4"), ("linked", "<i4"), ("valid", "<i4")], align=True)  # vslam_chain, 176 bytes
 
 
 class VslamError(RuntimeError):
@@ -138,6 +140,21 @@ class PoseOut(C.Structure):
                 ("front_bits_bytes", C.c_size_t)]
 
 
+class ChainParams(C.Structure):
+    _fields_ = [("min_links", C.c_uint32)]
+
+
+class Chain(C.Structure):
+    _fields_ = [("W", C.c_double * 9), ("w", C.c_double * 3), ("C", C.c_double * 3), ("Ct", C.c_double * 3), ("scale", C.c_double), ("ratio", C.c_double),
+                ("n_links", C.c_uint32), ("segment", C.c_int32), ("linked", C.c_int32), ("valid", C.c_int32)]
+
+
+class ChainOut(C.Structure):
+    """vslam_chain_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("chain", C.c_void_p), ("chain_bytes", C.c_size_t), ("map", C.c_void_p), ("map_bytes", C.c_size_t),
+                ("links", C.c_void_p), ("links_bytes", C.c_size_t), ("ratios", C.c_void_p), ("ratios_bytes", C.c_size_t)]
+
+
 class PyramidInfo(C.Structure):
     _fields_ = [
         ("n_octaves", C.c_int), ("n_levels", C.c_int), ("n_dogs", C.c_int), ("sigma0", C.c_double),
@@ -216,6 +233,8 @@ SIGNATURES = {
     "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
     "vslam_pose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(PoseParams), C.POINTER(PoseOut)]),
     "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
+    "vslam_chain_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
+    "vslam_chain_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -840,6 +859,65 @@ class Context:
         self._chk(lib().vslam_pose_host(self._h, mod.ctypes.data, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp), C.byref(prm), pose.ctypes.data,
                                         _ptr(cand), _ptr(pts), _ptr(bits)), "vslam_pose_host")
         return pose[0], cand, (pts[:m] if want_points and int(pose["best"][0]) >= 0 else None), bits
+
+    def chain(self, poses, matches, match_counts, points, front_bits, point_cap: int, min_links: int = 16, n_pairs: int | None = None, chain=None,
+              map=None, links=None, ratios=None):
+        """vslam_chain_dev: the poses and points pose() wrote for n consecutive pairs (pair j: frames j and j + 1), chained with the
+        recovered scale into one world frame per segment; asynchronous on the context stream.  poses, matches [n, match_cap, 3],
+        match_counts, points float64 [n, match_cap, 3] and front_bits [n, (match_cap + 63) // 64] are the tensors pose() read and
+        wrote; point_cap is the capacity of the frames' point lists.  Outputs, CUDA tensors: chain - any contiguous tensor of
+        n_pairs * 176 bytes (CHAIN_DTYPE after .cpu().numpy().view), map float64 [n, match_cap, 3] (world coordinates), links int32
+        [n, match_cap], ratios float64 [n, match_cap]."""
+        tensors = dict(poses=poses, matches=matches, match_counts=match_counts, points=points, front_bits=front_bits, chain=chain, map=map, links=links,
+                       ratios=ratios)
+        for name, t in tensors.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"chain: {name} must be a contiguous tensor on cuda:{self.device}")
+        for name in ("poses", "matches", "match_counts", "points", "front_bits", "chain"):
+            if tensors[name] is None:
+                raise ValueError(f"chain: {name} is required")
+        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12:
+            raise ValueError("chain: matches must be [n, match_cap, 3] 4-byte elements")
+        n = matches.shape[0] if n_pairs is None else int(n_pairs)
+        cap = matches.shape[1]
+        size = lambda t: t.numel() * t.element_size()
+        if (matches.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n or size(poses) < n * 112 or size(points) < n * cap * 24
+                or size(front_bits) < n * ((cap + 63) // 64) * 8):
+            raise ValueError("chain: fewer sets than pairs")
+        co = _fill_out(ChainOut(), dict(chain=chain, map=map, links=links, ratios=ratios))
+        prm = ChainParams(int(min_links))
+        self._chk(lib().vslam_chain_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, points.data_ptr(),
+                                        front_bits.data_ptr(), int(point_cap), n, C.byref(prm), C.byref(co)), "vslam_chain_dev")
+
+    def chain_host(self, poses, matches, match_counts, points, front_bits, point_cap: int, min_links: int = 16, map=None, links=None, ratios=None):
+        """vslam_chain_host: the same call over numpy arrays - poses [n] POSE_DTYPE, matches [n, match_cap] MATCH_DTYPE, match_counts
+        [n], points float64 [n, match_cap, 3], front_bits uint64 [n, (match_cap + 63) // 64] - -> chain [n] CHAIN_DTYPE.  map float64
+        [n, match_cap, 3], links int32 [n, match_cap] and ratios float64 [n, match_cap] are written in place when given (C-contiguous
+        arrays of exactly that type); the rows the call leaves untouched keep their bytes."""
+        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
+        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(ps)
+        if mt.ndim != 2 or mt.shape[0] != n:
+            raise ValueError("chain_host: matches must be [n, match_cap]")
+        cap = mt.shape[1]
+        cnt = np.ascontiguousarray(match_counts).astype(np.uint32).reshape(-1)
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        fb = np.ascontiguousarray(front_bits).view(np.uint64)
+        if len(cnt) != n or pts.size != n * cap * 3 or fb.size != n * ((cap + 63) // 64):
+            raise ValueError("chain_host: one count, match_cap points and (match_cap + 63) // 64 words per pair")
+        for name, a, dt, size in (("map", map, np.float64, n * cap * 3), ("links", links, np.int32, n * cap), ("ratios", ratios, np.float64, n * cap)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
+                raise ValueError(f"chain_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        chain = np.zeros(max(n, 1), CHAIN_DTYPE)
+        co = ChainOut(C.sizeof(ChainOut), chain.ctypes.data, chain.nbytes)
+        for name, a in (("map", map), ("links", links), ("ratios", ratios)):
+            if a is not None:
+                setattr(co, name, a.ctypes.data)
+                setattr(co, name + "_bytes", a.nbytes)
+        prm = ChainParams(int(min_links))
+        self._chk(lib().vslam_chain_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, pts.ctypes.data, fb.ctypes.data, int(point_cap), n,
+                                         C.byref(prm), C.byref(co)), "vslam_chain_host")
+        return chain[:n]
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -92,4 +92,10 @@ G3 inline void g3_store_word(unsigned long long* words, size_t j, unsigned int f
     if (store) words[j * fwords + (i >> 6)] = w;
 }
 
+#ifdef __HIPCC__
+// A NaN leaves as the quiet NaN 0x7ff8000000000000: IEEE fixes neither the sign nor the payload of a NaN an operation makes.
+// (k_pose_points and the trajectory kernels, kernels_chain.hip.h.)
+__device__ __forceinline__ double pose_canonical(double x) { return x == x ? x : __longlong_as_double(0x7ff8000000000000ll); }
+#endif
+
 }  // namespace vslam

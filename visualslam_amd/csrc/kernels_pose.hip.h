@@ -186,9 +186,6 @@ __global__ __launch_bounds__(POSE_PAIR_WG) void k_pose_select(const vslam_pose_c
     poses[j] = out;
 }
 
-// A NaN leaves as the quiet NaN 0x7ff8000000000000: IEEE fixes neither the sign nor the payload of a NaN an operation makes.
-__device__ __forceinline__ double pose_canonical(double x) { return x == x ? x : __longlong_as_double(0x7ff8000000000000ll); }
-
 // grid = (record blocks of 256, pairs): X of every record below the count (points may be null), and bit i % 64 of word i / 64
 // = record i is in front under the winner (bits may be null).  Without a winner the words are zero and no point is written.
 __global__ __launch_bounds__(POSE_REC_WG) void k_pose_points(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts,

@@ -1,0 +1,100 @@
+// The trajectory step of the C ABI (include/vslam.h, "trajectory"): argument checks and sizing (vslam_chain_plan.h), scratch
+// and launches of kernels_chain.hip.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/vslam.h"
+#include "kernels_chain.hip.h"
+#include "vslam_ctx.h"
+#include "vslam_launch.h"
+#include "vslam_chain_plan.h"
+
+using namespace vslam;
+
+extern "C" {
+
+int vslam_chain_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
+                    const double* points, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain_params* prm,
+                    const vslam_chain_out* out) {
+    static_assert(sizeof(vslam_chain) == 176 && sizeof(vslam_pose) == 112 && sizeof(vslam_match) == 12, "record layouts");
+    if (const char* why = chain_check_args(poses, matches, match_counts, match_cap, points, front_bits, point_cap, n_pairs, prm, out))
+        return fail(c, VSLAM_ERR_INVALID, std::string("chain: ") + why);
+    TRY(usable_ctx(c));
+    if (n_pairs == 0) return VSLAM_OK;
+
+    const ChainPlan pl = chain_plan(match_cap, point_cap, n_pairs);
+    unsigned int *prev = nullptr, *usable = nullptr;
+    unsigned long long* keys = nullptr;
+    double* median = nullptr;
+    WsPlan ws;
+    ws.add(prev, pl.table_elems);
+    ws.add(keys, pl.key_elems);
+    ws.add(usable, pl.pair_elems);
+    ws.add(median, pl.pair_elems);
+    TRY(ws.commit(c));
+
+    const ChainIn in{poses, matches, match_counts, points, reinterpret_cast<const unsigned long long*>(front_bits), match_cap, pl.fwords, point_cap};
+    const dim3 records(pl.rec_blocks, n_pairs);
+    HIPCHK(c, hipMemsetAsync(usable, 0, pl.pair_elems * sizeof(unsigned int), c->stream));
+    if (pl.link_pairs) {
+        HIPCHK(c, hipMemsetAsync(prev, 0xff, pl.table_elems * sizeof(unsigned int), c->stream));
+        LAUNCH(c, "k_chain_link", k_chain_link, dim3(pl.rec_blocks, pl.link_pairs), dim3(CHAIN_REC_WG), in, prev);
+    }
+    if (pl.link_pairs || out->links || out->ratios)  // (pair 0 alone has no ratios: only its rows of links and ratios to write)
+        LAUNCH(c, "k_chain_ratio", k_chain_ratio, records, dim3(CHAIN_REC_WG), in, prev, keys, usable, out->links, out->ratios);
+    if (pl.link_pairs)
+        LAUNCH(c, "k_chain_median", k_chain_median, dim3(pl.link_pairs), dim3(CHAIN_MEDIAN_WG), keys, match_counts, match_cap, usable, median);
+    LAUNCH(c, "k_chain_walk", k_chain_walk, dim3(1), dim3(1), poses, usable, median, n_pairs, prm->min_links, out->chain);
+    if (out->map) LAUNCH(c, "k_chain_map", k_chain_map, records, dim3(CHAIN_REC_WG), in, out->chain, out->map);
+    return VSLAM_OK;
+}
+
+int vslam_chain_host(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
+                     const double* points, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain_params* prm,
+                     const vslam_chain_out* out) {
+    if (const char* why = chain_check_args(poses, matches, match_counts, match_cap, points, front_bits, point_cap, n_pairs, prm, out))
+        return fail(c, VSLAM_ERR_INVALID, std::string("chain_host: ") + why);
+    TRY(usable_ctx(c));
+    if (n_pairs == 0) return VSLAM_OK;
+
+    const size_t np = (size_t)n_pairs, recs = np * match_cap, words = np * twoview_fwords(match_cap);
+    DevBufs dev;
+    vslam_pose* d_poses = nullptr;
+    vslam_match* d_matches = nullptr;
+    uint32_t* d_counts = nullptr;
+    double* d_points = nullptr;
+    uint64_t* d_bits = nullptr;
+    TRY(dev.put(c, d_poses, poses, np));
+    TRY(dev.put(c, d_matches, matches, recs));
+    TRY(dev.put(c, d_counts, match_counts, np));
+    TRY(dev.put(c, d_points, points, recs * 3));
+    TRY(dev.put(c, d_bits, front_bits, words));
+    // the optional outputs go up first: the rows the call leaves untouched come back as the caller had them
+    vslam_chain_out d{};
+    d.struct_size = sizeof(d);
+    TRY(dev.get(c, d.chain, np));
+    d.chain_bytes = np * sizeof(vslam_chain);
+    if (out->map) {
+        TRY(dev.put(c, d.map, static_cast<const double*>(out->map), recs * 3));
+        d.map_bytes = recs * 3 * sizeof(double);
+    }
+    if (out->links) {
+        TRY(dev.put(c, d.links, static_cast<const int32_t*>(out->links), recs));
+        d.links_bytes = recs * sizeof(int32_t);
+    }
+    if (out->ratios) {
+        TRY(dev.put(c, d.ratios, static_cast<const double*>(out->ratios), recs));
+        d.ratios_bytes = recs * sizeof(double);
+    }
+    TRY(vslam_chain_dev(c, d_poses, d_matches, d_counts, match_cap, d_points, d_bits, point_cap, n_pairs, prm, &d));
+    HIPCHK(c, hipMemcpyAsync(out->chain, d.chain, np * sizeof(vslam_chain), hipMemcpyDeviceToHost, c->stream));
+    if (out->map) HIPCHK(c, hipMemcpyAsync(out->map, d.map, recs * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (out->links) HIPCHK(c, hipMemcpyAsync(out->links, d.links, recs * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (out->ratios) HIPCHK(c, hipMemcpyAsync(out->ratios, d.ratios, recs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
+}
+
+}  // extern "C"

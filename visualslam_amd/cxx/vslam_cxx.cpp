@@ -501,3 +501,29 @@ vslam::Pose vslam::relativePose(const vslam_epipolar& model, const std::vector<v
     if (out.pose.best < 0) out.points.clear();
     return out;
 }
+
+vslam::Trajectory vslam::chainPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                                    uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
+                                    const vslam_chain_params& params) {
+    const size_t n = poses.size(), recs = n * matchCap;
+    require(n <= 65535 && matchCounts.size() == n && matches.size() == recs && points.size() == recs * 3 &&
+                frontBits.size() == n * (((size_t)matchCap + 63) / 64),
+            "chainPoses: one count, matchCap records, matchCap points and (matchCap + 63) / 64 words per pair");
+    vslam::Trajectory out;
+    out.chain.resize(n);
+    out.map.assign(recs * 3, 0.0);
+    out.links.assign(recs, -1);
+    out.ratios.assign(recs, 0.0);
+    if (n == 0) return out;
+    vslam_chain_out o{};
+    o.struct_size = sizeof(o);
+    o.chain = out.chain.data(), o.chain_bytes = n * sizeof(vslam_chain);
+    o.map = out.map.data(), o.map_bytes = out.map.size() * sizeof(double);
+    o.links = out.links.data(), o.links_bytes = out.links.size() * sizeof(int32_t);
+    o.ratios = out.ratios.data(), o.ratios_bytes = out.ratios.size() * sizeof(double);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_chain_host(c, poses.data(), matches.data(), matchCounts.data(), matchCap, points.data(), frontBits.data(), pointCap, (int)n, &params,
+                                  &o),
+                 c, "chainPoses");
+    return out;
+}

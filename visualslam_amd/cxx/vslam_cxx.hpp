@@ -211,4 +211,19 @@ struct Pose {
 };
 Pose relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                   const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera);
+
+// The step after that over a sequence: the poses and points of consecutive pairs (pair j: frames j and j + 1) chained with the
+// recovered scale into one world frame per segment, on the GPU (vslam_chain_host; the link, the median ratio, the walk and the
+// map are stated in include/vslam.h).  The inputs are what relativePose gave for every pair, laid side by side at one
+// capacity: matches [pairs][matchCap], matchCounts [pairs], points [pairs][matchCap][3], frontBits [pairs][(matchCap + 63) / 64];
+// pointCap is the capacity of the frames' point lists.
+struct Trajectory {
+    std::vector<vslam_chain> chain;  // [pairs]: W, w (x_camera = W x_world + w), the camera centres, scale, segment
+    std::vector<double> map;         // [pairs][matchCap][3], world coordinates; NaN: the record is not live; 0: past the count
+    std::vector<int32_t> links;      // [pairs][matchCap]: the linked record of the pair before, or -1
+    std::vector<double> ratios;      // [pairs][matchCap]: the distance ratio of a linked record, NaN otherwise
+};
+Trajectory chainPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                      uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
+                      const vslam_chain_params& params = {16});
 }  // namespace vslam
