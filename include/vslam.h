@@ -596,7 +596,7 @@ int vslam_match_host(vslam_ctx* ctx, const float* query, const uint8_t* query_de
 /* ---------------------------------------------------------------- two-view geometry
  * The step after matching (the reference's README: "3. 3D Reconstruction - Epipolar Geometry"): the fundamental matrix of
  * every pair, by RANSAC over the match list vslam_match_dev wrote and the point lists vslam_detect_batch_dev wrote, and the
- * inlier subset of each list.  A fixed number of hypotheses, no adaptive stop, no final least-squares refit.  The arithmetic
+ * inlier subset of each list.  A fixed number of hypotheses, no adaptive stop; the least-squares refit is a stage of its own (vslam_refit_dev).  The arithmetic
  * is fixed here so that a CPU can restate it bit for bit (tests/epiref.py).  Everything is IEEE f64; every + - * / sqrt is
  * rounded on its own (no fused multiply-add); a sum of more than two terms runs left to right as written, (a + b) + c.
  *
@@ -689,6 +689,96 @@ int vslam_epipolar_host(vslam_ctx* ctx, const vslam_match* matches, size_t n_mat
                         const vslam_point* train_points, size_t n_train, const vslam_epipolar_params* params, vslam_epipolar* model,
                         uint64_t* inlier_bits, vslam_match* inliers, size_t inlier_cap, size_t* n_inliers,
                         vslam_epipolar_hyp* hypotheses);
+
+/* ---------------------------------------------------------------- fundamental matrix: least-squares refit over the inliers
+ * The step between vslam_epipolar_dev and vslam_pose_dev: the winning minimal hypothesis is replaced by the normalised 8-point
+ * model over ALL its inliers, the inliers are classified again under the new F, and so on for a fixed number of rounds; a
+ * round whose model has fewer inliers than the one before it is dropped, so the result never has fewer inliers than the
+ * input.  Inputs: the `models` buffer vslam_epipolar_dev wrote, the FULL match list it read (not the inlier list: membership
+ * is computed here) and the point lists.  Coordinates, "trusted" and m = min(match_counts[j], match_cap) are those of the
+ * two-view geometry section.  IEEE f64, every + - * / sqrt rounded on its own, sums of a few terms left to right as written.
+ * This is the first stage with a floating-point sum over the records of a pair, so the order of that sum is fixed here
+ * (tests/refitref.py restates it bit for bit).
+ *
+ * A record is a MEMBER under F iff it is trusted and passes the inlier test of the two-view section under F with max_dist2.
+ *
+ * The ordered sum, written SUM(t), of a term t(i) over the records of a pair.  A record that is not a member contributes
+ * +0.0.  Block b covers records 4096*b .. 4096*b + 4095.  Slot l (0 .. 255) of a block starts at +0.0 and adds, in this
+ * order, the terms of records 4096*b + 256*k + l for k = 0 .. 15, skipping every record at or past m.  Then for h = 128, 64,
+ * 32, 16, 8, 4, 2, 1:  s_l = s_l + s_(l+h) for every l < h, all from the values of the step before; B_b = s_0.  The pair's
+ * sum is ((B_0 + B_1) + B_2) + ... over the (m + 4095) / 4096 blocks, and +0.0 for m = 0.  The result depends on m and the
+ * terms only: not on match_cap, not on the grid, not on the device.
+ *
+ * Per pair.  F_cur = models_in[j].F, n_cur = the number of members under F_cur (an integer), n_before = n_cur, accepted = 0.
+ * A pair with models_in[j].best < 0 is copied through unchanged with stop = 5 and n_before = n_after = accepted = 0.
+ * Round 1 .. rounds, until a stop:
+ *  1. n_cur < 8: stop = 1.
+ *  2. Normalisation per side, members under F_cur, n = (double)n_cur:  cx = SUM(x) / n;  cy = SUM(y) / n;
+ *     d = SUM(sqrt(dx*dx + dy*dy)) / n with dx = x - cx, dy = y - cy;  d zero or not finite (either side): stop = 2;
+ *     s = 1.4142135623730951 / d; the normalised point is ((x - cx) * s, (y - cy) * s).  (Both sides' centroids come before
+ *     either side's d is looked at.)
+ *  3. Moment matrix.  a = the row of step 2 of the two-view model from the member's normalised (x, y), (x', y'):
+ *     [x'*x, x'*y, x', y'*x, y'*y, y', x, y, 1].  M[p][q] = SUM(a_p * a_q) for p <= q - 45 sums, M[8][8] = SUM(1.0) -,
+ *     mirrored below the diagonal.
+ *  4. Eigenvector.  S = M, V = the 9 x 9 identity.  VSLAM_REFIT_SWEEPS sweeps of cyclic Jacobi over the pairs (p, q), p < q,
+ *     row-major ((0,1), (0,2) .. (0,8), (1,2) .. (7,8)); a pair with S[p][q] == 0 is skipped; theta, t, c, s as in step 4 of
+ *     the two-view model;  S[p][p] -= t * S[p][q];  S[q][q] += t * S[p][q];  for every r not in {p, q}, from the old values:
+ *     S[r][p] = c*S[r][p] - s*S[r][q];  S[r][q] = s*S[r][p] + c*S[r][q]  (S stays symmetric);  S[p][q] = 0;  for i = 0 .. 8:
+ *     V[i][p] = c*V[i][p] - s*V[i][q];  V[i][q] = s*V[i][p] + c*V[i][q].   f = column k of V, k the smallest S[k][k] (lowest k
+ *     on ties; a NaN is never smaller).
+ *  5. F_new from f (row-major) by steps 4, 5 and 6 of the two-view model verbatim - rank 2, Tt^T F Tq with the (s, cx, cy) of
+ *     step 2 here, Frobenius norm 1 -; the norm zero or not finite: stop = 3.
+ *  6. n_new = the number of members under F_new.  n_new >= n_cur: F_cur = F_new, n_cur = n_new, accepted += 1; otherwise
+ *     stop = 4.
+ * All rounds done without a stop: stop = 0.  After a stop the pair does nothing more.  Output: models[j] = models_in[j] with
+ * F = F_cur and n_inliers = n_cur (n_matches, best, n_valid copied); n_after = n_cur >= n_before.  The inlier outputs are the
+ * members under the output F, whatever its stop (vslam_epipolar_dev writes F = 0 with best < 0: no record is a member then).
+ * VSLAM_REFIT_SWEEPS was fixed by measurement: from 6 sweeps on, every sweep count up to 20 gives the same f
+ * bit for bit on every planted scene and hostile fixture of the tests; the constant is that plus two. */
+#define VSLAM_REFIT_SWEEPS 8
+typedef struct {
+    uint32_t rounds;  /* 1 .. 8 */
+    double max_dist2; /* as vslam_epipolar_params: squared Sampson distance in pixels^2, finite and positive */
+} vslam_refit_params;
+typedef struct {
+    uint32_t n_before, n_after; /* members under the input F / under the output F */
+    uint32_t accepted;          /* rounds whose refit was kept */
+    int32_t stop;               /* 0: ran all rounds, 1: fewer than 8 members, 2: degenerate normalisation, 3: model invalid
+                                 * (step 5), 4: the refit had fewer inliers, 5: no input model */
+} vslam_refit;                  /* 16 bytes */
+/* Like vslam_epipolar_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;      /* = sizeof(vslam_refit_out) */
+    vslam_epipolar* models;  /* [n_pairs], required; may be the very pointer passed as models_in, must not otherwise overlap it */
+    size_t models_bytes;
+    vslam_refit* info;       /* [n_pairs] optional */
+    size_t info_bytes;
+    uint64_t* inlier_bits;   /* [n_pairs][(match_cap + 63) / 64] optional: bit i % 64 of word i / 64 = record i is a member under
+                              * the output F; the first (n_matches + 63) / 64 words of a pair are written, the rest untouched */
+    size_t inlier_bits_bytes;
+    vslam_match* inliers;    /* [n_pairs][inlier_cap] optional: the member records, list order kept */
+    size_t inliers_bytes;
+    uint32_t* inlier_counts; /* [n_pairs], required with inliers: totals (may exceed inlier_cap) */
+    size_t inlier_counts_bytes;
+    uint32_t inlier_cap;
+} vslam_refit_out;
+/* Pair j reads models_in[j] and the lists as vslam_epipolar_dev does (DEVICE pointers).  Asynchronous on the context stream,
+ * never waits on the host (the counts are read on the device, the grids are sized from the capacities, a stopped pair's
+ * workgroups leave at once); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch - and before the context is
+ * looked at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing), rounds outside 1 .. 8, a
+ * max_dist2 that is not finite or not positive, match_cap / query_cap / train_cap == 0, an undersized buffer, inliers without
+ * inlier_counts or with inlier_cap == 0; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_refit_dev(vslam_ctx* ctx, const vslam_epipolar* models_in, const vslam_match* matches, const uint32_t* match_counts,
+                    uint32_t match_cap, const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points,
+                    uint32_t train_cap, int n_pairs, const vslam_refit_params* params, const vslam_refit_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call).  model_in and model are required (they
+ * may be the same record); info, inlier_bits [(n_matches + 63) / 64] and (inliers [inlier_cap], n_inliers) are each optional;
+ * *n_inliers is the total, which may exceed inlier_cap.  n_query / n_train are the capacities the indices are checked
+ * against.  Errors as for vslam_refit_dev. */
+int vslam_refit_host(vslam_ctx* ctx, const vslam_epipolar* model_in, const vslam_match* matches, size_t n_matches,
+                     const vslam_point* query_points, size_t n_query, const vslam_point* train_points, size_t n_train,
+                     const vslam_refit_params* params, vslam_epipolar* model, vslam_refit* info, uint64_t* inlier_bits,
+                     vslam_match* inliers, size_t inlier_cap, size_t* n_inliers);
 
 /* ---------------------------------------------------------------- relative pose and triangulation
  * The step after the fundamental matrix: the camera motion of every pair and the 3-D point of every match record, from the

@@ -52,8 +52,9 @@ def measure(ctx, label, models, lists, counts, qpts, tpts, runs):
                 pairs_with_a_pose=int((hp["best"] >= 0).sum()), records_in_front=int(hp["n_front"].sum()))
 
 
-def workload_lists(ctx, frames_n, rows, cols, octaves):
-    """detect -> describe -> match -> epipolar on the synthetic frames -> (models, inliers, inlier counts, points of the pairs)."""
+def workload_lists(ctx, frames_n, rows, cols, octaves, full_lists=False):
+    """detect -> describe -> match -> epipolar on the synthetic frames -> (models, inliers, inlier counts, points of the pairs);
+    full_lists: the match lists epipolar read in place of its inlier lists (tools/bench_refit.py)."""
     frames = synth.frames_torch(frames_n, rows, cols, stream_id=0, device=DEV, noise_every=2)
     p = capi.default_params(rows, cols, n_octaves=octaves, localize=1, orient=1)
     L = capi.batch_layout(p)
@@ -77,7 +78,7 @@ def workload_lists(ctx, frames_n, rows, cols, octaves):
     torch.cuda.synchronize()
     info = dict(frames=n, rows=rows, cols=cols, octaves=octaves, oriented_cap=int(cap), oriented_points=int(c.sum()), accepted_matches=int(counts.sum()),
                 inlier_matches=int(icounts.sum()))
-    return (models, inliers, icounts, pts[:-1], pts[1:]), info
+    return ((models, matches, counts, pts[:-1], pts[1:]) if full_lists else (models, inliers, icounts, pts[:-1], pts[1:])), info
 
 
 def planted_lists(ctx, pairs, m, model_from=2048):

@@ -33,6 +33,7 @@ NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4"
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
+REFIT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4")], align=True)  # vslam_refit, 16 bytes
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
 CHAIN_DTYPE = np.dtype([("W", "<f8", (9,)), ("w", "<f8", (3,)), ("C", "<f8", (3,)), ("Ct", "<f8", (3,)), ("scale", "<f8"), ("ratio", "<f8"), ("n_links", "<u4"),
@@ -118,6 +119,21 @@ class EpipolarOut(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("inlier_bits", C.c_void_p),
                 ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t), ("inlier_counts", C.c_void_p),
                 ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t)]
+
+
+class RefitParams(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("max_dist2", C.c_double)]
+
+
+class Refit(C.Structure):
+    _fields_ = [("n_before", C.c_uint32), ("n_after", C.c_uint32), ("accepted", C.c_uint32), ("stop", C.c_int32)]
+
+
+class RefitOut(C.Structure):
+    """vslam_refit_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("info", C.c_void_p), ("info_bytes", C.c_size_t),
+                ("inlier_bits", C.c_void_p), ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t),
+                ("inlier_counts", C.c_void_p), ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32)]
 
 
 class PoseParams(C.Structure):
@@ -231,6 +247,8 @@ SIGNATURES = {
     "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_epipolar_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(EpipolarParams), C.POINTER(EpipolarOut)]),
     "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
+    "vslam_refit_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(RefitParams), C.POINTER(RefitOut)]),
+    "vslam_refit_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(RefitParams), _P, _P, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_pose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(PoseParams), C.POINTER(PoseOut)]),
     "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
     "vslam_chain_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
@@ -825,6 +843,43 @@ class Context:
                                             None if inl is None else inl.ctypes.data, cap, C.byref(total) if want_inliers else None, _ptr(hyp)),
                   "vslam_epipolar_host")
         return (model[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None, hyp)
+
+    def refit(self, models_in, matches, match_counts, query_points, train_points, n_pairs: int | None = None, rounds: int = 4, max_dist2: float = 4.0,
+              models=None, info=None, inlier_bits=None, inliers=None, inlier_counts=None):
+        """vslam_refit_dev: the least-squares refit of every pair's fundamental matrix over its inliers, between epipolar() and
+        pose(); asynchronous on the context stream.  models_in: the tensor epipolar() wrote; matches / match_counts: the FULL list
+        epipolar() read.  Outputs, CUDA tensors: models n_pairs * 88 bytes (may be models_in itself), info n_pairs * 16 bytes
+        (REFIT_DTYPE), inlier_bits / inliers / inlier_counts as epipolar()'s, under the output F."""
+        outs = dict(models=models, info=info, inlier_bits=inlier_bits, inliers=inliers, inlier_counts=inlier_counts)
+        n = self._two_view_lists("refit", n_pairs, "models", dict(models_in=models_in, matches=matches, match_counts=match_counts, query_points=query_points, train_points=train_points, **outs))
+        if models_in.numel() * models_in.element_size() < n * 88:
+            raise ValueError("refit: models_in must hold n_pairs * 88 bytes")
+        ro = _fill_out(RefitOut(), outs)
+        if inliers is not None:
+            ro.inlier_cap = inliers.shape[1]
+        prm = RefitParams(int(rounds), float(max_dist2))
+        self._chk(lib().vslam_refit_dev(self._h, models_in.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), matches.shape[1],
+                                        query_points.data_ptr(), query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n,
+                                        C.byref(prm), C.byref(ro)), "vslam_refit_dev")
+
+    def refit_host(self, model, matches, query_points, train_points, rounds: int = 4, max_dist2: float = 4.0, inlier_cap: int | None = None,
+                   want_bits: bool = True, want_inliers: bool = True):
+        """vslam_refit_host: one pair of numpy arrays (one EPIPOLAR_DTYPE record, MATCH_DTYPE, POINT_DTYPE, POINT_DTYPE) -> (model: one
+        EPIPOLAR_DTYPE record, info: one REFIT_DTYPE record, inlier_bits uint64 [(m + 63) // 64] or None, inliers MATCH_DTYPE or None,
+        total inliers or None)."""
+        mod = np.ascontiguousarray(model, dtype=EPIPOLAR_DTYPE).reshape(-1)[:1]
+        mt, qp, tp = _host_lists(matches, query_points, train_points)
+        m = len(mt)
+        cap = max(m, 1) if inlier_cap is None else int(inlier_cap)
+        out, info = np.zeros(1, EPIPOLAR_DTYPE), np.zeros(1, REFIT_DTYPE)
+        bits = np.zeros((m + 63) // 64, np.uint64) if want_bits else None
+        inl = np.zeros(cap, MATCH_DTYPE) if want_inliers else None
+        total = C.c_size_t()
+        prm = RefitParams(int(rounds), float(max_dist2))
+        self._chk(lib().vslam_refit_host(self._h, mod.ctypes.data, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp), C.byref(prm), out.ctypes.data,
+                                         info.ctypes.data, _ptr(bits), None if inl is None else inl.ctypes.data, cap,
+                                         C.byref(total) if want_inliers else None), "vslam_refit_host")
+        return out[0], info[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None
 
     def pose(self, models, matches, match_counts, query_points, train_points, intrinsics, n_pairs: int | None = None, poses=None, candidates=None,
              points=None, front_bits=None):

@@ -205,15 +205,6 @@ __global__ __launch_bounds__(EPI_MODEL_WG) void k_epi_models(const EpiXY* __rest
     out->valid = ok ? 1 : 0;
 }
 
-// The Sampson test of one record under F; false for NaN coordinates, for a zero denominator and for F = 0.
-__device__ __forceinline__ bool epi_inlier(const double (&F)[9], const EpiXY& p, double max_dist2) {
-    const double a0 = (F[0] * p.x + F[1] * p.y) + F[2], a1 = (F[3] * p.x + F[4] * p.y) + F[5], a2 = (F[6] * p.x + F[7] * p.y) + F[8];
-    const double b0 = (F[0] * p.u + F[3] * p.v) + F[6], b1 = (F[1] * p.u + F[4] * p.v) + F[7];
-    const double e = (p.u * a0 + p.v * a1) + a2;
-    const double den = ((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1;
-    return e * e < max_dist2 * den;
-}
-
 // grid = (hypothesis blocks of 256, nsplit, pairs).  Lane = hypothesis; the workgroup's record tiles (tile index = blockIdx.y
 // + k * nsplit) are staged in LDS and every lane walks them in step: the LDS address is the same in all lanes.  The lane's
 // integer count goes into its hypothesis by atomicAdd: integer sums merge exactly in any order.

@@ -1,5 +1,5 @@
-// The 3 x 3 f64 arithmetic and the record walk that the two-view stages share (kernels_epipolar.hip.h, kernels_pose.hip.h),
-// each stated once.  Of include/vslam.h this states "two-view geometry" steps 4 (the Jacobi sweeps on F^T F), 5 (the
+// The 3 x 3 f64 arithmetic, the inlier test and the record walk that the two-view stages share (kernels_epipolar.hip.h,
+// kernels_refit.hip.h, kernels_pose.hip.h), each stated once.  Of include/vslam.h this states "two-view geometry" steps 4 (the Jacobi sweeps on F^T F), 5 (the
 // normalisation undone: a product L^T F R) and 6 (Frobenius norm, finite and non-zero), and "relative pose and triangulation"
 // steps 1 (E = K^T F K: the same product and norm) and 2 (the same sweeps on E^T E).  Every + - * / sqrt is an IEEE operation
 // of its own and sums run left to right: the order written here is the ABI's.  Plain C++ - G3 is __host__ __device__ under
@@ -9,6 +9,8 @@
 #pragma once
 #include <cmath>
 #include <cstddef>
+
+#include "vslam_epipolar_plan.h"
 #ifdef __HIPCC__
 #define G3 __host__ __device__
 #else
@@ -55,6 +57,24 @@ G3 inline void g3_gram_jacobi(const double (&M)[9], double (&d)[3], double (&V)[
     d[0] = S00, d[1] = S11, d[2] = S22;
 }
 
+// Rank 2 (step 4 of the two-view model): the right singular vector of f's smallest singular value is projected out of
+// every row.  (The refit's k_refit_solve; k_epi_models keeps the same lines in its own body: routed through this function
+// its register allocation changes, and its budget - above - must not.)
+G3 inline void g3_rank2(double (&f)[9]) {
+    double S[3], V[3][3];
+    g3_gram_jacobi<1>(f, S, V);
+    double v0 = V[0][0], v1 = V[1][0], v2 = V[2][0], smin = S[0];
+    if (S[1] < smin) v0 = V[0][1], v1 = V[1][1], v2 = V[2][1], smin = S[1];
+    if (S[2] < smin) v0 = V[0][2], v1 = V[1][2], v2 = V[2][2], smin = S[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double g = (f[3 * i] * v0 + f[3 * i + 1] * v1) + f[3 * i + 2] * v2;
+        f[3 * i] = f[3 * i] - g * v0;
+        f[3 * i + 1] = f[3 * i + 1] - g * v1;
+        f[3 * i + 2] = f[3 * i + 2] - g * v2;
+    }
+}
+
 struct G3Affine {  // the matrix [[sx, 0, ax], [0, sy, ay], [0, 0, 1]]: a normalisation, or the intrinsics
     double sx, sy, ax, ay;
 };
@@ -79,6 +99,16 @@ G3 inline double g3_frobenius(const double (&M)[9]) {
 #pragma unroll
     for (int i = 1; i < 9; ++i) n2 = n2 + M[i] * M[i];
     return sqrt(n2);
+}
+
+// The Sampson test of one record under F (the two-view section's inlier test); false for NaN coordinates, for a zero
+// denominator and for F = 0.  (k_epi_score, k_epi_flags and the refit's streaming kernels.)
+G3 inline bool epi_inlier(const double (&F)[9], const EpiXY& p, double max_dist2) {
+    const double a0 = (F[0] * p.x + F[1] * p.y) + F[2], a1 = (F[3] * p.x + F[4] * p.y) + F[5], a2 = (F[6] * p.x + F[7] * p.y) + F[8];
+    const double b0 = (F[0] * p.u + F[3] * p.v) + F[6], b1 = (F[1] * p.u + F[4] * p.v) + F[7];
+    const double e = (p.u * a0 + p.v * a1) + a2;
+    const double den = ((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1;
+    return e * e < max_dist2 * den;
 }
 
 // The record walk.  Pair j has min(count, capacity) records; lane `lane` of workgroup `block` has record i, 64 bits (the last

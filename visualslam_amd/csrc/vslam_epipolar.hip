@@ -21,6 +21,14 @@ int vslam::enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const un
     return VSLAM_OK;
 }
 
+int vslam::enqueue_epi_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_epipolar* models,
+                             double max_dist2, int n_pairs, unsigned long long* flags) {
+    const TwoViewPlan pl = twoview_plan(match_cap, n_pairs);
+    LAUNCH(c, "k_epi_flags", k_epi_flags, dim3(pl.rec_blocks, n_pairs), dim3(TWOVIEW_REC_WG), xy, match_counts, match_cap, models, max_dist2, flags,
+           pl.fwords);
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_epipolar_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
@@ -53,9 +61,7 @@ int vslam_epipolar_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t*
     LAUNCH(c, "k_epi_score", k_epi_score, dim3(pl.score_blocks, pl.nsplit, n_pairs), dim3(EPI_SCORE_WG), xy, match_counts, match_cap, H,
            prm->max_dist2, hyp);
     LAUNCH(c, "k_epi_select", k_epi_select, dim3(n_pairs), dim3(256), hyp, match_counts, match_cap, H, out->models);
-    if (lists)
-        LAUNCH(c, "k_epi_flags", k_epi_flags, dim3(pl.rec_blocks, n_pairs), dim3(256), xy, match_counts, match_cap, out->models, prm->max_dist2,
-               flags, pl.fwords);
+    if (lists) TRY(enqueue_epi_flags(c, xy, match_counts, match_cap, out->models, prm->max_dist2, n_pairs, flags));
     if (out->inlier_counts)
         TRY(enqueue_inlier_list(c, flags, pl.fwords, matches, match_counts, match_cap, n_pairs, chunk_ws, out->inliers, out->inlier_cap,
                                 out->inlier_counts));

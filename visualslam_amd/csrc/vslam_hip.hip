@@ -56,6 +56,7 @@ static const char* const kKernelNames =
     "k_extrema_pack\nk_harris_strip\nk_flag_count\nk_chunk_scan\nk_flag_scatter\nk_level_gradients\nk_sift_descriptors\nk_pack_offsets\nk_pack_copy\nk_count_totals\n"
     "k_desc_norms\nk_match_nn2\nk_match_merge\n"
     "k_epi_coords\nk_epi_models\nk_epi_score\nk_epi_select\nk_epi_flags\n"
+    "k_refit_init\nk_refit_count\nk_refit_begin\nk_refit_dist\nk_refit_scale\nk_refit_moments\nk_refit_solve\n"
     "k_pose_candidates\nk_pose_vote\nk_pose_select\nk_pose_points\n"
     "k_chain_link\nk_chain_ratio\nk_chain_median\nk_chain_walk\nk_chain_map";
 

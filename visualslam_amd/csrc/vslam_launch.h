@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_pose.hip, vslam_chain.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_pose.hip, vslam_chain.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,6 +44,10 @@ struct EpiXY;
 int enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
                        const vslam_point* query_points, unsigned int query_cap, const vslam_point* train_points, unsigned int train_cap,
                        int n_pairs, EpiXY* xy);
+// The inlier ballot words of every pair under models[j].F (k_epi_flags, compiled in vslam_epipolar.hip; vslam_refit_dev asks
+// for them under its output models): flags [n_pairs][fwords], the words that hold a record below the count.
+int enqueue_epi_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_epipolar* models,
+                      double max_dist2, int n_pairs, unsigned long long* flags);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
@@ -84,7 +88,7 @@ class WsPlan {
 }  // namespace
 
 // What the entry points that work from host memory through per-call device buffers share (vslam_match_host,
-// vslam_epipolar_host, vslam_pose_host), and the answer of a device entry point whose caller has no HIP device.
+// vslam_epipolar_host, vslam_refit_host, vslam_pose_host), and the answer of a device entry point whose caller has no HIP device.
 namespace {
 // No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
 // after the arguments, before the context is touched.

@@ -3,10 +3,12 @@
 // filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
 // second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --epipolar adds
 // the step after that: the RANSAC fundamental matrix of the accepted matches (vslam::fundamentalRansac: 512 hypotheses, seed 1,
-// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --pose fx,fy,cx,cy (after --epipolar)
-// adds the step after that: the camera motion from the inlier matches (vslam::relativePose) as a "pose" object with R, t, the
-// winning candidate and the number of inliers in front of both cameras.
-//   usage: Match [--epipolar [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --refit ROUNDS (after --epipolar)
+// refits that model over all its inliers (vslam::refitFundamental) and prints a "refit" object with n_before, n_after,
+// accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
+// from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
+// candidate and the number of inliers in front of both cameras.
+//   usage: Match [--epipolar [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -48,6 +50,13 @@ int main(int argc, char** argv) {
     try {
         const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
         if (epipolar) --argc, ++argv;
+        vslam_refit_params refitParams{0, 4.0};
+        const bool refit = epipolar && argc > 2 && std::strcmp(argv[1], "--refit") == 0;
+        if (refit) {
+            if (std::sscanf(argv[2], "%u", &refitParams.rounds) != 1 || refitParams.rounds < 1 || refitParams.rounds > 8)
+                throw std::runtime_error("--refit takes the number of rounds, 1 .. 8");
+            argc -= 2, argv += 2;
+        }
         vslam_pose_params camera{};
         const bool pose = epipolar && argc > 2 && std::strcmp(argv[1], "--pose") == 0;
         if (pose) {
@@ -62,7 +71,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -82,8 +91,22 @@ int main(int argc, char** argv) {
                 extra += buf;
             }
             extra += "]}";
+            vslam_epipolar model = e.model;
+            std::vector<vslam_match> inliers = e.inliers;
+            if (refit) {
+                const vslam::Refit r = vslam::refitFundamental(e.model, m.matches, q.points, t.points, refitParams);
+                std::snprintf(buf, sizeof buf, ", \"refit\": {\"rounds\": %u, \"n_before\": %u, \"n_after\": %u, \"accepted\": %u, \"stop\": %d, \"F\": [",
+                              refitParams.rounds, r.info.n_before, r.info.n_after, r.info.accepted, r.info.stop);
+                extra += buf;
+                for (int i = 0; i < 9; ++i) {
+                    std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", r.model.F[i]);
+                    extra += buf;
+                }
+                extra += "]}";
+                model = r.model, inliers = r.inliers;
+            }
             if (pose) {
-                const vslam::Pose p = vslam::relativePose(e.model, e.inliers, q.points, t.points, camera);
+                const vslam::Pose p = vslam::relativePose(model, inliers, q.points, t.points, camera);
                 std::snprintf(buf, sizeof buf, ", \"pose\": {\"n_matches\": %u, \"n_front\": %u, \"best\": %d, \"valid\": %d, \"R\": [", p.pose.n_matches,
                               p.pose.n_front, p.pose.best, p.pose.valid);
                 extra += buf;

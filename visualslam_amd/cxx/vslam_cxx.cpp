@@ -487,6 +487,21 @@ vslam::Epipolar vslam::fundamentalRansac(const std::vector<vslam_match>& matches
     return out;
 }
 
+vslam::Refit vslam::refitFundamental(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                                     const std::vector<SLAM::point>& trainPoints, const vslam_refit_params& params) {
+    vslam::Refit out{};
+    out.inliers.resize(matches.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_refit_host(c, &model, matches.empty() ? nullptr : matches.data(), matches.size(),
+                                  reinterpret_cast<const vslam_point*>(queryPoints.data()), queryPoints.size(),
+                                  reinterpret_cast<const vslam_point*>(trainPoints.data()), trainPoints.size(), &params, &out.model, &out.info, nullptr,
+                                  out.inliers.empty() ? nullptr : out.inliers.data(), out.inliers.size(), &total),
+                 c, "refitFundamental");
+    out.inliers.resize(total);
+    return out;
+}
+
 vslam::Pose vslam::relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                                 const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera) {
     vslam::Pose out{};

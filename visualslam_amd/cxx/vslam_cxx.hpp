@@ -199,6 +199,18 @@ struct Epipolar {
 Epipolar fundamentalRansac(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                            const std::vector<SLAM::point>& trainPoints, const vslam_epipolar_params& params = {512, 1, 4.0});
 
+// Between the two: the least-squares refit of the model over all its inliers, the inliers classified again, for `rounds`
+// rounds, on the GPU (vslam_refit_host; the ordered sums, the 9 x 9 Jacobi and the acceptance rule are stated in
+// include/vslam.h).  `matches` is the FULL list fundamentalRansac read, not its inliers.  The result never has fewer inliers
+// than `model`; feed Refit::model and Refit::inliers to relativePose.
+struct Refit {
+    vslam_epipolar model;              // `model` with the refitted F and its inlier count
+    vslam_refit info;                  // inliers before and after, rounds kept, why it stopped
+    std::vector<vslam_match> inliers;  // the matches the refitted model accepts, list order kept
+};
+Refit refitFundamental(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                       const std::vector<SLAM::point>& trainPoints, const vslam_refit_params& params = {4, 4.0});
+
 // The step after that: the camera motion of the pair (x_train ~ R x_query + t, |t| = 1) and the 3-D point of every record of
 // `matches` - the intended list is Epipolar::inliers - from the model fundamentalRansac found, on the GPU (vslam_pose_host;
 // the decomposition, the cheirality vote and the triangulation are stated in include/vslam.h).  One pinhole camera
