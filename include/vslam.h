@@ -780,13 +780,130 @@ int vslam_refit_host(vslam_ctx* ctx, const vslam_epipolar* model_in, const vslam
                      const vslam_refit_params* params, vslam_epipolar* model, vslam_refit* info, uint64_t* inlier_bits,
                      vslam_match* inliers, size_t inlier_cap, size_t* n_inliers);
 
+/* ---------------------------------------------------------------- homography and the degeneracy verdict
+ * Beside vslam_epipolar_dev, over the same lists: the RANSAC homography of every pair, and - given the fundamental matrices
+ * of the same pairs - a verdict per pair on whether the homography explains the matches as well as F does (a planar scene, a
+ * pure rotation, a pure image translation), in which case F is one arbitrary member of a family and must not be decomposed.
+ * The verdict acts through a GATE: a copy of the epipolar models in which a degenerate pair is the "no model" record, which
+ * vslam_refit_dev copies through, vslam_pose_dev gives no pose and vslam_chain_dev starts a new segment at.  A fixed number
+ * of hypotheses, no adaptive stop, no least-squares refit of H, no decomposition of H into R, t, n.  Coordinates, "trusted",
+ * m = min(match_counts[j], match_cap) and mix() are those of the two-view geometry section.  The arithmetic is fixed here so
+ * that a CPU can restate it bit for bit (tests/homref.py): IEEE f64, every + - * / sqrt rounded on its own (no fused
+ * multiply-add), sums left to right as written.  Matrices are row-major, M[i][j] = M[3*i + j].
+ *
+ * Sampling: base = mix(mix(seed + j) + h); draw t = 0, 1, ... gives r = mix(base + t) and the index (uint64(r) * m) >> 32, kept
+ * if it is not among the indices kept so far; the sample is the first 4 kept indices, in that order.  Fewer than 4 after 64
+ * draws: invalid.  m < 4: every hypothesis is invalid.  A sample that contains a record that is not trusted is invalid.
+ *
+ * Model from the 4 records (x, y) = query, (x', y') = train - the normalised direct linear transform:
+ *  1. Per side: cx = (((x0 + x1) + x2) + x3) / 4, cy likewise; d = (((r0 + r1) + r2) + r3) / 4 with ri = sqrt(dx*dx + dy*dy),
+ *     dx = xi - cx, dy = yi - cy; d == 0: invalid; s = 1.4142135623730951 / d; normalised point ((xi - cx) * s, (yi - cy) * s).
+ *  2. The 8 x 9 matrix a from the normalised (x, y), (x', y') of record i = 0 .. 3:
+ *       row 2i     = [x, y, 1, 0, 0, 0, -(x'*x), -(x'*y), -x'];
+ *       row 2i + 1 = [0, 0, 0, x, y, 1, -(y'*x), -(y'*y), -y'].
+ *  3. Step 3 of the two-view model, word for word: Gauss-Jordan with full pivoting over steps k = 0 .. 7, the same scan order
+ *     (r ascending, then c ascending, strictly larger replaces, starting at 0), the same validity rules (no choice, or an
+ *     infinite pivot: invalid), the same row operations.  With `free` the column no step chose: h[free] = 1,
+ *     h[c_k] = -a[k][free]; Hn = h row-major.
+ *  4. M = Tt^-1 Hn Tq, with aq = -(sq * cqx), bq = -(sq * cqy), r = 1 / st:
+ *       G1[i][0] = Hn[i][0]*sq;  G1[i][1] = Hn[i][1]*sq;  G1[i][2] = (Hn[i][0]*aq + Hn[i][1]*bq) + Hn[i][2];
+ *       M[0][j] = r*G1[0][j] + ctx*G1[2][j];  M[1][j] = r*G1[1][j] + cty*G1[2][j];  M[2][j] = G1[2][j].
+ *  5. n = sqrt(M[0][0]^2 + M[0][1]^2 + ... + M[2][2]^2), row-major, left to right; n zero or not finite: invalid; H = M / n.
+ *  6. Sign.  w = (H[2][0]*x0 + H[2][1]*y0) + H[2][2] with (x0, y0) the query point of the sample's first record, in pixels.
+ *     Neither w > 0 nor w < 0: invalid.  w < 0: all nine entries of H are negated.
+ *  7. G = adj(H), each entry one a*b - c*d (two products, one difference):
+ *       G[0][0] = H[1][1]*H[2][2] - H[1][2]*H[2][1];  G[0][1] = H[0][2]*H[2][1] - H[0][1]*H[2][2];  G[0][2] = H[0][1]*H[1][2] - H[0][2]*H[1][1];
+ *       G[1][0] = H[1][2]*H[2][0] - H[1][0]*H[2][2];  G[1][1] = H[0][0]*H[2][2] - H[0][2]*H[2][0];  G[1][2] = H[0][2]*H[1][0] - H[0][0]*H[1][2];
+ *       G[2][0] = H[1][0]*H[2][1] - H[1][1]*H[2][0];  G[2][1] = H[0][1]*H[2][0] - H[0][0]*H[2][1];  G[2][2] = H[0][0]*H[1][1] - H[0][1]*H[1][0].
+ *     wg = (G[2][0]*x'0 + G[2][1]*y'0) + G[2][2] with (x'0, y'0) the train point of the sample's first record.  wg zero or
+ *     not finite: invalid.  wg < 0: all nine entries of G are negated.  (G is not scaled: the inlier test is homogeneous.)
+ *
+ * Inlier test (symmetric transfer, image pixels, no division):  p_i = (H[i][0]*x + H[i][1]*y) + H[i][2];
+ * q_i = (G[i][0]*x' + G[i][1]*y') + G[i][2].  Forward: p2 > 0 and dx*dx + dy*dy < max_dist2 * (p2*p2) with dx = p0 - x'*p2,
+ * dy = p1 - y'*p2.  Backward: q2 > 0 and ex*ex + ey*ey < max_dist2 * (q2*q2) with ex = q0 - x*q2, ey = q1 - y*q2.  A record is
+ * an inlier iff it is trusted and both tests hold (max_dist2 bounds each direction's squared transfer error in pixels^2).
+ * Selection: the valid hypothesis with the most inliers, the lowest h on ties.  Counts are integers, so the result does not
+ * depend on how the records are split over lanes and workgroups, nor on vslam_ctx_set_f32_fused / vslam_ctx_set_matrix_path.
+ *
+ * Verdict, integers only.  n_epipolar = epipolar_models[j].n_inliers, and 0 without epipolar_models or when
+ * epipolar_models[j].best < 0.  degenerate = best >= 0 && epipolar_models[j].best >= 0 && n_inliers >= min_inliers &&
+ * uint64(n_inliers) * degenerate_den >= uint64(degenerate_num) * n_epipolar;  0 without epipolar_models.
+ * Gate.  gated_models[j] = epipolar_models[j], except that a degenerate pair becomes the "no model" record: F all zero,
+ * n_inliers = 0, best = -1, n_matches and n_valid kept. */
+typedef struct {
+    double H[9];      /* query -> train; all zero when not valid */
+    double G[9];      /* train -> query: adj(H) up to sign; all zero when not valid */
+    uint32_t inliers;
+    int32_t valid;
+} vslam_homography_hyp; /* 152 bytes */
+typedef struct {
+    double H[9];         /* row-major; x_train ~ H x_query; Frobenius norm 1; all zero when best < 0 */
+    double G[9];         /* x_query ~ G x_train; all zero when best < 0 */
+    uint32_t n_matches;  /* min(match_counts[j], match_cap): the records considered */
+    uint32_t n_inliers;
+    int32_t best;        /* winning hypothesis, -1: none */
+    uint32_t n_valid;    /* hypotheses that produced a model */
+    uint32_t n_epipolar; /* the verdict's other count */
+    int32_t degenerate;  /* 1: H explains the matches as well as F does - F must not be decomposed */
+} vslam_homography;      /* 168 bytes */
+typedef struct {
+    uint32_t n_hypotheses;   /* 1 .. 65535 */
+    uint32_t seed;
+    double max_dist2;        /* squared transfer error in pixels^2, each direction; finite and positive */
+    uint32_t degenerate_num; /* the verdict's ratio n_inliers / n_epipolar >= degenerate_num / degenerate_den */
+    uint32_t degenerate_den; /* > 0 */
+    uint32_t min_inliers;    /* fewer H-inliers than this: never degenerate */
+} vslam_homography_params;
+/* Like vslam_epipolar_out: every pointer with the bytes behind it, checked before anything is launched.  inlier_bits,
+ * inliers, inlier_counts, inlier_cap and hypotheses follow vslam_epipolar_out's rules exactly. */
+typedef struct {
+    size_t struct_size;        /* = sizeof(vslam_homography_out) */
+    vslam_homography* models;  /* [n_pairs], required */
+    size_t models_bytes;
+    uint64_t* inlier_bits;     /* [n_pairs][(match_cap + 63) / 64] optional: bit i % 64 of word i / 64 = record i is an inlier of
+                                * the winner; the first (n_matches + 63) / 64 words of a pair are written, the rest untouched */
+    size_t inlier_bits_bytes;
+    vslam_match* inliers;      /* [n_pairs][inlier_cap] optional: the inlier records, list order kept */
+    size_t inliers_bytes;
+    uint32_t* inlier_counts;   /* [n_pairs], required with inliers: totals (may exceed inlier_cap) */
+    size_t inlier_counts_bytes;
+    uint32_t inlier_cap;
+    vslam_homography_hyp* hypotheses; /* [n_pairs][n_hypotheses] optional: every hypothesis with its count */
+    size_t hypotheses_bytes;
+    vslam_epipolar* gated_models; /* [n_pairs] optional, needs epipolar_models: the gate; may be the very pointer passed as
+                                   * epipolar_models, must not otherwise overlap it */
+    size_t gated_models_bytes;
+} vslam_homography_out;
+/* Pair j reads the lists as vslam_epipolar_dev does (DEVICE pointers) and, when given, epipolar_models[j] - the `models`
+ * buffer of vslam_epipolar_dev or vslam_refit_dev over the same pairs; NULL: no verdict (n_epipolar = degenerate = 0).
+ * Asynchronous on the context stream, never waits on the host (the counts are read on the device, the grids are sized from
+ * the capacities); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch - and before the context is looked
+ * at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing), n_hypotheses outside 1 .. 65535,
+ * a max_dist2 that is not finite or not positive, degenerate_den == 0, match_cap / query_cap / train_cap == 0, an undersized
+ * buffer, inliers without inlier_counts or with inlier_cap == 0, gated_models without epipolar_models; then VSLAM_ERR_HIP
+ * when there is no usable HIP device.  Not for stream capture. */
+int vslam_homography_dev(vslam_ctx* ctx, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
+                         const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points, uint32_t train_cap,
+                         int n_pairs, const vslam_epipolar* epipolar_models, const vslam_homography_params* params,
+                         const vslam_homography_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call).  model is required; epipolar_model
+ * (one record, the verdict's input), inlier_bits [(n_matches + 63) / 64], (inliers [inlier_cap], n_inliers), hypotheses
+ * [n_hypotheses] and gated_model (one record, needs epipolar_model) are each optional; *n_inliers is the total, which may
+ * exceed inlier_cap.  n_query / n_train are the capacities the indices are checked against.  Errors as for
+ * vslam_homography_dev. */
+int vslam_homography_host(vslam_ctx* ctx, const vslam_match* matches, size_t n_matches, const vslam_point* query_points,
+                          size_t n_query, const vslam_point* train_points, size_t n_train, const vslam_epipolar* epipolar_model,
+                          const vslam_homography_params* params, vslam_homography* model, uint64_t* inlier_bits,
+                          vslam_match* inliers, size_t inlier_cap, size_t* n_inliers, vslam_homography_hyp* hypotheses,
+                          vslam_epipolar* gated_model);
+
 /* ---------------------------------------------------------------- relative pose and triangulation
  * The step after the fundamental matrix: the camera motion of every pair and the 3-D point of every match record, from the
  * `models` buffer vslam_epipolar_dev wrote (only F and best are read), a match list (any list; the intended one is the
  * inliers / inlier_counts / inlier_cap of vslam_epipolar_dev) and the point lists.  One pinhole camera for both frames, no
  * skew, no distortion.  Convention: x_train ~ R * x_query + t with |t| = 1 (the scale of a two-view reconstruction is free);
- * a point X is in the QUERY camera's frame.  No degeneracy handling: a planar scene or a pure rotation gets whatever the
- * decomposition gives.  Records are trusted, and their coordinates (x, y) = query, (x', y') = train computed, exactly as in
+ * a point X is in the QUERY camera's frame.  No degeneracy handling of its own: a planar scene or a pure rotation gets whatever the
+ * decomposition gives - unless `models` is the gated_models buffer of vslam_homography_dev, where such a pair has best < 0.  Records are trusted, and their coordinates (x, y) = query, (x', y') = train computed, exactly as in
  * the two-view geometry section; m = min(match_counts[j], match_cap) records are considered.  The arithmetic is fixed here so
  * that a CPU can restate it bit for bit (tests/poseref.py): IEEE f64, every + - * / sqrt rounded on its own, sums left to
  * right as written.  Matrices are row-major, M[i][j] = M[3*i + j].

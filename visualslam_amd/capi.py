@@ -33,6 +33,9 @@ NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4"
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
+HOMOGRAPHY_HYP_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_homography_hyp, 152 bytes
+HOMOGRAPHY_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4"),
+                             ("n_epipolar", "<u4"), ("degenerate", "<i4")], align=True)  # vslam_homography, 168 bytes
 REFIT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4")], align=True)  # vslam_refit, 16 bytes
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
@@ -134,6 +137,28 @@ class RefitOut(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("info", C.c_void_p), ("info_bytes", C.c_size_t),
                 ("inlier_bits", C.c_void_p), ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t),
                 ("inlier_counts", C.c_void_p), ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32)]
+
+
+class HomographyHyp(C.Structure):
+    _fields_ = [("H", C.c_double * 9), ("G", C.c_double * 9), ("inliers", C.c_uint32), ("valid", C.c_int32)]
+
+
+class Homography(C.Structure):
+    _fields_ = [("H", C.c_double * 9), ("G", C.c_double * 9), ("n_matches", C.c_uint32), ("n_inliers", C.c_uint32), ("best", C.c_int32),
+                ("n_valid", C.c_uint32), ("n_epipolar", C.c_uint32), ("degenerate", C.c_int32)]
+
+
+class HomographyParams(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_uint32), ("seed", C.c_uint32), ("max_dist2", C.c_double), ("degenerate_num", C.c_uint32),
+                ("degenerate_den", C.c_uint32), ("min_inliers", C.c_uint32)]
+
+
+class HomographyOut(C.Structure):
+    """vslam_homography_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("inlier_bits", C.c_void_p),
+                ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t), ("inlier_counts", C.c_void_p),
+                ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t),
+                ("gated_models", C.c_void_p), ("gated_models_bytes", C.c_size_t)]
 
 
 class PoseParams(C.Structure):
@@ -249,6 +274,8 @@ SIGNATURES = {
     "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
     "vslam_refit_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(RefitParams), C.POINTER(RefitOut)]),
     "vslam_refit_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(RefitParams), _P, _P, _P, _P, _Z, C.POINTER(_Z)]),
+    "vslam_homography_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, _P, C.POINTER(HomographyParams), C.POINTER(HomographyOut)]),
+    "vslam_homography_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, _P, C.POINTER(HomographyParams), _P, _P, _P, _Z, C.POINTER(_Z), _P, _P]),
     "vslam_pose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(PoseParams), C.POINTER(PoseOut)]),
     "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
     "vslam_chain_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
@@ -880,6 +907,52 @@ class Context:
                                          info.ctypes.data, _ptr(bits), None if inl is None else inl.ctypes.data, cap,
                                          C.byref(total) if want_inliers else None), "vslam_refit_host")
         return out[0], info[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None
+
+    def homography(self, matches, match_counts, query_points, train_points, n_pairs: int | None = None, n_hypotheses: int = 512, seed: int = 1,
+                   max_dist2: float = 4.0, degenerate_num: int = 1, degenerate_den: int = 2, min_inliers: int = 16, epipolar_models=None,
+                   models=None, inlier_bits=None, inliers=None, inlier_counts=None, hypotheses=None, gated_models=None):
+        """vslam_homography_dev: the RANSAC homography of every pair over the lists epipolar() reads and, with epipolar_models (the
+        models tensor epipolar() or refit() wrote), the degeneracy verdict; asynchronous on the context stream.  Outputs, CUDA
+        tensors: models - any contiguous tensor of n_pairs * 168 bytes (HOMOGRAPHY_DTYPE after .cpu().numpy().view), inlier_bits /
+        inliers / inlier_counts as epipolar()'s, hypotheses n_pairs * n_hypotheses * 152 bytes (HOMOGRAPHY_HYP_DTYPE), gated_models
+        n_pairs * 88 bytes (may be epipolar_models itself): the epipolar models with every degenerate pair made "no model", for
+        refit() and pose().  max_dist2 is the SQUARED transfer error in pixels, each direction."""
+        outs = dict(models=models, inlier_bits=inlier_bits, inliers=inliers, inlier_counts=inlier_counts, hypotheses=hypotheses, gated_models=gated_models)
+        n = self._two_view_lists("homography", n_pairs, "models", dict(matches=matches, match_counts=match_counts, query_points=query_points, train_points=train_points, epipolar_models=epipolar_models, **outs))
+        if epipolar_models is not None and epipolar_models.numel() * epipolar_models.element_size() < n * 88:
+            raise ValueError("homography: epipolar_models must hold n_pairs * 88 bytes")
+        ho = _fill_out(HomographyOut(), outs)
+        if inliers is not None:
+            ho.inlier_cap = inliers.shape[1]
+        prm = HomographyParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), int(degenerate_num), int(degenerate_den), int(min_inliers))
+        self._chk(lib().vslam_homography_dev(self._h, matches.data_ptr(), match_counts.data_ptr(), matches.shape[1], query_points.data_ptr(),
+                                             query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n,
+                                             None if epipolar_models is None else epipolar_models.data_ptr(), C.byref(prm), C.byref(ho)),
+                  "vslam_homography_dev")
+
+    def homography_host(self, matches, query_points, train_points, n_hypotheses: int = 512, seed: int = 1, max_dist2: float = 4.0,
+                        degenerate_num: int = 1, degenerate_den: int = 2, min_inliers: int = 16, epipolar_model=None, inlier_cap: int | None = None,
+                        want_bits: bool = True, want_inliers: bool = True, want_hypotheses: bool = False):
+        """vslam_homography_host: one pair of numpy arrays (MATCH_DTYPE, POINT_DTYPE, POINT_DTYPE; epipolar_model: one EPIPOLAR_DTYPE
+        record or None) -> (model: one HOMOGRAPHY_DTYPE record, inlier_bits uint64 [(m + 63) // 64] or None, inliers MATCH_DTYPE or
+        None, total inliers or None, hypotheses or None, gated model: one EPIPOLAR_DTYPE record, or None without epipolar_model)."""
+        mt, qp, tp = _host_lists(matches, query_points, train_points)
+        m = len(mt)
+        cap = max(m, 1) if inlier_cap is None else int(inlier_cap)
+        epi = None if epipolar_model is None else np.ascontiguousarray(epipolar_model, dtype=EPIPOLAR_DTYPE).reshape(-1)[:1]
+        model = np.zeros(1, HOMOGRAPHY_DTYPE)
+        gated = None if epi is None else np.zeros(1, EPIPOLAR_DTYPE)
+        bits = np.zeros((m + 63) // 64, np.uint64) if want_bits else None
+        inl = np.zeros(cap, MATCH_DTYPE) if want_inliers else None
+        hyp = np.zeros(int(n_hypotheses), HOMOGRAPHY_HYP_DTYPE) if want_hypotheses else None
+        total = C.c_size_t()
+        prm = HomographyParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), int(degenerate_num), int(degenerate_den), int(min_inliers))
+        self._chk(lib().vslam_homography_host(self._h, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp), None if epi is None else epi.ctypes.data,
+                                              C.byref(prm), model.ctypes.data, _ptr(bits), None if inl is None else inl.ctypes.data, cap,
+                                              C.byref(total) if want_inliers else None, _ptr(hyp), None if gated is None else gated.ctypes.data),
+                  "vslam_homography_host")
+        return (model[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None, hyp,
+                None if gated is None else gated[0])
 
     def pose(self, models, matches, match_counts, query_points, train_points, intrinsics, n_pairs: int | None = None, poses=None, candidates=None,
              points=None, front_bits=None):

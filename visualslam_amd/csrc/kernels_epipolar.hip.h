@@ -16,15 +16,6 @@
 
 namespace vslam {
 
-__device__ __forceinline__ unsigned int epi_mix(unsigned int x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // grid = (record blocks, pairs)
 __global__ __launch_bounds__(256) void k_epi_coords(const vslam_match* __restrict__ matches, const unsigned int* __restrict__ counts,
                                                      unsigned int mcap, const vslam_point* __restrict__ qpts, unsigned int qcap,

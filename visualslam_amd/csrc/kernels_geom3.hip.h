@@ -111,6 +111,16 @@ G3 inline bool epi_inlier(const double (&F)[9], const EpiXY& p, double max_dist2
     return e * e < max_dist2 * den;
 }
 
+// The counter hash of the sampling (the two-view section's mix(); k_epi_models and k_hom_models).
+G3 inline unsigned int epi_mix(unsigned int x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
 // The record walk.  Pair j has min(count, capacity) records; lane `lane` of workgroup `block` has record i, 64 bits (the last
 // block of a capacity near 2^32 runs past it); a wave none of whose records lies below m leaves (wave-uniform); lane 0 of a
 // wave speaks for it and stores its ballot word, word i / 64 of pair j.

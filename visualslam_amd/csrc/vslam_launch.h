@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_pose.hip, vslam_chain.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -88,7 +88,7 @@ class WsPlan {
 }  // namespace
 
 // What the entry points that work from host memory through per-call device buffers share (vslam_match_host,
-// vslam_epipolar_host, vslam_refit_host, vslam_pose_host), and the answer of a device entry point whose caller has no HIP device.
+// vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host), and the answer of a device entry point whose caller has no HIP device.
 namespace {
 // No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
 // after the arguments, before the context is touched.

@@ -3,12 +3,15 @@
 // filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
 // second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --epipolar adds
 // the step after that: the RANSAC fundamental matrix of the accepted matches (vslam::fundamentalRansac: 512 hypotheses, seed 1,
-// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --refit ROUNDS (after --epipolar)
+// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --homography (after --epipolar) adds
+// the RANSAC homography of the same matches and the degeneracy verdict (vslam::findHomography: 512 hypotheses, seed 1, transfer
+// error below 2 pixels, degenerate from n_H / n_F >= 1 / 2 with at least 16 inliers) as a "homography" object; the steps after
+// it then read the gated model, so a degenerate pair gets no refit and no pose.  --refit ROUNDS (after these)
 // refits that model over all its inliers (vslam::refitFundamental) and prints a "refit" object with n_before, n_after,
 // accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
 // from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
 // candidate and the number of inliers in front of both cameras.
-//   usage: Match [--epipolar [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+//   usage: Match [--epipolar [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -50,6 +53,8 @@ int main(int argc, char** argv) {
     try {
         const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
         if (epipolar) --argc, ++argv;
+        const bool homography = epipolar && argc > 1 && std::strcmp(argv[1], "--homography") == 0;
+        if (homography) --argc, ++argv;
         vslam_refit_params refitParams{0, 4.0};
         const bool refit = epipolar && argc > 2 && std::strcmp(argv[1], "--refit") == 0;
         if (refit) {
@@ -71,7 +76,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -93,8 +98,20 @@ int main(int argc, char** argv) {
             extra += "]}";
             vslam_epipolar model = e.model;
             std::vector<vslam_match> inliers = e.inliers;
+            if (homography) {
+                const vslam::Homography hg = vslam::findHomography(m.matches, q.points, t.points, &e.model);
+                std::snprintf(buf, sizeof buf, ", \"homography\": {\"n_inliers\": %u, \"best\": %d, \"n_valid\": %u, \"n_epipolar\": %u, \"degenerate\": %d, \"H\": [",
+                              hg.model.n_inliers, hg.model.best, hg.model.n_valid, hg.model.n_epipolar, hg.model.degenerate);
+                extra += buf;
+                for (int i = 0; i < 9; ++i) {
+                    std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", hg.model.H[i]);
+                    extra += buf;
+                }
+                extra += "]}";
+                model = hg.gated;
+            }
             if (refit) {
-                const vslam::Refit r = vslam::refitFundamental(e.model, m.matches, q.points, t.points, refitParams);
+                const vslam::Refit r = vslam::refitFundamental(model, m.matches, q.points, t.points, refitParams);
                 std::snprintf(buf, sizeof buf, ", \"refit\": {\"rounds\": %u, \"n_before\": %u, \"n_after\": %u, \"accepted\": %u, \"stop\": %d, \"F\": [",
                               refitParams.rounds, r.info.n_before, r.info.n_after, r.info.accepted, r.info.stop);
                 extra += buf;

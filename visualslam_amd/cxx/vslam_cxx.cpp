@@ -502,6 +502,23 @@ vslam::Refit vslam::refitFundamental(const vslam_epipolar& model, const std::vec
     return out;
 }
 
+vslam::Homography vslam::findHomography(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                                        const std::vector<SLAM::point>& trainPoints, const vslam_epipolar* epipolarModel,
+                                        const vslam_homography_params& params) {
+    vslam::Homography out{};
+    out.inliers.resize(matches.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_homography_host(c, matches.empty() ? nullptr : matches.data(), matches.size(),
+                                       reinterpret_cast<const vslam_point*>(queryPoints.data()), queryPoints.size(),
+                                       reinterpret_cast<const vslam_point*>(trainPoints.data()), trainPoints.size(), epipolarModel, &params, &out.model,
+                                       nullptr, out.inliers.empty() ? nullptr : out.inliers.data(), out.inliers.size(), &total, nullptr,
+                                       epipolarModel ? &out.gated : nullptr),
+                 c, "findHomography");
+    out.inliers.resize(total);
+    return out;
+}
+
 vslam::Pose vslam::relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                                 const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera) {
     vslam::Pose out{};

@@ -211,6 +211,19 @@ struct Refit {
 Refit refitFundamental(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                        const std::vector<SLAM::point>& trainPoints, const vslam_refit_params& params = {4, 4.0});
 
+// Beside fundamentalRansac, over the same lists: the homography of the pair by RANSAC and - given the fundamental matrix - the
+// verdict whether H explains the matches as well as F does (a plane, a pure rotation, a pure translation of the image), on the
+// GPU (vslam_homography_host; the 4-point DLT, the transfer test and the integer verdict are stated in include/vslam.h).
+// Feed Homography::gated to refitFundamental / relativePose in place of the model: a degenerate pair is "no model" there.
+struct Homography {
+    vslam_homography model;            // H row-major with x_train ~ H x_query, G the way back; best = -1: none; the verdict
+    vslam_epipolar gated;              // *epipolarModel, made "no model" when the pair is degenerate; all zero without one
+    std::vector<vslam_match> inliers;  // the matches H accepts, list order kept
+};
+Homography findHomography(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                          const std::vector<SLAM::point>& trainPoints, const vslam_epipolar* epipolarModel = nullptr,
+                          const vslam_homography_params& params = {512, 1, 4.0, 1, 2, 16});
+
 // The step after that: the camera motion of the pair (x_train ~ R x_query + t, |t| = 1) and the 3-D point of every record of
 // `matches` - the intended list is Epipolar::inliers - from the model fundamentalRansac found, on the GPU (vslam_pose_host;
 // the decomposition, the cheirality vote and the triangulation are stated in include/vslam.h).  One pinhole camera
