@@ -1062,6 +1062,128 @@ int vslam_chain_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match*
                      uint32_t match_cap, const double* points, const uint64_t* front_bits, uint32_t point_cap, int n_pairs,
                      const vslam_chain_params* params, const vslam_chain_out* out);
 
+/* ---------------------------------------------------------------- resection: camera pose from the previous pair's 3-D points
+ * Beside the two-view pose: the camera of frame j + 1 relative to frame j, estimated from the points pair j - 1 triangulated
+ * (3-D) and their observations in frame j + 1 (2-D) - a RANSAC absolute pose.  The translation comes out in pair j - 1's unit,
+ * so |t| estimates the trajectory's ratio[j] directly, and a pair whose F is degenerate (vslam_homography_dev's gate) still
+ * gets a pose.  A fixed number of hypotheses, no adaptive stop, no refit over the inliers; the result is not fed into
+ * vslam_chain_dev.  n_pairs CONSECUTIVE pairs (pair j: query frame j, train frame j + 1).
+ *   Structure side: exactly what vslam_chain_dev reads - poses, matches, match_counts, match_cap, points, front_bits, point_cap -
+ *   and the LIVE rule of the trajectory section, verbatim.
+ *   Observation side: obs_matches [n_pairs][obs_cap] with obs_counts - any match list of the pair: the same buffers as the
+ *   structure side (the F inliers), or the raw list vslam_match_dev wrote, which is the one to use for a pair the gate left
+ *   without a model -, train_points [n_pairs][train_cap] laid out as for vslam_epipolar_dev (set j = frame j + 1), and the
+ *   intrinsics.  n_obs = min(obs_counts[j], obs_cap) records are considered.
+ * The arithmetic is fixed here so that a CPU can restate it bit for bit (tests/resectref.py): IEEE f64, every + - * / sqrt
+ * rounded on its own (no fused multiply-add), sums left to right as written, matrices row-major.  mix() and the Gauss-Jordan
+ * step are those of the two-view geometry section, the Jacobi sweeps and the cross product those of the pose section.
+ *
+ *  1. Link.  Step 1 of the trajectory section, unchanged: for pair j >= 1, prev_j[k] is the lowest live record of pair j - 1
+ *     whose train == k.  Pair 0 has no links and no correspondences.
+ *  2. Correspondence of observation record b < n_obs of pair j >= 1, (query, train) its indices as unsigned.  link_b =
+ *     prev_j[query] when query < point_cap and that exists, else -1 (a pair j - 1 with poses[j - 1].best < 0 has no live
+ *     record, so no links).  The record is a CANDIDATE iff link_b >= 0, train < train_cap and the train point's octave is in
+ *     0 .. 31.  With a = link_b, (R, t) = poses[j - 1], X = points[j - 1][a]:
+ *       Y_i = ((R[i][0]*X0 + R[i][1]*X1) + R[i][2]*X2) + t_i     (the point in frame j's camera, in pair j - 1's unit);
+ *       (x', y') the exact coordinate of the train point (two-view section);  u = (x' - cx)/fx;  v = (y' - cy)/fy.
+ *     The record is USABLE iff it is a candidate and Y0, Y1, Y2 are all finite.  The usable records, in list order, are the
+ *     pair's dense list of n_corr correspondences {Y, u, v, b}.
+ *  3. Sample.  base = mix(mix(seed + j) + h); draw d = 0, 1, ... gives r = mix(base + d) and the index (uint64(r) * n_corr) >> 32
+ *     into the dense list, kept if it is not among the indices kept so far; the sample is the first 6 kept, in that order.
+ *     Fewer than 6 after 64 draws: invalid.  n_corr < 6: every hypothesis is invalid.
+ *  4. Model from the 6 correspondences - a calibrated direct linear transform.
+ *     a. c_k = (((((Y0_k + Y1_k) + Y2_k) + Y3_k) + Y4_k) + Y5_k) / 6 for k = 0, 1, 2 (Yi the i-th sample point);
+ *        r_i = sqrt((e0*e0 + e1*e1) + e2*e2) with e_k = Yi_k - c_k;  d = (((((r0 + r1) + r2) + r3) + r4) + r5) / 6;  d == 0: invalid;
+ *        s = 1.7320508075688772 / d;  the normalised point N_k = (Yi_k - c_k) * s.
+ *     b. The 12 x 12 matrix a, unknowns p = the 3 x 4 matrix [Mn | mn] row-major:
+ *          row 2i     = [N0, N1, N2, 1,  0, 0, 0, 0,  -(u*N0), -(u*N1), -(u*N2), -u];
+ *          row 2i + 1 = [0, 0, 0, 0,  N0, N1, N2, 1,  -(v*N0), -(v*N1), -(v*N2), -v].
+ *     c. Step 3 of the two-view model over 12 rows and 12 columns, steps k = 0 .. 10: the same scan (rows r >= k ascending, then
+ *        the columns no earlier step chose ascending, strictly larger replaces, starting at 0), the same validity rules (no
+ *        choice, or an infinite pivot: invalid), the same row operations over all twelve columns and all twelve rows.  With
+ *        `free` the column no step chose: p[free] = 1, p[c_k] = -a[k][free].
+ *     d. The normalisation undone:  M[i][k] = p[4i + k] * s;   m_i = p[4i + 3] - ((M[i][0]*c0 + M[i][1]*c1) + M[i][2]*c2).
+ *     e. det = (M[0][0]*(M[1][1]*M[2][2] - M[1][2]*M[2][1]) - M[0][1]*(M[1][0]*M[2][2] - M[1][2]*M[2][0]))
+ *              + M[0][2]*(M[1][0]*M[2][1] - M[1][1]*M[2][0]).   det zero or not finite: invalid.  det < 0: all twelve entries of
+ *        M and m are negated.
+ *  5. Rotation - steps 2 and 3 of the pose section applied to M.  S = M^T M and the six Jacobi sweeps, verbatim, give S and V;
+ *     k = the index of the smallest S[k][k] (lowest on ties), p < q the other two;  v1 = V[:, p], v2 = V[:, q], v3 = v1 x v2.
+ *     w1_i = (M[i][0]*v1_0 + M[i][1]*v1_1) + M[i][2]*v1_2;  n1 = sqrt((w1_0*w1_0 + w1_1*w1_1) + w1_2*w1_2);  n1 zero or not
+ *     finite: invalid;  u1 = w1 / n1.  w2 likewise from v2;  g = (u1_0*w2_0 + u1_1*w2_1) + u1_2*w2_2;  w2_i = w2_i - g*u1_i;
+ *     n2 = the norm of that w2, same rule;  u2 = w2 / n2;  u3 = u1 x u2.  w3 from v3 as w1 from v1, n3 its norm (no rule).
+ *       R[i][j] = (u1_i*v1_j + u2_i*v2_j) + u3_i*v3_j;   lambda = ((n1 + n2) + n3) / 3;   lambda zero or not finite: invalid;
+ *       t_i = m_i / lambda.   A hypothesis any of whose twelve R, t is not finite is invalid.
+ *  6. Inlier test of a correspondence under (R, t), no division:
+ *       Z_i = ((R[i][0]*Y0 + R[i][1]*Y1) + R[i][2]*Y2) + t_i;   ex = (u*Z2 - Z0)*fx;   ey = (v*Z2 - Z1)*fy;
+ *     an inlier iff Z2 > 0 && (ex*ex + ey*ey) < max_dist2 * (Z2*Z2): the squared reprojection error in pixels^2.
+ *  7. Selection: the valid hypothesis with the most inliers, the lowest h on ties.  Counts are integers, so the result does
+ *     not depend on how the correspondences are split over lanes and workgroups.
+ * Convention: x_{j+1} = R x_j + t.  Every NaN in a double output of this section is written as 0x7ff8000000000000.
+ *
+ * Scratch (the context's): the link table, (n_pairs - 1) * point_cap * 4 bytes, 24 bytes per observation record of capacity
+ * (n_pairs * obs_cap), 48 more without a correspondences buffer, and n_pairs * n_hypotheses * 104 bytes without a hypotheses
+ * buffer; an allocation that fails is VSLAM_ERR_NOMEM. */
+typedef struct {
+    uint32_t n_hypotheses; /* 1 .. 65535 */
+    uint32_t seed;
+    double max_dist2;      /* squared reprojection error in pixels^2, finite and positive */
+    vslam_pose_params K;   /* all finite, fx and fy positive */
+} vslam_resect_params;
+typedef struct {
+    double R[9];      /* all zero when not valid */
+    double t[3];
+    uint32_t inliers;
+    int32_t valid;
+} vslam_resect_hyp; /* 104 bytes */
+typedef struct {
+    double Y[3];       /* step 2: the point in frame j's camera */
+    double u, v;       /* the calibrated observation in frame j + 1 */
+    uint32_t b;        /* the observation record it came from */
+    uint32_t reserved; /* 0 */
+} vslam_resect_corr; /* 48 bytes */
+typedef struct {
+    double R[9];        /* the winner; all zero when best < 0 */
+    double t[3];        /* in pair j - 1's unit */
+    uint32_t n_obs;     /* min(obs_counts[j], obs_cap): the records considered */
+    uint32_t n_corr;    /* usable correspondences, 0 for pair 0 */
+    uint32_t n_inliers; /* the winner's count, 0 when best < 0 */
+    int32_t best;       /* winning hypothesis, -1: none (always for pair 0) */
+    uint32_t n_valid;   /* hypotheses that produced a model */
+    uint32_t reserved;  /* 0 */
+} vslam_resect;         /* 120 bytes */
+/* Like vslam_chain_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;       /* = sizeof(vslam_resect_out) */
+    vslam_resect* models;     /* [n_pairs], required */
+    size_t models_bytes;
+    uint64_t* inlier_bits;    /* [n_pairs][(obs_cap + 63) / 64] optional: bit b % 64 of word b / 64 = observation record b is
+                               * usable and an inlier of the winner; the first (n_obs + 63) / 64 words of a pair are written
+                               * (all zero when best < 0), the rest untouched */
+    size_t inlier_bits_bytes;
+    vslam_resect_hyp* hypotheses; /* [n_pairs][n_hypotheses] optional: every hypothesis with its count */
+    size_t hypotheses_bytes;
+    vslam_resect_corr* correspondences; /* [n_pairs][obs_cap] optional: the first n_corr rows of a pair are written */
+    size_t correspondences_bytes;
+    int32_t* links;           /* [n_pairs][obs_cap] optional: for b < n_obs link_b of step 2 (-1 in pair 0); the rest untouched */
+    size_t links_bytes;
+} vslam_resect_out;
+/* DEVICE pointers, all inputs required.  Asynchronous on the context stream, never waits on the host (the counts are read on
+ * the device, the grids are sized from the capacities); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch -
+ * and before the context is looked at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing),
+ * n_hypotheses outside 1 .. 65535, a max_dist2 that is not finite or not positive, an intrinsic that is not finite, fx or fy
+ * not positive, match_cap / point_cap / obs_cap / train_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when there is no
+ * usable HIP device.  Not for stream capture. */
+int vslam_resect_dev(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                     uint32_t match_cap, const double* points, const uint64_t* front_bits, uint32_t point_cap,
+                     const vslam_match* obs_matches, const uint32_t* obs_counts, uint32_t obs_cap, const vslam_point* train_points,
+                     uint32_t train_cap, int n_pairs, const vslam_resect_params* params, const vslam_resect_out* out);
+/* The same call over HOST arrays, all n_pairs pairs at once, synchronous (a convenience path: device buffers per call).  The
+ * rows the device call leaves untouched keep the caller's bytes.  Errors as for vslam_resect_dev. */
+int vslam_resect_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                      uint32_t match_cap, const double* points, const uint64_t* front_bits, uint32_t point_cap,
+                      const vslam_match* obs_matches, const uint32_t* obs_counts, uint32_t obs_cap, const vslam_point* train_points,
+                      uint32_t train_cap, int n_pairs, const vslam_resect_params* params, const vslam_resect_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

@@ -41,6 +41,10 @@ POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
 CHAIN_DTYPE = np.dtype([("W", "<f8", (9,)), ("w", "<f8", (3,)), ("C", "<f8", (3,)), ("Ct", "<f8", (3,)), ("scale", "<f8"), ("ratio", "<f8"), ("n_links", "<u4"),
                         ("segment", "<i4"), ("linked", "<i4"), ("valid", "<i4")], align=True)  # vslam_chain, 176 bytes
+RESECT_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_resect_hyp, 104 bytes
+RESECT_CORR_DTYPE = np.dtype([("Y", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"), ("b", "<u4"), ("reserved", "<u4")], align=True)  # vslam_resect_corr, 48 bytes
+RESECT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_obs", "<u4"), ("n_corr", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"),
+                         ("n_valid", "<u4"), ("reserved", "<u4")], align=True)  # vslam_resect, 120 bytes
 
 
 class VslamError(RuntimeError):
@@ -196,6 +200,30 @@ class ChainOut(C.Structure):
                 ("links", C.c_void_p), ("links_bytes", C.c_size_t), ("ratios", C.c_void_p), ("ratios_bytes", C.c_size_t)]
 
 
+class ResectParams(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_uint32), ("seed", C.c_uint32), ("max_dist2", C.c_double), ("K", PoseParams)]
+
+
+class ResectHyp(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("inliers", C.c_uint32), ("valid", C.c_int32)]
+
+
+class ResectCorr(C.Structure):
+    _fields_ = [("Y", C.c_double * 3), ("u", C.c_double), ("v", C.c_double), ("b", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Resect(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("n_obs", C.c_uint32), ("n_corr", C.c_uint32), ("n_inliers", C.c_uint32),
+                ("best", C.c_int32), ("n_valid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ResectOut(C.Structure):
+    """vslam_resect_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("inlier_bits", C.c_void_p),
+                ("inlier_bits_bytes", C.c_size_t), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t), ("correspondences", C.c_void_p),
+                ("correspondences_bytes", C.c_size_t), ("links", C.c_void_p), ("links_bytes", C.c_size_t)]
+
+
 class PyramidInfo(C.Structure):
     _fields_ = [
         ("n_octaves", C.c_int), ("n_levels", C.c_int), ("n_dogs", C.c_int), ("sigma0", C.c_double),
@@ -280,6 +308,10 @@ SIGNATURES = {
     "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
     "vslam_chain_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
     "vslam_chain_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
+    "vslam_resect_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(ResectParams),
+                              C.POINTER(ResectOut)]),
+    "vslam_resect_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(ResectParams),
+                               C.POINTER(ResectOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -1046,6 +1078,80 @@ class Context:
         self._chk(lib().vslam_chain_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, pts.ctypes.data, fb.ctypes.data, int(point_cap), n,
                                          C.byref(prm), C.byref(co)), "vslam_chain_host")
         return chain[:n]
+
+    def resect(self, poses, matches, match_counts, points, front_bits, point_cap: int, obs_matches, obs_counts, train_points, intrinsics,
+               n_hypotheses: int = 512, seed: int = 0, max_dist2: float = 4.0, n_pairs: int | None = None, models=None, inlier_bits=None,
+               hypotheses=None, correspondences=None, links=None):
+        """vslam_resect_dev: the camera of frame j + 1 relative to frame j from the points pair j - 1 triangulated (the tensors
+        chain() reads: poses, matches [n, match_cap, 3], match_counts, points, front_bits, point_cap) and their observations -
+        obs_matches [n, obs_cap, 3] with obs_counts (any match list of the pairs: the same tensors, or match()'s raw list) and
+        train_points [n, train_cap, 6]; intrinsics = (fx, fy, cx, cy).  Asynchronous on the context stream.  Outputs, CUDA tensors:
+        models - any contiguous tensor of n_pairs * 120 bytes (RESECT_DTYPE after .cpu().numpy().view), inlier_bits [n, (obs_cap +
+        63) // 64] 8-byte words, hypotheses n * n_hypotheses * 104 bytes (RESECT_HYP_DTYPE), correspondences n * obs_cap * 48 bytes
+        (RESECT_CORR_DTYPE), links int32 [n, obs_cap]."""
+        tensors = dict(poses=poses, matches=matches, match_counts=match_counts, points=points, front_bits=front_bits, obs_matches=obs_matches,
+                       obs_counts=obs_counts, train_points=train_points, models=models, inlier_bits=inlier_bits, hypotheses=hypotheses,
+                       correspondences=correspondences, links=links)
+        for name, t in tensors.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"resect: {name} must be a contiguous tensor on cuda:{self.device}")
+        for name in ("poses", "matches", "match_counts", "points", "front_bits", "obs_matches", "obs_counts", "train_points", "models"):
+            if tensors[name] is None:
+                raise ValueError(f"resect: {name} is required")
+        for name, t in (("matches", matches), ("obs_matches", obs_matches)):
+            if t.dim() != 3 or t.shape[2] * t.element_size() != 12:
+                raise ValueError(f"resect: {name} must be [n, cap, 3] 4-byte elements")
+        if train_points.dim() != 3 or train_points.shape[2] * train_points.element_size() != 24:
+            raise ValueError("resect: train_points must be [n, train_cap, 6] 4-byte elements")
+        n = matches.shape[0] if n_pairs is None else int(n_pairs)
+        cap, ocap, tcap = matches.shape[1], obs_matches.shape[1], train_points.shape[1]
+        size = lambda t: t.numel() * t.element_size()
+        if (matches.shape[0] < n or obs_matches.shape[0] < n or train_points.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n
+                or obs_counts.element_size() != 4 or obs_counts.numel() < n or size(poses) < n * 112 or size(points) < n * cap * 24
+                or size(front_bits) < n * ((cap + 63) // 64) * 8):
+            raise ValueError("resect: fewer sets than pairs")
+        ro = _fill_out(ResectOut(), dict(models=models, inlier_bits=inlier_bits, hypotheses=hypotheses, correspondences=correspondences, links=links))
+        prm = ResectParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
+        self._chk(lib().vslam_resect_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, points.data_ptr(),
+                                         front_bits.data_ptr(), int(point_cap), obs_matches.data_ptr(), obs_counts.data_ptr(), ocap,
+                                         train_points.data_ptr(), tcap, n, C.byref(prm), C.byref(ro)), "vslam_resect_dev")
+
+    def resect_host(self, poses, matches, match_counts, points, front_bits, point_cap: int, obs_matches, obs_counts, train_points, intrinsics,
+                    n_hypotheses: int = 512, seed: int = 0, max_dist2: float = 4.0, inlier_bits=None, hypotheses=None, correspondences=None,
+                    links=None):
+        """vslam_resect_host: the same call over numpy arrays - poses [n] POSE_DTYPE, matches [n, match_cap] MATCH_DTYPE, match_counts
+        [n], points float64 [n, match_cap, 3], front_bits uint64 [n, (match_cap + 63) // 64], obs_matches [n, obs_cap] MATCH_DTYPE,
+        obs_counts [n], train_points [n, train_cap] POINT_DTYPE - -> models [n] RESECT_DTYPE.  inlier_bits uint64 [n, (obs_cap + 63) //
+        64], hypotheses [n, n_hypotheses] RESECT_HYP_DTYPE, correspondences [n, obs_cap] RESECT_CORR_DTYPE and links int32 [n, obs_cap]
+        are written in place when given (C-contiguous arrays of exactly that type); the rows the call leaves untouched keep their
+        bytes."""
+        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
+        mt, ob, tp = (np.ascontiguousarray(a, dtype=dt) for a, dt in ((matches, MATCH_DTYPE), (obs_matches, MATCH_DTYPE), (train_points, POINT_DTYPE)))
+        n = len(ps)
+        if any(a.ndim != 2 or a.shape[0] != n for a in (mt, ob, tp)):
+            raise ValueError("resect_host: matches, obs_matches and train_points must be [n, capacity]")
+        cap, ocap, tcap = mt.shape[1], ob.shape[1], tp.shape[1]
+        cnt, ocnt = (np.ascontiguousarray(a).astype(np.uint32).reshape(-1) for a in (match_counts, obs_counts))
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        fb = np.ascontiguousarray(front_bits).view(np.uint64)
+        if len(cnt) != n or len(ocnt) != n or pts.size != n * cap * 3 or fb.size != n * ((cap + 63) // 64):
+            raise ValueError("resect_host: one count, match_cap points and (match_cap + 63) // 64 words per pair")
+        outs = (("inlier_bits", inlier_bits, np.uint64, n * ((ocap + 63) // 64)), ("hypotheses", hypotheses, RESECT_HYP_DTYPE, n * int(n_hypotheses)),
+                ("correspondences", correspondences, RESECT_CORR_DTYPE, n * ocap), ("links", links, np.int32, n * ocap))
+        for name, a, dt, size in outs:
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
+                raise ValueError(f"resect_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        models = np.zeros(max(n, 1), RESECT_DTYPE)
+        ro = ResectOut(C.sizeof(ResectOut), models.ctypes.data, models.nbytes)
+        for name, a, _, _ in outs:
+            if a is not None:
+                setattr(ro, name, a.ctypes.data)
+                setattr(ro, name + "_bytes", a.nbytes)
+        prm = ResectParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
+        self._chk(lib().vslam_resect_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, pts.ctypes.data, fb.ctypes.data, int(point_cap),
+                                          ob.ctypes.data, ocnt.ctypes.data, ocap, tp.ctypes.data, tcap, n, C.byref(prm), C.byref(ro)),
+                  "vslam_resect_host")
+        return models[:n]
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -13,6 +13,15 @@
 
 using namespace vslam;
 
+int vslam::enqueue_chain_link(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
+                              const uint64_t* front_bits, unsigned int point_cap, int n_pairs, unsigned int* prev) {
+    const ChainPlan pl = chain_plan(match_cap, point_cap, n_pairs);
+    const ChainIn in{poses, matches, match_counts, nullptr, reinterpret_cast<const unsigned long long*>(front_bits), match_cap, pl.fwords, point_cap};
+    HIPCHK(c, hipMemsetAsync(prev, 0xff, pl.table_elems * sizeof(unsigned int), c->stream));
+    LAUNCH(c, "k_chain_link", k_chain_link, dim3(pl.rec_blocks, pl.link_pairs), dim3(CHAIN_REC_WG), in, prev);
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_chain_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
@@ -38,10 +47,7 @@ int vslam_chain_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* ma
     const ChainIn in{poses, matches, match_counts, points, reinterpret_cast<const unsigned long long*>(front_bits), match_cap, pl.fwords, point_cap};
     const dim3 records(pl.rec_blocks, n_pairs);
     HIPCHK(c, hipMemsetAsync(usable, 0, pl.pair_elems * sizeof(unsigned int), c->stream));
-    if (pl.link_pairs) {
-        HIPCHK(c, hipMemsetAsync(prev, 0xff, pl.table_elems * sizeof(unsigned int), c->stream));
-        LAUNCH(c, "k_chain_link", k_chain_link, dim3(pl.rec_blocks, pl.link_pairs), dim3(CHAIN_REC_WG), in, prev);
-    }
+    if (pl.link_pairs) TRY(enqueue_chain_link(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, prev));
     if (pl.link_pairs || out->links || out->ratios)  // (pair 0 alone has no ratios: only its rows of links and ratios to write)
         LAUNCH(c, "k_chain_ratio", k_chain_ratio, records, dim3(CHAIN_REC_WG), in, prev, keys, usable, out->links, out->ratios);
     if (pl.link_pairs)

@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,6 +48,11 @@ int enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned 
 // for them under its output models): flags [n_pairs][fwords], the words that hold a record below the count.
 int enqueue_epi_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_epipolar* models,
                       double max_dist2, int n_pairs, unsigned long long* flags);
+// The link table of the trajectory's step 1 (k_chain_link, compiled in vslam_chain.hip; vslam_resect_dev links by the same
+// rule): prev [n_pairs - 1][point_cap] is preset to 0xffffffff and row j - 1 gets, per train index, the lowest live record of
+// pair j - 1.  n_pairs >= 2.
+int enqueue_chain_link(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
+                       const uint64_t* front_bits, unsigned int point_cap, int n_pairs, unsigned int* prev);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -

@@ -559,3 +559,33 @@ vslam::Trajectory vslam::chainPoses(const std::vector<vslam_pose>& poses, const 
                  c, "chainPoses");
     return out;
 }
+
+vslam::Resection vslam::resectPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                                    uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
+                                    const std::vector<vslam_match>& obsMatches, const std::vector<uint32_t>& obsCounts, uint32_t obsCap,
+                                    const std::vector<SLAM::point>& trainPoints, uint32_t trainCap, const vslam_resect_params& params) {
+    const size_t n = poses.size(), recs = n * matchCap, orecs = n * obsCap, owords = n * (((size_t)obsCap + 63) / 64);
+    require(n <= 65535 && matchCounts.size() == n && matches.size() == recs && points.size() == recs * 3 &&
+                frontBits.size() == n * (((size_t)matchCap + 63) / 64),
+            "resectPoses: one count, matchCap records, matchCap points and (matchCap + 63) / 64 words per pair");
+    require(obsCounts.size() == n && obsMatches.size() == orecs && trainPoints.size() == n * trainCap,
+            "resectPoses: one count, obsCap observation records and trainCap points per pair");
+    vslam::Resection out;
+    out.models.resize(n);
+    out.inlierBits.assign(owords, 0);
+    out.correspondences.assign(orecs, vslam_resect_corr{});
+    out.links.assign(orecs, -1);
+    if (n == 0) return out;
+    vslam_resect_out o{};
+    o.struct_size = sizeof(o);
+    o.models = out.models.data(), o.models_bytes = n * sizeof(vslam_resect);
+    o.inlier_bits = out.inlierBits.data(), o.inlier_bits_bytes = owords * sizeof(uint64_t);
+    o.correspondences = out.correspondences.data(), o.correspondences_bytes = orecs * sizeof(vslam_resect_corr);
+    o.links = out.links.data(), o.links_bytes = orecs * sizeof(int32_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_resect_host(c, poses.data(), matches.data(), matchCounts.data(), matchCap, points.data(), frontBits.data(), pointCap,
+                                   obsMatches.data(), obsCounts.data(), obsCap, reinterpret_cast<const vslam_point*>(trainPoints.data()), trainCap, (int)n,
+                                   &params, &o),
+                 c, "resectPoses");
+    return out;
+}

@@ -251,4 +251,20 @@ struct Trajectory {
 Trajectory chainPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
                       uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
                       const vslam_chain_params& params = {16});
+
+// Beside the chain: the camera of frame j + 1 relative to frame j resected against the points pair j - 1 triangulated, on the
+// GPU (vslam_resect_host; the link, the calibrated 6-point DLT, the reprojection test and the selection are stated in
+// include/vslam.h).  The structure side is what chainPoses takes; the observation side is any match list of the pairs -
+// obsMatches [pairs][obsCap] with obsCounts, the same lists or the raw matches - and the train frames' points, trainPoints
+// [pairs][trainCap].  t comes out in pair j - 1's unit; pair 0 has no model.
+struct Resection {
+    std::vector<vslam_resect> models;              // [pairs]: R, t, the counts; best = -1: none
+    std::vector<uint64_t> inlierBits;              // [pairs][(obsCap + 63) / 64]: observation record b is an inlier of the winner
+    std::vector<vslam_resect_corr> correspondences; // [pairs][obsCap]: the first n_corr rows of a pair hold {Y, u, v, b}; 0: past them
+    std::vector<int32_t> links;                    // [pairs][obsCap]: the linked record of the pair before, or -1
+};
+Resection resectPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                      uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
+                      const std::vector<vslam_match>& obsMatches, const std::vector<uint32_t>& obsCounts, uint32_t obsCap,
+                      const std::vector<SLAM::point>& trainPoints, uint32_t trainCap, const vslam_resect_params& params);
 }  // namespace vslam
