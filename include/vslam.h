@@ -1066,8 +1066,8 @@ int vslam_chain_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match*
  * Beside the two-view pose: the camera of frame j + 1 relative to frame j, estimated from the points pair j - 1 triangulated
  * (3-D) and their observations in frame j + 1 (2-D) - a RANSAC absolute pose.  The translation comes out in pair j - 1's unit,
  * so |t| estimates the trajectory's ratio[j] directly, and a pair whose F is degenerate (vslam_homography_dev's gate) still
- * gets a pose.  A fixed number of hypotheses, no adaptive stop, no refit over the inliers; the result is not fed into
- * vslam_chain_dev.  n_pairs CONSECUTIVE pairs (pair j: query frame j, train frame j + 1).
+ * gets a pose.  A fixed number of hypotheses, no adaptive stop; the refinement over all inliers is a stage of its own
+ * (vslam_resect_refine_dev); the result is not fed into vslam_chain_dev.  n_pairs CONSECUTIVE pairs (pair j: query frame j, train frame j + 1).
  *   Structure side: exactly what vslam_chain_dev reads - poses, matches, match_counts, match_cap, points, front_bits, point_cap -
  *   and the LIVE rule of the trajectory section, verbatim.
  *   Observation side: obs_matches [n_pairs][obs_cap] with obs_counts - any match list of the pair: the same buffers as the
@@ -1183,6 +1183,101 @@ int vslam_resect_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match
                       uint32_t match_cap, const double* points, const uint64_t* front_bits, uint32_t point_cap,
                       const vslam_match* obs_matches, const uint32_t* obs_counts, uint32_t obs_cap, const vslam_point* train_points,
                       uint32_t train_cap, int n_pairs, const vslam_resect_params* params, const vslam_resect_out* out);
+
+/* ---------------------------------------------------------------- resection: Gauss-Newton refinement over all inliers
+ * The step after vslam_resect_dev: the winning minimal hypothesis is refined by Gauss-Newton on the reprojection error of ALL
+ * its inliers (a motion-only bundle adjustment), the inliers are classified again under the new pose, and so on for a fixed
+ * number of rounds; a round whose pose has fewer inliers - or as many and no lower cost - is dropped, so the result never has
+ * fewer inliers than the input.  Inputs: the `models` buffer vslam_resect_dev wrote and the dense `correspondences` list of
+ * the same call ([n_pairs][obs_cap], 16-byte aligned); the link, the gather and the calibration are not repeated.  Pair j
+ * reads n_corr = min(models_in[j].n_corr, obs_cap) rows {Y, u, v, b} and n_obs = min(models_in[j].n_obs, obs_cap).  IEEE f64,
+ * every + - * / rounded on its own (no fused multiply-add, no sqrt, no sin / cos), sums of a few terms left to right as
+ * written, matrices row-major (tests/resectrefineref.py restates it bit for bit).
+ *
+ * A row is a MEMBER under (R, t) iff it passes the inlier test of step 6 of the resection section under (R, t) with max_dist2:
+ *   Z_i = ((R[i][0]*Y0 + R[i][1]*Y1) + R[i][2]*Y2) + t_i;   ex = (u*Z2 - Z0)*fx;   ey = (v*Z2 - Z1)*fy;
+ *   Z2 > 0 && (ex*ex + ey*ey) < max_dist2 * (Z2*Z2).
+ *
+ * The ordered sum SUM(term) is that of the refit section, verbatim, over the dense rows r < n_corr instead of the records i <
+ * m: a row that is not a member contributes +0.0; block b covers rows 4096*b .. 4096*b + 4095; slot l (0 .. 255) starts at
+ * +0.0 and adds the terms of rows 4096*b + 256*k + l, k = 0 .. 15, skipping every row at or past n_corr; then for h = 128, 64,
+ * 32, 16, 8, 4, 2, 1: s_l = s_l + s_(l+h) for every l < h, all from the values of the step before; B_b = s_0; the pair's sum is
+ * ((B_0 + B_1) + B_2) + ... over the (n_corr + 4095) / 4096 blocks, and +0.0 for n_corr = 0.  It depends on n_corr and the terms
+ * only: not on obs_cap, not on the grid, not on the device.
+ *
+ * EVALUATE (R, t) - 29 ordered sums.  Per member, with Z as above:
+ *   iz = 1 / Z2;   px = Z0*iz;   py = Z1*iz;   rx = (px - u)*fx;   ry = (py - v)*fy;   pxy = px*py;
+ *   Jx = { fx*(-pxy),  fx*(1 + px*px),  fx*(-py),  fx*iz,  fx*0.0,  fx*(-(px*iz)) };
+ *   Jy = { fy*(-(1 + py*py)),  fy*pxy,  fy*px,  fy*0.0,  fy*iz,  fy*(-(py*iz)) }
+ * - the rows of the Jacobian of (rx, ry) for the left perturbation Z' = Z + w x Z + tau, unknowns (w0, w1, w2, tau0, tau1, tau2).
+ *   H[p][q] = SUM(Jx_p*Jx_q + Jy_p*Jy_q) for p <= q, row-major (21 sums), mirrored below the diagonal;
+ *   g_p = SUM(Jx_p*rx + Jy_p*ry) (6 sums);   cost = SUM(rx*rx + ry*ry);   n = SUM(1.0), the member count, exact.
+ *
+ * STEP from (R, t), H, g:
+ *  a. The 6 x 7 matrix a = [H | -g].  Step 3 of the two-view model over 6 rows, steps k = 0 .. 5: the pivot is the entry of
+ *     largest |a[r][c]| over rows r >= k and the columns c < 6 no earlier step chose, the same scan (r ascending, then c
+ *     ascending, strictly larger replaces, starting at 0: a zero or a NaN is never chosen), the same validity rules (no choice,
+ *     or an infinite pivot: invalid); rows k and r are swapped; every entry of row k is divided by the pivot; for every other
+ *     row i, with g = a[i][c]: a[i][c'] = a[i][c'] - g * a[k][c'] for all seven c'.  c_k = c.  d[c_k] = a[k][6].  Any of the six
+ *     d not finite: invalid.  w = (d0, d1, d2), tau = (d3, d4, d5).
+ *  b. The Cayley rotation of w.  a_i = w_i / 2;   q = (a0*a0 + a1*a1) + a2*a2;   e = 1 - q;   den = 1 + q;
+ *       D[i][i] = (e + 2*(a_i*a_i)) / den;
+ *       D[0][1] = (2*(a0*a1) - 2*a2) / den;   D[1][0] = (2*(a1*a0) + 2*a2) / den;   D[0][2] = (2*(a0*a2) + 2*a1) / den;
+ *       D[2][0] = (2*(a2*a0) - 2*a1) / den;   D[1][2] = (2*(a1*a2) - 2*a0) / den;   D[2][1] = (2*(a2*a1) + 2*a0) / den.
+ *  c. R_new[i][j] = (D[i][0]*R[0][j] + D[i][1]*R[1][j]) + D[i][2]*R[2][j];
+ *     t_new_i = ((D[i][0]*t0 + D[i][1]*t1) + D[i][2]*t2) + tau_i.   Any of the twelve not finite: invalid.
+ *
+ * Per pair.  A pair with models_in[j].best < 0 is copied through, byte for byte, with stop = 5 and n_before = n_after =
+ * accepted = 0, cost_before = cost_after = 0.  Otherwise (R, t)_cur = models_in[j]'s; EVALUATE it: n_cur = n, cost_cur = cost,
+ * n_before = n_cur, cost_before = cost_cur, accepted = 0.  Round 1 .. rounds, until a stop:
+ *  1. n_cur < 6: stop = 1.
+ *  2. STEP from (R, t)_cur with the H and g of its evaluation; invalid: stop = 3.
+ *  3. EVALUATE (R, t)_new.  It is kept iff n_new > n_cur, or n_new == n_cur && cost_new < cost_cur: then (R, t)_cur = (R,
+ *     t)_new with its n, cost, H and g, and accepted += 1; otherwise stop = 4.
+ * All rounds done without a stop: stop = 0.  After a stop the pair does nothing more.  Output: models[j] = models_in[j] with
+ * R, t = (R, t)_cur and n_inliers = n_cur (every other field copied); n_after = n_cur >= n_before, cost_after = cost_cur.  Every
+ * NaN in a double output of a pair with best >= 0 is written as 0x7ff8000000000000.  inlier_bits: bit b % 64 of word b / 64 is
+ * set iff best >= 0, b < n_obs and a row r < n_corr with corr.b == b is a member under the output pose.
+ *
+ * Scratch (the context's): n_pairs * ((obs_cap + 4095) / 4096) * 232 bytes of block sums and n_pairs * 344 bytes of state; an
+ * allocation that fails is VSLAM_ERR_NOMEM. */
+typedef struct {
+    uint32_t rounds;     /* 1 .. 8 */
+    double max_dist2;    /* as vslam_resect_params: squared reprojection error in pixels^2, finite and positive */
+    vslam_pose_params K; /* all finite, fx and fy positive (fx, fy enter the arithmetic) */
+} vslam_resect_refine_params;
+typedef struct {
+    uint32_t n_before, n_after;     /* members under the input pose / under the output pose */
+    uint32_t accepted;              /* rounds whose pose was kept */
+    int32_t stop;                   /* 0: ran all rounds, 1: fewer than 6 members, 3: the step was invalid, 4: the new pose was
+                                     * not better, 5: no input model */
+    double cost_before, cost_after; /* SUM(rx*rx + ry*ry) in pixels^2 under the input pose / under the output pose */
+} vslam_resect_refine;              /* 32 bytes */
+/* Like vslam_resect_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;        /* = sizeof(vslam_resect_refine_out) */
+    vslam_resect* models;      /* [n_pairs], required; may be the very pointer passed as models_in, must not otherwise overlap it */
+    size_t models_bytes;
+    vslam_resect_refine* info; /* [n_pairs] optional */
+    size_t info_bytes;
+    uint64_t* inlier_bits;     /* [n_pairs][(obs_cap + 63) / 64] optional: indexed by observation record b as
+                                * vslam_resect_out.inlier_bits; the first (n_obs + 63) / 64 words of a pair are written (all zero
+                                * when best < 0), the rest untouched */
+    size_t inlier_bits_bytes;
+} vslam_resect_refine_out;
+/* DEVICE pointers.  Asynchronous on the context stream, never waits on the host (the counts are read on the device, the grids
+ * are sized from the capacity, a stopped pair's workgroups leave at once); scratch belongs to the context.  VSLAM_ERR_INVALID
+ * before any launch - and before the context is looked at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535
+ * (0 does nothing), rounds outside 1 .. 8, a max_dist2 that is not finite or not positive, an intrinsic that is not finite, fx
+ * or fy not positive, obs_cap == 0, correspondences not 16-byte aligned, an undersized buffer, models overlapping models_in
+ * without being equal to it; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_resect_refine_dev(vslam_ctx* ctx, const vslam_resect* models_in, const vslam_resect_corr* correspondences, uint32_t obs_cap,
+                            int n_pairs, const vslam_resect_refine_params* params, const vslam_resect_refine_out* out);
+/* The same call over HOST arrays, all n_pairs pairs at once, synchronous (a convenience path: device buffers per call; the
+ * alignment rule does not apply).  The words of inlier_bits the device call leaves untouched keep the caller's bytes.  Errors
+ * as for vslam_resect_refine_dev. */
+int vslam_resect_refine_host(vslam_ctx* ctx, const vslam_resect* models_in, const vslam_resect_corr* correspondences, uint32_t obs_cap,
+                             int n_pairs, const vslam_resect_refine_params* params, const vslam_resect_refine_out* out);
 
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the

@@ -45,6 +45,8 @@ RESECT_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("inliers",
 RESECT_CORR_DTYPE = np.dtype([("Y", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"), ("b", "<u4"), ("reserved", "<u4")], align=True)  # vslam_resect_corr, 48 bytes
 RESECT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_obs", "<u4"), ("n_corr", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"),
                          ("n_valid", "<u4"), ("reserved", "<u4")], align=True)  # vslam_resect, 120 bytes
+RESECT_REFINE_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4"), ("cost_before", "<f8"),
+                                ("cost_after", "<f8")], align=True)  # vslam_resect_refine, 32 bytes
 
 
 class VslamError(RuntimeError):
@@ -224,6 +226,21 @@ class ResectOut(C.Structure):
                 ("correspondences_bytes", C.c_size_t), ("links", C.c_void_p), ("links_bytes", C.c_size_t)]
 
 
+class ResectRefineParams(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("max_dist2", C.c_double), ("K", PoseParams)]
+
+
+class ResectRefine(C.Structure):
+    _fields_ = [("n_before", C.c_uint32), ("n_after", C.c_uint32), ("accepted", C.c_uint32), ("stop", C.c_int32), ("cost_before", C.c_double),
+                ("cost_after", C.c_double)]
+
+
+class ResectRefineOut(C.Structure):
+    """vslam_resect_refine_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("info", C.c_void_p), ("info_bytes", C.c_size_t),
+                ("inlier_bits", C.c_void_p), ("inlier_bits_bytes", C.c_size_t)]
+
+
 class PyramidInfo(C.Structure):
     _fields_ = [
         ("n_octaves", C.c_int), ("n_levels", C.c_int), ("n_dogs", C.c_int), ("sigma0", C.c_double),
@@ -312,6 +329,8 @@ SIGNATURES = {
                               C.POINTER(ResectOut)]),
     "vslam_resect_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(ResectParams),
                                C.POINTER(ResectOut)]),
+    "vslam_resect_refine_dev": (_I, [_P, _P, _P, C.c_uint32, _I, C.POINTER(ResectRefineParams), C.POINTER(ResectRefineOut)]),
+    "vslam_resect_refine_host": (_I, [_P, _P, _P, C.c_uint32, _I, C.POINTER(ResectRefineParams), C.POINTER(ResectRefineOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -1152,6 +1171,51 @@ class Context:
                                           ob.ctypes.data, ocnt.ctypes.data, ocap, tp.ctypes.data, tcap, n, C.byref(prm), C.byref(ro)),
                   "vslam_resect_host")
         return models[:n]
+
+    def resect_refine(self, models_in, correspondences, obs_cap: int, intrinsics, rounds: int = 4, max_dist2: float = 4.0, n_pairs: int | None = None,
+                      models=None, info=None, inlier_bits=None):
+        """vslam_resect_refine_dev: the Gauss-Newton refinement of every pair's resected pose over all its inliers, after resect();
+        asynchronous on the context stream.  models_in: the tensor resect() wrote (n_pairs * 120 bytes); correspondences: the dense
+        list of the same call (n_pairs * obs_cap * 48 bytes); intrinsics = (fx, fy, cx, cy).  Outputs, CUDA tensors: models n_pairs *
+        120 bytes (may be models_in itself), info n_pairs * 32 bytes (RESECT_REFINE_DTYPE), inlier_bits [n, (obs_cap + 63) // 64]
+        8-byte words, indexed by observation record like resect()'s, under the output pose."""
+        tensors = dict(models_in=models_in, correspondences=correspondences, models=models, info=info, inlier_bits=inlier_bits)
+        for name, t in tensors.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"resect_refine: {name} must be a contiguous tensor on cuda:{self.device}")
+        for name in ("models_in", "correspondences", "models"):
+            if tensors[name] is None:
+                raise ValueError(f"resect_refine: {name} is required")
+        size = lambda t: t.numel() * t.element_size()
+        n = size(models_in) // 120 if n_pairs is None else int(n_pairs)
+        if size(models_in) < n * 120 or size(correspondences) < n * int(obs_cap) * 48:
+            raise ValueError("resect_refine: models_in must hold n_pairs * 120 bytes, correspondences n_pairs * obs_cap * 48")
+        ro = _fill_out(ResectRefineOut(), dict(models=models, info=info, inlier_bits=inlier_bits))
+        prm = ResectRefineParams(int(rounds), float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
+        self._chk(lib().vslam_resect_refine_dev(self._h, models_in.data_ptr(), correspondences.data_ptr(), int(obs_cap), n, C.byref(prm), C.byref(ro)),
+                  "vslam_resect_refine_dev")
+
+    def resect_refine_host(self, models_in, correspondences, intrinsics, rounds: int = 4, max_dist2: float = 4.0, inlier_bits=None):
+        """vslam_resect_refine_host: the same call over numpy arrays - models_in [n] RESECT_DTYPE, correspondences [n, obs_cap]
+        RESECT_CORR_DTYPE - -> (models [n] RESECT_DTYPE, info [n] RESECT_REFINE_DTYPE).  inlier_bits uint64 [n, (obs_cap + 63) // 64]
+        is written in place when given; the words the call leaves untouched keep their bytes."""
+        mi = np.ascontiguousarray(models_in, dtype=RESECT_DTYPE).reshape(-1)
+        cs = np.ascontiguousarray(correspondences, dtype=RESECT_CORR_DTYPE)
+        n = len(mi)
+        if cs.ndim != 2 or cs.shape[0] != n:
+            raise ValueError("resect_refine_host: correspondences must be [n, obs_cap]")
+        ocap = cs.shape[1]
+        words = n * ((ocap + 63) // 64)
+        if inlier_bits is not None and not (isinstance(inlier_bits, np.ndarray) and inlier_bits.dtype == np.uint64 and inlier_bits.flags.c_contiguous
+                                            and inlier_bits.size == words):
+            raise ValueError(f"resect_refine_host: inlier_bits must be a C-contiguous uint64 array of {words} elements")
+        models, info = np.zeros(max(n, 1), RESECT_DTYPE), np.zeros(max(n, 1), RESECT_REFINE_DTYPE)
+        ro = ResectRefineOut(C.sizeof(ResectRefineOut), models.ctypes.data, models.nbytes, info.ctypes.data, info.nbytes)
+        if inlier_bits is not None:
+            ro.inlier_bits, ro.inlier_bits_bytes = inlier_bits.ctypes.data, inlier_bits.nbytes
+        prm = ResectRefineParams(int(rounds), float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
+        self._chk(lib().vslam_resect_refine_host(self._h, mi.ctypes.data, cs.ctypes.data, ocap, n, C.byref(prm), C.byref(ro)), "vslam_resect_refine_host")
+        return models[:n], info[:n]
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -133,6 +133,37 @@ G3 inline void g3_store_word(unsigned long long* words, size_t j, unsigned int f
 }
 
 #ifdef __HIPCC__
+// The tree of the ordered sum (the refit section's SUM) over the 256 slots of a workgroup, N sums at once: h = 128 and 64 through LDS (lds [N][128] f64, slot-major:
+// the lanes of one access hit consecutive f64), h = 32 .. 1 by __shfl_down inside wave 0.  Lane 0 ends with B_b.
+template <int N>
+__device__ __forceinline__ void refit_tree(double (&s)[N], double* lds) {
+    const unsigned int l = threadIdx.x;
+    if (l >= 128) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) lds[k * 128 + (l - 128)] = s[k];
+    }
+    __syncthreads();
+    if (l < 128) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] = s[k] + lds[k * 128 + l];
+    }
+    __syncthreads();
+    if (l >= 64 && l < 128) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) lds[k * 128 + (l - 64)] = s[k];
+    }
+    __syncthreads();
+    if (l < 64) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] = s[k] + lds[k * 128 + l];
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k] = s[k] + __shfl_down(s[k], h);
+        }
+    }
+}
+
 // A NaN leaves as the quiet NaN 0x7ff8000000000000: IEEE fixes neither the sign nor the payload of a NaN an operation makes.
 // (k_pose_points and the trajectory kernels, kernels_chain.hip.h.)
 __device__ __forceinline__ double pose_canonical(double x) { return x == x ? x : __longlong_as_double(0x7ff8000000000000ll); }

@@ -23,36 +23,7 @@
 
 namespace vslam {
 
-// The tree of the ordered sum over the 256 slots, N sums at once: h = 128 and 64 through LDS (lds [N][128] f64, slot-major:
-// the lanes of one access hit consecutive f64), h = 32 .. 1 by __shfl_down inside wave 0.  Lane 0 ends with B_b.
-template <int N>
-__device__ __forceinline__ void refit_tree(double (&s)[N], double* lds) {
-    const unsigned int l = threadIdx.x;
-    if (l >= 128) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) lds[k * 128 + (l - 128)] = s[k];
-    }
-    __syncthreads();
-    if (l < 128) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k] = s[k] + lds[k * 128 + l];
-    }
-    __syncthreads();
-    if (l >= 64 && l < 128) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) lds[k * 128 + (l - 64)] = s[k];
-    }
-    __syncthreads();
-    if (l < 64) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k] = s[k] + lds[k * 128 + l];
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k] = s[k] + __shfl_down(s[k], h);
-        }
-    }
-}
+// (refit_tree<N>, the tree of the ordered sum over the 256 slots, is kernels_geom3.hip.h's: the resection's refinement sums the same way.)
 
 // One block of the ordered sum: add(s, p) adds a member's N terms to the slot's sums, in the header's order of records.
 template <int N, class Add>

@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip, vslam_resect_refine.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -589,3 +589,22 @@ vslam::Resection vslam::resectPoses(const std::vector<vslam_pose>& poses, const 
                  c, "resectPoses");
     return out;
 }
+
+vslam::RefinedResection vslam::refineResection(const std::vector<vslam_resect>& models, const std::vector<vslam_resect_corr>& correspondences,
+                                               uint32_t obsCap, const vslam_resect_refine_params& params) {
+    const size_t n = models.size(), orecs = n * obsCap, owords = n * (((size_t)obsCap + 63) / 64);
+    require(n <= 65535 && correspondences.size() == orecs, "refineResection: obsCap correspondence rows per pair");
+    vslam::RefinedResection out;
+    out.models.resize(n);
+    out.info.assign(n, vslam_resect_refine{});
+    out.inlierBits.assign(owords, 0);
+    if (n == 0) return out;
+    vslam_resect_refine_out o{};
+    o.struct_size = sizeof(o);
+    o.models = out.models.data(), o.models_bytes = n * sizeof(vslam_resect);
+    o.info = out.info.data(), o.info_bytes = n * sizeof(vslam_resect_refine);
+    o.inlier_bits = out.inlierBits.data(), o.inlier_bits_bytes = owords * sizeof(uint64_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_resect_refine_host(c, models.data(), correspondences.data(), obsCap, (int)n, &params, &o), c, "refineResection");
+    return out;
+}

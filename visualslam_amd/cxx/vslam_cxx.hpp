@@ -267,4 +267,15 @@ Resection resectPoses(const std::vector<vslam_pose>& poses, const std::vector<vs
                       uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
                       const std::vector<vslam_match>& obsMatches, const std::vector<uint32_t>& obsCounts, uint32_t obsCap,
                       const std::vector<SLAM::point>& trainPoints, uint32_t trainCap, const vslam_resect_params& params);
+
+// After resectPoses: every pair's pose refined by Gauss-Newton over all its inliers, on the GPU (vslam_resect_refine_host; the
+// residual, the Jacobian, the ordered sums, the elimination, the Cayley update and the acceptance rule are stated in
+// include/vslam.h).  models and correspondences are Resection's; the result never has fewer inliers than its input.
+struct RefinedResection {
+    std::vector<vslam_resect> models;       // [pairs]: R, t and n_inliers of the refined pose, the other fields copied
+    std::vector<vslam_resect_refine> info;  // [pairs]: counts and costs before and after, kept rounds, stop
+    std::vector<uint64_t> inlierBits;       // [pairs][(obsCap + 63) / 64]: observation record b is a member under the refined pose
+};
+RefinedResection refineResection(const std::vector<vslam_resect>& models, const std::vector<vslam_resect_corr>& correspondences, uint32_t obsCap,
+                                 const vslam_resect_refine_params& params);
 }  // namespace vslam
