@@ -1279,6 +1279,110 @@ int vslam_resect_refine_dev(vslam_ctx* ctx, const vslam_resect* models_in, const
 int vslam_resect_refine_host(vslam_ctx* ctx, const vslam_resect* models_in, const vslam_resect_corr* correspondences, uint32_t obs_cap,
                              int n_pairs, const vslam_resect_refine_params* params, const vslam_resect_refine_out* out);
 
+/* ---------------------------------------------------------------- tracks: points linked across pairs, triangulated from all views
+ * The step after vslam_chain_dev.  The trajectory links pair j to pair j - 1 by index for one distance ratio and forgets the
+ * link; this step keeps it: a TRACK is one scene point, the records of consecutive pairs that saw it, and one 3-D position
+ * computed from all of its views at once (the point that is closest, in the least-squares sense, to every view's ray).  The
+ * inputs are what vslam_chain_dev read, minus `points` - poses [n_pairs], matches [n_pairs][match_cap], match_counts, front_bits
+ * [n_pairs][(match_cap + 63) / 64], point_cap -, the chain records [n_pairs] that call wrote, and the frames' point lists
+ * frame_points [n_pairs + 1][point_cap]: frame j is the query of pair j and the train of pair j - 1.  The arithmetic is fixed here
+ * so that a CPU can restate it bit for bit (tests/tracksref.py): IEEE f64, every + - * / rounded on its own (no fused
+ * multiply-add), sums left to right as written, matrices row-major.
+ *
+ *  1. Live records and prev_j: m_j, the LIVE rule and step 1 of the trajectory section, verbatim.  For pair j >= 1 and point
+ *     index k < point_cap, prev_j[k] is the lowest live record of pair j - 1 whose train == k.
+ *  2. Continuation, one-to-one.  For j >= 1 with chain[j].linked != 0: a live record b of pair j for which a = prev_j[query_b]
+ *     exists is a CANDIDATE for a.  next_{j-1}[a] is the LOWEST candidate b for a (an integer minimum: the same in any order).
+ *     Record b CONTINUES a iff next_{j-1}[a] == b.  A live record that continues nothing is a HEAD.  A track is a head and
+ *     the chain of records that continue it: record (j0, i0), then (j0 + 1, next_{j0}[i0]), and so on while that exists.  A
+ *     record has at most one successor and at most one predecessor, so a track is a path, never a tree - also on lists where
+ *     several records share a query or a train index; every live record lies on exactly one track.  A track never crosses a
+ *     pair with linked == 0: it lies in one segment, one world frame.
+ *     A track of L records (j0, i0) .. (j0 + L - 1, i_{L-1}) has n_views = L + 1 VIEWS, in this order:
+ *       view p < L: the query side of record p: pixel = frame_points[j][query], camera (W, w) = (chain[j].W, chain[j].w), centre
+ *         C = chain[j].C, with j = j0 + p;
+ *       view L: the train side of the last record, j = j0 + L - 1: pixel = frame_points[j + 1][train], camera
+ *         W[i][k] = (R[i][0]*Wj[0][k] + R[i][1]*Wj[1][k]) + R[i][2]*Wj[2][k],   w_i = ((R[i][0]*wj0 + R[i][1]*wj1) + R[i][2]*wj2) + s*t_i
+ *         with (R, t) = (poses[j].R, poses[j].t), (Wj, wj, s) = (chain[j].W, chain[j].w, chain[j].scale) - the trajectory's two
+ *         product rules -, centre C = chain[j].Ct.
+ *  3. Normal equations.  Six sums A00, A01, A02, A11, A12, A22 and three sums g0, g1, g2, each starting at 0.0, each view
+ *     added in the order of step 2.  Per view:
+ *       (x, y): the exact coordinate of the view's point record p (two-view geometry section) when p.octave is in 0 .. 31; NaN,
+ *         NaN otherwise, carried through;
+ *       q0 = (x - cx)/fx;  q1 = (y - cy)/fy;
+ *       d_i = (W[0][i]*q0 + W[1][i]*q1) + W[2][i]           (the ray W^T (q0, q1, 1) in the world);
+ *       dd = (d0*d0 + d1*d1) + d2*d2;   e_i = d_i / dd;
+ *       P_ii = 1.0 - e_i*d_i;   P_ik = 0.0 - e_i*d_k for i < k, and P_ki = P_ik           (the projector I - d d^T / dd);
+ *       A_ik = A_ik + P_ik for i <= k;   g_i = g_i + ((P_i0*C0 + P_i1*C1) + P_i2*C2).
+ *  4. Point.  The cofactors of the symmetric A:
+ *       c00 = A11*A22 - A12*A12;   c01 = A02*A12 - A01*A22;   c02 = A01*A12 - A02*A11;
+ *       c11 = A00*A22 - A02*A02;   c12 = A01*A02 - A00*A12;   c22 = A00*A11 - A01*A01;       c_ki = c_ik;
+ *       det = (A00*c00 + A01*c01) + A02*c02;    X_i = ((c_i0*g0 + c_i1*g1) + c_i2*g2) / det.
+ *     SOLVED iff det > 0 && det < +inf && X0, X1, X2 are all finite.  X and det are written as computed.
+ *  5. Reprojection, per view under that view's camera and with (u, v) = (q0, q1) of step 3, no division:
+ *       Z_i = ((W[i][0]*X0 + W[i][1]*X1) + W[i][2]*X2) + w_i;    ex = (u*Z2 - Z0)*fx;    ey = (v*Z2 - Z1)*fy;
+ *     the view is OK iff Z2 > 0 && (ex*ex + ey*ey) < max_dist2 * (Z2*Z2).  n_ok = the number of ok views, an integer: no
+ *     order matters.  GOOD iff solved && n_ok == n_views && n_views >= min_views.
+ * Every NaN in a double output of this section is written as 0x7ff8000000000000.  Nothing here refines X, feeds a later
+ * stage, or lists the tracks densely: a track lives at its head's slot.
+ *
+ * Scratch (the context's): the two tables prev and next, (n_pairs - 1) * (point_cap + match_cap) * 4 bytes; an allocation that
+ * fails is VSLAM_ERR_NOMEM. */
+typedef struct {
+    vslam_pose_params K; /* all finite, fx and fy positive */
+    double max_dist2;    /* squared reprojection error in pixels^2, finite and positive */
+    uint32_t min_views;  /* >= 2: the views a good track needs */
+    uint32_t reserved;   /* not read */
+} vslam_tracks_params;
+typedef struct {
+    double X[3];       /* step 4, in the world frame of the track's segment */
+    double det;        /* step 4 */
+    uint32_t n_views;  /* records on the track + 1 */
+    uint32_t n_ok;     /* step 5 */
+    uint32_t status;   /* bit 0: solved, bit 1: good */
+    uint32_t reserved; /* 0 */
+} vslam_track;         /* 48 bytes */
+typedef struct {
+    uint32_t head_record; /* the record of pair j - pos the track starts at */
+    uint32_t pos;         /* this record's position on the track: j - the head's pair */
+} vslam_track_ref;        /* 8 bytes */
+typedef struct {
+    uint32_t n_heads;   /* tracks that start in pair j */
+    uint32_t n_good;    /* of those, the good ones */
+    uint32_t max_views; /* the most views of a track that starts in pair j, 0 without one */
+    uint32_t reserved;  /* 0 */
+} vslam_track_summary;  /* 16 bytes */
+/* Like vslam_chain_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;  /* = sizeof(vslam_tracks_out) */
+    vslam_track* tracks; /* [n_pairs][match_cap], required: row i < m_j of pair j holds the track whose head is record i; a record
+                          * that is not a head gets X = det = the quiet NaN and n_views = n_ok = status = 0; rows past m_j are
+                          * left untouched */
+    size_t tracks_bytes;
+    vslam_track_ref* refs; /* [n_pairs][match_cap] optional, the observation -> track table: for i < m_j the track record i lies
+                            * on, all ones in both fields for a record that is not live; the rest untouched */
+    size_t refs_bytes;
+    uint64_t* good_bits; /* [n_pairs][(match_cap + 63) / 64] optional: bit i % 64 of word i / 64 = record i is the head of a good
+                          * track; the first (m_j + 63) / 64 words of a pair are written, the rest untouched */
+    size_t good_bits_bytes;
+    vslam_track_summary* summary; /* [n_pairs] optional: integer counts, every record written */
+    size_t summary_bytes;
+} vslam_tracks_out;
+/* DEVICE pointers, all inputs required.  Asynchronous on the context stream, never waits on the host (the counts are read on
+ * the device, the grids are sized from the capacities); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch -
+ * and before the context is looked at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing; 1
+ * gives tracks of two views), an intrinsic that is not finite, fx or fy not positive, a max_dist2 that is not finite or not
+ * positive, min_views < 2, match_cap or point_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP
+ * device.  Not for stream capture. */
+int vslam_tracks_dev(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                     uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain* chain,
+                     const vslam_point* frame_points, const vslam_tracks_params* params, const vslam_tracks_out* out);
+/* The same call over HOST arrays, all n_pairs pairs at once, synchronous (a convenience path: device buffers per call).  The
+ * rows the device call leaves untouched keep the caller's bytes.  Errors as for vslam_tracks_dev. */
+int vslam_tracks_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                      uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain* chain,
+                      const vslam_point* frame_points, const vslam_tracks_params* params, const vslam_tracks_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

@@ -47,6 +47,10 @@ RESECT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_obs", "<u4"
                          ("n_valid", "<u4"), ("reserved", "<u4")], align=True)  # vslam_resect, 120 bytes
 RESECT_REFINE_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4"), ("cost_before", "<f8"),
                                 ("cost_after", "<f8")], align=True)  # vslam_resect_refine, 32 bytes
+TRACK_DTYPE = np.dtype([("X", "<f8", (3,)), ("det", "<f8"), ("n_views", "<u4"), ("n_ok", "<u4"), ("status", "<u4"), ("reserved", "<u4")],
+                       align=True)  # vslam_track, 48 bytes
+TRACK_REF_DTYPE = np.dtype([("head_record", "<u4"), ("pos", "<u4")], align=True)  # vslam_track_ref, 8 bytes
+TRACK_SUMMARY_DTYPE = np.dtype([("n_heads", "<u4"), ("n_good", "<u4"), ("max_views", "<u4"), ("reserved", "<u4")], align=True)  # vslam_track_summary, 16 bytes
 
 
 class VslamError(RuntimeError):
@@ -241,6 +245,16 @@ class ResectRefineOut(C.Structure):
                 ("inlier_bits", C.c_void_p), ("inlier_bits_bytes", C.c_size_t)]
 
 
+class TracksParams(C.Structure):
+    _fields_ = [("K", PoseParams), ("max_dist2", C.c_double), ("min_views", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TracksOut(C.Structure):
+    """vslam_tracks_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("tracks", C.c_void_p), ("tracks_bytes", C.c_size_t), ("refs", C.c_void_p), ("refs_bytes", C.c_size_t),
+                ("good_bits", C.c_void_p), ("good_bits_bytes", C.c_size_t), ("summary", C.c_void_p), ("summary_bytes", C.c_size_t)]
+
+
 class PyramidInfo(C.Structure):
     _fields_ = [
         ("n_octaves", C.c_int), ("n_levels", C.c_int), ("n_dogs", C.c_int), ("sigma0", C.c_double),
@@ -331,6 +345,8 @@ SIGNATURES = {
                                C.POINTER(ResectOut)]),
     "vslam_resect_refine_dev": (_I, [_P, _P, _P, C.c_uint32, _I, C.POINTER(ResectRefineParams), C.POINTER(ResectRefineOut)]),
     "vslam_resect_refine_host": (_I, [_P, _P, _P, C.c_uint32, _I, C.POINTER(ResectRefineParams), C.POINTER(ResectRefineOut)]),
+    "vslam_tracks_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, C.POINTER(TracksParams), C.POINTER(TracksOut)]),
+    "vslam_tracks_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, C.POINTER(TracksParams), C.POINTER(TracksOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -1097,6 +1113,70 @@ class Context:
         self._chk(lib().vslam_chain_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, pts.ctypes.data, fb.ctypes.data, int(point_cap), n,
                                          C.byref(prm), C.byref(co)), "vslam_chain_host")
         return chain[:n]
+
+    def tracks(self, poses, matches, match_counts, front_bits, point_cap: int, chain, frame_points, intrinsics, max_dist2: float = 4.0,
+               min_views: int = 2, n_pairs: int | None = None, tracks=None, refs=None, good_bits=None, summary=None):
+        """vslam_tracks_dev: the records of consecutive pairs that saw one scene point linked into tracks, and every track's point
+        triangulated from all of its views; asynchronous on the context stream.  poses, matches [n, match_cap, 3], match_counts and
+        front_bits are the tensors chain() read, chain the records it wrote, frame_points [n + 1, point_cap, 6] the frames' point
+        lists; intrinsics = (fx, fy, cx, cy).  Outputs, CUDA tensors: tracks - any contiguous tensor of n * match_cap * 48 bytes
+        (TRACK_DTYPE after .cpu().numpy().view), refs n * match_cap * 8 bytes (TRACK_REF_DTYPE), good_bits [n, (match_cap + 63) // 64]
+        8-byte words, summary n * 16 bytes (TRACK_SUMMARY_DTYPE)."""
+        tensors = dict(poses=poses, matches=matches, match_counts=match_counts, front_bits=front_bits, chain=chain, frame_points=frame_points,
+                       tracks=tracks, refs=refs, good_bits=good_bits, summary=summary)
+        for name, t in tensors.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"tracks: {name} must be a contiguous tensor on cuda:{self.device}")
+        for name in ("poses", "matches", "match_counts", "front_bits", "chain", "frame_points", "tracks"):
+            if tensors[name] is None:
+                raise ValueError(f"tracks: {name} is required")
+        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12:
+            raise ValueError("tracks: matches must be [n, match_cap, 3] 4-byte elements")
+        n = matches.shape[0] if n_pairs is None else int(n_pairs)
+        cap = matches.shape[1]
+        size = lambda t: t.numel() * t.element_size()
+        if (matches.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n or size(poses) < n * 112 or size(chain) < n * 176
+                or size(front_bits) < n * ((cap + 63) // 64) * 8 or size(frame_points) < (n + 1) * int(point_cap) * 24):
+            raise ValueError("tracks: fewer sets than pairs")
+        to = _fill_out(TracksOut(), dict(tracks=tracks, refs=refs, good_bits=good_bits, summary=summary))
+        prm = TracksParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), 0)
+        self._chk(lib().vslam_tracks_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, front_bits.data_ptr(),
+                                         int(point_cap), n, chain.data_ptr(), frame_points.data_ptr(), C.byref(prm), C.byref(to)), "vslam_tracks_dev")
+
+    def tracks_host(self, poses, matches, match_counts, front_bits, point_cap: int, chain, frame_points, intrinsics, max_dist2: float = 4.0,
+                    min_views: int = 2, tracks=None, refs=None, good_bits=None, summary=None):
+        """vslam_tracks_host: the same call over numpy arrays - poses [n] POSE_DTYPE, matches [n, match_cap] MATCH_DTYPE, match_counts
+        [n], front_bits uint64 [n, (match_cap + 63) // 64], chain [n] CHAIN_DTYPE, frame_points [n + 1, point_cap] POINT_DTYPE - ->
+        tracks [n, match_cap] TRACK_DTYPE.  tracks (TRACK_DTYPE [n, match_cap]: the rows the call leaves untouched keep their bytes),
+        refs (TRACK_REF_DTYPE [n, match_cap]), good_bits (uint64 [n, words]) and summary (TRACK_SUMMARY_DTYPE [n]) are written in
+        place when given (C-contiguous arrays of exactly that type)."""
+        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
+        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(ps)
+        if mt.ndim != 2 or mt.shape[0] != n:
+            raise ValueError("tracks_host: matches must be [n, match_cap]")
+        cap, words = mt.shape[1], (mt.shape[1] + 63) // 64
+        cnt = np.ascontiguousarray(match_counts).astype(np.uint32).reshape(-1)
+        fb = np.ascontiguousarray(front_bits).view(np.uint64)
+        ch = np.ascontiguousarray(chain, dtype=CHAIN_DTYPE).reshape(-1)
+        fp = np.ascontiguousarray(frame_points, dtype=POINT_DTYPE).reshape(-1)
+        if len(cnt) != n or fb.size != n * words or len(ch) != n or len(fp) != (n + 1) * int(point_cap):
+            raise ValueError("tracks_host: one count, one chain record and (match_cap + 63) // 64 words per pair, point_cap points per frame")
+        if tracks is None:
+            tracks = np.zeros((n, cap), TRACK_DTYPE)
+        for name, a, dt, size in (("tracks", tracks, TRACK_DTYPE, n * cap), ("refs", refs, TRACK_REF_DTYPE, n * cap),
+                                  ("good_bits", good_bits, np.dtype(np.uint64), n * words), ("summary", summary, TRACK_SUMMARY_DTYPE, n)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
+                raise ValueError(f"tracks_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        to = TracksOut(C.sizeof(TracksOut))
+        for name, a in (("tracks", tracks), ("refs", refs), ("good_bits", good_bits), ("summary", summary)):
+            if a is not None:
+                setattr(to, name, a.ctypes.data)
+                setattr(to, name + "_bytes", a.nbytes)
+        prm = TracksParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), 0)
+        self._chk(lib().vslam_tracks_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, fb.ctypes.data, int(point_cap), n,
+                                          ch.ctypes.data, fp.ctypes.data, C.byref(prm), C.byref(to)), "vslam_tracks_host")
+        return tracks
 
     def resect(self, poses, matches, match_counts, points, front_bits, point_cap: int, obs_matches, obs_counts, train_points, intrinsics,
                n_hypotheses: int = 512, seed: int = 0, max_dist2: float = 4.0, n_pairs: int | None = None, models=None, inlier_bits=None,

@@ -560,6 +560,32 @@ vslam::Trajectory vslam::chainPoses(const std::vector<vslam_pose>& poses, const 
     return out;
 }
 
+vslam::Tracks vslam::buildTracks(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                                 uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain,
+                                 const std::vector<SLAM::point>& framePoints, const vslam_tracks_params& params) {
+    const size_t n = poses.size(), recs = n * matchCap, words = n * (((size_t)matchCap + 63) / 64);
+    require(n <= 65535 && matchCounts.size() == n && matches.size() == recs && frontBits.size() == words && chain.size() == n &&
+                (n == 0 || framePoints.size() == (n + 1) * pointCap),
+            "buildTracks: one count and one chain record, matchCap records and (matchCap + 63) / 64 words per pair, pointCap points per frame");
+    vslam::Tracks out;
+    out.tracks.assign(recs, vslam_track{});
+    out.refs.assign(recs, vslam_track_ref{0xffffffffu, 0xffffffffu});
+    out.goodBits.assign(words, 0);
+    out.summary.assign(n, vslam_track_summary{});
+    if (n == 0) return out;
+    vslam_tracks_out o{};
+    o.struct_size = sizeof(o);
+    o.tracks = out.tracks.data(), o.tracks_bytes = recs * sizeof(vslam_track);
+    o.refs = out.refs.data(), o.refs_bytes = recs * sizeof(vslam_track_ref);
+    o.good_bits = out.goodBits.data(), o.good_bits_bytes = words * sizeof(uint64_t);
+    o.summary = out.summary.data(), o.summary_bytes = n * sizeof(vslam_track_summary);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_tracks_host(c, poses.data(), matches.data(), matchCounts.data(), matchCap, frontBits.data(), pointCap, (int)n, chain.data(),
+                                   reinterpret_cast<const vslam_point*>(framePoints.data()), &params, &o),
+                 c, "buildTracks");
+    return out;
+}
+
 vslam::Resection vslam::resectPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
                                     uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
                                     const std::vector<vslam_match>& obsMatches, const std::vector<uint32_t>& obsCounts, uint32_t obsCap,

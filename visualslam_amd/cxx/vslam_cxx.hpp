@@ -252,6 +252,20 @@ Trajectory chainPoses(const std::vector<vslam_pose>& poses, const std::vector<vs
                       uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
                       const vslam_chain_params& params = {16});
 
+// The step after the chain: the records of consecutive pairs that saw one scene point linked into tracks, and every track's
+// point triangulated from all of its views, on the GPU (vslam_tracks_host; the continuation rule, the normal equations, the
+// cofactor solve and the reprojection test are stated in include/vslam.h).  The inputs are what chainPoses took, minus the
+// points, the chain records it gave, and the frames' point lists framePoints [pairs + 1][pointCap].
+struct Tracks {
+    std::vector<vslam_track> tracks;          // [pairs][matchCap]: at the head's slot; NaN and 0 for a record that is not a head; 0: past the count
+    std::vector<vslam_track_ref> refs;        // [pairs][matchCap]: the track a record lies on; all ones: not live, or past the count
+    std::vector<uint64_t> goodBits;           // [pairs][(matchCap + 63) / 64]: the heads of good tracks
+    std::vector<vslam_track_summary> summary; // [pairs]
+};
+Tracks buildTracks(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                   uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain,
+                   const std::vector<SLAM::point>& framePoints, const vslam_tracks_params& params);
+
 // Beside the chain: the camera of frame j + 1 relative to frame j resected against the points pair j - 1 triangulated, on the
 // GPU (vslam_resect_host; the link, the calibrated 6-point DLT, the reprojection test and the selection are stated in
 // include/vslam.h).  The structure side is what chainPoses takes; the observation side is any match list of the pairs -
