@@ -84,16 +84,16 @@ class Call:
                         hypotheses=full((n + 1, nh * 26), torch.int32), correspondences=full((n + 1, self.ocap, 6), torch.int64),
                         links=full((n + 1, self.ocap), torch.int32))
 
-    def run(self, ctx, torch, seed=3, only=None, first=0):
+    def run(self, ctx, torch, seed=3, only=None, first=0, max_dist2=D2):
         """first: the call starts at pair `first`, every pointer advanced."""
         outs = {k: v[first:] for k, v in self.out.items() if only is None or k in only}
         ctx.resect(*(t[first:] for t in self.struct), self.d["point_cap"], self.obs[0][first:], self.obs[1][first:], self.train[first:], self.d["K"],
-                   self.nh, seed, D2, n_pairs=self.n - first, **outs)
+                   self.nh, seed, max_dist2, n_pairs=self.n - first, **outs)
         torch.cuda.synchronize()
         return {k: v.cpu().numpy() for k, v in self.out.items()}
 
-    def want(self, seed=3):
-        return resectref.run(self.d, self.nh, seed, D2)
+    def want(self, seed=3, max_dist2=D2):
+        return resectref.run(self.d, self.nh, seed, max_dist2)
 
     def check(self, got, want):
         models, links, corrs, flags, hyps = want
