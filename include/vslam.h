@@ -1323,8 +1323,8 @@ int vslam_resect_refine_host(vslam_ctx* ctx, const vslam_resect* models_in, cons
  *       Z_i = ((W[i][0]*X0 + W[i][1]*X1) + W[i][2]*X2) + w_i;    ex = (u*Z2 - Z0)*fx;    ey = (v*Z2 - Z1)*fy;
  *     the view is OK iff Z2 > 0 && (ex*ex + ey*ey) < max_dist2 * (Z2*Z2).  n_ok = the number of ok views, an integer: no
  *     order matters.  GOOD iff solved && n_ok == n_views && n_views >= min_views.
- * Every NaN in a double output of this section is written as 0x7ff8000000000000.  Nothing here refines X, feeds a later
- * stage, or lists the tracks densely: a track lives at its head's slot.
+ * Every NaN in a double output of this section is written as 0x7ff8000000000000.  Nothing here refines X (vslam_bundle_dev
+ * does) or lists the tracks densely: a track lives at its head's slot.
  *
  * Scratch (the context's): the two tables prev and next, (n_pairs - 1) * (point_cap + match_cap) * 4 bytes; an allocation that
  * fails is VSLAM_ERR_NOMEM. */
@@ -1382,6 +1382,129 @@ int vslam_tracks_dev(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match*
 int vslam_tracks_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
                       uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain* chain,
                       const vslam_point* frame_points, const vslam_tracks_params* params, const vslam_tracks_out* out);
+
+/* ---------------------------------------------------------------- bundle adjustment: alternating point and camera Gauss-Newton
+ * The step after vslam_tracks_dev: cameras and track points are moved together, by resection-intersection.  Given the
+ * cameras, every track's point takes one Gauss-Newton step on the reprojection error of its member views (A); given the points,
+ * every camera takes one Gauss-Newton step on the reprojection error of its member rows (B); this repeats `sweeps` times.
+ * Points are independent of each other given the cameras and cameras given the points, so each half-sweep is an exact block
+ * step: no coupled linear system, no damping, no robust kernel.  Inputs: everything vslam_tracks_dev read - poses, matches,
+ * match_counts, match_cap, front_bits, point_cap, n_pairs, chain, frame_points -, tracks_in [n_pairs][match_cap], the rows that
+ * call wrote, refs [n_pairs][match_cap], the table it wrote (required here), and optionally cams_in [n_pairs].  IEEE f64,
+ * every + - * / rounded on its own (no fused multiply-add, no sqrt), sums of a few terms left to right as written, matrices
+ * row-major (tests/bundleref.py restates it bit for bit).
+ *
+ * Cameras.  Pair j is VALID iff poses[j].best >= 0.  The unknowns are the train cameras T_j = (W, w) of the valid pairs: T_j is
+ * the camera of frame j + 1 in the world of pair j's segment, x_camera = W x_world + w.  The QUERY CAMERA of pair j is T_{j-1}
+ * when j >= 1 and chain[j].linked != 0, and the held camera (I, 0) of a segment start otherwise: that is the gauge, the first
+ * camera of every segment never moves.  The overall scale of a segment is left free: the cost does not depend on it and every
+ * block step is well posed without fixing it.  T_j starts as cams_in[j]'s W, w when cams_in is given (so the cams of one call
+ * feed the next; resect-refined poses can come in the same way), and otherwise as view L of the tracks section, step 2, formed
+ * from chain[j] and poses[j] by the trajectory's two product rules - chain[j + 1].W, w bit for bit where pair j + 1 is linked.
+ * An invalid pair's camera is (I, 0), takes no step and is read by nothing that is live.
+ *
+ * Tracks and views.  m_j, LIVE, prev, next, HEAD and the path of a track: the tracks section, steps 1 and 2, verbatim.  The
+ * track headed by live head record (j0, i0) is ACTIVE iff tracks_in[j0][i0] has status bit 0 set and n_views >= min_views.  Its
+ * point X starts as that row's X.  Its L records give L + 1 views in the order of step 2: view 0 has the query camera of pair
+ * j0 and the pixel frame_points[j0][query]; view p, 1 <= p < L, has T_{j0+p-1} and frame_points[j0 + p][query of record p];
+ * view L has T_{j0+L-1} and frame_points[j0 + L][train of the last record].  (u, v) = (q0, q1) of step 3 of the tracks section
+ * (NaN for an untrusted point record).  A view is a MEMBER under (camera, X) iff it passes step 5 of the tracks section:
+ *   Z_i = ((W[i][0]*X0 + W[i][1]*X1) + W[i][2]*X2) + w_i;   ex = (u*Z2 - Z0)*fx;   ey = (v*Z2 - Z1)*fy;
+ *   Z2 > 0 && (ex*ex + ey*ey) < max_dist2 * (Z2*Z2)       (a NaN pixel fails it).
+ *
+ * One sweep, `sweeps` times:
+ *  A. Point step, per active track, under the cameras as they stand.  EVALUATE-POINT (X): ten sums H00, H01, H02, H11, H12,
+ *     H22, g0, g1, g2, cost, each starting at +0.0, and the integer n, the views added in track order, a view that is not a
+ *     member skipped.  Per member, with Z as above:
+ *       iz = 1 / Z2;   px = Z0*iz;   py = Z1*iz;   rx = (px - u)*fx;   ry = (py - v)*fy;   sx = fx*iz;   sy = fy*iz;
+ *       ax_k = sx*(W[0][k] - px*W[2][k]);   ay_k = sy*(W[1][k] - py*W[2][k])       (k = 0, 1, 2: the Jacobian of (rx, ry) by X);
+ *       H_kl = H_kl + (ax_k*ax_l + ay_k*ay_l) for k <= l;   g_k = g_k + (ax_k*rx + ay_k*ry);   cost = cost + (rx*rx + ry*ry);   n += 1.
+ *     1. EVALUATE-POINT (X) gives n_cur, cost_cur (in the first sweep also n_before, cost_before).
+ *     2. n_cur < 2: skipped += 1.
+ *     3. Otherwise the cofactors c_ik and det of the symmetric H by the expressions of the tracks section, step 4 (A = H), and
+ *        delta_i = -(((c_i0*g0 + c_i1*g1) + c_i2*g2) / det).  det not > 0, det not < +inf or a delta not finite: invalid += 1.
+ *     4. Otherwise X_new_i = X_i + delta_i; EVALUATE-POINT (X_new) gives n_new, cost_new; X = X_new iff n_new > n_cur, or n_new
+ *        == n_cur && cost_new < cost_cur (the refinement's rule): accepted += 1; otherwise rejected += 1.
+ *  B. Camera step, per valid pair j, all cameras from the points step A left.  The ROWS of camera T_j, n_rows = m_j + h_j of them:
+ *       r < m_j: the train side of record r of pair j: pixel frame_points[j + 1][train];
+ *       m_j <= r < m_j + h_j, with h_j = m_{j+1} when j + 1 < n_pairs and chain[j + 1].linked != 0, else 0: the query side of
+ *       record r - m_j of pair j + 1, counted only if that record is a head: pixel frame_points[j + 1][query].
+ *     The row of record i of pair jj COUNTS iff the record is live, (h, pos) = refs[jj][i] has pos <= jj and h < m_{jj-pos} (and
+ *     pos == 0 where a head is required), and the row (jj - pos, h) of the output tracks - the rows of tracks_in, X as step A
+ *     left it - has status bit 0 set and n_views >= min_views; its Y is that row's X, its (u, v) the pixel's.  So every (track,
+ *     frame) observation is one row of exactly one camera, or a held camera's view 0.  A row that does not count adds +0.0.
+ *     EVALUATE (W, w) is the 29 ordered sums of the resect-refine section, verbatim, with (R, t) = (W, w) over these rows: n_rows
+ *     in place of n_corr, blocks of 4096 rows, the same slots and tree, block sums left to right.  STEP is that section's, on (W, w).
+ *     1. EVALUATE (T_j) gives n_cur, cost_cur, H, g (the first sweep's are n_before, cost_before).
+ *     2. n_cur < 6: skipped += 1.
+ *     3. Otherwise STEP; invalid: invalid += 1.
+ *     4. Otherwise EVALUATE the candidate; T_j = the candidate iff n_new > n_cur, or n_new == n_cur && cost_new < cost_cur:
+ *        accepted += 1; otherwise rejected += 1.
+ * A camera or point that was rejected tries again in the next sweep - the other block has moved; there are no permanent stops.
+ * After the last sweep: EVALUATE (T_j) once more gives the camera's n_after, cost_after; EVALUATE-POINT (X) gives the point's.
+ *
+ * Outputs.  tracks: rows i < m_j of every pair are the rows of tracks_in, byte for byte, except the head rows of active tracks:
+ * X = the refined point, n_ok = the point's n_after (the ok views of step 5 of the tracks section under the final cameras),
+ * status = (solved ? 1 : 0) | (good ? 2 : 0) with solved = det > 0 && det < +inf && X0, X1, X2 all finite and good = solved &&
+ * n_ok == n_views && n_views >= min_views, and det, n_views, reserved copied.  cams[j]: W, w, the centre C_i = -((W[0][i]*w0 +
+ * W[1][i]*w1) + W[2][i]*w2) (the trajectory's expression), the counters and costs; an invalid pair gets W = I, w = C = +0.0,
+ * skipped = sweeps and every other field 0.  point_info: the row at the head slot of every active track; nothing else is
+ * written.  member_bits: for record i < m_j, bit i % 64 of word i / 64 of half 0 = the row "query side of record i" counts
+ * (no head required) and is a member under the query camera of pair j and the output; of half 1 the same for the train side
+ * under T_j; an invalid pair's words are zero.  Every NaN in a double output written by this section is 0x7ff8000000000000.
+ * Nothing here is fed back into vslam_chain_dev or the resection.
+ *
+ * Scratch (the context's): the two tables of the tracks stage, n_pairs * ((2 * match_cap + 4095) / 4096) * 232 bytes of block
+ * sums and n_pairs * 240 bytes of camera state; an allocation that fails is VSLAM_ERR_NOMEM. */
+typedef struct {
+    vslam_pose_params K; /* all finite, fx and fy positive (fx, fy enter the arithmetic) */
+    double max_dist2;    /* squared reprojection error in pixels^2, finite and positive */
+    uint32_t min_views;  /* >= 2: the views an active track needs */
+    uint32_t sweeps;     /* 1 .. 64 */
+} vslam_bundle_params;   /* 48 bytes */
+typedef struct {
+    double W[9], w[3];              /* T_j: x_camera = W x_world + w */
+    double C[3];                    /* its centre in the world */
+    uint32_t n_before, n_after;     /* member rows at the first evaluation / under the output */
+    uint32_t accepted, rejected, invalid, skipped; /* sweeps by outcome: they add up to `sweeps` */
+    double cost_before, cost_after; /* SUM(rx*rx + ry*ry) in pixels^2 at the first evaluation / under the output */
+} vslam_bundle_cam;                 /* 160 bytes, a multiple of 8 */
+typedef struct {
+    uint32_t n_before, n_after;     /* member views at the first evaluation / under the output */
+    uint32_t accepted, rejected, invalid, skipped; /* sweeps by outcome */
+    double cost_before, cost_after;
+} vslam_bundle_point;               /* 40 bytes */
+/* Like vslam_tracks_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;           /* = sizeof(vslam_bundle_out) */
+    vslam_track* tracks;          /* [n_pairs][match_cap], required; may be the very pointer passed as tracks_in, must not otherwise
+                                   * overlap it; rows past m_j are left untouched */
+    size_t tracks_bytes;
+    vslam_bundle_cam* cams;       /* [n_pairs], required */
+    size_t cams_bytes;
+    vslam_bundle_point* point_info; /* [n_pairs][match_cap] optional: written at the head slots of active tracks only */
+    size_t point_info_bytes;
+    uint64_t* member_bits;        /* [n_pairs][2][(match_cap + 63) / 64] optional: the first (m_j + 63) / 64 words of each half of
+                                   * a pair are written, the rest untouched */
+    size_t member_bits_bytes;
+} vslam_bundle_out;
+/* DEVICE pointers; cams_in may be NULL, every other input is required.  Asynchronous on the context stream, never waits on
+ * the host (the counts are read on the device, the grids are sized from the capacities; the number of launches depends on
+ * `sweeps` alone); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch - and before the context is looked at -
+ * for a null required pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing), sweeps outside 1 .. 64,
+ * min_views < 2, a max_dist2 that is not finite or not positive, an intrinsic that is not finite, fx or fy not positive,
+ * match_cap or point_cap == 0, an undersized buffer, tracks overlapping tracks_in without being equal to it; then VSLAM_ERR_HIP
+ * when there is no usable HIP device.  Not for stream capture. */
+int vslam_bundle_dev(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                     uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain* chain,
+                     const vslam_point* frame_points, const vslam_track* tracks_in, const vslam_track_ref* refs,
+                     const vslam_bundle_cam* cams_in, const vslam_bundle_params* params, const vslam_bundle_out* out);
+/* The same call over HOST arrays, all n_pairs pairs at once, synchronous (a convenience path: device buffers per call).  The
+ * rows and words the device call leaves untouched keep the caller's bytes.  Errors as for vslam_bundle_dev. */
+int vslam_bundle_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                      uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, int n_pairs, const vslam_chain* chain,
+                      const vslam_point* frame_points, const vslam_track* tracks_in, const vslam_track_ref* refs,
+                      const vslam_bundle_cam* cams_in, const vslam_bundle_params* params, const vslam_bundle_out* out);
 
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the

@@ -51,6 +51,11 @@ TRACK_DTYPE = np.dtype([("X", "<f8", (3,)), ("det", "<f8"), ("n_views", "<u4"), 
                        align=True)  # vslam_track, 48 bytes
 TRACK_REF_DTYPE = np.dtype([("head_record", "<u4"), ("pos", "<u4")], align=True)  # vslam_track_ref, 8 bytes
 TRACK_SUMMARY_DTYPE = np.dtype([("n_heads", "<u4"), ("n_good", "<u4"), ("max_views", "<u4"), ("reserved", "<u4")], align=True)  # vslam_track_summary, 16 bytes
+BUNDLE_CAM_DTYPE = np.dtype([("W", "<f8", (9,)), ("w", "<f8", (3,)), ("C", "<f8", (3,)), ("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"),
+                             ("rejected", "<u4"), ("invalid", "<u4"), ("skipped", "<u4"), ("cost_before", "<f8"), ("cost_after", "<f8")],
+                            align=True)  # vslam_bundle_cam, 160 bytes
+BUNDLE_POINT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("rejected", "<u4"), ("invalid", "<u4"), ("skipped", "<u4"),
+                               ("cost_before", "<f8"), ("cost_after", "<f8")], align=True)  # vslam_bundle_point, 40 bytes
 
 
 class VslamError(RuntimeError):
@@ -255,6 +260,27 @@ class TracksOut(C.Structure):
                 ("good_bits", C.c_void_p), ("good_bits_bytes", C.c_size_t), ("summary", C.c_void_p), ("summary_bytes", C.c_size_t)]
 
 
+class BundleParams(C.Structure):
+    _fields_ = [("K", PoseParams), ("max_dist2", C.c_double), ("min_views", C.c_uint32), ("sweeps", C.c_uint32)]
+
+
+class BundleCam(C.Structure):
+    _fields_ = [("W", C.c_double * 9), ("w", C.c_double * 3), ("C", C.c_double * 3), ("n_before", C.c_uint32), ("n_after", C.c_uint32),
+                ("accepted", C.c_uint32), ("rejected", C.c_uint32), ("invalid", C.c_uint32), ("skipped", C.c_uint32), ("cost_before", C.c_double),
+                ("cost_after", C.c_double)]
+
+
+class BundlePoint(C.Structure):
+    _fields_ = [("n_before", C.c_uint32), ("n_after", C.c_uint32), ("accepted", C.c_uint32), ("rejected", C.c_uint32), ("invalid", C.c_uint32),
+                ("skipped", C.c_uint32), ("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+
+class BundleOut(C.Structure):
+    """vslam_bundle_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("tracks", C.c_void_p), ("tracks_bytes", C.c_size_t), ("cams", C.c_void_p), ("cams_bytes", C.c_size_t),
+                ("point_info", C.c_void_p), ("point_info_bytes", C.c_size_t), ("member_bits", C.c_void_p), ("member_bits_bytes", C.c_size_t)]
+
+
 class PyramidInfo(C.Structure):
     _fields_ = [
         ("n_octaves", C.c_int), ("n_levels", C.c_int), ("n_dogs", C.c_int), ("sigma0", C.c_double),
@@ -347,6 +373,8 @@ SIGNATURES = {
     "vslam_resect_refine_host": (_I, [_P, _P, _P, C.c_uint32, _I, C.POINTER(ResectRefineParams), C.POINTER(ResectRefineOut)]),
     "vslam_tracks_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, C.POINTER(TracksParams), C.POINTER(TracksOut)]),
     "vslam_tracks_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, C.POINTER(TracksParams), C.POINTER(TracksOut)]),
+    "vslam_bundle_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, _P, _P, _P, C.POINTER(BundleParams), C.POINTER(BundleOut)]),
+    "vslam_bundle_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, _P, _P, _P, C.POINTER(BundleParams), C.POINTER(BundleOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -1177,6 +1205,77 @@ class Context:
         self._chk(lib().vslam_tracks_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, fb.ctypes.data, int(point_cap), n,
                                           ch.ctypes.data, fp.ctypes.data, C.byref(prm), C.byref(to)), "vslam_tracks_host")
         return tracks
+
+    def bundle(self, poses, matches, match_counts, front_bits, point_cap: int, chain, frame_points, tracks_in, refs, intrinsics, max_dist2: float = 4.0,
+               min_views: int = 2, sweeps: int = 4, n_pairs: int | None = None, cams_in=None, tracks=None, cams=None, point_info=None, member_bits=None):
+        """vslam_bundle_dev: alternating Gauss-Newton over the tracks' points and the train cameras; asynchronous on the context
+        stream.  poses .. frame_points are the tensors tracks() read, tracks_in and refs the tensors it wrote; cams_in (optional) n * 160
+        bytes (BUNDLE_CAM_DTYPE: only W, w are read).  Outputs, CUDA tensors: tracks - n * match_cap * 48 bytes, may be tracks_in itself -,
+        cams n * 160 bytes (BUNDLE_CAM_DTYPE), point_info n * match_cap * 40 bytes (BUNDLE_POINT_DTYPE), member_bits [n, 2, (match_cap +
+        63) // 64] 8-byte words."""
+        tensors = dict(poses=poses, matches=matches, match_counts=match_counts, front_bits=front_bits, chain=chain, frame_points=frame_points,
+                       tracks_in=tracks_in, refs=refs, cams_in=cams_in, tracks=tracks, cams=cams, point_info=point_info, member_bits=member_bits)
+        for name, t in tensors.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
+                raise ValueError(f"bundle: {name} must be a contiguous tensor on cuda:{self.device}")
+        for name in ("poses", "matches", "match_counts", "front_bits", "chain", "frame_points", "tracks_in", "refs", "tracks", "cams"):
+            if tensors[name] is None:
+                raise ValueError(f"bundle: {name} is required")
+        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12:
+            raise ValueError("bundle: matches must be [n, match_cap, 3] 4-byte elements")
+        n = matches.shape[0] if n_pairs is None else int(n_pairs)
+        cap = matches.shape[1]
+        size = lambda t: t.numel() * t.element_size()
+        if (matches.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n or size(poses) < n * 112 or size(chain) < n * 176
+                or size(front_bits) < n * ((cap + 63) // 64) * 8 or size(frame_points) < (n + 1) * int(point_cap) * 24 or size(tracks_in) < n * cap * 48
+                or size(refs) < n * cap * 8 or (cams_in is not None and size(cams_in) < n * 160)):
+            raise ValueError("bundle: fewer sets than pairs")
+        bo = _fill_out(BundleOut(), dict(tracks=tracks, cams=cams, point_info=point_info, member_bits=member_bits))
+        prm = BundleParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), int(sweeps))
+        self._chk(lib().vslam_bundle_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, front_bits.data_ptr(),
+                                         int(point_cap), n, chain.data_ptr(), frame_points.data_ptr(), tracks_in.data_ptr(), refs.data_ptr(),
+                                         None if cams_in is None else cams_in.data_ptr(), C.byref(prm), C.byref(bo)), "vslam_bundle_dev")
+
+    def bundle_host(self, poses, matches, match_counts, front_bits, point_cap: int, chain, frame_points, tracks_in, refs, intrinsics,
+                    max_dist2: float = 4.0, min_views: int = 2, sweeps: int = 4, cams_in=None, tracks=None, point_info=None, member_bits=None):
+        """vslam_bundle_host: the same call over numpy arrays (the shapes of tracks_host; tracks_in [n, match_cap] TRACK_DTYPE, refs [n,
+        match_cap] TRACK_REF_DTYPE, cams_in [n] BUNDLE_CAM_DTYPE or None) -> (tracks [n, match_cap] TRACK_DTYPE, cams [n] BUNDLE_CAM_DTYPE).
+        tracks (default: a copy of tracks_in), point_info (BUNDLE_POINT_DTYPE [n, match_cap]) and member_bits (uint64 [n, 2, words]) are
+        written in place when given (C-contiguous arrays of exactly that type)."""
+        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
+        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(ps)
+        if mt.ndim != 2 or mt.shape[0] != n:
+            raise ValueError("bundle_host: matches must be [n, match_cap]")
+        cap, words = mt.shape[1], (mt.shape[1] + 63) // 64
+        cnt = np.ascontiguousarray(match_counts).astype(np.uint32).reshape(-1)
+        fb = np.ascontiguousarray(front_bits).view(np.uint64)
+        ch = np.ascontiguousarray(chain, dtype=CHAIN_DTYPE).reshape(-1)
+        fp = np.ascontiguousarray(frame_points, dtype=POINT_DTYPE).reshape(-1)
+        ti = np.ascontiguousarray(tracks_in, dtype=TRACK_DTYPE).reshape(-1)
+        rf = np.ascontiguousarray(refs, dtype=TRACK_REF_DTYPE).reshape(-1)
+        ci = None if cams_in is None else np.ascontiguousarray(cams_in, dtype=BUNDLE_CAM_DTYPE).reshape(-1)
+        if (len(cnt) != n or fb.size != n * words or len(ch) != n or len(fp) != (n + 1) * int(point_cap) or len(ti) != n * cap or len(rf) != n * cap
+                or (ci is not None and len(ci) != n)):
+            raise ValueError("bundle_host: one count, one chain record, one camera and (match_cap + 63) // 64 words per pair, match_cap tracks and refs, "
+                             "point_cap points per frame")
+        if tracks is None:
+            tracks = ti.reshape(n, cap).copy()
+        for name, a, dt, size in (("tracks", tracks, TRACK_DTYPE, n * cap), ("point_info", point_info, BUNDLE_POINT_DTYPE, n * cap),
+                                  ("member_bits", member_bits, np.dtype(np.uint64), n * 2 * words)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
+                raise ValueError(f"bundle_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        cams = np.zeros(max(n, 1), BUNDLE_CAM_DTYPE)
+        bo = BundleOut(C.sizeof(BundleOut))
+        for name, a in (("tracks", tracks), ("cams", cams), ("point_info", point_info), ("member_bits", member_bits)):
+            if a is not None:
+                setattr(bo, name, a.ctypes.data)
+                setattr(bo, name + "_bytes", a.nbytes)
+        prm = BundleParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), int(sweeps))
+        self._chk(lib().vslam_bundle_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, fb.ctypes.data, int(point_cap), n,
+                                          ch.ctypes.data, fp.ctypes.data, ti.ctypes.data, rf.ctypes.data, None if ci is None else ci.ctypes.data,
+                                          C.byref(prm), C.byref(bo)), "vslam_bundle_host")
+        return tracks, cams[:n]
 
     def resect(self, poses, matches, match_counts, points, front_bits, point_cap: int, obs_matches, obs_counts, train_points, intrinsics,
                n_hypotheses: int = 512, seed: int = 0, max_dist2: float = 4.0, n_pairs: int | None = None, models=None, inlier_bits=None,

@@ -13,13 +13,13 @@
 //                     the same in any order)
 // No floating-point atomics, no flags or fences between workgroups: kernel boundaries order everything.  A workgroup of a
 // stopped pair, or of a block past the pair's n_corr, leaves before its first barrier (workgroup-uniform).  The arithmetic is
-// the header's, operation for operation, under the rules of kernels_epipolar.hip.h.
+// the header's, operation for operation, under the rules of kernels_epipolar.hip.h.  The member test, EVALUATE of one row and
+// STEP are kernels_resect_refine_step.hip.h's: the bundle adjustment's camera step runs the same lines.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
-#include "kernels_geom3.hip.h"
-#include "vslam_resect_refine_plan.h"
+#include "kernels_resect_refine_step.hip.h"
 
 namespace vslam {
 
@@ -29,16 +29,6 @@ struct __attribute__((aligned(16))) RrRow {  // vslam_resect_corr as three 16-by
 static_assert(sizeof(RrRow) == sizeof(vslam_resect_corr), "a row is 48 bytes");
 
 __device__ __forceinline__ unsigned int rr_ncorr(const RrState& st, unsigned int ocap) { return st.in.n_corr < ocap ? st.in.n_corr : ocap; }
-
-// Z = R Y + t and the member test of one row (step 6 of the resection section).
-__device__ __forceinline__ bool rr_member(const double (&R)[9], const double (&t)[3], double fx, double fy, double Y0, double Y1, double Y2, double u,
-                                          double v, double max_dist2, double (&Z)[3]) {
-    Z[0] = ((R[0] * Y0 + R[1] * Y1) + R[2] * Y2) + t[0];
-    Z[1] = ((R[3] * Y0 + R[4] * Y1) + R[5] * Y2) + t[1];
-    Z[2] = ((R[6] * Y0 + R[7] * Y1) + R[8] * Y2) + t[2];
-    const double ex = (u * Z[2] - Z[0]) * fx, ey = (v * Z[2] - Z[1]) * fy;
-    return Z[2] > 0.0 && (ex * ex + ey * ey) < max_dist2 * (Z[2] * Z[2]);
-}
 
 __global__ __launch_bounds__(RR_PAIR_WG) void k_rr_init(const vslam_resect* __restrict__ models_in, int n_pairs, RrState* __restrict__ state) {
     const int j = blockIdx.x * RR_PAIR_WG + threadIdx.x;
@@ -81,25 +71,7 @@ __global__ __launch_bounds__(REFIT_WG) void k_rr_pass(const vslam_resect_corr* _
         if (i < m) {
             const RrRow row = src[i];
             const double u = row.b.y, v = row.c.x;
-            double Z[3];
-            if (rr_member(R, t, fx, fy, row.a.x, row.a.y, row.b.x, u, v, max_dist2, Z)) {  // (a row that is not a member adds +0.0: nothing)
-                const double iz = 1.0 / Z[2];
-                const double px = Z[0] * iz, py = Z[1] * iz;
-                const double rx = (px - u) * fx, ry = (py - v) * fy;
-                const double pxy = px * py;
-                const double Jx[6] = {fx * (-pxy), fx * (1.0 + px * px), fx * (-py), fx * iz, fx * 0.0, fx * (-(px * iz))};
-                const double Jy[6] = {fy * (-(1.0 + py * py)), fy * pxy, fy * px, fy * 0.0, fy * iz, fy * (-(py * iz))};
-                int e = 0;
-#pragma unroll
-                for (int p = 0; p < 6; ++p) {
-#pragma unroll
-                    for (int q = p; q < 6; ++q, ++e) s[e] = s[e] + (Jx[p] * Jx[q] + Jy[p] * Jy[q]);
-                }
-#pragma unroll
-                for (int p = 0; p < 6; ++p) s[21 + p] = s[21 + p] + (Jx[p] * rx + Jy[p] * ry);
-                s[27] = s[27] + (rx * rx + ry * ry);
-                s[28] = s[28] + 1.0;
-            }
+            RR_ROW_SUMS(R, t, fx, fy, row.a.x, row.a.y, row.b.x, u, v, max_dist2, s);
         }
     }
     refit_tree<(int)RR_SUMS>(s, lds);
@@ -109,9 +81,6 @@ __global__ __launch_bounds__(REFIT_WG) void k_rr_pass(const vslam_resect_corr* _
         for (int k = 0; k < (int)RR_SUMS; ++k) out[k] = s[k];
     }
 }
-
-__device__ __forceinline__ double rr_canonical(double x) { return x == x ? x : __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ bool rr_finite(double x) { return fabs(x) < __builtin_huge_val(); }
 
 // `models` may be the buffer k_rr_init read: it is written by the last launch only (r == rounds), so it is not __restrict__.
 __global__ __launch_bounds__(RR_PAIR_WG) void k_rr_step(const double* __restrict__ partial, unsigned int sum_blocks, unsigned int ocap, int n_pairs,
@@ -156,93 +125,7 @@ __global__ __launch_bounds__(RR_PAIR_WG) void k_rr_step(const double* __restrict
             } else if (st->n_cur < 6) {  // round step 1
                 st->stop = 1;
             } else {  // round step 2: STEP from the pose just evaluated (it is the current one)
-                // a. [H | -g]
-                {
-                    int e = 0;
-#pragma unroll
-                    for (int p = 0; p < 6; ++p) {
-#pragma unroll
-                        for (int q = p; q < 6; ++q, ++e) a[7 * p + q][l] = s[e], a[7 * q + p][l] = s[e];
-                        a[7 * p + 6][l] = -s[21 + p];
-                    }
-                }
-                unsigned int used = 0, pcs = 0;  // chosen columns: bit mask, and 3 bits per step
-                bool ok = true;
-                for (int k = 0; k < 6; ++k) {
-                    double best = 0.0;
-                    int pr = -1, pc = -1;
-                    for (int rr = k; rr < 6; ++rr)
-                        for (int c = 0; c < 6; ++c) {
-                            if (used >> c & 1u) continue;
-                            const double x = fabs(a[7 * rr + c][l]);
-                            if (x > best) best = x, pr = rr, pc = c;
-                        }
-                    if (pr < 0 || !(best < __builtin_huge_val())) {
-                        ok = false;
-                        break;
-                    }
-                    if (pr != k)
-                        for (int c = 0; c < 7; ++c) {
-                            const double x = a[7 * k + c][l];
-                            a[7 * k + c][l] = a[7 * pr + c][l];
-                            a[7 * pr + c][l] = x;
-                        }
-                    const double p = a[7 * k + pc][l];
-                    double rowk[7];
-#pragma unroll
-                    for (int c = 0; c < 7; ++c) {
-                        rowk[c] = a[7 * k + c][l] / p;
-                        a[7 * k + c][l] = rowk[c];
-                    }
-                    for (int i = 0; i < 6; ++i) {
-                        if (i == k) continue;
-                        const double g = a[7 * i + pc][l];
-#pragma unroll
-                        for (int c = 0; c < 7; ++c) a[7 * i + c][l] = a[7 * i + c][l] - g * rowk[c];
-                    }
-                    used |= 1u << pc;
-                    pcs |= (unsigned int)pc << (3 * k);
-                }
-                double Rn[9], tn[3];
-                if (ok) {
-                    // d lives in row 0's slots from here on (the matrix is no longer needed once the last column is read out)
-                    double dk[6];
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) dk[k] = a[7 * k + 6][l];
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) a[(pcs >> (3 * k)) & 7u][l] = dk[k];
-                    double d[6];
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) {
-                        d[k] = a[k][l];
-                        ok &= rr_finite(d[k]);
-                    }
-                    // b. the Cayley rotation
-                    const double a0 = d[0] / 2.0, a1 = d[1] / 2.0, a2 = d[2] / 2.0;
-                    const double q = (a0 * a0 + a1 * a1) + a2 * a2;
-                    const double e = 1.0 - q, den = 1.0 + q;
-                    double D[9];
-                    D[0] = (e + 2.0 * (a0 * a0)) / den;
-                    D[4] = (e + 2.0 * (a1 * a1)) / den;
-                    D[8] = (e + 2.0 * (a2 * a2)) / den;
-                    D[1] = (2.0 * (a0 * a1) - 2.0 * a2) / den;
-                    D[3] = (2.0 * (a1 * a0) + 2.0 * a2) / den;
-                    D[2] = (2.0 * (a0 * a2) + 2.0 * a1) / den;
-                    D[6] = (2.0 * (a2 * a0) - 2.0 * a1) / den;
-                    D[5] = (2.0 * (a1 * a2) - 2.0 * a0) / den;
-                    D[7] = (2.0 * (a2 * a1) + 2.0 * a0) / den;
-                    // c. the new pose
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            Rn[3 * i + c] = (D[3 * i] * st->Rcur[c] + D[3 * i + 1] * st->Rcur[3 + c]) + D[3 * i + 2] * st->Rcur[6 + c];
-                            ok &= rr_finite(Rn[3 * i + c]);
-                        }
-                        tn[i] = ((D[3 * i] * st->tcur[0] + D[3 * i + 1] * st->tcur[1]) + D[3 * i + 2] * st->tcur[2]) + d[3 + i];
-                        ok &= rr_finite(tn[i]);
-                    }
-                }
+                RR_STEP_SOLVE(a, l, s, st->Rcur, st->tcur);
                 if (ok) {
 #pragma unroll
                     for (int k = 0; k < 9; ++k) st->Rcand[k] = Rn[k];

@@ -62,7 +62,8 @@ static const char* const kKernelNames =
     "k_chain_link\nk_chain_ratio\nk_chain_median\nk_chain_walk\nk_chain_map\n"
     "k_res_corr\nk_res_gather\nk_res_models\nk_res_score\nk_res_select\nk_res_flags\n"
     "k_rr_init\nk_rr_pass\nk_rr_step\nk_rr_flags_zero\nk_rr_flags\n"
-    "k_trk_next\nk_trk_walk\nk_trk_rows";
+    "k_trk_next\nk_trk_walk\nk_trk_rows\n"
+    "k_ba_init\nk_ba_points\nk_ba_cam_pass\nk_ba_cam_step\nk_ba_member_bits\nk_ba_points_final";
 
 
 // Runs `body` with the context's launch stream temporarily replaced (LAUNCH uses ctx->stream).

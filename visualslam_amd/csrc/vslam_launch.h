@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip, vslam_resect_refine.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip, vslam_resect_refine.hip, vslam_tracks.hip, vslam_bundle.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -53,6 +53,12 @@ int enqueue_epi_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_c
 // pair j - 1.  n_pairs >= 2.
 int enqueue_chain_link(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
                        const uint64_t* front_bits, unsigned int point_cap, int n_pairs, unsigned int* prev);
+// The continuation table of the tracks section's step 2 (k_trk_next, compiled in vslam_tracks.hip; vslam_bundle_dev walks the
+// same paths): next [n_pairs - 1][match_cap] is preset to 0xffffffff and row j - 1 gets, per record of pair j - 1, the lowest
+// candidate of pair j.  prev: the link table above.  n_pairs >= 2.
+int enqueue_trk_next(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
+                     const uint64_t* front_bits, unsigned int point_cap, int n_pairs, const vslam_chain* chain, const unsigned int* prev,
+                     unsigned int* next);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -

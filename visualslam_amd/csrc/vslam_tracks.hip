@@ -1,5 +1,6 @@
 // The tracks step of the C ABI (include/vslam.h, "tracks"): argument checks and sizing (vslam_tracks_plan.h), scratch and
-// launches of kernels_tracks.hip.h.  The link table is the trajectory's (enqueue_chain_link).
+// launches of kernels_tracks.hip.h.  The link table is the trajectory's (enqueue_chain_link); the continuation table is filled
+// by enqueue_trk_next, which vslam_bundle_dev calls too.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +13,16 @@
 #include "vslam_tracks_plan.h"
 
 using namespace vslam;
+
+int vslam::enqueue_trk_next(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
+                            const uint64_t* front_bits, unsigned int point_cap, int n_pairs, const vslam_chain* chain, const unsigned int* prev,
+                            unsigned int* next) {
+    const TracksPlan pl = tracks_plan(match_cap, point_cap, n_pairs);
+    const TrkIn in{poses, matches, match_counts, reinterpret_cast<const unsigned long long*>(front_bits), chain, nullptr, match_cap, pl.fwords, point_cap, n_pairs};
+    HIPCHK(c, hipMemsetAsync(next, 0xff, pl.next_elems * sizeof(unsigned int), c->stream));
+    LAUNCH(c, "k_trk_next", k_trk_next, dim3(pl.rec_blocks, pl.link_pairs), dim3(TRK_REC_WG), in, prev, next);
+    return VSLAM_OK;
+}
 
 extern "C" {
 
@@ -38,8 +49,7 @@ int vslam_tracks_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* m
     if (out->summary) HIPCHK(c, hipMemsetAsync(out->summary, 0, (size_t)n_pairs * sizeof(vslam_track_summary), c->stream));
     if (pl.link_pairs) {
         TRY(enqueue_chain_link(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, prev));
-        HIPCHK(c, hipMemsetAsync(next, 0xff, pl.next_elems * sizeof(unsigned int), c->stream));
-        LAUNCH(c, "k_trk_next", k_trk_next, dim3(pl.rec_blocks, pl.link_pairs), dim3(TRK_REC_WG), in, prev, next);
+        TRY(enqueue_trk_next(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, chain, prev, next));
     }
     LAUNCH(c, "k_trk_walk", k_trk_walk, records, dim3(TRK_REC_WG), in, *prm, prev, next, out->tracks, out->refs, out->summary);
     LAUNCH(c, "k_trk_rows", k_trk_rows, records, dim3(TRK_REC_WG), in, prev, next, out->tracks, out->refs,

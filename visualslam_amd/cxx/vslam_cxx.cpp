@@ -586,6 +586,37 @@ vslam::Tracks vslam::buildTracks(const std::vector<vslam_pose>& poses, const std
     return out;
 }
 
+vslam::Bundle vslam::bundleAdjust(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                                  uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain,
+                                  const std::vector<SLAM::point>& framePoints, const std::vector<vslam_track>& tracksIn,
+                                  const std::vector<vslam_track_ref>& refs, const std::vector<vslam_bundle_cam>& camsIn,
+                                  const vslam_bundle_params& params) {
+    const size_t n = poses.size(), recs = n * matchCap, words = n * (((size_t)matchCap + 63) / 64);
+    require(n <= 65535 && matchCounts.size() == n && matches.size() == recs && frontBits.size() == words && chain.size() == n &&
+                (n == 0 || framePoints.size() == (n + 1) * pointCap),
+            "bundleAdjust: one count and one chain record, matchCap records and (matchCap + 63) / 64 words per pair, pointCap points per frame");
+    require(tracksIn.size() == recs && refs.size() == recs && (camsIn.empty() || camsIn.size() == n),
+            "bundleAdjust: matchCap tracks and refs per pair, and no cameras or one per pair");
+    vslam::Bundle out;
+    out.tracks = tracksIn;
+    out.cams.assign(n, vslam_bundle_cam{});
+    out.pointInfo.assign(recs, vslam_bundle_point{});
+    out.memberBits.assign(2 * words, 0);
+    if (n == 0) return out;
+    vslam_bundle_out o{};
+    o.struct_size = sizeof(o);
+    o.tracks = out.tracks.data(), o.tracks_bytes = recs * sizeof(vslam_track);
+    o.cams = out.cams.data(), o.cams_bytes = n * sizeof(vslam_bundle_cam);
+    o.point_info = out.pointInfo.data(), o.point_info_bytes = recs * sizeof(vslam_bundle_point);
+    o.member_bits = out.memberBits.data(), o.member_bits_bytes = 2 * words * sizeof(uint64_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_bundle_host(c, poses.data(), matches.data(), matchCounts.data(), matchCap, frontBits.data(), pointCap, (int)n, chain.data(),
+                                   reinterpret_cast<const vslam_point*>(framePoints.data()), tracksIn.data(), refs.data(),
+                                   camsIn.empty() ? nullptr : camsIn.data(), &params, &o),
+                 c, "bundleAdjust");
+    return out;
+}
+
 vslam::Resection vslam::resectPoses(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
                                     uint32_t matchCap, const std::vector<double>& points, const std::vector<uint64_t>& frontBits, uint32_t pointCap,
                                     const std::vector<vslam_match>& obsMatches, const std::vector<uint32_t>& obsCounts, uint32_t obsCap,

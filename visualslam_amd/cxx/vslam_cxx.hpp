@@ -266,6 +266,20 @@ Tracks buildTracks(const std::vector<vslam_pose>& poses, const std::vector<vslam
                    uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain,
                    const std::vector<SLAM::point>& framePoints, const vslam_tracks_params& params);
 
+// After buildTracks: cameras and track points moved together by an alternating bundle adjustment, on the GPU (vslam_bundle_host;
+// the views, the point step, the camera rows, the sweeps and the outputs are stated in include/vslam.h).  The inputs are what
+// buildTracks took and the tracks and refs it gave; camsIn is empty (the cameras start from the chain) or one record per pair.
+struct Bundle {
+    std::vector<vslam_track> tracks;           // [pairs][matchCap]: the input rows, the heads of active tracks refined
+    std::vector<vslam_bundle_cam> cams;        // [pairs]: the train cameras, their centres, counters and costs
+    std::vector<vslam_bundle_point> pointInfo; // [pairs][matchCap]: at the head slots of active tracks; 0 elsewhere
+    std::vector<uint64_t> memberBits;          // [pairs][2][(matchCap + 63) / 64]: the member views by record, query side then train side
+};
+Bundle bundleAdjust(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                    uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain,
+                    const std::vector<SLAM::point>& framePoints, const std::vector<vslam_track>& tracksIn, const std::vector<vslam_track_ref>& refs,
+                    const std::vector<vslam_bundle_cam>& camsIn, const vslam_bundle_params& params);
+
 // Beside the chain: the camera of frame j + 1 relative to frame j resected against the points pair j - 1 triangulated, on the
 // GPU (vslam_resect_host; the link, the calibrated 6-point DLT, the reprojection test and the selection are stated in
 // include/vslam.h).  The structure side is what chainPoses takes; the observation side is any match list of the pairs -
