@@ -780,6 +780,61 @@ int vslam_refit_host(vslam_ctx* ctx, const vslam_epipolar* model_in, const vslam
                      const vslam_refit_params* params, vslam_epipolar* model, vslam_refit* info, uint64_t* inlier_bits,
                      vslam_match* inliers, size_t inlier_cap, size_t* n_inliers);
 
+/* ---------------------------------------------------------------- guided matching
+ * A second matching pass, once a pair's fundamental matrix is known: the nearest-two search of the descriptor matching section,
+ * restricted for every query row to the train rows whose point lies in the query's epipolar band.  The ratio test of the first
+ * pass rejects a correct match whenever a similar descriptor exists anywhere in the other frame (repeated structure); almost all
+ * such look-alikes lie off the query's epipolar line and no longer count here.  Inputs per pair j: set j of `query` and of
+ * `train` (points required on both sides), models[j] - a vslam_epipolar record as vslam_epipolar_dev, vslam_refit_dev or the
+ * gate of vslam_homography_dev writes it - and the parameters.  The arithmetic is fixed here so that a CPU can restate it bit
+ * for bit (tests/guidedref.py).
+ *
+ * Coordinates are the two-view section's, exact in f64: x = (p.col - p.padding) * 2^(p.octave - 1), y likewise from p.row.  A
+ * row is TRUSTED iff its point's octave is in 0 .. 31.
+ *
+ * Train row j is IN BAND of query row i iff models[p].best >= 0, both rows are trusted, and the two-view section's inlier
+ * test holds under F = models[p].F with (x, y) the query row's point and (x', y') the train row's:
+ *   a_k = (F[k][0]*x + F[k][1]*y) + F[k][2];   b_k = (F[0][k]*x' + F[1][k]*y') + F[2][k];   e = (x'*a0 + y'*a1) + a2;
+ *   in band iff  e*e < max_dist2 * (((a0*a0 + a1*a1) + b0*b0) + b1*b1).
+ * IEEE f64, every operation rounded on its own, no fused multiply-add.  The predicate is a pure function of F, the two points
+ * and max_dist2; a false comparison (a NaN, F = 0) is "not in band"; a pair with best < 0 has no row in band, whatever its F
+ * holds.
+ *
+ * d2 is the descriptor matching section's, unchanged, and so is the sequential selection over j = 0 .. nt-1 ascending, with
+ * one more skipped case: a train row that is not in band of the query row (besides a `defined` byte of 0 and, with
+ * same_octave, a differing octave).  second_dist2 is therefore the second nearest IN THE BAND.  Ties, NaN and +-inf behave as
+ * there.  A query row that is undefined or not trusted gets {-1, +inf, +inf}.
+ *
+ * A query is ACCEPTED iff index >= 0 and (second == +inf or best < ratio2 * second, the product rounded once to f32) and
+ * best < max_desc_dist2.  A lone candidate in a narrow band passes the ratio clause whatever its distance: the absolute bound
+ * is there for that case, and max_desc_dist2 = +inf switches it off.
+ *
+ * Output: vslam_match_out, layout and ordering as vslam_match_dev writes it; the list goes straight into vslam_epipolar_dev
+ * and vslam_refit_dev.  Results depend neither on vslam_ctx_set_f32_fused nor on vslam_ctx_set_matrix_path. */
+typedef struct {
+    float ratio2;         /* the SQUARED ratio of Lowe's test, finite and positive */
+    float max_desc_dist2; /* accepted only below this d2; positive, +inf = no bound */
+    double max_dist2;     /* half-width of the band: squared Sampson distance in pixels^2, finite and positive */
+    int32_t same_octave;  /* as vslam_match_dev */
+    uint32_t reserved;    /* must be 0 */
+} vslam_guided_params;    /* 24 bytes */
+/* Pair j searches set j of `train` for every row of set j of `query` under models[j] (DEVICE pointers), j < n_pairs (at most
+ * 65535; 0 does nothing).  Asynchronous on the context stream, never waits on the host (the counts and the models are read on
+ * the device); scratch belongs to the context and is sized from the capacities before the launches.  VSLAM_ERR_INVALID before
+ * any launch - and before the context is looked at - for everything vslam_match_dev rejects, null points on either side,
+ * null models or params, a reserved word that is not 0, a ratio2 or max_dist2 that is not finite or not positive, a
+ * max_desc_dist2 that is NaN or not positive; then VSLAM_ERR_HIP as for vslam_match_dev.  Not for stream capture. */
+int vslam_match_guided_dev(vslam_ctx* ctx, const vslam_desc_sets* query, const vslam_desc_sets* train, const vslam_epipolar* models,
+                           int n_pairs, const vslam_guided_params* params, const vslam_match_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call): the arguments of vslam_match_host with
+ * both point lists required ([nq] and [nt]; NULL only with no rows), one model and the parameters.  nn [nq] and (matches
+ * [match_cap], n_matches) are each optional; *n_matches is the total, which may exceed match_cap.  Errors as for
+ * vslam_match_guided_dev. */
+int vslam_match_guided_host(vslam_ctx* ctx, const float* query, const uint8_t* query_defined, const vslam_point* query_points, size_t nq,
+                            const float* train, const uint8_t* train_defined, const vslam_point* train_points, size_t nt,
+                            const vslam_epipolar* model, const vslam_guided_params* params, vslam_nn2* nn, vslam_match* matches,
+                            size_t match_cap, size_t* n_matches);
+
 /* ---------------------------------------------------------------- homography and the degeneracy verdict
  * Beside vslam_epipolar_dev, over the same lists: the RANSAC homography of every pair, and - given the fundamental matrices
  * of the same pairs - a verdict per pair on whether the homography explains the matches as well as F does (a planar scene, a

@@ -36,6 +36,8 @@ EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers
 HOMOGRAPHY_HYP_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_homography_hyp, 152 bytes
 HOMOGRAPHY_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4"),
                              ("n_epipolar", "<u4"), ("degenerate", "<i4")], align=True)  # vslam_homography, 168 bytes
+GUIDED_PARAMS_DTYPE = np.dtype([("ratio2", "<f4"), ("max_desc_dist2", "<f4"), ("max_dist2", "<f8"), ("same_octave", "<i4"), ("reserved", "<u4")],
+                               align=True)  # vslam_guided_params, 24 bytes
 REFIT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4")], align=True)  # vslam_refit, 16 bytes
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
@@ -137,6 +139,10 @@ class EpipolarOut(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("inlier_bits", C.c_void_p),
                 ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t), ("inlier_counts", C.c_void_p),
                 ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t)]
+
+
+class GuidedParams(C.Structure):
+    _fields_ = [("ratio2", C.c_float), ("max_desc_dist2", C.c_float), ("max_dist2", C.c_double), ("same_octave", C.c_int32), ("reserved", C.c_uint32)]
 
 
 class RefitParams(C.Structure):
@@ -355,6 +361,8 @@ SIGNATURES = {
     "vslam_count_totals_dev": (_I, [_P, _P, _P, _I, _P]),
     "vslam_match_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _I, _F, _I, C.POINTER(MatchOut)]),
     "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
+    "vslam_match_guided_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _P, _I, C.POINTER(GuidedParams), C.POINTER(MatchOut)]),
+    "vslam_match_guided_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, C.POINTER(GuidedParams), _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_epipolar_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(EpipolarParams), C.POINTER(EpipolarOut)]),
     "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
     "vslam_refit_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(RefitParams), C.POINTER(RefitOut)]),
@@ -911,6 +919,49 @@ class Context:
         total = C.c_size_t()
         self._chk(lib().vslam_match_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), float(ratio2),
                                          int(bool(same_octave)), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_host")
+        return nn, matches[: min(total.value, cap)], total.value
+
+    def match_guided(self, query: DescSets, train: DescSets, models, n_pairs: int | None = None, ratio2: float = 0.64,
+                     max_desc_dist2: float = float("inf"), max_dist2: float = 4.0, same_octave: bool = False, nn=None, matches=None,
+                     match_counts=None):
+        """vslam_match_guided_dev: match() restricted, per query row, to the train rows in its epipolar band under models[j].F;
+        asynchronous on the context stream.  query / train: desc_sets() WITH points; models: the CUDA tensor epipolar(), refit() or
+        homography()'s gate wrote (n_pairs * 88 bytes).  Outputs as match()'s.  ratio2 is the SQUARED ratio, max_desc_dist2 the
+        absolute bound on an accepted d2 (inf: none), max_dist2 the SQUARED Sampson distance in pixels."""
+        n = min(query.n, train.n) if n_pairs is None else int(n_pairs)
+        outs = dict(nn=nn, matches=matches, match_counts=match_counts)
+        for name, t in outs.items():
+            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous() and t.element_size() == 4):
+                raise ValueError(f"match_guided: {name} must be a contiguous 4-byte-element tensor on cuda:{self.device}")
+        if not (models.is_cuda and models.device.index == self.device and models.is_contiguous()) or models.numel() * models.element_size() < n * 88:
+            raise ValueError(f"match_guided: models must be a contiguous tensor of n_pairs * 88 bytes on cuda:{self.device}")
+        mo = _fill_out(MatchOut(), outs)
+        if matches is not None:
+            mo.match_cap = matches.shape[1]
+        prm = GuidedParams(float(ratio2), float(max_desc_dist2), float(max_dist2), int(bool(same_octave)), 0)
+        self._chk(lib().vslam_match_guided_dev(self._h, C.byref(query), C.byref(train), models.data_ptr(), n, C.byref(prm), C.byref(mo)),
+                  "vslam_match_guided_dev")
+
+    def match_guided_host(self, q, t, q_points, t_points, model, ratio2: float = 0.64, max_desc_dist2: float = float("inf"), max_dist2: float = 4.0,
+                          same_octave: bool = False, q_defined=None, t_defined=None, match_cap: int | None = None):
+        """vslam_match_guided_host: one pair of numpy arrays (descriptors [n, 128], POINT_DTYPE points, one EPIPOLAR_DTYPE record) ->
+        (nn [nq] NN2_DTYPE, matches MATCH_DTYPE, total accepted)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 128)
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in
+               ((q_defined, np.uint8), (q_points, POINT_DTYPE), (t_defined, np.uint8), (t_points, POINT_DTYPE))]
+        for a, rows in zip(opt, (len(q), len(q), len(t), len(t))):
+            if a is not None and a.size != rows:
+                raise ValueError("match_guided_host: defined / points must have one entry per descriptor row")
+        ptr = [_ptr(a) for a in opt]
+        mod = np.ascontiguousarray(model, dtype=EPIPOLAR_DTYPE).reshape(-1)[:1]
+        cap = max(len(q), 1) if match_cap is None else int(match_cap)
+        nn = np.zeros(len(q), NN2_DTYPE)
+        matches = np.zeros(cap, MATCH_DTYPE)
+        total = C.c_size_t()
+        prm = GuidedParams(float(ratio2), float(max_desc_dist2), float(max_dist2), int(bool(same_octave)), 0)
+        self._chk(lib().vslam_match_guided_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), mod.ctypes.data,
+                                                C.byref(prm), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_guided_host")
         return nn, matches[: min(total.value, cap)], total.value
 
     def _two_view_lists(self, stage, n_pairs, required, tensors):

@@ -1,4 +1,4 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip, vslam_resect_refine.hip, vslam_tracks.hip, vslam_bundle.hip) share to enqueue kernels: the launch macros
+// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_match_guided.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip, vslam_resect_refine.hip, vslam_tracks.hip, vslam_bundle.hip) share to enqueue kernels: the launch macros
 // the timing hook sees, and the context's bump workspace with its per-call plan.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,9 @@ int ws_reserve(vslam_ctx* c, size_t bytes);
 size_t match_list_ws_elems(size_t fwords, int n_pairs);
 int enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_nn2* nn, unsigned int qcap, int n_pairs,
                        unsigned int* chunk_ws, vslam_match* matches, unsigned int match_cap, unsigned int* match_counts);
+// n(row) of every row in use of n_pairs descriptor sets (k_desc_norms, compiled in vslam_match.hip; vslam_match_guided_dev forms
+// d2 from the same norms): norms [n_pairs][S.cap].
+int enqueue_desc_norms(vslam_ctx* c, const vslam_desc_sets& S, int n_pairs, float* norms);
 // The inlier list of vslam_epipolar_dev, the same way (EpipolarEntries): the winner's ballot words over the match records of
 // n_pairs pairs -> the inlier records in list order.  chunk_ws as above; inliers may be null (totals only).
 int enqueue_inlier_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_match* matches, const unsigned int* match_counts,

@@ -12,6 +12,11 @@
 
 using namespace vslam;
 
+int vslam::enqueue_desc_norms(vslam_ctx* c, const vslam_desc_sets& S, int n_pairs, float* norms) {
+    LAUNCH(c, "k_desc_norms", k_desc_norms, dim3((unsigned int)(((size_t)S.cap + 255) / 256), n_pairs), dim3(256), S, norms);
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_match_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_desc_sets* T, int n_pairs, float ratio2, int same_octave,
@@ -57,8 +62,8 @@ int vslam_match_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_desc_set
     TRY(ws.commit(c));
     vslam_nn2* nn = out->nn ? out->nn : nn_ws;
 
-    LAUNCH(c, "k_desc_norms", k_desc_norms, dim3((Q->cap + 255) / 256, n_pairs), dim3(256), *Q, qnorm);
-    LAUNCH(c, "k_desc_norms", k_desc_norms, dim3((T->cap + 255) / 256, n_pairs), dim3(256), *T, tnorm);
+    TRY(enqueue_desc_norms(c, *Q, n_pairs, qnorm));
+    TRY(enqueue_desc_norms(c, *T, n_pairs, tnorm));
     const dim3 grid(qtiles, nsplit, n_pairs);
     if (same_octave)
         LAUNCH(c, "k_match_nn2", k_match_nn2<true>, grid, dim3(256), *Q, *T, qnorm, tnorm, nsplit, part);

@@ -3,7 +3,10 @@
 // filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
 // second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --epipolar adds
 // the step after that: the RANSAC fundamental matrix of the accepted matches (vslam::fundamentalRansac: 512 hypotheses, seed 1,
-// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --homography (after --epipolar) adds
+// Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --guided [max_dist2[,ratio[,max_desc_dist2]]]
+// (after --epipolar; defaults 4.0, 0.8, no bound) matches again inside each query's epipolar band under that F
+// (vslam::matchGuided) and runs the same RANSAC on the guided list: "guided_matches" and "guided_inliers"; the steps after it
+// still read the first list.  --homography (after these) adds
 // the RANSAC homography of the same matches and the degeneracy verdict (vslam::findHomography: 512 hypotheses, seed 1, transfer
 // error below 2 pixels, degenerate from n_H / n_F >= 1 / 2 with at least 16 inliers) as a "homography" object; the steps after
 // it then read the gated model, so a degenerate pair gets no refit and no pose.  --refit ROUNDS (after these)
@@ -11,7 +14,7 @@
 // accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
 // from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
 // candidate and the number of inliers in front of both cameras.
-//   usage: Match [--epipolar [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+//   usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -53,6 +56,21 @@ int main(int argc, char** argv) {
     try {
         const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
         if (epipolar) --argc, ++argv;
+        vslam_guided_params guidedParams{0.64f, HUGE_VALF, 4.0, 0, 0};
+        const bool guided = epipolar && argc > 1 && std::strcmp(argv[1], "--guided") == 0;
+        if (guided) {
+            --argc, ++argv;
+            // the optional value is all numbers and commas ("4.0", "4.0,0.8,1.0"): "512x384" and "a.pgm" are not
+            double md = 0.0, ratio = 0.0, bound = 0.0;
+            int used = 0;
+            const int got = argc > 1 ? std::sscanf(argv[1], "%lf%n,%lf%n,%lf%n", &md, &used, &ratio, &used, &bound, &used) : 0;
+            if (got >= 1 && argv[1][used] == '\0') {
+                guidedParams.max_dist2 = md;
+                if (got >= 2) guidedParams.ratio2 = (float)ratio * (float)ratio;
+                if (got >= 3) guidedParams.max_desc_dist2 = (float)bound;
+                --argc, ++argv;
+            }
+        }
         const bool homography = epipolar && argc > 1 && std::strcmp(argv[1], "--homography") == 0;
         if (homography) --argc, ++argv;
         vslam_refit_params refitParams{0, 4.0};
@@ -76,7 +94,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -96,6 +114,12 @@ int main(int argc, char** argv) {
                 extra += buf;
             }
             extra += "]}";
+            if (guided) {
+                const vslam::Matches g = vslam::matchGuided(q.descriptors, t.descriptors, q.points, t.points, e.model, guidedParams, &q.defined, &t.defined);
+                const vslam::Epipolar ge = vslam::fundamentalRansac(g.matches, q.points, t.points);
+                std::snprintf(buf, sizeof buf, ", \"guided_matches\": %zu, \"guided_inliers\": %u", g.matches.size(), ge.model.n_inliers);
+                extra += buf;
+            }
             vslam_epipolar model = e.model;
             std::vector<vslam_match> inliers = e.inliers;
             if (homography) {

@@ -22,6 +22,7 @@
 // The per-level gradient getters (octaveGradX/Y/Mag/Orient, processGradients, SURVEY.md section 8f
 // row 1) are computed on the GPU on first access instead of in the constructor.
 #pragma once
+#include <cmath>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -223,6 +224,16 @@ struct Homography {
 Homography findHomography(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                           const std::vector<SLAM::point>& trainPoints, const vslam_epipolar* epipolarModel = nullptr,
                           const vslam_homography_params& params = {512, 1, 4.0, 1, 2, 16});
+
+// A second matching pass once the pair has a model: matchDescriptors restricted, per query descriptor, to the train descriptors
+// whose keypoint lies in the query keypoint's epipolar band under model.F, on the GPU (vslam_match_guided_host; the band, the
+// selection and the acceptance with its absolute bound are stated in include/vslam.h, "guided matching").  On repeated structure
+// it recovers the matches the global ratio test rejects; feed Matches::matches to fundamentalRansac / refitFundamental again.
+// `model`: Epipolar::model, Refit::model or Homography::gated.  One keypoint per descriptor on both sides.
+Matches matchGuided(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train,
+                    const std::vector<SLAM::point>& queryPoints, const std::vector<SLAM::point>& trainPoints, const vslam_epipolar& model,
+                    const vslam_guided_params& params = {0.64f, HUGE_VALF, 4.0, 0, 0}, const std::vector<unsigned char>* query_defined = nullptr,
+                    const std::vector<unsigned char>* train_defined = nullptr);
 
 // The step after that: the camera motion of the pair (x_train ~ R x_query + t, |t| = 1) and the 3-D point of every record of
 // `matches` - the intended list is Epipolar::inliers - from the model fundamentalRansac found, on the GPU (vslam_pose_host;
