@@ -1,5 +1,6 @@
-// What the host drivers of the plan headers share (tests/epipolar_plan_driver.cpp, tests/pose_plan_driver.cpp): the tally of
-// checks with the first failure kept, and REJECT: a valid Call, one change to it, and the expectation that it is refused.
+// What the host drivers of the stages' plan headers share (the ten tests/*_plan_driver.cpp with a Call struct: epipolar,
+// guided, refit, homography, pose, chain, resect, resect_refine, tracks, bundle): the tally of checks with the first failure
+// kept, and REJECT: a valid Call, one change to it, and the expectation that it is refused.
 #pragma once
 #include <cstdio>
 

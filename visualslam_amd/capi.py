@@ -560,19 +560,87 @@ def _f32(a):
     return a
 
 
-def _fill_out(out, tensors):
-    """A vslam_*_out struct from its output tensors by field name: struct_size, pointers, byte sizes."""
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _fill_out(out, buffers):
+    """A vslam_*_out struct from its output tensors (device entry points) or numpy arrays (host entry points) by field name:
+    struct_size, pointers, byte sizes."""
     out.struct_size = C.sizeof(out)
-    for name, t in tensors.items():
+    for name, t in buffers.items():
         if t is not None:
-            setattr(out, name, t.data_ptr())
-            setattr(out, name + "_bytes", t.numel() * t.element_size())
+            at, nbytes = (t.ctypes.data, t.nbytes) if isinstance(t, np.ndarray) else (t.data_ptr(), t.numel() * t.element_size())
+            setattr(out, name, at)
+            setattr(out, name + "_bytes", nbytes)
     return out
 
 
 def _host_lists(matches, query_points, train_points):
     """The three lists of one host pair as flat record arrays."""
     return tuple(np.ascontiguousarray(a, dtype=dt).reshape(-1) for a, dt in ((matches, MATCH_DTYPE), (query_points, POINT_DTYPE), (train_points, POINT_DTYPE)))
+
+
+# What the device entry points check before the library is called (each raises the ValueError of the first check that fails, with
+# the stage in front), and what the batched host entry points do with their arrays.  None of it needs a context or the library.
+
+def _check_tensors(stage, where, tensors, required):
+    """Every tensor given (by argument name, in the order they are reported) is contiguous on the device `where` (a torch.device:
+    Context.where); then every name in `required` is there."""
+    for name, t in tensors.items():
+        if t is not None and not (t.device == where and t.is_contiguous()):
+            raise ValueError(f"{stage}: {name} must be a contiguous tensor on {where}")
+    for name in required:
+        if tensors[name] is None:
+            raise ValueError(f"{stage}: {name} is required")
+
+
+def _check_records(stage, name, t, width, shape):
+    """t is [n, cap, k] with k elements of `width` bytes together; shape: how the message words it."""
+    if t.dim() != 3 or t.shape[2] * t.element_size() != width:
+        raise ValueError(f"{stage}: {name} must be {shape} 4-byte elements")
+
+
+def _check_sets(stage, n, lists, counts, sizes):
+    """n pairs are there: n rows in every tensor of `lists`, n 4-byte elements in every tensor of `counts`, and the bytes needed
+    in every (tensor, bytes needed) pair of `sizes` (a tensor that is None needs none)."""
+    ok = True
+    for t in lists:
+        ok = ok and t.shape[0] >= n
+    for t in counts:
+        ok = ok and t.element_size() == 4 and t.numel() >= n
+    for t, need in sizes:
+        ok = ok and (t is None or t.numel() * t.element_size() >= need)
+    if not ok:
+        raise ValueError(f"{stage}: fewer sets than pairs")
+
+
+def _host_structure(stage, poses, matches):
+    """poses [n] and matches [n, match_cap] of a batched host call as record arrays -> (poses, matches, n, match_cap)."""
+    ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
+    mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+    if mt.ndim != 2 or mt.shape[0] != len(ps):
+        raise ValueError(f"{stage}: matches must be [n, match_cap]")
+    return ps, mt, len(ps), mt.shape[1]
+
+
+def _records(a, dtype):
+    return np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+
+
+def _counts(a):
+    return np.ascontiguousarray(a).astype(np.uint32).reshape(-1)
+
+
+def _words(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def _check_host_outs(stage, outs):
+    """The optional outputs of a host call, rows of (name, array or None, dtype, elements): written in place, so each is exactly that."""
+    for name, a, dt, size in outs:
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
+            raise ValueError(f"{stage}: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
 
 
 def _ptr(a):
@@ -602,6 +670,11 @@ class Context:
             raise VslamError(rc, "vslam_ctx_create", "no usable HIP device" if rc == -2 else "")
         self._h = h
         self.device = device
+        try:  # where the device entry points want their tensors (without torch there are none to check)
+            import torch
+            self.where = torch.device("cuda", device)
+        except ImportError:
+            self.where = None
         self._pyramids = weakref.WeakSet()  # the live Pyramid objects built on this context
 
     def close(self):
@@ -968,11 +1041,7 @@ class Context:
         """The checks epipolar() and pose() share over their tensors (by argument name, in the order they are reported) -> the number of pairs."""
         matches, match_counts, query_points, train_points = (tensors[k] for k in ("matches", "match_counts", "query_points", "train_points"))
         n = min(matches.shape[0], query_points.shape[0], train_points.shape[0]) if n_pairs is None else int(n_pairs)
-        for name, t in tensors.items():
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"{stage}: {name} must be a contiguous tensor on cuda:{self.device}")
-        if tensors[required] is None:
-            raise ValueError(f"{stage}: {required} is required")
+        _check_tensors(stage, self.where, tensors, (required,))
         if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12 or query_points.dim() != 3 or train_points.dim() != 3:
             raise ValueError(f"{stage}: matches must be [n, match_cap, 3] 4-byte elements, the points [n, cap, 6]")
         if query_points.shape[2] * query_points.element_size() != 24 or train_points.shape[2] * train_points.element_size() != 24:
@@ -1144,20 +1213,10 @@ class Context:
         [n, match_cap], ratios float64 [n, match_cap]."""
         tensors = dict(poses=poses, matches=matches, match_counts=match_counts, points=points, front_bits=front_bits, chain=chain, map=map, links=links,
                        ratios=ratios)
-        for name, t in tensors.items():
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"chain: {name} must be a contiguous tensor on cuda:{self.device}")
-        for name in ("poses", "matches", "match_counts", "points", "front_bits", "chain"):
-            if tensors[name] is None:
-                raise ValueError(f"chain: {name} is required")
-        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12:
-            raise ValueError("chain: matches must be [n, match_cap, 3] 4-byte elements")
-        n = matches.shape[0] if n_pairs is None else int(n_pairs)
-        cap = matches.shape[1]
-        size = lambda t: t.numel() * t.element_size()
-        if (matches.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n or size(poses) < n * 112 or size(points) < n * cap * 24
-                or size(front_bits) < n * ((cap + 63) // 64) * 8):
-            raise ValueError("chain: fewer sets than pairs")
+        _check_tensors("chain", self.where, tensors, ("poses", "matches", "match_counts", "points", "front_bits", "chain"))
+        _check_records("chain", "matches", matches, 12, "[n, match_cap, 3]")
+        n, cap = matches.shape[0] if n_pairs is None else int(n_pairs), matches.shape[1]
+        _check_sets("chain", n, (matches,), (match_counts,), ((poses, n * 112), (points, n * cap * 24), (front_bits, n * ((cap + 63) // 64) * 8)))
         co = _fill_out(ChainOut(), dict(chain=chain, map=map, links=links, ratios=ratios))
         prm = ChainParams(int(min_links))
         self._chk(lib().vslam_chain_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, points.data_ptr(),
@@ -1168,26 +1227,13 @@ class Context:
         [n], points float64 [n, match_cap, 3], front_bits uint64 [n, (match_cap + 63) // 64] - -> chain [n] CHAIN_DTYPE.  map float64
         [n, match_cap, 3], links int32 [n, match_cap] and ratios float64 [n, match_cap] are written in place when given (C-contiguous
         arrays of exactly that type); the rows the call leaves untouched keep their bytes."""
-        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
-        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
-        n = len(ps)
-        if mt.ndim != 2 or mt.shape[0] != n:
-            raise ValueError("chain_host: matches must be [n, match_cap]")
-        cap = mt.shape[1]
-        cnt = np.ascontiguousarray(match_counts).astype(np.uint32).reshape(-1)
-        pts = np.ascontiguousarray(points, dtype=np.float64)
-        fb = np.ascontiguousarray(front_bits).view(np.uint64)
+        ps, mt, n, cap = _host_structure("chain_host", poses, matches)
+        cnt, pts, fb = _counts(match_counts), np.ascontiguousarray(points, dtype=np.float64), _words(front_bits)
         if len(cnt) != n or pts.size != n * cap * 3 or fb.size != n * ((cap + 63) // 64):
             raise ValueError("chain_host: one count, match_cap points and (match_cap + 63) // 64 words per pair")
-        for name, a, dt, size in (("map", map, np.float64, n * cap * 3), ("links", links, np.int32, n * cap), ("ratios", ratios, np.float64, n * cap)):
-            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
-                raise ValueError(f"chain_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        _check_host_outs("chain_host", (("map", map, np.float64, n * cap * 3), ("links", links, np.int32, n * cap), ("ratios", ratios, np.float64, n * cap)))
         chain = np.zeros(max(n, 1), CHAIN_DTYPE)
-        co = ChainOut(C.sizeof(ChainOut), chain.ctypes.data, chain.nbytes)
-        for name, a in (("map", map), ("links", links), ("ratios", ratios)):
-            if a is not None:
-                setattr(co, name, a.ctypes.data)
-                setattr(co, name + "_bytes", a.nbytes)
+        co = _fill_out(ChainOut(), dict(chain=chain, map=map, links=links, ratios=ratios))
         prm = ChainParams(int(min_links))
         self._chk(lib().vslam_chain_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, pts.ctypes.data, fb.ctypes.data, int(point_cap), n,
                                          C.byref(prm), C.byref(co)), "vslam_chain_host")
@@ -1203,20 +1249,11 @@ class Context:
         8-byte words, summary n * 16 bytes (TRACK_SUMMARY_DTYPE)."""
         tensors = dict(poses=poses, matches=matches, match_counts=match_counts, front_bits=front_bits, chain=chain, frame_points=frame_points,
                        tracks=tracks, refs=refs, good_bits=good_bits, summary=summary)
-        for name, t in tensors.items():
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"tracks: {name} must be a contiguous tensor on cuda:{self.device}")
-        for name in ("poses", "matches", "match_counts", "front_bits", "chain", "frame_points", "tracks"):
-            if tensors[name] is None:
-                raise ValueError(f"tracks: {name} is required")
-        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12:
-            raise ValueError("tracks: matches must be [n, match_cap, 3] 4-byte elements")
-        n = matches.shape[0] if n_pairs is None else int(n_pairs)
-        cap = matches.shape[1]
-        size = lambda t: t.numel() * t.element_size()
-        if (matches.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n or size(poses) < n * 112 or size(chain) < n * 176
-                or size(front_bits) < n * ((cap + 63) // 64) * 8 or size(frame_points) < (n + 1) * int(point_cap) * 24):
-            raise ValueError("tracks: fewer sets than pairs")
+        _check_tensors("tracks", self.where, tensors, ("poses", "matches", "match_counts", "front_bits", "chain", "frame_points", "tracks"))
+        _check_records("tracks", "matches", matches, 12, "[n, match_cap, 3]")
+        n, cap = matches.shape[0] if n_pairs is None else int(n_pairs), matches.shape[1]
+        _check_sets("tracks", n, (matches,), (match_counts,), ((poses, n * 112), (chain, n * 176), (front_bits, n * ((cap + 63) // 64) * 8),
+                                                               (frame_points, (n + 1) * int(point_cap) * 24)))
         to = _fill_out(TracksOut(), dict(tracks=tracks, refs=refs, good_bits=good_bits, summary=summary))
         prm = TracksParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), 0)
         self._chk(lib().vslam_tracks_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, front_bits.data_ptr(),
@@ -1229,29 +1266,16 @@ class Context:
         tracks [n, match_cap] TRACK_DTYPE.  tracks (TRACK_DTYPE [n, match_cap]: the rows the call leaves untouched keep their bytes),
         refs (TRACK_REF_DTYPE [n, match_cap]), good_bits (uint64 [n, words]) and summary (TRACK_SUMMARY_DTYPE [n]) are written in
         place when given (C-contiguous arrays of exactly that type)."""
-        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
-        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
-        n = len(ps)
-        if mt.ndim != 2 or mt.shape[0] != n:
-            raise ValueError("tracks_host: matches must be [n, match_cap]")
-        cap, words = mt.shape[1], (mt.shape[1] + 63) // 64
-        cnt = np.ascontiguousarray(match_counts).astype(np.uint32).reshape(-1)
-        fb = np.ascontiguousarray(front_bits).view(np.uint64)
-        ch = np.ascontiguousarray(chain, dtype=CHAIN_DTYPE).reshape(-1)
-        fp = np.ascontiguousarray(frame_points, dtype=POINT_DTYPE).reshape(-1)
+        ps, mt, n, cap = _host_structure("tracks_host", poses, matches)
+        words = (cap + 63) // 64
+        cnt, fb, ch, fp = _counts(match_counts), _words(front_bits), _records(chain, CHAIN_DTYPE), _records(frame_points, POINT_DTYPE)
         if len(cnt) != n or fb.size != n * words or len(ch) != n or len(fp) != (n + 1) * int(point_cap):
             raise ValueError("tracks_host: one count, one chain record and (match_cap + 63) // 64 words per pair, point_cap points per frame")
         if tracks is None:
             tracks = np.zeros((n, cap), TRACK_DTYPE)
-        for name, a, dt, size in (("tracks", tracks, TRACK_DTYPE, n * cap), ("refs", refs, TRACK_REF_DTYPE, n * cap),
-                                  ("good_bits", good_bits, np.dtype(np.uint64), n * words), ("summary", summary, TRACK_SUMMARY_DTYPE, n)):
-            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
-                raise ValueError(f"tracks_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
-        to = TracksOut(C.sizeof(TracksOut))
-        for name, a in (("tracks", tracks), ("refs", refs), ("good_bits", good_bits), ("summary", summary)):
-            if a is not None:
-                setattr(to, name, a.ctypes.data)
-                setattr(to, name + "_bytes", a.nbytes)
+        _check_host_outs("tracks_host", (("tracks", tracks, TRACK_DTYPE, n * cap), ("refs", refs, TRACK_REF_DTYPE, n * cap),
+                                         ("good_bits", good_bits, np.uint64, n * words), ("summary", summary, TRACK_SUMMARY_DTYPE, n)))
+        to = _fill_out(TracksOut(), dict(tracks=tracks, refs=refs, good_bits=good_bits, summary=summary))
         prm = TracksParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), 0)
         self._chk(lib().vslam_tracks_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, fb.ctypes.data, int(point_cap), n,
                                           ch.ctypes.data, fp.ctypes.data, C.byref(prm), C.byref(to)), "vslam_tracks_host")
@@ -1266,21 +1290,12 @@ class Context:
         63) // 64] 8-byte words."""
         tensors = dict(poses=poses, matches=matches, match_counts=match_counts, front_bits=front_bits, chain=chain, frame_points=frame_points,
                        tracks_in=tracks_in, refs=refs, cams_in=cams_in, tracks=tracks, cams=cams, point_info=point_info, member_bits=member_bits)
-        for name, t in tensors.items():
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"bundle: {name} must be a contiguous tensor on cuda:{self.device}")
-        for name in ("poses", "matches", "match_counts", "front_bits", "chain", "frame_points", "tracks_in", "refs", "tracks", "cams"):
-            if tensors[name] is None:
-                raise ValueError(f"bundle: {name} is required")
-        if matches.dim() != 3 or matches.shape[2] * matches.element_size() != 12:
-            raise ValueError("bundle: matches must be [n, match_cap, 3] 4-byte elements")
-        n = matches.shape[0] if n_pairs is None else int(n_pairs)
-        cap = matches.shape[1]
-        size = lambda t: t.numel() * t.element_size()
-        if (matches.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n or size(poses) < n * 112 or size(chain) < n * 176
-                or size(front_bits) < n * ((cap + 63) // 64) * 8 or size(frame_points) < (n + 1) * int(point_cap) * 24 or size(tracks_in) < n * cap * 48
-                or size(refs) < n * cap * 8 or (cams_in is not None and size(cams_in) < n * 160)):
-            raise ValueError("bundle: fewer sets than pairs")
+        _check_tensors("bundle", self.where, tensors, ("poses", "matches", "match_counts", "front_bits", "chain", "frame_points", "tracks_in", "refs", "tracks", "cams"))
+        _check_records("bundle", "matches", matches, 12, "[n, match_cap, 3]")
+        n, cap = matches.shape[0] if n_pairs is None else int(n_pairs), matches.shape[1]
+        _check_sets("bundle", n, (matches,), (match_counts,), ((poses, n * 112), (chain, n * 176), (front_bits, n * ((cap + 63) // 64) * 8),
+                                                               (frame_points, (n + 1) * int(point_cap) * 24), (tracks_in, n * cap * 48),
+                                                               (refs, n * cap * 8), (cams_in, n * 160)))
         bo = _fill_out(BundleOut(), dict(tracks=tracks, cams=cams, point_info=point_info, member_bits=member_bits))
         prm = BundleParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), int(sweeps))
         self._chk(lib().vslam_bundle_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, front_bits.data_ptr(),
@@ -1293,35 +1308,20 @@ class Context:
         match_cap] TRACK_REF_DTYPE, cams_in [n] BUNDLE_CAM_DTYPE or None) -> (tracks [n, match_cap] TRACK_DTYPE, cams [n] BUNDLE_CAM_DTYPE).
         tracks (default: a copy of tracks_in), point_info (BUNDLE_POINT_DTYPE [n, match_cap]) and member_bits (uint64 [n, 2, words]) are
         written in place when given (C-contiguous arrays of exactly that type)."""
-        ps = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
-        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
-        n = len(ps)
-        if mt.ndim != 2 or mt.shape[0] != n:
-            raise ValueError("bundle_host: matches must be [n, match_cap]")
-        cap, words = mt.shape[1], (mt.shape[1] + 63) // 64
-        cnt = np.ascontiguousarray(match_counts).astype(np.uint32).reshape(-1)
-        fb = np.ascontiguousarray(front_bits).view(np.uint64)
-        ch = np.ascontiguousarray(chain, dtype=CHAIN_DTYPE).reshape(-1)
-        fp = np.ascontiguousarray(frame_points, dtype=POINT_DTYPE).reshape(-1)
-        ti = np.ascontiguousarray(tracks_in, dtype=TRACK_DTYPE).reshape(-1)
-        rf = np.ascontiguousarray(refs, dtype=TRACK_REF_DTYPE).reshape(-1)
-        ci = None if cams_in is None else np.ascontiguousarray(cams_in, dtype=BUNDLE_CAM_DTYPE).reshape(-1)
+        ps, mt, n, cap = _host_structure("bundle_host", poses, matches)
+        words = (cap + 63) // 64
+        cnt, fb, ch, fp = _counts(match_counts), _words(front_bits), _records(chain, CHAIN_DTYPE), _records(frame_points, POINT_DTYPE)
+        ti, rf, ci = _records(tracks_in, TRACK_DTYPE), _records(refs, TRACK_REF_DTYPE), None if cams_in is None else _records(cams_in, BUNDLE_CAM_DTYPE)
         if (len(cnt) != n or fb.size != n * words or len(ch) != n or len(fp) != (n + 1) * int(point_cap) or len(ti) != n * cap or len(rf) != n * cap
                 or (ci is not None and len(ci) != n)):
             raise ValueError("bundle_host: one count, one chain record, one camera and (match_cap + 63) // 64 words per pair, match_cap tracks and refs, "
                              "point_cap points per frame")
         if tracks is None:
             tracks = ti.reshape(n, cap).copy()
-        for name, a, dt, size in (("tracks", tracks, TRACK_DTYPE, n * cap), ("point_info", point_info, BUNDLE_POINT_DTYPE, n * cap),
-                                  ("member_bits", member_bits, np.dtype(np.uint64), n * 2 * words)):
-            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
-                raise ValueError(f"bundle_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        _check_host_outs("bundle_host", (("tracks", tracks, TRACK_DTYPE, n * cap), ("point_info", point_info, BUNDLE_POINT_DTYPE, n * cap),
+                                         ("member_bits", member_bits, np.uint64, n * 2 * words)))
         cams = np.zeros(max(n, 1), BUNDLE_CAM_DTYPE)
-        bo = BundleOut(C.sizeof(BundleOut))
-        for name, a in (("tracks", tracks), ("cams", cams), ("point_info", point_info), ("member_bits", member_bits)):
-            if a is not None:
-                setattr(bo, name, a.ctypes.data)
-                setattr(bo, name + "_bytes", a.nbytes)
+        bo = _fill_out(BundleOut(), dict(tracks=tracks, cams=cams, point_info=point_info, member_bits=member_bits))
         prm = BundleParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), int(min_views), int(sweeps))
         self._chk(lib().vslam_bundle_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, fb.ctypes.data, int(point_cap), n,
                                           ch.ctypes.data, fp.ctypes.data, ti.ctypes.data, rf.ctypes.data, None if ci is None else ci.ctypes.data,
@@ -1341,24 +1341,14 @@ class Context:
         tensors = dict(poses=poses, matches=matches, match_counts=match_counts, points=points, front_bits=front_bits, obs_matches=obs_matches,
                        obs_counts=obs_counts, train_points=train_points, models=models, inlier_bits=inlier_bits, hypotheses=hypotheses,
                        correspondences=correspondences, links=links)
-        for name, t in tensors.items():
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"resect: {name} must be a contiguous tensor on cuda:{self.device}")
-        for name in ("poses", "matches", "match_counts", "points", "front_bits", "obs_matches", "obs_counts", "train_points", "models"):
-            if tensors[name] is None:
-                raise ValueError(f"resect: {name} is required")
-        for name, t in (("matches", matches), ("obs_matches", obs_matches)):
-            if t.dim() != 3 or t.shape[2] * t.element_size() != 12:
-                raise ValueError(f"resect: {name} must be [n, cap, 3] 4-byte elements")
-        if train_points.dim() != 3 or train_points.shape[2] * train_points.element_size() != 24:
-            raise ValueError("resect: train_points must be [n, train_cap, 6] 4-byte elements")
+        _check_tensors("resect", self.where, tensors, ("poses", "matches", "match_counts", "points", "front_bits", "obs_matches", "obs_counts", "train_points", "models"))
+        _check_records("resect", "matches", matches, 12, "[n, cap, 3]")
+        _check_records("resect", "obs_matches", obs_matches, 12, "[n, cap, 3]")
+        _check_records("resect", "train_points", train_points, 24, "[n, train_cap, 6]")
         n = matches.shape[0] if n_pairs is None else int(n_pairs)
         cap, ocap, tcap = matches.shape[1], obs_matches.shape[1], train_points.shape[1]
-        size = lambda t: t.numel() * t.element_size()
-        if (matches.shape[0] < n or obs_matches.shape[0] < n or train_points.shape[0] < n or match_counts.element_size() != 4 or match_counts.numel() < n
-                or obs_counts.element_size() != 4 or obs_counts.numel() < n or size(poses) < n * 112 or size(points) < n * cap * 24
-                or size(front_bits) < n * ((cap + 63) // 64) * 8):
-            raise ValueError("resect: fewer sets than pairs")
+        _check_sets("resect", n, (matches, obs_matches, train_points), (match_counts, obs_counts),
+                    ((poses, n * 112), (points, n * cap * 24), (front_bits, n * ((cap + 63) // 64) * 8)))
         ro = _fill_out(ResectOut(), dict(models=models, inlier_bits=inlier_bits, hypotheses=hypotheses, correspondences=correspondences, links=links))
         prm = ResectParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
         self._chk(lib().vslam_resect_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, points.data_ptr(),
@@ -1380,22 +1370,14 @@ class Context:
         if any(a.ndim != 2 or a.shape[0] != n for a in (mt, ob, tp)):
             raise ValueError("resect_host: matches, obs_matches and train_points must be [n, capacity]")
         cap, ocap, tcap = mt.shape[1], ob.shape[1], tp.shape[1]
-        cnt, ocnt = (np.ascontiguousarray(a).astype(np.uint32).reshape(-1) for a in (match_counts, obs_counts))
-        pts = np.ascontiguousarray(points, dtype=np.float64)
-        fb = np.ascontiguousarray(front_bits).view(np.uint64)
+        cnt, ocnt, pts, fb = _counts(match_counts), _counts(obs_counts), np.ascontiguousarray(points, dtype=np.float64), _words(front_bits)
         if len(cnt) != n or len(ocnt) != n or pts.size != n * cap * 3 or fb.size != n * ((cap + 63) // 64):
             raise ValueError("resect_host: one count, match_cap points and (match_cap + 63) // 64 words per pair")
         outs = (("inlier_bits", inlier_bits, np.uint64, n * ((ocap + 63) // 64)), ("hypotheses", hypotheses, RESECT_HYP_DTYPE, n * int(n_hypotheses)),
                 ("correspondences", correspondences, RESECT_CORR_DTYPE, n * ocap), ("links", links, np.int32, n * ocap))
-        for name, a, dt, size in outs:
-            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.size == size):
-                raise ValueError(f"resect_host: {name} must be a C-contiguous {np.dtype(dt).name} array of {size} elements")
+        _check_host_outs("resect_host", outs)
         models = np.zeros(max(n, 1), RESECT_DTYPE)
-        ro = ResectOut(C.sizeof(ResectOut), models.ctypes.data, models.nbytes)
-        for name, a, _, _ in outs:
-            if a is not None:
-                setattr(ro, name, a.ctypes.data)
-                setattr(ro, name + "_bytes", a.nbytes)
+        ro = _fill_out(ResectOut(), dict(models=models, inlier_bits=inlier_bits, hypotheses=hypotheses, correspondences=correspondences, links=links))
         prm = ResectParams(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
         self._chk(lib().vslam_resect_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, pts.ctypes.data, fb.ctypes.data, int(point_cap),
                                           ob.ctypes.data, ocnt.ctypes.data, ocap, tp.ctypes.data, tcap, n, C.byref(prm), C.byref(ro)),
@@ -1410,15 +1392,9 @@ class Context:
         120 bytes (may be models_in itself), info n_pairs * 32 bytes (RESECT_REFINE_DTYPE), inlier_bits [n, (obs_cap + 63) // 64]
         8-byte words, indexed by observation record like resect()'s, under the output pose."""
         tensors = dict(models_in=models_in, correspondences=correspondences, models=models, info=info, inlier_bits=inlier_bits)
-        for name, t in tensors.items():
-            if t is not None and not (t.is_cuda and t.device.index == self.device and t.is_contiguous()):
-                raise ValueError(f"resect_refine: {name} must be a contiguous tensor on cuda:{self.device}")
-        for name in ("models_in", "correspondences", "models"):
-            if tensors[name] is None:
-                raise ValueError(f"resect_refine: {name} is required")
-        size = lambda t: t.numel() * t.element_size()
-        n = size(models_in) // 120 if n_pairs is None else int(n_pairs)
-        if size(models_in) < n * 120 or size(correspondences) < n * int(obs_cap) * 48:
+        _check_tensors("resect_refine", self.where, tensors, ("models_in", "correspondences", "models"))
+        n = _nbytes(models_in) // 120 if n_pairs is None else int(n_pairs)
+        if _nbytes(models_in) < n * 120 or _nbytes(correspondences) < n * int(obs_cap) * 48:
             raise ValueError("resect_refine: models_in must hold n_pairs * 120 bytes, correspondences n_pairs * obs_cap * 48")
         ro = _fill_out(ResectRefineOut(), dict(models=models, info=info, inlier_bits=inlier_bits))
         prm = ResectRefineParams(int(rounds), float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
@@ -1436,13 +1412,9 @@ class Context:
             raise ValueError("resect_refine_host: correspondences must be [n, obs_cap]")
         ocap = cs.shape[1]
         words = n * ((ocap + 63) // 64)
-        if inlier_bits is not None and not (isinstance(inlier_bits, np.ndarray) and inlier_bits.dtype == np.uint64 and inlier_bits.flags.c_contiguous
-                                            and inlier_bits.size == words):
-            raise ValueError(f"resect_refine_host: inlier_bits must be a C-contiguous uint64 array of {words} elements")
+        _check_host_outs("resect_refine_host", (("inlier_bits", inlier_bits, np.uint64, words),))
         models, info = np.zeros(max(n, 1), RESECT_DTYPE), np.zeros(max(n, 1), RESECT_REFINE_DTYPE)
-        ro = ResectRefineOut(C.sizeof(ResectRefineOut), models.ctypes.data, models.nbytes, info.ctypes.data, info.nbytes)
-        if inlier_bits is not None:
-            ro.inlier_bits, ro.inlier_bits_bytes = inlier_bits.ctypes.data, inlier_bits.nbytes
+        ro = _fill_out(ResectRefineOut(), dict(models=models, info=info, inlier_bits=inlier_bits))
         prm = ResectRefineParams(int(rounds), float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
         self._chk(lib().vslam_resect_refine_host(self._h, mi.ctypes.data, cs.ctypes.data, ocap, n, C.byref(prm), C.byref(ro)), "vslam_resect_refine_host")
         return models[:n], info[:n]

@@ -42,8 +42,9 @@ int vslam_bundle_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* m
                    pl.trk.fwords, point_cap, n_pairs};
     const dim3 records(pl.trk.rec_blocks, n_pairs), rows(pl.sum_blocks, n_pairs), pairs(pl.pair_blocks);
     if (pl.trk.link_pairs) {
-        TRY(enqueue_chain_link(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, prev));
-        TRY(enqueue_trk_next(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, chain, prev, next));
+        const StructLists L{poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs};
+        TRY(enqueue_chain_link(c, L, prev));
+        TRY(enqueue_trk_next(c, L, chain, prev, next));
     }
     LAUNCH(c, "k_ba_init", k_ba_init, records, dim3(TRK_REC_WG), in, *prm, prev, next, tracks_in, cams_in, out->tracks, out->point_info, state);
     for (unsigned int sweep = 0; sweep < prm->sweeps; ++sweep) {
@@ -73,47 +74,25 @@ int vslam_bundle_host(vslam_ctx* c, const vslam_pose* poses, const vslam_match* 
     if (n_pairs == 0) return VSLAM_OK;
 
     const size_t np = (size_t)n_pairs, recs = np * match_cap, words = np * twoview_fwords(match_cap);
-    DevBufs dev;
-    vslam_pose* d_poses = nullptr;
-    vslam_match* d_matches = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bits = nullptr;
-    vslam_chain* d_chain = nullptr;
-    vslam_point* d_frames = nullptr;
-    vslam_track* d_tracks_in = nullptr;
-    vslam_track_ref* d_refs = nullptr;
-    vslam_bundle_cam* d_cams_in = nullptr;
-    TRY(dev.put(c, d_poses, poses, np));
-    TRY(dev.put(c, d_matches, matches, recs));
-    TRY(dev.put(c, d_counts, match_counts, np));
-    TRY(dev.put(c, d_bits, front_bits, words));
-    TRY(dev.put(c, d_chain, chain, np));
-    TRY(dev.put(c, d_frames, frame_points, (np + 1) * point_cap));
-    TRY(dev.put(c, d_tracks_in, tracks_in, recs));
-    TRY(dev.put(c, d_refs, refs, recs));
-    if (cams_in) TRY(dev.put(c, d_cams_in, cams_in, np));
-    // the outputs go up first: the rows and words the call leaves untouched come back as the caller had them
+    HostMirror m(c);
+    const auto d_poses = m.in(poses, np);
+    const auto d_matches = m.in(matches, recs);
+    const auto d_counts = m.in(match_counts, np);
+    const auto d_bits = m.in(front_bits, words);
+    const auto d_chain = m.in(chain, np);
+    const auto d_frames = m.in(frame_points, (np + 1) * point_cap);
+    const auto d_tracks_in = m.in(tracks_in, recs);
+    const auto d_refs = m.in(refs, recs);
+    const auto d_cams_in = m.in(cams_in, np);  // (optional)
     vslam_bundle_out d{};
     d.struct_size = sizeof(d);
-    TRY(dev.put(c, d.tracks, static_cast<const vslam_track*>(out->tracks), recs));
-    d.tracks_bytes = recs * sizeof(vslam_track);
-    TRY(dev.get(c, d.cams, np));
-    d.cams_bytes = np * sizeof(vslam_bundle_cam);
-    if (out->point_info) {
-        TRY(dev.put(c, d.point_info, static_cast<const vslam_bundle_point*>(out->point_info), recs));
-        d.point_info_bytes = recs * sizeof(vslam_bundle_point);
-    }
-    if (out->member_bits) {
-        TRY(dev.put(c, d.member_bits, static_cast<const uint64_t*>(out->member_bits), 2 * words));
-        d.member_bits_bytes = 2 * words * sizeof(uint64_t);
-    }
+    m.out(d.tracks, d.tracks_bytes, out->tracks, recs, true);
+    m.out(d.cams, d.cams_bytes, out->cams, np, false);
+    m.out(d.point_info, d.point_info_bytes, out->point_info, recs, true);
+    m.out(d.member_bits, d.member_bits_bytes, out->member_bits, 2 * words, true);
+    TRY(m.status());
     TRY(vslam_bundle_dev(c, d_poses, d_matches, d_counts, match_cap, d_bits, point_cap, n_pairs, d_chain, d_frames, d_tracks_in, d_refs, d_cams_in, prm, &d));
-    HIPCHK(c, hipMemcpyAsync(out->tracks, d.tracks, recs * sizeof(vslam_track), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out->cams, d.cams, np * sizeof(vslam_bundle_cam), hipMemcpyDeviceToHost, c->stream));
-    if (out->point_info) HIPCHK(c, hipMemcpyAsync(out->point_info, d.point_info, d.point_info_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->member_bits) HIPCHK(c, hipMemcpyAsync(out->member_bits, d.member_bits, d.member_bits_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return m.finish();
 }
 
 }  // extern "C"

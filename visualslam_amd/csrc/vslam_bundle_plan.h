@@ -30,21 +30,17 @@ inline const char* bundle_check_args(const vslam_pose* poses, const vslam_match*
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
     if (prm->sweeps < 1 || prm->sweeps > 64) return "1 .. 64 sweeps";
     if (prm->min_views < 2) return "min_views must be at least 2";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
-    if (!std::isfinite(prm->K.fx) || !std::isfinite(prm->K.fy) || !std::isfinite(prm->K.cx) || !std::isfinite(prm->K.cy))
-        return "the intrinsics must be finite";
-    if (!(prm->K.fx > 0.0) || !(prm->K.fy > 0.0)) return "fx and fy must be positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
+    if (const char* why = check_intrinsics(prm->K)) return why;
     if (const char* why = twoview_check_inputs(poses && matches && match_counts && front_bits && chain && frame_points && tracks_in && refs, match_cap,
                                                point_cap, point_cap))
         return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
-    if (!out->tracks) return "tracks is required";
     // np * match_cap < 2^48: no element count wraps, and the byte counts are compared by division
-    if (out->tracks_bytes / sizeof(vslam_track) < np * match_cap) return "tracks buffer too small";
-    if (!out->cams) return "cams is required";
-    if (out->cams_bytes / sizeof(vslam_bundle_cam) < np) return "cams buffer too small";
-    if (out->point_info && out->point_info_bytes / sizeof(vslam_bundle_point) < np * match_cap) return "point_info buffer too small";
-    if (out->member_bits && out->member_bits_bytes / sizeof(uint64_t) < np * 2 * fwords) return "member_bits buffer too small";
+    OUT_NEEDS(out, tracks, vslam_track, np * match_cap);
+    OUT_NEEDS(out, cams, vslam_bundle_cam, np);
+    OUT_FITS(out, point_info, vslam_bundle_point, np * match_cap);
+    OUT_FITS(out, member_bits, uint64_t, np * 2 * fwords);
     // (np * match_cap * 48 < 2^54)
     const uintptr_t a = reinterpret_cast<uintptr_t>(tracks_in), b = reinterpret_cast<uintptr_t>(out->tracks), span = np * match_cap * sizeof(vslam_track);
     if (a != b && (a < b ? b - a : a - b) < span) return "tracks overlaps tracks_in without being equal to it";

@@ -13,10 +13,10 @@
 
 using namespace vslam;
 
-int vslam::enqueue_chain_link(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
-                              const uint64_t* front_bits, unsigned int point_cap, int n_pairs, unsigned int* prev) {
-    const ChainPlan pl = chain_plan(match_cap, point_cap, n_pairs);
-    const ChainIn in{poses, matches, match_counts, nullptr, reinterpret_cast<const unsigned long long*>(front_bits), match_cap, pl.fwords, point_cap};
+int vslam::enqueue_chain_link(vslam_ctx* c, const StructLists& L, unsigned int* prev) {
+    const ChainPlan pl = chain_plan(L.match_cap, L.point_cap, L.n_pairs);
+    const ChainIn in{L.poses, L.matches, L.match_counts, nullptr, reinterpret_cast<const unsigned long long*>(L.front_bits), L.match_cap, pl.fwords,
+                     L.point_cap};
     HIPCHK(c, hipMemsetAsync(prev, 0xff, pl.table_elems * sizeof(unsigned int), c->stream));
     LAUNCH(c, "k_chain_link", k_chain_link, dim3(pl.rec_blocks, pl.link_pairs), dim3(CHAIN_REC_WG), in, prev);
     return VSLAM_OK;
@@ -47,7 +47,7 @@ int vslam_chain_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* ma
     const ChainIn in{poses, matches, match_counts, points, reinterpret_cast<const unsigned long long*>(front_bits), match_cap, pl.fwords, point_cap};
     const dim3 records(pl.rec_blocks, n_pairs);
     HIPCHK(c, hipMemsetAsync(usable, 0, pl.pair_elems * sizeof(unsigned int), c->stream));
-    if (pl.link_pairs) TRY(enqueue_chain_link(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, prev));
+    if (pl.link_pairs) TRY(enqueue_chain_link(c, StructLists{poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs}, prev));
     if (pl.link_pairs || out->links || out->ratios)  // (pair 0 alone has no ratios: only its rows of links and ratios to write)
         LAUNCH(c, "k_chain_ratio", k_chain_ratio, records, dim3(CHAIN_REC_WG), in, prev, keys, usable, out->links, out->ratios);
     if (pl.link_pairs)
@@ -66,41 +66,21 @@ int vslam_chain_host(vslam_ctx* c, const vslam_pose* poses, const vslam_match* m
     if (n_pairs == 0) return VSLAM_OK;
 
     const size_t np = (size_t)n_pairs, recs = np * match_cap, words = np * twoview_fwords(match_cap);
-    DevBufs dev;
-    vslam_pose* d_poses = nullptr;
-    vslam_match* d_matches = nullptr;
-    uint32_t* d_counts = nullptr;
-    double* d_points = nullptr;
-    uint64_t* d_bits = nullptr;
-    TRY(dev.put(c, d_poses, poses, np));
-    TRY(dev.put(c, d_matches, matches, recs));
-    TRY(dev.put(c, d_counts, match_counts, np));
-    TRY(dev.put(c, d_points, points, recs * 3));
-    TRY(dev.put(c, d_bits, front_bits, words));
-    // the optional outputs go up first: the rows the call leaves untouched come back as the caller had them
+    HostMirror m(c);
+    const auto d_poses = m.in(poses, np);
+    const auto d_matches = m.in(matches, recs);
+    const auto d_counts = m.in(match_counts, np);
+    const auto d_points = m.in(points, recs * 3);
+    const auto d_bits = m.in(front_bits, words);
     vslam_chain_out d{};
     d.struct_size = sizeof(d);
-    TRY(dev.get(c, d.chain, np));
-    d.chain_bytes = np * sizeof(vslam_chain);
-    if (out->map) {
-        TRY(dev.put(c, d.map, static_cast<const double*>(out->map), recs * 3));
-        d.map_bytes = recs * 3 * sizeof(double);
-    }
-    if (out->links) {
-        TRY(dev.put(c, d.links, static_cast<const int32_t*>(out->links), recs));
-        d.links_bytes = recs * sizeof(int32_t);
-    }
-    if (out->ratios) {
-        TRY(dev.put(c, d.ratios, static_cast<const double*>(out->ratios), recs));
-        d.ratios_bytes = recs * sizeof(double);
-    }
+    m.out(d.chain, d.chain_bytes, out->chain, np, false);
+    m.out(d.map, d.map_bytes, out->map, recs * 3, true);
+    m.out(d.links, d.links_bytes, out->links, recs, true);
+    m.out(d.ratios, d.ratios_bytes, out->ratios, recs, true);
+    TRY(m.status());
     TRY(vslam_chain_dev(c, d_poses, d_matches, d_counts, match_cap, d_points, d_bits, point_cap, n_pairs, prm, &d));
-    HIPCHK(c, hipMemcpyAsync(out->chain, d.chain, np * sizeof(vslam_chain), hipMemcpyDeviceToHost, c->stream));
-    if (out->map) HIPCHK(c, hipMemcpyAsync(out->map, d.map, recs * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (out->links) HIPCHK(c, hipMemcpyAsync(out->links, d.links, recs * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (out->ratios) HIPCHK(c, hipMemcpyAsync(out->ratios, d.ratios, recs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return m.finish();
 }
 
 }  // extern "C"

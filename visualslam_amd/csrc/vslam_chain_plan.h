@@ -20,12 +20,11 @@ inline const char* chain_check_args(const vslam_pose* poses, const vslam_match* 
     if (prm->min_links == 0) return "min_links must be at least 1";
     if (const char* why = twoview_check_inputs(poses && matches && match_counts && points && front_bits, match_cap, point_cap, point_cap)) return why;
     const size_t np = (size_t)n_pairs;
-    if (!out->chain) return "chain is required";
-    if (out->chain_bytes / sizeof(vslam_chain) < np) return "chain buffer too small";
+    OUT_NEEDS(out, chain, vslam_chain, np);
     // np * match_cap < 2^48: the element count cannot wrap, and the byte count is compared by division
-    if (out->map && out->map_bytes / (3 * sizeof(double)) < np * match_cap) return "map buffer too small";
-    if (out->links && out->links_bytes / sizeof(int32_t) < np * match_cap) return "links buffer too small";
-    if (out->ratios && out->ratios_bytes / sizeof(double) < np * match_cap) return "ratios buffer too small";
+    OUT_FITS(out, map, double[3], np * match_cap);
+    OUT_FITS(out, links, int32_t, np * match_cap);
+    OUT_FITS(out, ratios, double, np * match_cap);
     return nullptr;
 }
 
@@ -44,8 +43,8 @@ inline ChainPlan chain_plan(uint32_t match_cap, uint32_t point_cap, int n_pairs)
     const TwoViewPlan tv = twoview_plan(match_cap, n_pairs);
     ChainPlan p{};
     p.fwords = tv.fwords, p.rec_blocks = tv.rec_blocks;
-    p.link_pairs = (unsigned int)n_pairs - 1;
-    p.table_elems = (size_t)p.link_pairs * point_cap;
+    const LinkTable lt = link_table(point_cap, n_pairs);
+    p.link_pairs = lt.link_pairs, p.table_elems = lt.elems;
     p.key_elems = (size_t)p.link_pairs * match_cap;
     p.pair_elems = (size_t)n_pairs;
     return p;

@@ -36,6 +36,29 @@ inline const char* twoview_check_inputs(bool inputs, uint32_t match_cap, uint32_
     return !inputs ? "null input" : match_cap == 0 || query_cap == 0 || train_cap == 0 ? "a capacity is zero" : nullptr;
 }
 
+// The checks and sizes that more than one stage's plan header states, once.
+inline const char* check_max_dist2(double max_dist2) {
+    return !std::isfinite(max_dist2) || !(max_dist2 > 0.0) ? "max_dist2 must be finite and positive" : nullptr;
+}
+// `not_finite`: the stage's wording of the first message ("an intrinsic is not finite" in the resection stages).
+inline const char* check_intrinsics(const vslam_pose_params& K, const char* not_finite = "the intrinsics must be finite") {
+    if (!std::isfinite(K.fx) || !std::isfinite(K.fy) || !std::isfinite(K.cx) || !std::isfinite(K.cy)) return not_finite;
+    return !(K.fx > 0.0) || !(K.fy > 0.0) ? "fx and fy must be positive" : nullptr;
+}
+// An output of `out` that is there holds n elements of T (the byte count is compared by division: n may be anything below
+// 2^64); OUT_NEEDS: an output the stage cannot do without.  Both return from the *_check_args that uses them.
+#define OUT_FITS(out, field, T, n) \
+    if ((out)->field && (out)->field##_bytes / sizeof(T) < (n)) return #field " buffer too small"
+#define OUT_NEEDS(out, field, T, n)                   \
+    if (!(out)->field) return #field " is required"; \
+    OUT_FITS(out, field, T, n)
+// The link table of enqueue_chain_link (vslam_launch.h): row j - 1 links pair j to pair j - 1.
+struct LinkTable {
+    unsigned int link_pairs;  // n_pairs - 1: grid.y of k_chain_link (0: not launched)
+    size_t elems;             // uint32 [link_pairs][point_cap]
+};
+inline LinkTable link_table(uint32_t point_cap, int n_pairs) { return {(unsigned int)n_pairs - 1, (size_t)((unsigned int)n_pairs - 1) * point_cap}; }
+
 // The message of the first failed check - the entry point puts its stage in front ("epipolar: ") -, in the order of vslam_match_dev's
 // (null, struct_size, n_pairs, the parameters, the inputs, the buffers); nullptr: the call is valid.
 inline const char* epipolar_check_args(const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap, const vslam_point* query_points,
@@ -45,16 +68,15 @@ inline const char* epipolar_check_args(const vslam_match* matches, const uint32_
     if (out->struct_size != sizeof(vslam_epipolar_out)) return "out->struct_size is not sizeof(vslam_epipolar_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
     if (prm->n_hypotheses < 1 || prm->n_hypotheses > 65535) return "1 .. 65535 hypotheses";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
     if (const char* why = twoview_check_inputs(matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
-    if (!out->models) return "models is required";
-    if (out->models_bytes / sizeof(vslam_epipolar) < np) return "models buffer too small";
-    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "inlier_bits buffer too small";
+    OUT_NEEDS(out, models, vslam_epipolar, np);
+    OUT_FITS(out, inlier_bits, uint64_t, np * fwords);
     if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "inliers needs inlier_counts and an inlier_cap";
-    if (out->inliers && out->inliers_bytes / sizeof(vslam_match) < np * out->inlier_cap) return "inliers buffer too small";
-    if (out->inlier_counts && out->inlier_counts_bytes / sizeof(uint32_t) < np) return "inlier_counts buffer too small";
-    if (out->hypotheses && out->hypotheses_bytes / sizeof(vslam_epipolar_hyp) < np * prm->n_hypotheses) return "hypotheses buffer too small";
+    OUT_FITS(out, inliers, vslam_match, np * out->inlier_cap);
+    OUT_FITS(out, inlier_counts, uint32_t, np);
+    OUT_FITS(out, hypotheses, vslam_epipolar_hyp, np * prm->n_hypotheses);
     return nullptr;
 }
 

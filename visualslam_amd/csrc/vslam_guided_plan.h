@@ -3,12 +3,9 @@
 // Stated once, here, so that a host program can run it under the sanitizers with extreme capacities
 // (tests/guided_plan_driver.cpp).
 #pragma once
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
 #include <initializer_list>
 
-#include "../../include/vslam.h"
+#include "vslam_epipolar_plan.h"
 
 namespace vslam {
 
@@ -36,7 +33,7 @@ inline const char* guided_check_args(const vslam_desc_sets* Q, const vslam_desc_
     if (prm->reserved != 0) return "params->reserved must be 0";
     if (!std::isfinite(prm->ratio2) || !(prm->ratio2 > 0.0f)) return "ratio2 must be finite and positive";
     if (!(prm->max_desc_dist2 > 0.0f)) return "max_desc_dist2 must be positive (+inf: no bound)";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
     for (const vslam_desc_sets* s : {Q, T}) {
         if (!s->desc || !s->counts || s->cap == 0) return "a descriptor set needs desc, counts and a capacity";
         if ((reinterpret_cast<uintptr_t>(s->desc) & 15) != 0) return "desc must be 16-byte aligned";

@@ -21,7 +21,7 @@ inline const char* homography_check_args(const vslam_match* matches, const uint3
     if (out->struct_size != sizeof(vslam_homography_out)) return "out->struct_size is not sizeof(vslam_homography_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
     if (prm->n_hypotheses < 1 || prm->n_hypotheses > 65535) return "1 .. 65535 hypotheses";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
     if (prm->degenerate_den == 0) return "degenerate_den must be positive";
     if (const char* why = twoview_check_inputs(matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);

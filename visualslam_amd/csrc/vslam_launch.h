@@ -1,5 +1,6 @@
-// What the HIP translation units of the C ABI (vslam_hip.hip, vslam_match.hip, vslam_match_guided.hip, vslam_epipolar.hip, vslam_refit.hip, vslam_homography.hip, vslam_pose.hip, vslam_chain.hip, vslam_resect.hip, vslam_resect_refine.hip, vslam_tracks.hip, vslam_bundle.hip) share to enqueue kernels: the launch macros
-// the timing hook sees, and the context's bump workspace with its per-call plan.
+// What the HIP translation units of the C ABI (every vslam_*.hip but the matrix-core octave kernels' vslam_mx.hip and
+// vslam_mx0.hip) share to enqueue kernels: the launch macros the timing hook sees, the helpers one unit compiles for the
+// others, the context's bump workspace with its per-call plan, and the plumbing of the host-memory entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,17 +52,25 @@ int enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned 
 // for them under its output models): flags [n_pairs][fwords], the words that hold a record below the count.
 int enqueue_epi_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_epipolar* models,
                       double max_dist2, int n_pairs, unsigned long long* flags);
-// The link table of the trajectory's step 1 (k_chain_link, compiled in vslam_chain.hip; vslam_resect_dev links by the same
-// rule): prev [n_pairs - 1][point_cap] is preset to 0xffffffff and row j - 1 gets, per train index, the lowest live record of
-// pair j - 1.  n_pairs >= 2.
-int enqueue_chain_link(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
-                       const uint64_t* front_bits, unsigned int point_cap, int n_pairs, unsigned int* prev);
+// The structure side of the multi-view stages (vslam_chain_dev, vslam_resect_dev, vslam_tracks_dev, vslam_bundle_dev): what
+// vslam_pose_dev read and wrote for n_pairs consecutive pairs, and the capacity of the frames' point lists.
+struct StructLists {
+    const vslam_pose* poses;
+    const vslam_match* matches;
+    const unsigned int* match_counts;
+    unsigned int match_cap;
+    const uint64_t* front_bits;
+    unsigned int point_cap;
+    int n_pairs;
+};
+// The link table of the trajectory's step 1 (k_chain_link, compiled in vslam_chain.hip; vslam_resect_dev, vslam_tracks_dev and
+// vslam_bundle_dev link by the same rule): prev [n_pairs - 1][point_cap] is preset to 0xffffffff and row j - 1 gets, per train
+// index, the lowest live record of pair j - 1.  n_pairs >= 2.
+int enqueue_chain_link(vslam_ctx* c, const StructLists& L, unsigned int* prev);
 // The continuation table of the tracks section's step 2 (k_trk_next, compiled in vslam_tracks.hip; vslam_bundle_dev walks the
 // same paths): next [n_pairs - 1][match_cap] is preset to 0xffffffff and row j - 1 gets, per record of pair j - 1, the lowest
 // candidate of pair j.  prev: the link table above.  n_pairs >= 2.
-int enqueue_trk_next(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
-                     const uint64_t* front_bits, unsigned int point_cap, int n_pairs, const vslam_chain* chain, const unsigned int* prev,
-                     unsigned int* next);
+int enqueue_trk_next(vslam_ctx* c, const StructLists& L, const vslam_chain* chain, const unsigned int* prev, unsigned int* next);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -
@@ -101,8 +110,10 @@ class WsPlan {
 };
 }  // namespace
 
-// What the entry points that work from host memory through per-call device buffers share (vslam_match_host,
-// vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host), and the answer of a device entry point whose caller has no HIP device.
+// What the entry points that work from host memory through per-call device buffers share - DevBufs: every *_host entry point;
+// HostPair: the single-pair ones (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host); HostMirror: the
+// batched ones (vslam_chain_host, vslam_resect_host, vslam_resect_refine_host, vslam_tracks_host, vslam_bundle_host) -, and the
+// answer of a device entry point whose caller has no HIP device.
 namespace {
 // No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
 // after the arguments, before the context is touched.
@@ -135,8 +146,8 @@ struct DevBufs {
     }
 };
 
-// One host pair of the two-view entry points (vslam_epipolar_host, vslam_pose_host): the checks they share, in the ABI's
-// order, and the device copies of the three lists and of the count.
+// One host pair of the two-view entry points (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host):
+// the checks they share, in the ABI's order, and the device copies of the three lists and of the count.
 struct HostPair {
     const vslam_match* matches;
     const vslam_point *query_points, *train_points;
@@ -162,6 +173,52 @@ struct HostPair {
         TRY(dev.put(c, d_cnt, &h_cnt, 1));
         mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
         fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
+        return VSLAM_OK;
+    }
+};
+
+// The device mirror of one batched host-memory call: each input and each output is stated once - the host array, its element
+// count, where its device pointer goes -, and finish() brings the outputs back whole.  The first failure is kept and what is
+// stated after it is skipped: the entry point asks status() once, before the device entry point.  (The single-pair entry
+// points copy back parts of their lists and keep their own code.)
+class HostMirror {
+    struct Back {
+        void* host;
+        const void* dev;
+        size_t bytes;
+    };
+    static constexpr int kMaxOut = 8;  // the most any entry point has is 5 (vslam_resect_host)
+    vslam_ctx* c;
+    DevBufs bufs;
+    Back back[kMaxOut];
+    int n = 0, rc = VSLAM_OK;
+
+  public:
+    explicit HostMirror(vslam_ctx* ctx) : c(ctx) {}
+    // An input goes up; an optional one that is not there stays null.
+    template <typename T>
+    T* in(const T* host, size_t count) {
+        T* d = nullptr;
+        if (host && !rc) rc = bufs.put(c, d, host, count);
+        return d;
+    }
+    // An output the caller gave (the others are skipped): d gets `count` elements on the device and bytes their size.  keep: the
+    // caller's bytes go up first, so that the rows the call leaves untouched come back as they were; otherwise the call writes
+    // every element.  A d that is set already is the buffer (in place over an input).
+    template <typename T>
+    void out(T*& d, size_t& bytes, T* host, size_t count, bool keep) {
+        if (!host || rc) return;
+        if (n == kMaxOut) rc = fail(c, VSLAM_ERR_NOMEM, "host mirror: more outputs than HostMirror::kMaxOut");
+        else if (!d) rc = keep ? bufs.put(c, d, static_cast<const T*>(host), count) : bufs.get(c, d, count);
+        if (rc) return;
+        bytes = count * sizeof(T);
+        back[n++] = Back{host, d, bytes};
+    }
+    int status() const { return rc; }
+    // After the device entry point: the outputs come back in the order they were stated, and the call waits for them.
+    int finish() {
+        for (int i = 0; i < n; ++i) HIPCHK(c, hipMemcpyAsync(back[i].host, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         return VSLAM_OK;
     }
 };

@@ -47,8 +47,7 @@ int vslam_pose_host(vslam_ctx* c, const vslam_epipolar* model, const vslam_match
                     size_t n_query, const vslam_point* train_points, size_t n_train, const vslam_pose_params* prm, vslam_pose* pose,
                     vslam_pose_cand* candidates, double* points, uint64_t* front_bits) {
     ARGCHK(c, prm && model && pose, "pose_host: null argument");
-    ARGCHK(c, std::isfinite(prm->fx) && std::isfinite(prm->fy) && std::isfinite(prm->cx) && std::isfinite(prm->cy), "pose_host: the intrinsics must be finite");
-    ARGCHK(c, prm->fx > 0.0 && prm->fy > 0.0, "pose_host: fx and fy must be positive");
+    if (const char* why = check_intrinsics(*prm)) return fail(c, VSLAM_ERR_INVALID, std::string("pose_host: ") + why);
     HostPair in{matches, query_points, train_points, n_matches, n_query, n_train};
     TRY(in.check(c, "pose_host"));
     TRY(usable_ctx(c));

@@ -17,17 +17,14 @@ inline const char* pose_check_args(const vslam_epipolar* models, const vslam_mat
     if (!prm || !out) return "null argument";
     if (out->struct_size != sizeof(vslam_pose_out)) return "out->struct_size is not sizeof(vslam_pose_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
-    if (!std::isfinite(prm->fx) || !std::isfinite(prm->fy) || !std::isfinite(prm->cx) || !std::isfinite(prm->cy))
-        return "the intrinsics must be finite";
-    if (!(prm->fx > 0.0) || !(prm->fy > 0.0)) return "fx and fy must be positive";
+    if (const char* why = check_intrinsics(*prm)) return why;
     if (const char* why = twoview_check_inputs(models && matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
-    if (!out->poses) return "poses is required";
-    if (out->poses_bytes / sizeof(vslam_pose) < np) return "poses buffer too small";
-    if (out->candidates && out->candidates_bytes / (4 * sizeof(vslam_pose_cand)) < np) return "candidates buffer too small";
+    OUT_NEEDS(out, poses, vslam_pose, np);
+    OUT_FITS(out, candidates, vslam_pose_cand[4], np);
     // np * match_cap < 2^48: the element count cannot wrap, and the byte count is compared by division
-    if (out->points && out->points_bytes / (3 * sizeof(double)) < np * match_cap) return "points buffer too small";
-    if (out->front_bits && out->front_bits_bytes / sizeof(uint64_t) < np * fwords) return "front_bits buffer too small";
+    OUT_FITS(out, points, double[3], np * match_cap);
+    OUT_FITS(out, front_bits, uint64_t, np * fwords);
     return nullptr;
 }
 

@@ -34,7 +34,7 @@ inline const char* refit_check_args(const vslam_epipolar* models_in, const vslam
     if (out->struct_size != sizeof(vslam_refit_out)) return "out->struct_size is not sizeof(vslam_refit_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
     if (prm->rounds < 1 || prm->rounds > 8) return "1 .. 8 rounds";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
     if (const char* why = twoview_check_inputs(models_in && matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
     if (!out->models) return "models is required";

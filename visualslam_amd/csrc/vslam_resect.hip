@@ -51,7 +51,7 @@ int vslam_resect_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* m
 
     const ResIn in{poses, points, match_cap, point_cap, obs_matches, obs_counts, obs_cap, train_points, train_cap, prm->K};
     const dim3 records(pl.rec_blocks, n_pairs);
-    if (pl.link_pairs) TRY(enqueue_chain_link(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, prev));
+    if (pl.link_pairs) TRY(enqueue_chain_link(c, StructLists{poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs}, prev));
     LAUNCH(c, "k_res_corr", k_res_corr, records, dim3(TWOVIEW_REC_WG), in, prev, idx, uflags, pl.fwords, out->links);
     TRY(enqueue_inlier_list(c, uflags, pl.fwords, idx, obs_counts, obs_cap, n_pairs, chunk_ws, didx, obs_cap, ncorr));
     LAUNCH(c, "k_res_gather", k_res_gather, records, dim3(TWOVIEW_REC_WG), in, didx, ncorr, corr);
@@ -77,52 +77,26 @@ int vslam_resect_host(vslam_ctx* c, const vslam_pose* poses, const vslam_match* 
 
     const size_t np = (size_t)n_pairs, recs = np * match_cap, words = np * twoview_fwords(match_cap);
     const size_t orecs = np * obs_cap, owords = np * twoview_fwords(obs_cap), hyps = np * prm->n_hypotheses;
-    DevBufs dev;
-    vslam_pose* d_poses = nullptr;
-    vslam_match *d_matches = nullptr, *d_obs = nullptr;
-    uint32_t *d_counts = nullptr, *d_ocounts = nullptr;
-    double* d_points = nullptr;
-    uint64_t* d_bits = nullptr;
-    vslam_point* d_train = nullptr;
-    TRY(dev.put(c, d_poses, poses, np));
-    TRY(dev.put(c, d_matches, matches, recs));
-    TRY(dev.put(c, d_counts, match_counts, np));
-    TRY(dev.put(c, d_points, points, recs * 3));
-    TRY(dev.put(c, d_bits, front_bits, words));
-    TRY(dev.put(c, d_obs, obs_matches, orecs));
-    TRY(dev.put(c, d_ocounts, obs_counts, np));
-    TRY(dev.put(c, d_train, train_points, np * train_cap));
-    // the optional outputs go up first: the rows the call leaves untouched come back as the caller had them
+    HostMirror m(c);
+    const auto d_poses = m.in(poses, np);
+    const auto d_matches = m.in(matches, recs);
+    const auto d_counts = m.in(match_counts, np);
+    const auto d_points = m.in(points, recs * 3);
+    const auto d_bits = m.in(front_bits, words);
+    const auto d_obs = m.in(obs_matches, orecs);
+    const auto d_ocounts = m.in(obs_counts, np);
+    const auto d_train = m.in(train_points, np * train_cap);
     vslam_resect_out d{};
     d.struct_size = sizeof(d);
-    TRY(dev.get(c, d.models, np));
-    d.models_bytes = np * sizeof(vslam_resect);
-    if (out->inlier_bits) {
-        TRY(dev.put(c, d.inlier_bits, static_cast<const uint64_t*>(out->inlier_bits), owords));
-        d.inlier_bits_bytes = owords * sizeof(uint64_t);
-    }
-    if (out->hypotheses) {
-        TRY(dev.get(c, d.hypotheses, hyps));
-        d.hypotheses_bytes = hyps * sizeof(vslam_resect_hyp);
-    }
-    if (out->correspondences) {
-        TRY(dev.put(c, d.correspondences, static_cast<const vslam_resect_corr*>(out->correspondences), orecs));
-        d.correspondences_bytes = orecs * sizeof(vslam_resect_corr);
-    }
-    if (out->links) {
-        TRY(dev.put(c, d.links, static_cast<const int32_t*>(out->links), orecs));
-        d.links_bytes = orecs * sizeof(int32_t);
-    }
+    m.out(d.models, d.models_bytes, out->models, np, false);
+    m.out(d.inlier_bits, d.inlier_bits_bytes, out->inlier_bits, owords, true);
+    m.out(d.hypotheses, d.hypotheses_bytes, out->hypotheses, hyps, false);
+    m.out(d.correspondences, d.correspondences_bytes, out->correspondences, orecs, true);
+    m.out(d.links, d.links_bytes, out->links, orecs, true);
+    TRY(m.status());
     TRY(vslam_resect_dev(c, d_poses, d_matches, d_counts, match_cap, d_points, d_bits, point_cap, d_obs, d_ocounts, obs_cap, d_train, train_cap, n_pairs,
                          prm, &d));
-    HIPCHK(c, hipMemcpyAsync(out->models, d.models, np * sizeof(vslam_resect), hipMemcpyDeviceToHost, c->stream));
-    if (out->inlier_bits) HIPCHK(c, hipMemcpyAsync(out->inlier_bits, d.inlier_bits, d.inlier_bits_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->hypotheses) HIPCHK(c, hipMemcpyAsync(out->hypotheses, d.hypotheses, d.hypotheses_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->correspondences)
-        HIPCHK(c, hipMemcpyAsync(out->correspondences, d.correspondences, d.correspondences_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->links) HIPCHK(c, hipMemcpyAsync(out->links, d.links, d.links_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return m.finish();
 }
 
 }  // extern "C"

@@ -24,19 +24,17 @@ inline const char* resect_check_args(const vslam_pose* poses, const vslam_match*
     if (out->struct_size != sizeof(vslam_resect_out)) return "out->struct_size is not sizeof(vslam_resect_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
     if (prm->n_hypotheses < 1 || prm->n_hypotheses > 65535) return "1 .. 65535 hypotheses";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
-    if (!std::isfinite(prm->K.fx) || !std::isfinite(prm->K.fy) || !std::isfinite(prm->K.cx) || !std::isfinite(prm->K.cy)) return "an intrinsic is not finite";
-    if (!(prm->K.fx > 0.0) || !(prm->K.fy > 0.0)) return "fx and fy must be positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
+    if (const char* why = check_intrinsics(prm->K, "an intrinsic is not finite")) return why;
     if (const char* why = twoview_check_inputs(poses && matches && match_counts && points && front_bits, match_cap, point_cap, point_cap)) return why;
     if (const char* why = twoview_check_inputs(obs_matches && obs_counts && train_points, obs_cap, train_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(obs_cap);
-    if (!out->models) return "models is required";
-    if (out->models_bytes / sizeof(vslam_resect) < np) return "models buffer too small";
+    OUT_NEEDS(out, models, vslam_resect, np);
     // np * obs_cap < 2^48 and np * n_hypotheses < 2^32: no element count wraps, and the byte counts are compared by division
-    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "inlier_bits buffer too small";
-    if (out->hypotheses && out->hypotheses_bytes / sizeof(vslam_resect_hyp) < np * prm->n_hypotheses) return "hypotheses buffer too small";
-    if (out->correspondences && out->correspondences_bytes / sizeof(vslam_resect_corr) < np * obs_cap) return "correspondences buffer too small";
-    if (out->links && out->links_bytes / sizeof(int32_t) < np * obs_cap) return "links buffer too small";
+    OUT_FITS(out, inlier_bits, uint64_t, np * fwords);
+    OUT_FITS(out, hypotheses, vslam_resect_hyp, np * prm->n_hypotheses);
+    OUT_FITS(out, correspondences, vslam_resect_corr, np * obs_cap);
+    OUT_FITS(out, links, int32_t, np * obs_cap);
     return nullptr;
 }
 
@@ -58,8 +56,8 @@ inline ResectPlan resect_plan(uint32_t match_cap, uint32_t point_cap, uint32_t o
     static_cast<EpipolarPlan&>(p) = epipolar_plan(obs_cap, n_pairs, n_hypotheses);
     const TwoViewPlan st = twoview_plan(match_cap, n_pairs);
     p.struct_rec_blocks = st.rec_blocks, p.struct_fwords = st.fwords;
-    p.link_pairs = (unsigned int)n_pairs - 1;
-    p.table_elems = (size_t)p.link_pairs * point_cap;
+    const LinkTable lt = link_table(point_cap, n_pairs);
+    p.link_pairs = lt.link_pairs, p.table_elems = lt.elems;
     p.rec_elems = (size_t)n_pairs * obs_cap;
     p.pair_elems = (size_t)n_pairs;
     return p;

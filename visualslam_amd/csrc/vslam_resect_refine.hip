@@ -57,29 +57,18 @@ int vslam_resect_refine_host(vslam_ctx* c, const vslam_resect* models_in, const 
     if (n_pairs == 0) return VSLAM_OK;
 
     const size_t np = (size_t)n_pairs, rows = np * obs_cap, words = np * twoview_fwords(obs_cap);
-    DevBufs dev;
-    vslam_resect* d_models = nullptr;
-    vslam_resect_corr* d_corr = nullptr;
-    TRY(dev.put(c, d_models, models_in, np));
-    TRY(dev.put(c, d_corr, corr, rows));
+    HostMirror m(c);
+    const auto d_models = m.in(models_in, np);
+    const auto d_corr = m.in(corr, rows);
     vslam_resect_refine_out d{};
     d.struct_size = sizeof(d);
     d.models = d_models;  // in place: the ABI allows the very pointer
-    d.models_bytes = np * sizeof(vslam_resect);
-    if (out->info) {
-        TRY(dev.get(c, d.info, np));
-        d.info_bytes = np * sizeof(vslam_resect_refine);
-    }
-    if (out->inlier_bits) {  // goes up first: the words the call leaves untouched come back as the caller had them
-        TRY(dev.put(c, d.inlier_bits, static_cast<const uint64_t*>(out->inlier_bits), words));
-        d.inlier_bits_bytes = words * sizeof(uint64_t);
-    }
+    m.out(d.models, d.models_bytes, out->models, np, false);
+    m.out(d.info, d.info_bytes, out->info, np, false);
+    m.out(d.inlier_bits, d.inlier_bits_bytes, out->inlier_bits, words, true);
+    TRY(m.status());
     TRY(vslam_resect_refine_dev(c, d_models, d_corr, obs_cap, n_pairs, prm, &d));
-    HIPCHK(c, hipMemcpyAsync(out->models, d.models, np * sizeof(vslam_resect), hipMemcpyDeviceToHost, c->stream));
-    if (out->info) HIPCHK(c, hipMemcpyAsync(out->info, d.info, d.info_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->inlier_bits) HIPCHK(c, hipMemcpyAsync(out->inlier_bits, d.inlier_bits, d.inlier_bits_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return m.finish();
 }
 
 }  // extern "C"

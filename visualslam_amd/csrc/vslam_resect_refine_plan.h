@@ -31,17 +31,15 @@ inline const char* resect_refine_check_args(const vslam_resect* models_in, const
     if (out->struct_size != sizeof(vslam_resect_refine_out)) return "out->struct_size is not sizeof(vslam_resect_refine_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
     if (prm->rounds < 1 || prm->rounds > 8) return "1 .. 8 rounds";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
-    if (!std::isfinite(prm->K.fx) || !std::isfinite(prm->K.fy) || !std::isfinite(prm->K.cx) || !std::isfinite(prm->K.cy)) return "an intrinsic is not finite";
-    if (!(prm->K.fx > 0.0) || !(prm->K.fy > 0.0)) return "fx and fy must be positive";
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
+    if (const char* why = check_intrinsics(prm->K, "an intrinsic is not finite")) return why;
     if (const char* why = twoview_check_inputs(models_in && corr, obs_cap, 1, 1)) return why;
     if (aligned && (reinterpret_cast<uintptr_t>(corr) & 15u)) return "correspondences must be 16-byte aligned";
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(obs_cap);
-    if (!out->models) return "models is required";
-    if (out->models_bytes / sizeof(vslam_resect) < np) return "models buffer too small";
-    if (out->info && out->info_bytes / sizeof(vslam_resect_refine) < np) return "info buffer too small";
+    OUT_NEEDS(out, models, vslam_resect, np);
+    OUT_FITS(out, info, vslam_resect_refine, np);
     // np * fwords < 2^42: no element count wraps, and the byte counts are compared by division
-    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "inlier_bits buffer too small";
+    OUT_FITS(out, inlier_bits, uint64_t, np * fwords);
     const uintptr_t a = reinterpret_cast<uintptr_t>(models_in), b = reinterpret_cast<uintptr_t>(out->models), span = np * sizeof(vslam_resect);
     if (a != b && (a < b ? b - a : a - b) < span) return "models overlaps models_in without being equal to it";
     return nullptr;

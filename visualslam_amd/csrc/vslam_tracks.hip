@@ -14,11 +14,10 @@
 
 using namespace vslam;
 
-int vslam::enqueue_trk_next(vslam_ctx* c, const vslam_pose* poses, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap,
-                            const uint64_t* front_bits, unsigned int point_cap, int n_pairs, const vslam_chain* chain, const unsigned int* prev,
-                            unsigned int* next) {
-    const TracksPlan pl = tracks_plan(match_cap, point_cap, n_pairs);
-    const TrkIn in{poses, matches, match_counts, reinterpret_cast<const unsigned long long*>(front_bits), chain, nullptr, match_cap, pl.fwords, point_cap, n_pairs};
+int vslam::enqueue_trk_next(vslam_ctx* c, const StructLists& L, const vslam_chain* chain, const unsigned int* prev, unsigned int* next) {
+    const TracksPlan pl = tracks_plan(L.match_cap, L.point_cap, L.n_pairs);
+    const TrkIn in{L.poses,     L.matches, L.match_counts, reinterpret_cast<const unsigned long long*>(L.front_bits), chain, nullptr, L.match_cap,
+                   pl.fwords, L.point_cap, L.n_pairs};
     HIPCHK(c, hipMemsetAsync(next, 0xff, pl.next_elems * sizeof(unsigned int), c->stream));
     LAUNCH(c, "k_trk_next", k_trk_next, dim3(pl.rec_blocks, pl.link_pairs), dim3(TRK_REC_WG), in, prev, next);
     return VSLAM_OK;
@@ -48,8 +47,9 @@ int vslam_tracks_dev(vslam_ctx* c, const vslam_pose* poses, const vslam_match* m
     const dim3 records(pl.rec_blocks, n_pairs);
     if (out->summary) HIPCHK(c, hipMemsetAsync(out->summary, 0, (size_t)n_pairs * sizeof(vslam_track_summary), c->stream));
     if (pl.link_pairs) {
-        TRY(enqueue_chain_link(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, prev));
-        TRY(enqueue_trk_next(c, poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs, chain, prev, next));
+        const StructLists L{poses, matches, match_counts, match_cap, front_bits, point_cap, n_pairs};
+        TRY(enqueue_chain_link(c, L, prev));
+        TRY(enqueue_trk_next(c, L, chain, prev, next));
     }
     LAUNCH(c, "k_trk_walk", k_trk_walk, records, dim3(TRK_REC_WG), in, *prm, prev, next, out->tracks, out->refs, out->summary);
     LAUNCH(c, "k_trk_rows", k_trk_rows, records, dim3(TRK_REC_WG), in, prev, next, out->tracks, out->refs,
@@ -66,43 +66,22 @@ int vslam_tracks_host(vslam_ctx* c, const vslam_pose* poses, const vslam_match* 
     if (n_pairs == 0) return VSLAM_OK;
 
     const size_t np = (size_t)n_pairs, recs = np * match_cap, words = np * twoview_fwords(match_cap);
-    DevBufs dev;
-    vslam_pose* d_poses = nullptr;
-    vslam_match* d_matches = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bits = nullptr;
-    vslam_chain* d_chain = nullptr;
-    vslam_point* d_frames = nullptr;
-    TRY(dev.put(c, d_poses, poses, np));
-    TRY(dev.put(c, d_matches, matches, recs));
-    TRY(dev.put(c, d_counts, match_counts, np));
-    TRY(dev.put(c, d_bits, front_bits, words));
-    TRY(dev.put(c, d_chain, chain, np));
-    TRY(dev.put(c, d_frames, frame_points, (np + 1) * point_cap));
-    // the outputs go up first: the rows the call leaves untouched come back as the caller had them
+    HostMirror m(c);
+    const auto d_poses = m.in(poses, np);
+    const auto d_matches = m.in(matches, recs);
+    const auto d_counts = m.in(match_counts, np);
+    const auto d_bits = m.in(front_bits, words);
+    const auto d_chain = m.in(chain, np);
+    const auto d_frames = m.in(frame_points, (np + 1) * point_cap);
     vslam_tracks_out d{};
     d.struct_size = sizeof(d);
-    TRY(dev.put(c, d.tracks, static_cast<const vslam_track*>(out->tracks), recs));
-    d.tracks_bytes = recs * sizeof(vslam_track);
-    if (out->refs) {
-        TRY(dev.put(c, d.refs, static_cast<const vslam_track_ref*>(out->refs), recs));
-        d.refs_bytes = recs * sizeof(vslam_track_ref);
-    }
-    if (out->good_bits) {
-        TRY(dev.put(c, d.good_bits, static_cast<const uint64_t*>(out->good_bits), words));
-        d.good_bits_bytes = words * sizeof(uint64_t);
-    }
-    if (out->summary) {
-        TRY(dev.get(c, d.summary, np));
-        d.summary_bytes = np * sizeof(vslam_track_summary);
-    }
+    m.out(d.tracks, d.tracks_bytes, out->tracks, recs, true);
+    m.out(d.refs, d.refs_bytes, out->refs, recs, true);
+    m.out(d.good_bits, d.good_bits_bytes, out->good_bits, words, true);
+    m.out(d.summary, d.summary_bytes, out->summary, np, false);
+    TRY(m.status());
     TRY(vslam_tracks_dev(c, d_poses, d_matches, d_counts, match_cap, d_bits, point_cap, n_pairs, d_chain, d_frames, prm, &d));
-    HIPCHK(c, hipMemcpyAsync(out->tracks, d.tracks, recs * sizeof(vslam_track), hipMemcpyDeviceToHost, c->stream));
-    if (out->refs) HIPCHK(c, hipMemcpyAsync(out->refs, d.refs, recs * sizeof(vslam_track_ref), hipMemcpyDeviceToHost, c->stream));
-    if (out->good_bits) HIPCHK(c, hipMemcpyAsync(out->good_bits, d.good_bits, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (out->summary) HIPCHK(c, hipMemcpyAsync(out->summary, d.summary, np * sizeof(vslam_track_summary), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return m.finish();
 }
 
 }  // extern "C"

@@ -16,20 +16,17 @@ inline const char* tracks_check_args(const vslam_pose* poses, const vslam_match*
     if (!prm || !out) return "null argument";
     if (out->struct_size != sizeof(vslam_tracks_out)) return "out->struct_size is not sizeof(vslam_tracks_out)";
     if (const char* why = twoview_check_pairs(n_pairs)) return why;
-    if (!std::isfinite(prm->K.fx) || !std::isfinite(prm->K.fy) || !std::isfinite(prm->K.cx) || !std::isfinite(prm->K.cy))
-        return "the intrinsics must be finite";
-    if (!(prm->K.fx > 0.0) || !(prm->K.fy > 0.0)) return "fx and fy must be positive";
-    if (!std::isfinite(prm->max_dist2) || !(prm->max_dist2 > 0.0)) return "max_dist2 must be finite and positive";
+    if (const char* why = check_intrinsics(prm->K)) return why;
+    if (const char* why = check_max_dist2(prm->max_dist2)) return why;
     if (prm->min_views < 2) return "min_views must be at least 2";
     if (const char* why = twoview_check_inputs(poses && matches && match_counts && front_bits && chain && frame_points, match_cap, point_cap, point_cap))
         return why;
     const size_t np = (size_t)n_pairs;
-    if (!out->tracks) return "tracks is required";
     // np * match_cap < 2^48: the element count cannot wrap, and the byte count is compared by division
-    if (out->tracks_bytes / sizeof(vslam_track) < np * match_cap) return "tracks buffer too small";
-    if (out->refs && out->refs_bytes / sizeof(vslam_track_ref) < np * match_cap) return "refs buffer too small";
-    if (out->good_bits && out->good_bits_bytes / sizeof(uint64_t) < np * twoview_fwords(match_cap)) return "good_bits buffer too small";
-    if (out->summary && out->summary_bytes / sizeof(vslam_track_summary) < np) return "summary buffer too small";
+    OUT_NEEDS(out, tracks, vslam_track, np * match_cap);
+    OUT_FITS(out, refs, vslam_track_ref, np * match_cap);
+    OUT_FITS(out, good_bits, uint64_t, np * twoview_fwords(match_cap));
+    OUT_FITS(out, summary, vslam_track_summary, np);
     return nullptr;
 }
 
@@ -48,8 +45,8 @@ inline TracksPlan tracks_plan(uint32_t match_cap, uint32_t point_cap, int n_pair
     const TwoViewPlan tv = twoview_plan(match_cap, n_pairs);
     TracksPlan p{};
     p.fwords = tv.fwords, p.rec_blocks = tv.rec_blocks;
-    p.link_pairs = (unsigned int)n_pairs - 1;
-    p.prev_elems = (size_t)p.link_pairs * point_cap;
+    const LinkTable lt = link_table(point_cap, n_pairs);
+    p.link_pairs = lt.link_pairs, p.prev_elems = lt.elems;
     p.next_elems = (size_t)p.link_pairs * match_cap;
     p.frame_elems = ((size_t)n_pairs + 1) * point_cap;
     return p;
