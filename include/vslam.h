@@ -952,6 +952,65 @@ int vslam_homography_host(vslam_ctx* ctx, const vslam_match* matches, size_t n_m
                           vslam_match* inliers, size_t inlier_cap, size_t* n_inliers, vslam_homography_hyp* hypotheses,
                           vslam_epipolar* gated_model);
 
+/* ---------------------------------------------------------------- guided matching under H or F
+ * The guided pass for every pair of a batch, under the model that applies to it.  A pair the gate above judged degenerate - a
+ * planar scene, a pure rotation, a pure image translation - carries the "no model" record, and vslam_match_guided_dev finds
+ * nothing for it; but for such a pair H predicts a position, not a line, and a window around H x is a far narrower search than
+ * the epipolar band.  Everything that is not named here is the guided matching section's, unchanged: d2, the sequential
+ * nearest-two selection, ties, NaN and +-inf, "trusted", the coordinates, the acceptance rule with ratio2 and max_desc_dist2,
+ * and vslam_match_out with its ordering.  The arithmetic is fixed here so that a CPU can restate it bit for bit
+ * (tests/guidedhfref.py).
+ *
+ * KIND of pair p, read on the device:  F iff epipolar_models != NULL and epipolar_models[p].best >= 0;  otherwise H iff
+ * homography_models != NULL and homography_models[p].best >= 0;  otherwise NONE: every query row gets {-1, +inf, +inf} and
+ * the count is 0.  At least one of the two arrays must be given.  With the gate's gated_models as epipolar_models, H applies
+ * to the degenerate pairs and to the pairs RANSAC gave no F; with epipolar_models = NULL, H applies to every pair; with
+ * homography_models = NULL, the call is vslam_match_guided_dev.
+ *
+ * Kind F.  Train row j is a candidate of query row i iff it is IN BAND: the guided matching section's predicate under
+ * params.max_dist2, operation for operation.
+ *
+ * Kind H.  Train row j is a candidate iff it is IN WINDOW.  With (x, y) the query row's point, (x', y') the train row's and
+ * H = homography_models[p].H:
+ *   p_k = (H[k][0]*x + H[k][1]*y) + H[k][2]  for k = 0, 1, 2;   L = max_transfer2 * (p2*p2);
+ *   dx = p0 - x'*p2;   dy = p1 - y'*p2;
+ *   in window iff both rows are trusted, p2 > 0 and dx*dx + dy*dy < L.
+ * IEEE f64, every operation rounded on its own, no fused multiply-add.  A false comparison (a NaN, overflow to inf on both
+ * sides, H = 0) is "not in window".  This is the FORWARD clause of the homography section's inlier test, word for word; G is
+ * not read.  Forward only: it is what "predicted position" means, and the symmetric form changed at most 2 matches per scene
+ * on the planted scenes of the tests.  Whoever wants the symmetric test gets it from vslam_homography_dev on the guided list.
+ *
+ * The selection skips a train row that is not a candidate, exactly where the guided matching section skips one that is not
+ * in band; second_dist2 is the second nearest AMONG THE CANDIDATES.  Results depend neither on vslam_ctx_set_f32_fused nor on
+ * vslam_ctx_set_matrix_path. */
+typedef struct {
+    float ratio2;         /* the SQUARED ratio of Lowe's test, finite and positive */
+    float max_desc_dist2; /* accepted only below this d2; positive, +inf = no bound */
+    double max_dist2;     /* kind F: half-width of the band, squared Sampson distance in pixels^2; finite and positive - checked
+                           * only when epipolar_models is given */
+    double max_transfer2; /* kind H: radius^2 of the window, squared transfer error in pixels^2; finite and positive - checked
+                           * only when homography_models is given */
+    int32_t same_octave;  /* as vslam_match_dev */
+    uint32_t reserved;    /* must be 0 */
+} vslam_guided_hf_params; /* 32 bytes */
+/* Pair j searches set j of `train` for every row of set j of `query` under epipolar_models[j] or homography_models[j] (DEVICE
+ * pointers, either array may be NULL), j < n_pairs (at most 65535; 0 does nothing).  Asynchronous on the context stream, never
+ * waits on the host (the counts, the models and with them every pair's kind are read on the device); scratch belongs to the
+ * context and is sized from the capacities before the launches.  VSLAM_ERR_INVALID before any launch - and before the context
+ * is looked at - for everything vslam_match_guided_dev rejects (max_dist2 only with epipolar_models), both model arrays NULL,
+ * and with homography_models a max_transfer2 that is not finite or not positive; then VSLAM_ERR_HIP as for vslam_match_dev.
+ * Not for stream capture. */
+int vslam_match_guided_hf_dev(vslam_ctx* ctx, const vslam_desc_sets* query, const vslam_desc_sets* train,
+                              const vslam_epipolar* epipolar_models, const vslam_homography* homography_models, int n_pairs,
+                              const vslam_guided_hf_params* params, const vslam_match_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call): the arguments of vslam_match_guided_host
+ * with two model records, each optional, not both NULL.  Errors as for vslam_match_guided_hf_dev. */
+int vslam_match_guided_hf_host(vslam_ctx* ctx, const float* query, const uint8_t* query_defined, const vslam_point* query_points, size_t nq,
+                               const float* train, const uint8_t* train_defined, const vslam_point* train_points, size_t nt,
+                               const vslam_epipolar* epipolar_model, const vslam_homography* homography_model,
+                               const vslam_guided_hf_params* params, vslam_nn2* nn, vslam_match* matches, size_t match_cap,
+                               size_t* n_matches);
+
 /* ---------------------------------------------------------------- relative pose and triangulation
  * The step after the fundamental matrix: the camera motion of every pair and the 3-D point of every match record, from the
  * `models` buffer vslam_epipolar_dev wrote (only F and best are read), a match list (any list; the intended one is the

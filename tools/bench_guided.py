@@ -58,8 +58,8 @@ def timed(fn, runs):
     return statistics.median(ms)
 
 
-def kernel_ms(ctx, name, fn, runs):
-    """Median time of the launches of kernel `name` over `runs` calls of fn (one launch per call)."""
+def kernel_ms(ctx, name, fn, runs, launches=1):
+    """Median time of the launches of kernel `name` over `runs` calls of fn (`launches` per call, summed)."""
     for _ in range(2):
         fn()
     ms = []
@@ -67,7 +67,7 @@ def kernel_ms(ctx, name, fn, runs):
     for _ in range(runs):
         fn()
         n, total = ctx.kernel_timing_read()
-        assert n == 1, (name, n)
+        assert n == launches, (name, n)
         ms.append(total)
     ctx.kernel_timing_enable(None)
     return statistics.median(ms)

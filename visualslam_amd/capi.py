@@ -38,6 +38,8 @@ HOMOGRAPHY_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("n_matches
                              ("n_epipolar", "<u4"), ("degenerate", "<i4")], align=True)  # vslam_homography, 168 bytes
 GUIDED_PARAMS_DTYPE = np.dtype([("ratio2", "<f4"), ("max_desc_dist2", "<f4"), ("max_dist2", "<f8"), ("same_octave", "<i4"), ("reserved", "<u4")],
                                align=True)  # vslam_guided_params, 24 bytes
+GUIDED_HF_PARAMS_DTYPE = np.dtype([("ratio2", "<f4"), ("max_desc_dist2", "<f4"), ("max_dist2", "<f8"), ("max_transfer2", "<f8"), ("same_octave", "<i4"),
+                                   ("reserved", "<u4")], align=True)  # vslam_guided_hf_params, 32 bytes
 REFIT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4")], align=True)  # vslam_refit, 16 bytes
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
@@ -143,6 +145,11 @@ class EpipolarOut(C.Structure):
 
 class GuidedParams(C.Structure):
     _fields_ = [("ratio2", C.c_float), ("max_desc_dist2", C.c_float), ("max_dist2", C.c_double), ("same_octave", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class GuidedHfParams(C.Structure):
+    _fields_ = [("ratio2", C.c_float), ("max_desc_dist2", C.c_float), ("max_dist2", C.c_double), ("max_transfer2", C.c_double), ("same_octave", C.c_int32),
+                ("reserved", C.c_uint32)]
 
 
 class RefitParams(C.Structure):
@@ -363,6 +370,8 @@ SIGNATURES = {
     "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_match_guided_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _P, _I, C.POINTER(GuidedParams), C.POINTER(MatchOut)]),
     "vslam_match_guided_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, C.POINTER(GuidedParams), _P, _P, _Z, C.POINTER(_Z)]),
+    "vslam_match_guided_hf_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _P, _P, _I, C.POINTER(GuidedHfParams), C.POINTER(MatchOut)]),
+    "vslam_match_guided_hf_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, _P, C.POINTER(GuidedHfParams), _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_epipolar_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(EpipolarParams), C.POINTER(EpipolarOut)]),
     "vslam_epipolar_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(EpipolarParams), _P, _P, _P, _Z, C.POINTER(_Z), _P]),
     "vslam_refit_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(RefitParams), C.POINTER(RefitOut)]),
@@ -1035,6 +1044,57 @@ class Context:
         prm = GuidedParams(float(ratio2), float(max_desc_dist2), float(max_dist2), int(bool(same_octave)), 0)
         self._chk(lib().vslam_match_guided_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), mod.ctypes.data,
                                                 C.byref(prm), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_guided_host")
+        return nn, matches[: min(total.value, cap)], total.value
+
+    def match_guided_hf(self, query: DescSets, train: DescSets, epipolar_models=None, homography_models=None, n_pairs: int | None = None,
+                        ratio2: float = 0.64, max_desc_dist2: float = float("inf"), max_dist2: float = 4.0, max_transfer2: float = 4.0,
+                        same_octave: bool = False, nn=None, matches=None, match_counts=None):
+        """vslam_match_guided_hf_dev: match_guided() for every pair under the model that applies to it - the epipolar band where
+        epipolar_models[j] has an F, a window of max_transfer2 (SQUARED pixels) around H x where only homography_models[j] has an H,
+        nothing where neither has; asynchronous on the context stream.  epipolar_models: as match_guided()'s models (n_pairs * 88
+        bytes; the intended one is homography()'s gate), homography_models: the CUDA tensor homography() wrote (n_pairs * 168 bytes);
+        either may be None, not both.  Outputs as match()'s."""
+        n = min(query.n, train.n) if n_pairs is None else int(n_pairs)
+        stage = "match_guided_hf"
+        if epipolar_models is None and homography_models is None:
+            raise ValueError(f"{stage}: epipolar_models and homography_models are both None")
+        outs = dict(nn=nn, matches=matches, match_counts=match_counts)
+        _check_tensors(stage, self.where, dict(outs, epipolar_models=epipolar_models, homography_models=homography_models), ())
+        for name, t in outs.items():
+            if t is not None and t.element_size() != 4:
+                raise ValueError(f"{stage}: {name} must have 4-byte elements")
+        _check_sets(stage, n, (), (), ((epipolar_models, n * 88), (homography_models, n * 168)))
+        mo = _fill_out(MatchOut(), outs)
+        if matches is not None:
+            mo.match_cap = matches.shape[1]
+        prm = GuidedHfParams(float(ratio2), float(max_desc_dist2), float(max_dist2), float(max_transfer2), int(bool(same_octave)), 0)
+        at = lambda t: None if t is None else t.data_ptr()
+        self._chk(lib().vslam_match_guided_hf_dev(self._h, C.byref(query), C.byref(train), at(epipolar_models), at(homography_models), n, C.byref(prm),
+                                                  C.byref(mo)), "vslam_match_guided_hf_dev")
+
+    def match_guided_hf_host(self, q, t, q_points, t_points, epipolar_model=None, homography_model=None, ratio2: float = 0.64,
+                             max_desc_dist2: float = float("inf"), max_dist2: float = 4.0, max_transfer2: float = 4.0, same_octave: bool = False,
+                             q_defined=None, t_defined=None, match_cap: int | None = None):
+        """vslam_match_guided_hf_host: one pair of numpy arrays (descriptors [n, 128], POINT_DTYPE points, one EPIPOLAR_DTYPE and / or
+        one HOMOGRAPHY_DTYPE record) -> (nn [nq] NN2_DTYPE, matches MATCH_DTYPE, total accepted)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 128)
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in
+               ((q_defined, np.uint8), (q_points, POINT_DTYPE), (t_defined, np.uint8), (t_points, POINT_DTYPE))]
+        for a, rows in zip(opt, (len(q), len(q), len(t), len(t))):
+            if a is not None and a.size != rows:
+                raise ValueError("match_guided_hf_host: defined / points must have one entry per descriptor row")
+        ptr = [_ptr(a) for a in opt]
+        emod = None if epipolar_model is None else _records(epipolar_model, EPIPOLAR_DTYPE)[:1]
+        hmod = None if homography_model is None else _records(homography_model, HOMOGRAPHY_DTYPE)[:1]
+        cap = max(len(q), 1) if match_cap is None else int(match_cap)
+        nn = np.zeros(len(q), NN2_DTYPE)
+        matches = np.zeros(cap, MATCH_DTYPE)
+        total = C.c_size_t()
+        prm = GuidedHfParams(float(ratio2), float(max_desc_dist2), float(max_dist2), float(max_transfer2), int(bool(same_octave)), 0)
+        self._chk(lib().vslam_match_guided_hf_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), _ptr(emod),
+                                                   _ptr(hmod), C.byref(prm), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)),
+                  "vslam_match_guided_hf_host")
         return nn, matches[: min(total.value, cap)], total.value
 
     def _two_view_lists(self, stage, n_pairs, required, tensors):

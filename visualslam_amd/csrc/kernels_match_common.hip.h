@@ -1,7 +1,10 @@
-// What the two searches over descriptor rows share (kernels_match.hip.h: the matcher; kernels_match_guided.hip.h: the guided
-// pass): the tiling constants, the partial result of one workgroup for one query row, and the exact merge of two such results.
+// What the searches over descriptor rows share (kernels_match.hip.h: the matcher; kernels_match_guided.hip.h and
+// kernels_match_guided_hf.hip.h: the guided passes): the tiling constants, the partial result of one workgroup for one query row,
+// the exact merge of two such results, and what the guided passes know about a row beyond its descriptor.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "../../include/vslam.h"
 
 namespace vslam {
 
@@ -31,5 +34,21 @@ __device__ __forceinline__ void match_merge(float& b, float& s, int& i, float ob
     i = win ? oi : i;
     s = ns;
 }
+
+__device__ __forceinline__ double guided_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// The two-view section's coordinates of a point, exact; false: the point's octave is outside 0 .. 31
+__device__ __forceinline__ bool guided_xy(const vslam_point& p, double& x, double& y) {
+    if ((unsigned int)p.octave > 31u) return false;
+    const double s = p.octave == 0 ? 0.5 : (double)(1u << (p.octave - 1));
+    x = (double)((long long)p.col - (long long)p.padding) * s;
+    y = (double)((long long)p.row - (long long)p.padding) * s;
+    return true;
+}
+
+struct GuidedQn {  // the f32 side of a query row in LDS
+    float norm;
+    int octave;
+};
 
 }  // namespace vslam

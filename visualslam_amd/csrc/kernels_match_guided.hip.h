@@ -12,8 +12,8 @@
 //                          the same row, a broadcast.  The train tile's GuidedRows are staged with the tile (s_tc).  An element
 //                          that is not in band gets d2 = +inf before the selection, which is the header's "skipped".
 //   k_match_guided_merge : k_match_merge with the max_desc_dist2 clause in the acceptance.
-// The kernels of kernels_match.hip.h are not touched: these are siblings; match_merge, MatchPart and the tile constants are shared
-// (kernels_match_common.hip.h), and the norms come from the matcher's k_desc_norms (enqueue_desc_norms, vslam_launch.h).
+// The kernels of kernels_match.hip.h are not touched: these are siblings; match_merge, MatchPart, the tile constants and the guided
+// searches' row helpers (guided_xy, GuidedQn) are shared (kernels_match_common.hip.h), and the norms come from the matcher's k_desc_norms (enqueue_desc_norms, vslam_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,17 +22,6 @@
 #include "vslam_guided_plan.h"
 
 namespace vslam {
-
-__device__ __forceinline__ double guided_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// The two-view section's coordinates of a point, exact; false: the point's octave is outside 0 .. 31
-__device__ __forceinline__ bool guided_xy(const vslam_point& p, double& x, double& y) {
-    if ((unsigned int)p.octave > 31u) return false;
-    const double s = p.octave == 0 ? 0.5 : (double)(1u << (p.octave - 1));
-    x = (double)((long long)p.col - (long long)p.padding) * s;
-    y = (double)((long long)p.row - (long long)p.padding) * s;
-    return true;
-}
 
 // grid = (ceil(cap / GUIDED_ROW_WG), pairs); rows [pair][S.cap]
 template <bool QUERY>
@@ -60,11 +49,6 @@ __global__ __launch_bounds__(GUIDED_ROW_WG) void k_guided_rows(const vslam_desc_
 // Query rows whose LDS reads the epilogue of k_match_guided keeps in flight together.  From the compiler's resource report:
 // 1 -> 252 / 248 VGPRs (same_octave on / off), no scratch; 2 -> 256 with 4 spilled / 248; 4 -> 256 with 24 spilled / 256.
 constexpr int GUIDED_ROWS_IN_FLIGHT = 1;
-
-struct GuidedQn {  // the f32 side of a query row in LDS
-    float norm;
-    int octave;
-};
 
 // grid = (ceil(Q.cap / MT_Q), nsplit, pairs).  part: [pair][split][Q.cap].  The MFMA chain, the LDS image of a train tile and the
 // C / D map are k_match_nn2's (kernels_match.hip.h).

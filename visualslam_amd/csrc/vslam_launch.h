@@ -37,6 +37,12 @@ int enqueue_match_list(vslam_ctx* c, const unsigned long long* flags, size_t fwo
 // n(row) of every row in use of n_pairs descriptor sets (k_desc_norms, compiled in vslam_match.hip; vslam_match_guided_dev forms
 // d2 from the same norms): norms [n_pairs][S.cap].
 int enqueue_desc_norms(vslam_ctx* c, const vslam_desc_sets& S, int n_pairs, float* norms);
+// The merge of the guided searches' partial results with the guided acceptance (k_match_guided_merge, compiled in
+// vslam_match_guided.hip; vslam_match_guided_hf_dev merges its own search's parts the same way): part [n_pairs][nsplit][Q.cap]
+// -> nn [n_pairs][Q.cap] and the accepted-query ballot words flags [n_pairs][fwords].
+struct MatchPart;
+int enqueue_guided_merge(vslam_ctx* c, const vslam_desc_sets& Q, int n_pairs, const MatchPart* part, unsigned int nsplit, float ratio2,
+                         float max_desc_dist2, vslam_nn2* nn, unsigned long long* flags, unsigned int fwords);
 // The inlier list of vslam_epipolar_dev, the same way (EpipolarEntries): the winner's ballot words over the match records of
 // n_pairs pairs -> the inlier records in list order.  chunk_ws as above; inliers may be null (totals only).
 int enqueue_inlier_list(vslam_ctx* c, const unsigned long long* flags, size_t fwords, const vslam_match* matches, const unsigned int* match_counts,

@@ -13,6 +13,14 @@
 
 using namespace vslam;
 
+int vslam::enqueue_guided_merge(vslam_ctx* c, const vslam_desc_sets& Q, int n_pairs, const MatchPart* part, unsigned int nsplit, float ratio2,
+                                float max_desc_dist2, vslam_nn2* nn, unsigned long long* flags, unsigned int fwords) {
+    const unsigned int blocks = (unsigned int)(((size_t)Q.cap + GUIDED_ROW_WG - 1) / GUIDED_ROW_WG);  // GuidedPlan::qrow_blocks
+    LAUNCH(c, "k_match_guided_merge", k_match_guided_merge, dim3(blocks, n_pairs), dim3(GUIDED_ROW_WG), Q, part, (int)nsplit, ratio2, max_desc_dist2, nn, flags,
+           fwords);
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_match_guided_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_desc_sets* T, const vslam_epipolar* models, int n_pairs,
@@ -51,8 +59,7 @@ int vslam_match_guided_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_d
         LAUNCH(c, "k_match_guided", k_match_guided<true>, grid, dim3(256), *Q, *T, qnorm, tnorm, qrows, trows, prm->max_dist2, (int)pl.nsplit, part);
     else
         LAUNCH(c, "k_match_guided", k_match_guided<false>, grid, dim3(256), *Q, *T, qnorm, tnorm, qrows, trows, prm->max_dist2, (int)pl.nsplit, part);
-    LAUNCH(c, "k_match_guided_merge", k_match_guided_merge, dim3(pl.qrow_blocks, n_pairs), dim3(256), *Q, part, (int)pl.nsplit, prm->ratio2,
-           prm->max_desc_dist2, nn, flags, pl.fwords);
+    TRY(enqueue_guided_merge(c, *Q, n_pairs, part, pl.nsplit, prm->ratio2, prm->max_desc_dist2, nn, flags, pl.fwords));
     if (out->match_counts)
         TRY(enqueue_match_list(c, flags, pl.fwords, nn, Q->cap, n_pairs, chunk_ws, out->matches, out->match_cap, out->match_counts));
     return VSLAM_OK;

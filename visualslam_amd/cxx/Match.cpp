@@ -9,12 +9,15 @@
 // still read the first list.  --homography (after these) adds
 // the RANSAC homography of the same matches and the degeneracy verdict (vslam::findHomography: 512 hypotheses, seed 1, transfer
 // error below 2 pixels, degenerate from n_H / n_F >= 1 / 2 with at least 16 inliers) as a "homography" object; the steps after
-// it then read the gated model, so a degenerate pair gets no refit and no pose.  --refit ROUNDS (after these)
+// it then read the gated model, so a degenerate pair gets no refit and no pose.  --guided-h [max_transfer2[,ratio[,max_desc_dist2]]]
+// (after --homography; defaults 4.0, 0.8, no bound) matches again under the model that applies to the pair - the band under the
+// gated F, or a window around H x when the pair is degenerate (vslam::matchGuidedHF) - and runs the RANSAC homography on that
+// list: "guided_hf_kind", "guided_hf_matches" and "guided_hf_h_inliers".  --refit ROUNDS (after these)
 // refits that model over all its inliers (vslam::refitFundamental) and prints a "refit" object with n_before, n_after,
 // accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
 // from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
 // candidate and the number of inliers in front of both cameras.
-//   usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+//   usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -56,23 +59,32 @@ int main(int argc, char** argv) {
     try {
         const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
         if (epipolar) --argc, ++argv;
+        // the optional value of --guided / --guided-h is all numbers and commas ("4.0", "4.0,0.8,1.0"): "512x384" and "a.pgm" are not
+        auto threeNumbers = [&](double& first, float& ratio2, float& bound) {
+            double a = 0.0, ratio = 0.0, b = 0.0;
+            int used = 0;
+            const int got = argc > 1 ? std::sscanf(argv[1], "%lf%n,%lf%n,%lf%n", &a, &used, &ratio, &used, &b, &used) : 0;
+            if (got >= 1 && argv[1][used] == '\0') {
+                first = a;
+                if (got >= 2) ratio2 = (float)ratio * (float)ratio;
+                if (got >= 3) bound = (float)b;
+                --argc, ++argv;
+            }
+        };
         vslam_guided_params guidedParams{0.64f, HUGE_VALF, 4.0, 0, 0};
         const bool guided = epipolar && argc > 1 && std::strcmp(argv[1], "--guided") == 0;
         if (guided) {
             --argc, ++argv;
-            // the optional value is all numbers and commas ("4.0", "4.0,0.8,1.0"): "512x384" and "a.pgm" are not
-            double md = 0.0, ratio = 0.0, bound = 0.0;
-            int used = 0;
-            const int got = argc > 1 ? std::sscanf(argv[1], "%lf%n,%lf%n,%lf%n", &md, &used, &ratio, &used, &bound, &used) : 0;
-            if (got >= 1 && argv[1][used] == '\0') {
-                guidedParams.max_dist2 = md;
-                if (got >= 2) guidedParams.ratio2 = (float)ratio * (float)ratio;
-                if (got >= 3) guidedParams.max_desc_dist2 = (float)bound;
-                --argc, ++argv;
-            }
+            threeNumbers(guidedParams.max_dist2, guidedParams.ratio2, guidedParams.max_desc_dist2);
         }
         const bool homography = epipolar && argc > 1 && std::strcmp(argv[1], "--homography") == 0;
         if (homography) --argc, ++argv;
+        vslam_guided_hf_params guidedHfParams{0.64f, HUGE_VALF, 4.0, 4.0, 0, 0};
+        const bool guidedH = homography && argc > 1 && std::strcmp(argv[1], "--guided-h") == 0;
+        if (guidedH) {
+            --argc, ++argv;
+            threeNumbers(guidedHfParams.max_transfer2, guidedHfParams.ratio2, guidedHfParams.max_desc_dist2);
+        }
         vslam_refit_params refitParams{0, 4.0};
         const bool refit = epipolar && argc > 2 && std::strcmp(argv[1], "--refit") == 0;
         if (refit) {
@@ -94,7 +106,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -133,6 +145,14 @@ int main(int argc, char** argv) {
                 }
                 extra += "]}";
                 model = hg.gated;
+                if (guidedH) {
+                    const vslam::Matches g = vslam::matchGuidedHF(q.descriptors, t.descriptors, q.points, t.points, &hg.gated, &hg.model, guidedHfParams,
+                                                                  &q.defined, &t.defined);
+                    const vslam::Homography gh = vslam::findHomography(g.matches, q.points, t.points);
+                    std::snprintf(buf, sizeof buf, ", \"guided_hf_kind\": \"%s\", \"guided_hf_matches\": %zu, \"guided_hf_h_inliers\": %u",
+                                  hg.gated.best >= 0 ? "F" : hg.model.best >= 0 ? "H" : "none", g.matches.size(), gh.model.n_inliers);
+                    extra += buf;
+                }
             }
             if (refit) {
                 const vslam::Refit r = vslam::refitFundamental(model, m.matches, q.points, t.points, refitParams);

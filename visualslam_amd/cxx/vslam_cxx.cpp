@@ -501,6 +501,39 @@ vslam::Matches vslam::matchGuided(const std::vector<std::vector<float>>& query, 
     return out;
 }
 
+vslam::Matches vslam::matchGuidedHF(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train,
+                                    const std::vector<SLAM::point>& queryPoints, const std::vector<SLAM::point>& trainPoints,
+                                    const vslam_epipolar* epipolarModel, const vslam_homography* homographyModel, const vslam_guided_hf_params& params,
+                                    const std::vector<unsigned char>* query_defined, const std::vector<unsigned char>* train_defined) {
+    static_assert(sizeof(SLAM::point) == sizeof(vslam_point), "SLAM::point is the ABI's point record");
+    require(epipolarModel || homographyModel, "matchGuidedHF: no model");
+    require(queryPoints.size() == query.size() && trainPoints.size() == train.size(), "matchGuidedHF: one keypoint per descriptor");
+    auto flatten = [](const std::vector<std::vector<float>>& v, const std::vector<unsigned char>* defined) {
+        require(!defined || defined->size() == v.size(), "matchGuidedHF: one defined flag per descriptor");
+        std::vector<float> flat;
+        flat.reserve(128 * v.size());
+        for (const auto& d : v) {
+            require(d.size() == 128, "matchGuidedHF: a descriptor is not 128 floats");
+            flat.insert(flat.end(), d.begin(), d.end());
+        }
+        return flat;
+    };
+    const std::vector<float> q = flatten(query, query_defined), t = flatten(train, train_defined);
+    vslam::Matches out;
+    out.nn.resize(query.size());
+    out.matches.resize(query.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_match_guided_hf_host(c, q.data(), query_defined ? query_defined->data() : nullptr,
+                                            reinterpret_cast<const vslam_point*>(queryPoints.data()), query.size(), t.data(),
+                                            train_defined ? train_defined->data() : nullptr, reinterpret_cast<const vslam_point*>(trainPoints.data()),
+                                            train.size(), epipolarModel, homographyModel, &params, out.nn.empty() ? nullptr : out.nn.data(),
+                                            out.matches.empty() ? nullptr : out.matches.data(), out.matches.size(), &total),
+                 c, "matchGuidedHF");
+    out.matches.resize(total);
+    return out;
+}
+
 // ---- two-view geometry (the reference's README step 3; no reference code) ------------------------------------------
 
 vslam::Epipolar vslam::fundamentalRansac(const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,

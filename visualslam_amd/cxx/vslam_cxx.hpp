@@ -235,6 +235,15 @@ Matches matchGuided(const std::vector<std::vector<float>>& query, const std::vec
                     const vslam_guided_params& params = {0.64f, HUGE_VALF, 4.0, 0, 0}, const std::vector<unsigned char>* query_defined = nullptr,
                     const std::vector<unsigned char>* train_defined = nullptr);
 
+// The same pass under the model that applies to the pair: the epipolar band where `epipolarModel` has an F, a window of
+// params.max_transfer2 around H x where only `homographyModel` has an H - the degenerate pair, for which Homography::gated is "no
+// model" and matchGuided finds nothing -, nothing where neither has (vslam_match_guided_hf_host; include/vslam.h, "guided matching
+// under H or F").  Either record may be null, not both; the intended ones are &Homography::gated and &Homography::model.
+Matches matchGuidedHF(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train,
+                      const std::vector<SLAM::point>& queryPoints, const std::vector<SLAM::point>& trainPoints, const vslam_epipolar* epipolarModel,
+                      const vslam_homography* homographyModel, const vslam_guided_hf_params& params = {0.64f, HUGE_VALF, 4.0, 4.0, 0, 0},
+                      const std::vector<unsigned char>* query_defined = nullptr, const std::vector<unsigned char>* train_defined = nullptr);
+
 // The step after that: the camera motion of the pair (x_train ~ R x_query + t, |t| = 1) and the 3-D point of every record of
 // `matches` - the intended list is Epipolar::inliers - from the model fundamentalRansac found, on the GPU (vslam_pose_host;
 // the decomposition, the cheirality vote and the triangulation are stated in include/vslam.h).  One pinhole camera
