@@ -593,6 +593,51 @@ int vslam_match_host(vslam_ctx* ctx, const float* query, const uint8_t* query_de
                      const float* train, const uint8_t* train_defined, const vslam_point* train_points, size_t nt, float ratio2,
                      int same_octave, vslam_nn2* nn, vslam_match* matches, size_t match_cap, size_t* n_matches);
 
+/* ---------------------------------------------------------------- mutual matching
+ * The cross-check of a brute-force matcher, in the matcher's own pass: besides the nearest two train rows of every query row,
+ * the nearest QUERY row of every train row, and the list of the accepted queries whose train row chose them back.  d2(a, b)
+ * of the descriptor matching section is symmetric bit for bit (the products commute, the chain order is the same, the sum of
+ * the norms commutes), so the reverse nearest of train row t IS what vslam_match_dev(train, query) writes as nn[t].index and
+ * nn[t].dist2 (tests/mutualref.py restates both forms).
+ *   Forward.  nn and ACCEPTED are the descriptor matching section's, verbatim.
+ *   Reverse.  For a train row t that is in use and whose `defined` byte is not 0: walk the query rows q = 0 .. nq-1 ascending,
+ *     skipping a query row whose `defined` byte is 0 and, with same_octave, one whose points[q].octave differs from the train
+ *     row's; best = +inf, index = -1; if d2(q, t) < best then best = d2, index = q.  Ties keep the lowest query index, a NaN or
+ *     +inf distance never wins, -inf can.  An undefined train row, or one with no candidate, gets {-1, +inf}.
+ *   Mutual.  Query q is MUTUAL iff it is ACCEPTED and rnn[nn[q].index].index == q.  The list holds the mutual queries as
+ *     {q, nn[q].index, nn[q].dist2} in ascending query order; no train row appears twice in it.
+ * There is no ratio test on the reverse side (the second nearest of a train row is not kept).  The reverse minimum is an
+ * integer minimum over (ordered key of d2, q), so no bit of any output depends on scheduling, and none on
+ * vslam_ctx_set_f32_fused or vslam_ctx_set_matrix_path. */
+typedef struct {
+    int32_t index; /* query row, -1: none (dist2 = +inf) */
+    float dist2;
+} vslam_rnn;
+typedef struct {
+    size_t struct_size;     /* = sizeof(vslam_match_mutual_out) */
+    vslam_nn2* nn;          /* [n_pairs][query.cap] optional: exactly what vslam_match_dev writes */
+    size_t nn_bytes;
+    vslam_rnn* rnn;         /* [n_pairs][train.cap] optional; rows past a train set's count are left untouched */
+    size_t rnn_bytes;
+    vslam_match* matches;   /* [n_pairs][match_cap] optional, needs match_counts: the MUTUAL queries, ascending query order */
+    size_t matches_bytes;
+    uint32_t* match_counts; /* [n_pairs] totals of the mutual list (may exceed match_cap) */
+    size_t match_counts_bytes;
+    uint32_t match_cap;
+} vslam_match_mutual_out;
+/* Pairs, sets, ratio2, same_octave as for vslam_match_dev.  Asynchronous on the context stream, never waits on the host.
+ * Scratch belongs to the context: the matcher's, plus n_pairs * train.cap * 8 bytes for the reverse table, which is preset on
+ * the context stream in every call.  VSLAM_ERR_INVALID before any launch as for vslam_match_dev (no output at all: none of nn,
+ * rnn, match_counts), and for an undersized rnn buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for
+ * stream capture. */
+int vslam_match_mutual_dev(vslam_ctx* ctx, const vslam_desc_sets* query, const vslam_desc_sets* train, int n_pairs, float ratio2,
+                           int same_octave, const vslam_match_mutual_out* out);
+/* One pair in HOST memory, synchronous: vslam_match_host's arguments, and rnn [nt] (optional, like nn).  The list is the
+ * mutual list.  Errors as for vslam_match_mutual_dev. */
+int vslam_match_mutual_host(vslam_ctx* ctx, const float* query, const uint8_t* query_defined, const vslam_point* query_points, size_t nq,
+                            const float* train, const uint8_t* train_defined, const vslam_point* train_points, size_t nt, float ratio2,
+                            int same_octave, vslam_nn2* nn, vslam_rnn* rnn, vslam_match* matches, size_t match_cap, size_t* n_matches);
+
 /* ---------------------------------------------------------------- two-view geometry
  * The step after matching (the reference's README: "3. 3D Reconstruction - Epipolar Geometry"): the fundamental matrix of
  * every pair, by RANSAC over the match list vslam_match_dev wrote and the point lists vslam_detect_batch_dev wrote, and the

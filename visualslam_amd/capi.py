@@ -31,6 +31,7 @@ POINT_DTYPE = np.dtype([(n, "<i4") for n in ("row", "col", "value", "padding", "
 KP_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("response", "<f4")], align=True)
 NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4")], align=True)  # vslam_nn2
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
+RNN_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4")], align=True)  # vslam_rnn, 8 bytes
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
 HOMOGRAPHY_HYP_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_homography_hyp, 152 bytes
@@ -122,6 +123,17 @@ class MatchOut(C.Structure):
     """vslam_match_out: struct_size, then every pointer with the bytes behind it."""
     _fields_ = [("struct_size", C.c_size_t), ("nn", C.c_void_p), ("nn_bytes", C.c_size_t), ("matches", C.c_void_p), ("matches_bytes", C.c_size_t),
                 ("match_counts", C.c_void_p), ("match_counts_bytes", C.c_size_t), ("match_cap", C.c_uint32)]
+
+
+class Rnn(C.Structure):
+    _fields_ = [("index", C.c_int32), ("dist2", C.c_float)]
+
+
+class MatchMutualOut(C.Structure):
+    """vslam_match_mutual_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("nn", C.c_void_p), ("nn_bytes", C.c_size_t), ("rnn", C.c_void_p), ("rnn_bytes", C.c_size_t),
+                ("matches", C.c_void_p), ("matches_bytes", C.c_size_t), ("match_counts", C.c_void_p), ("match_counts_bytes", C.c_size_t),
+                ("match_cap", C.c_uint32)]
 
 
 class EpipolarHyp(C.Structure):
@@ -368,6 +380,8 @@ SIGNATURES = {
     "vslam_count_totals_dev": (_I, [_P, _P, _P, _I, _P]),
     "vslam_match_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _I, _F, _I, C.POINTER(MatchOut)]),
     "vslam_match_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _Z, C.POINTER(_Z)]),
+    "vslam_match_mutual_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _I, _F, _I, C.POINTER(MatchMutualOut)]),
+    "vslam_match_mutual_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _F, _I, _P, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_match_guided_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _P, _I, C.POINTER(GuidedParams), C.POINTER(MatchOut)]),
     "vslam_match_guided_host": (_I, [_P, _P, _P, _P, _Z, _P, _P, _P, _Z, _P, C.POINTER(GuidedParams), _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_match_guided_hf_dev": (_I, [_P, C.POINTER(DescSets), C.POINTER(DescSets), _P, _P, _I, C.POINTER(GuidedHfParams), C.POINTER(MatchOut)]),
@@ -1002,6 +1016,50 @@ class Context:
         self._chk(lib().vslam_match_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), float(ratio2),
                                          int(bool(same_octave)), nn.ctypes.data, matches.ctypes.data, cap, C.byref(total)), "vslam_match_host")
         return nn, matches[: min(total.value, cap)], total.value
+
+    def match_mutual(self, query: DescSets, train: DescSets, n_pairs: int | None = None, ratio2: float = 0.64, same_octave: bool = False,
+                     nn=None, rnn=None, matches=None, match_counts=None):
+        """vslam_match_mutual_dev: match() with the cross-check in the same pass; asynchronous on the context stream.  nn: as match()'s;
+        rnn: int32 / float32 tensor of n_pairs * train.cap vslam_rnn records (RNN_DTYPE), the nearest query row of every train row;
+        matches / match_counts: as match()'s, but the MUTUAL list - the accepted queries whose train row chose them back."""
+        stage = "match_mutual"
+        n = min(query.n, train.n) if n_pairs is None else int(n_pairs)
+        outs = dict(nn=nn, rnn=rnn, matches=matches, match_counts=match_counts)
+        _check_tensors(stage, self.where, outs, ())
+        for name, t in outs.items():
+            if t is not None and t.element_size() != 4:
+                raise ValueError(f"{stage}: {name} must have 4-byte elements")
+        if nn is None and rnn is None and match_counts is None:
+            raise ValueError(f"{stage}: no output requested")
+        if matches is not None and (match_counts is None or matches.dim() < 2):
+            raise ValueError(f"{stage}: matches must be [n_pairs, match_cap, 3] and needs match_counts")
+        mo = _fill_out(MatchMutualOut(), outs)
+        if matches is not None:
+            mo.match_cap = matches.shape[1]
+        self._chk(lib().vslam_match_mutual_dev(self._h, C.byref(query), C.byref(train), n, float(ratio2), int(bool(same_octave)), C.byref(mo)),
+                  "vslam_match_mutual_dev")
+
+    def match_mutual_host(self, q, t, ratio2: float = 0.64, same_octave: bool = False, q_defined=None, t_defined=None, q_points=None, t_points=None,
+                          match_cap: int | None = None):
+        """vslam_match_mutual_host: one pair of numpy descriptor arrays [n, 128] -> (nn [nq] NN2_DTYPE, rnn [nt] RNN_DTYPE, matches
+        MATCH_DTYPE: the mutual list, total mutual)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 128)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 128)
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in
+               ((q_defined, np.uint8), (q_points, POINT_DTYPE), (t_defined, np.uint8), (t_points, POINT_DTYPE))]
+        for a, rows in zip(opt, (len(q), len(q), len(t), len(t))):
+            if a is not None and a.size != rows:
+                raise ValueError("match_mutual_host: defined / points must have one entry per descriptor row")
+        ptr = [None if a is None else a.ctypes.data for a in opt]
+        cap = max(len(q), 1) if match_cap is None else int(match_cap)
+        nn = np.zeros(len(q), NN2_DTYPE)
+        rnn = np.zeros(len(t), RNN_DTYPE)
+        matches = np.zeros(cap, MATCH_DTYPE)
+        total = C.c_size_t()
+        self._chk(lib().vslam_match_mutual_host(self._h, q.ctypes.data, ptr[0], ptr[1], len(q), t.ctypes.data, ptr[2], ptr[3], len(t), float(ratio2),
+                                                int(bool(same_octave)), nn.ctypes.data, rnn.ctypes.data, matches.ctypes.data, cap, C.byref(total)),
+                  "vslam_match_mutual_host")
+        return nn, rnn, matches[: min(total.value, cap)], total.value
 
     def match_guided(self, query: DescSets, train: DescSets, models, n_pairs: int | None = None, ratio2: float = 0.64,
                      max_desc_dist2: float = float("inf"), max_dist2: float = 4.0, same_octave: bool = False, nn=None, matches=None,

@@ -57,6 +57,7 @@ static const char* const kKernelNames =
     "k_desc_norms\nk_match_nn2\nk_match_merge\n"
     "k_guided_rows\nk_match_guided\nk_match_guided_merge\n"
     "k_guided_hf_rows\nk_guided_hf_kinds\nk_match_guided_hf\n"
+    "k_match_nn2_mutual\nk_match_mutual_merge\nk_match_rnn_write\n"
     "k_epi_coords\nk_epi_models\nk_epi_score\nk_epi_select\nk_epi_flags\n"
     "k_refit_init\nk_refit_count\nk_refit_begin\nk_refit_dist\nk_refit_scale\nk_refit_moments\nk_refit_solve\n"
     "k_hom_models\nk_hom_score\nk_hom_select\nk_hom_flags\nk_hom_verdict\n"

@@ -1,7 +1,9 @@
 // The step the reference's `DoG` executable stops short of (Diff_of_Gauss.cpp:687, "final step is graphing and comparing
 // two images with each other"): the DoG pipeline of DoG.cpp on two images - pyramid, initialKeypointDetection,
 // filterKeypoints and SIFT per octave - and then every descriptor of the first matched against every descriptor of the
-// second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --epipolar adds
+// second (vslam::matchDescriptors: exact nearest two, ratio test 0.8).  Prints one JSON line with the counts.  --mutual (first)
+// takes the cross-checked list instead (vslam::matchMutual: the accepted queries whose train descriptor chose them back): the
+// line gains "mutual": true, "accepted" counts that list and every step after it reads it.  --epipolar adds
 // the step after that: the RANSAC fundamental matrix of the accepted matches (vslam::fundamentalRansac: 512 hypotheses, seed 1,
 // Sampson distance below 2 pixels) as an "epipolar" object with the inlier count and F.  --guided [max_dist2[,ratio[,max_desc_dist2]]]
 // (after --epipolar; defaults 4.0, 0.8, no bound) matches again inside each query's epipolar band under that F
@@ -17,7 +19,7 @@
 // accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
 // from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
 // candidate and the number of inliers in front of both cameras.
-//   usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+//   usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -57,6 +59,8 @@ Described describe(Mat img, int numOctaves) {  // (the reference's constructor t
 
 int main(int argc, char** argv) {
     try {
+        const bool mutual = argc > 1 && std::strcmp(argv[1], "--mutual") == 0;
+        if (mutual) --argc, ++argv;
         const bool epipolar = argc > 1 && std::strcmp(argv[1], "--epipolar") == 0;
         if (epipolar) --argc, ++argv;
         // the optional value of --guided / --guided-h is all numbers and commas ("4.0", "4.0,0.8,1.0"): "512x384" and "a.pgm" are not
@@ -106,21 +110,22 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
         const int numOctaves = argc > next ? std::atoi(argv[next]) : 4;
         const auto t0 = std::chrono::steady_clock::now();
         const Described q = describe(first, numOctaves), t = describe(second, numOctaves);
-        const vslam::Matches m = vslam::matchDescriptors(q.descriptors, t.descriptors, 0.8f, &q.defined, &t.defined);
-        std::string extra;
+        const vslam::Matches m = mutual ? vslam::matchMutual(q.descriptors, t.descriptors, 0.8f, &q.defined, &t.defined)
+                                        : vslam::matchDescriptors(q.descriptors, t.descriptors, 0.8f, &q.defined, &t.defined);
+        std::string extra = mutual ? ", \"mutual\": true" : "";
         if (epipolar) {
             const vslam::Epipolar e = vslam::fundamentalRansac(m.matches, q.points, t.points);
             char buf[512];
             std::snprintf(buf, sizeof buf, ", \"epipolar\": {\"n_inliers\": %u, \"best\": %d, \"n_valid\": %u, \"hypotheses\": 512, \"max_dist2\": 4.0, \"F\": [", e.model.n_inliers,
                           e.model.best, e.model.n_valid);
-            extra = buf;
+            extra += buf;
             for (int i = 0; i < 9; ++i) {
                 std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", e.model.F[i]);
                 extra += buf;

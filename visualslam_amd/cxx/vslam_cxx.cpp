@@ -469,6 +469,34 @@ vslam::Matches vslam::matchDescriptors(const std::vector<std::vector<float>>& qu
     return out;
 }
 
+vslam::Matches vslam::matchMutual(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train, float ratio,
+                                  const std::vector<unsigned char>* query_defined, const std::vector<unsigned char>* train_defined) {
+    auto flatten = [](const std::vector<std::vector<float>>& v, const std::vector<unsigned char>* defined) {
+        require(!defined || defined->size() == v.size(), "matchMutual: one defined flag per descriptor");
+        std::vector<float> flat;
+        flat.reserve(128 * v.size());
+        for (const auto& d : v) {
+            require(d.size() == 128, "matchMutual: a descriptor is not 128 floats");
+            flat.insert(flat.end(), d.begin(), d.end());
+        }
+        return flat;
+    };
+    const std::vector<float> q = flatten(query, query_defined), t = flatten(train, train_defined);
+    vslam::Matches out;
+    out.nn.resize(query.size());
+    out.rnn.resize(train.size());
+    out.matches.resize(query.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_match_mutual_host(c, q.data(), query_defined ? query_defined->data() : nullptr, nullptr, query.size(), t.data(),
+                                         train_defined ? train_defined->data() : nullptr, nullptr, train.size(), ratio * ratio, 0,
+                                         out.nn.empty() ? nullptr : out.nn.data(), out.rnn.empty() ? nullptr : out.rnn.data(),
+                                         out.matches.empty() ? nullptr : out.matches.data(), out.matches.size(), &total),
+                 c, "matchMutual");
+    out.matches.resize(total);
+    return out;
+}
+
 vslam::Matches vslam::matchGuided(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train,
                                   const std::vector<SLAM::point>& queryPoints, const std::vector<SLAM::point>& trainPoints, const vslam_epipolar& model,
                                   const vslam_guided_params& params, const std::vector<unsigned char>* query_defined,

@@ -185,9 +185,16 @@ namespace vslam {
 struct Matches {
     std::vector<vslam_nn2> nn;         // one per query descriptor: {train index or -1, dist2, second_dist2}
     std::vector<vslam_match> matches;  // the accepted queries, ascending query order
+    std::vector<vslam_rnn> rnn;        // matchMutual only - one per train descriptor: {query index or -1, dist2}
 };
 Matches matchDescriptors(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train, float ratio = 0.8f,
                          const std::vector<unsigned char>* query_defined = nullptr, const std::vector<unsigned char>* train_defined = nullptr);
+
+// matchDescriptors with the cross-check of a brute-force matcher in the same pass, on the GPU (vslam_match_mutual_host;
+// include/vslam.h, "mutual matching"): Matches::nn is matchDescriptors', Matches::rnn the nearest query descriptor of every train
+// descriptor, and Matches::matches holds only the accepted queries whose train descriptor chose them back - no train index twice.
+Matches matchMutual(const std::vector<std::vector<float>>& query, const std::vector<std::vector<float>>& train, float ratio = 0.8f,
+                    const std::vector<unsigned char>* query_defined = nullptr, const std::vector<unsigned char>* train_defined = nullptr);
 
 // The step after matching (the reference's README, "3. 3D Reconstruction - Epipolar Geometry"): the fundamental matrix of the
 // pair by RANSAC over the accepted matches, and their inlier subset, on the GPU (vslam_epipolar_host; sampling, the 8-point
