@@ -110,40 +110,102 @@ __global__ __launch_bounds__(256) void k_gauss_h_diff(const uint16_t* __restrict
     const size_t P = (size_t)rows * pitch;
     uint8_t* out = oct_out + blockIdx.z * pframe;
     const int ncs = (cols + HD_J - 1) / HD_J;
-    const int ccount = G::HL + HD_J * ncs + G::rmax;  // logical columns staged per row
-    const int n8 = cols >> 3, nb = ccount - 8 * n8;    // interior groups of 8; border columns (left halo + tail + right halo)
+    const int n8 = cols >> 3, tl = cols & 7;             // interior groups of 8 columns; tail columns past the last group
+    const int nh = hd_halo_cols(cols, G::HL, G::rmax);  // halo columns: left of column 0, and from column `cols` on
     const bool active = tid < npairs * ncs;
     const int ip = tid / ncs, is = tid - ip * ncs;
     const hd_f2* lane = hp + ip * pw + is * (HD_J + HD_PAD);
-    const int n8d = max(n8, 1);  // (no interior group at all below 8 columns)
-    const int i_p0 = tid / n8d, i_k0 = tid - i_p0 * n8d, i_dp = 256 / n8d, i_dk = 256 - i_dp * n8d;
-    const int b_p0 = tid / nb, b_i0 = tid - b_p0 * nb, b_dp = 256 / nb, b_di = 256 - b_dp * nb;
+
+    // The staging plan of this thread, the same for every level (only the plane differs), made once.  A thread holds at
+    // most two interior items, one tail item and HT halo items (hdiff_stage_fits, vslam_octave_launch.h).  An item the
+    // thread does not have loads column 0 of the workgroup's first row (always there) and writes nothing.
+    constexpr int HT = hd_halo_trips(G::HL, G::rmax);
+    const uint16_t* h0 = h + blockIdx.z * hframe;
+    auto row_of = [&](int p, int rho) { return h0 + (size_t)min(y0 + 2 * p + rho, rows - 1) * pitch; };
+    const uint16_t *ia[2], *ib[2], *ta, *tb;  // level 0's addresses of both rows of the pair
+    float4* iq[2];                            // where an interior item goes (HL % 16 == 0: inside one group of 16)
+    hd_f2* tq;
+    bool iv[2];
+    {
+        const int n8d = max(n8, 1);  // (no interior group at all below 8 columns)
+        int p = tid / n8d, k = tid - p * n8d;
+        const int dp = 256 / n8d, dk = 256 - dp * n8d;  // (item -> (pair, column) by increments)
+        hd_for<2>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            if (k >= n8d) k -= n8d, ++p;
+            iv[i] = tid + 256 * i < npairs * n8;
+            const int pp = iv[i] ? p : 0, kk = iv[i] ? k : 0;
+            ia[i] = row_of(pp, 0) + 8 * kk;
+            ib[i] = row_of(pp, 1) + 8 * kk;
+            iq[i] = reinterpret_cast<float4*>(hp + pp * pw + hd_phys(G::HL + 8 * kk));
+            p += dp, k += dk;
+        });
+    }
+    const bool tv = tid < npairs * tl;
+    {
+        const int tld = max(tl, 1);
+        const int p = tv ? tid / tld : 0, x = tv ? 8 * n8 + tid - p * tld : 0;
+        ta = row_of(p, 0) + x;
+        tb = row_of(p, 1) + x;
+        tq = hp + p * pw + hd_phys(G::HL + x);
+    }
+    // halo item: copy of the staged column it reflects to (reflect-101, repeated for kernels wider than the row), inside
+    // LDS: source index | destination index << 16 in hp (both < 2^16: LDS is below 512 KB); 0xffff: no item
+    uint32_t hx[HT];
+    {
+        int p = tid / nh, i = tid - p * nh;
+        const int dp = 256 / nh, di = 256 - dp * nh;
+        hd_for<HT>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            if (i >= nh) i -= nh, ++p;
+            const int c = i < G::HL ? i : cols + i;  // logical column: image column c - HL
+            const int x = reflect101(c - G::HL, cols);
+            hx[t] = tid + 256 * t < npairs * nh ? (uint32_t)(p * pw + hd_phys(G::HL + x)) | (uint32_t)(p * pw + hd_phys(c)) << 16 : 0xffff0000u;
+            p += dp, i += di;
+        });
+    }
+
+    // the level's interior and tail, held in registers from the loads (issued under the previous level's arithmetic)
+    // to the LDS writes (after the barrier that ends that level's reads)
+    uint4 ra[2], rb[2];
+    uint16_t rta, rtb;
+    auto load_level = [&](auto lc) {
+        const size_t lo = (size_t)decltype(lc)::value * P;
+        hd_for<2>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            ra[i] = *reinterpret_cast<const uint4*>(ia[i] + lo);
+            rb[i] = *reinterpret_cast<const uint4*>(ib[i] + lo);
+        });
+        rta = ta[lo];
+        rtb = tb[lo];
+    };
     uint32_t prev_e[2][4], prev_o[2][4];
 
+    load_level(std::integral_constant<int, 0>{});
     hd_for<VSLAM_NUM_LEVELS>([&](auto lc) {
         constexpr int L = decltype(lc)::value;
-        const uint16_t* hl = h + blockIdx.z * hframe + (size_t)L * P;
-        __syncthreads();  // the previous level's reads are done
-        // (item -> (pair, column) by increments: the same for every level, no division in the loops)
-        for (int it = tid, p = i_p0, k = i_k0; it < npairs * n8; it += 256, p += i_dp, k += i_dk) {  // interior: 8 columns of both rows
-            if (k >= n8) k -= n8, ++p;
-            const uint4 a = *reinterpret_cast<const uint4*>(hl + (size_t)min(y0 + 2 * p, rows - 1) * pitch + 8 * k);
-            const uint4 b = *reinterpret_cast<const uint4*>(hl + (size_t)min(y0 + 2 * p + 1, rows - 1) * pitch + 8 * k);
-            float4* q = reinterpret_cast<float4*>(hp + p * pw + hd_phys(G::HL + 8 * k));  // HL % 16 == 0: one group of 16
-            const uint32_t av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+        if constexpr (L > 0) __syncthreads();  // the previous level's reads are done
+        hd_for<2>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            if (iv[i]) {
+                const uint32_t av[4] = {ra[i].x, ra[i].y, ra[i].z, ra[i].w}, bv[4] = {rb[i].x, rb[i].y, rb[i].z, rb[i].w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                q[i] = make_float4((float)(av[i] & 0xffffu), (float)(bv[i] & 0xffffu), (float)(av[i] >> 16), (float)(bv[i] >> 16));
-        }
-        for (int it = tid, p = b_p0, i = b_i0; it < npairs * nb; it += 256, p += b_dp, i += b_di) {  // borders, reflect-101
-            if (i >= nb) i -= nb, ++p;
-            const int c = i < G::HL ? i : 8 * n8 + i;
-            const int x = reflect101(c - G::HL, cols);  // (repeated for kernels wider than the row)
-            const uint16_t* ra = hl + (size_t)min(y0 + 2 * p, rows - 1) * pitch;
-            const uint16_t* rb = hl + (size_t)min(y0 + 2 * p + 1, rows - 1) * pitch;
-            hp[p * pw + hd_phys(c)] = hd_f2{(float)ra[x], (float)rb[x]};
+                for (int j = 0; j < 4; ++j)
+                    iq[i][j] = make_float4((float)(av[j] & 0xffffu), (float)(bv[j] & 0xffffu), (float)(av[j] >> 16), (float)(bv[j] >> 16));
+            }
+        });
+        if (tv) *tq = hd_f2{(float)rta, (float)rtb};
+        __syncthreads();  // every image column of the row pairs is in LDS
+        {
+            hd_f2 hv[HT];
+            hd_for<HT>([&](auto tc) { hv[decltype(tc)::value] = hp[hx[decltype(tc)::value] & 0xffffu]; });
+            hd_for<HT>([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                if ((hx[t] >> 16) != 0xffffu) hp[hx[t] >> 16] = hv[t];
+            });
         }
         __syncthreads();
+        if constexpr (L + 1 < VSLAM_NUM_LEVELS) load_level(std::integral_constant<int, L + 1>{});
         if (active) {
             hd_f2 acc[HD_J];
             hd_level<dtaps::Lvl<O, L>, G::HL>(lane, acc);

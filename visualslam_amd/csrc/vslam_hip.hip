@@ -237,7 +237,7 @@ static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
         pl.sh = strip_plan_sh(rows, cols, nmax);
         if (pl.sh) pl.path = OctPath::Strip;
         // the default pyramid's octaves 2-3 (and any octave with the same taps): horizontal pass in difference form
-        if (pl.path == OctPath::Strip && hdiff_fits(cols))
+        if (pl.path == OctPath::Strip && hdiff_fits(cols) && hdiff_stage_fits(cols))
             pl.hdiff = hd_octave_matches<2>(pl.taps) ? 2 : hd_octave_matches<3>(pl.taps) ? 3 : 0;
     }
     if (pl.path != OctPath::Generic) pl.mx = mx_config_for(pl.ke);

@@ -56,6 +56,17 @@ constexpr int hd_pw(int cols, int HL, int rmax) {
 }
 // one item (row pair x 16 columns) per thread: a single row pair must fit the 256 threads
 constexpr bool hdiff_fits(int cols) { return (cols + HD_J - 1) / HD_J <= 256; }
+// the most row pairs a workgroup takes at this width (strip_launch starts here and only goes down)
+constexpr int hd_max_pairs(int cols) { return std::max(1, std::min(8, 256 / ((cols + HD_J - 1) / HD_J))); }
+// The kernel keeps the next level's staging loads in registers while it computes this one, a fixed number per thread:
+//   - interior items (8 columns of a row pair): at most TWO.  npairs <= 256 / ncs and cols >> 3 <= 2 ncs
+//     (ncs = ceil(cols / 16)), so npairs * (cols >> 3) <= 512;
+//   - tail items (one of the cols & 7 columns past the last group of 8, of a row pair): at most one, 8 * 7 <= 256;
+//   - halo items (one column of a row pair's reflect-101 extension, copied inside LDS): at most hd_halo_trips().
+// plan_octave keeps k_gauss_h_strip where this does not hold (nowhere today: tests/test_hdiff_staging_cpu.py sweeps it).
+constexpr int hd_halo_cols(int cols, int HL, int rmax) { return HL + HD_J * ((cols + HD_J - 1) / HD_J) - cols + rmax; }
+constexpr int hd_halo_trips(int HL, int rmax) { return (8 * (HL + HD_J - 1 + rmax) + 255) / 256; }
+constexpr bool hdiff_stage_fits(int cols) { return hd_max_pairs(cols) * (cols >> 3) <= 2 * 256 && hd_max_pairs(cols) * (cols & 7) <= 256; }
 
 // ---- the strip octave's two launches ---------------------------------------------------------------------------------
 struct StripLaunch {
@@ -79,10 +90,9 @@ inline StripLaunch strip_launch(int rows, int cols, int nf, int sh, bool hdiff, 
     const int want = (256 + strips * nf - 1) / (strips * nf);
     s.lsplit = want >= 6 ? 6 : want >= 3 ? 3 : want >= 2 ? 2 : 1;
     if (hdiff) {
-        const int ncs = (cols + HD_J - 1) / HD_J;
         s.pw = hd_pw(cols, hd_HL, hd_rmax);
         // row pairs per workgroup: at most 256 items (one per thread), LDS below the limit, and >= 256 workgroups for small batches
-        int npairs = std::max(1, std::min(8, 256 / ncs));
+        int npairs = hd_max_pairs(cols);
         while (npairs > 1 && ((size_t)npairs * s.pw * 8 > (size_t)kMaxDynLds || (long)((rows + 2 * npairs - 1) / (2 * npairs)) * nf < 256)) --npairs;
         s.diff = true;
         s.npairs = npairs;
