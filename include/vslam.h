@@ -1142,6 +1142,139 @@ int vslam_pose_host(vslam_ctx* ctx, const vslam_epipolar* model, const vslam_mat
                     const vslam_pose_params* params, vslam_pose* pose, vslam_pose_cand* candidates, double* points,
                     uint64_t* front_bits);
 
+/* ---------------------------------------------------------------- pose from homography: planar pairs get R, t and points
+ * The pairs the degeneracy gate took away from vslam_pose_dev.  For a pair whose matches a homography explains, H itself
+ * holds the motion: H ~ K (R + t n^T / d) K^-1 for a plane with unit normal n at distance d in the query frame.  This stage
+ * decomposes models[j].H (the `models` buffer of vslam_homography_dev) into its four (R, t, n) candidates, votes on them with
+ * the records H supports, and writes the SAME buffers vslam_pose_dev writes - poses, points, front_bits, same shapes, same
+ * rules - for the pairs it selects, and for no other pair: passed the very buffers vslam_pose_dev just wrote from the gated
+ * models, the call fills exactly the holes the gate made, and vslam_chain_dev, vslam_resect_dev, vslam_tracks_dev and
+ * vslam_bundle_dev read on without a new code path.  The match list must be the list the pose stage of the batch read (the
+ * intended one is the inliers / inlier_counts / inlier_cap of vslam_epipolar_dev, which the gate leaves in place): row i of
+ * points and bit i of front_bits then mean the same record for every pair, however it got its pose.  A pure rotation has no
+ * baseline to triangulate from: it gets its rotation in `info`, the "no pose" record in poses, and still breaks the
+ * trajectory's segment.  No refit of H, no plane carried from pair to pair.  Convention, coordinates, "trusted" and
+ * m = min(match_counts[j], match_cap) are the relative pose section's; the arithmetic is fixed here so that a CPU can restate
+ * it bit for bit (tests/hposeref.py): IEEE f64, every + - * / sqrt rounded on its own (no fused multiply-add), sums left to
+ * right as written.  Matrices are row-major, M[i][j] = M[3*i + j]; V[:, k] is column k.
+ *
+ * Pair j is SELECTED iff models[j].best >= 0 && (!only_degenerate || models[j].degenerate != 0).  A pair that is not
+ * selected has kind NONE, and its poses[j], its point rows and its front words are left untouched.
+ *
+ *  1. Euclidean homography A = K^-1 H K, the right factor first, as step 1 of the relative pose section forms F K:
+ *       G[i][0] = H[i][0]*fx;  G[i][1] = H[i][1]*fy;  G[i][2] = (H[i][0]*cx + H[i][1]*cy) + H[i][2];
+ *       A[0][j] = (G[0][j] - cx*G[2][j]) / fx;  A[1][j] = (G[1][j] - cy*G[2][j]) / fy;  A[2][j] = G[2][j].
+ *     No sign step: the sign rule of the homography section makes (H x)_2 > 0 on H's inliers, and the third row of K^-1 is
+ *     (0, 0, 1), so (A q)_2 > 0 for the ray q of every inlier already.
+ *  2. Eigenvalues and scaling: S = A^T A and the six Jacobi sweeps of step 4 of the two-view model, verbatim, give the
+ *     diagonal d and V.  Three conditional exchanges bring them into descending order - positions (0, 1), then (1, 2), then
+ *     (0, 1): d[a] and d[b], and columns a and b of V, change places iff d[b] > d[a] (a stable sort: on ties the lower index
+ *     stays first; a NaN never moves).  L1 = d[0], L2 = d[1], L3 = d[2] and v1 = V[:, 0], v2 = V[:, 1], v3 = V[:, 2] afterwards.
+ *     L2 not finite or not positive: the pair is INVALID - kind NONE, and poses[j] is the "no pose" record.  s = sqrt(L2);
+ *     A[i][j] = A[i][j] / s;  l1 = L1 / L2;  l3 = L3 / L2;  spread = l1 - l3.  (The ordering gives l3 <= 1 <= l1 exactly.)
+ *  3. Kind.  !(spread >= min_spread): ROTATION.  With c1, c2 the first two columns of the scaled A, by the rules of step 3
+ *     of the relative pose section: r1 = c1 / |c1|, |c| = sqrt((c_0*c_0 + c_1*c_1) + c_2*c_2);  g = (r1_0*c2_0 + r1_1*c2_1) +
+ *     r1_2*c2_2;  w_i = c2_i - g*r1_i;  r2 = w / |w|;  r3 = r1 x r2 (the cross product of that section);  R[i][0] = r1_i,
+ *     R[i][1] = r2_i, R[i][2] = r3_i.  A norm that is zero or not finite: the pair is invalid.  poses[j] is the "no pose"
+ *     record, the front words are zero, no point row is written; the rotation is in info[j].  Otherwise the kind is PLANE.
+ *  4. PLANE candidates (Ma, Soatto, Kosecka, Sastry: products, square roots and cross products only).
+ *     a = sqrt(1 - l3);  b = sqrt(l1 - 1);  c = sqrt(spread);  u+_i = (a*v1_i + b*v3_i) / c;  u-_i = (a*v1_i - b*v3_i) / c.
+ *     For u = u+ and for u = u-:  m1_i = (A[i][0]*v2_0 + A[i][1]*v2_1) + A[i][2]*v2_2;  m2_i likewise from u;  m3 = m1 x m2;
+ *     n = v2 x u;  R[i][j] = (m1_i*v2_j + m2_i*u_j) + m3_i*n_j;  An_i = (A[i][0]*n_0 + A[i][1]*n_1) + A[i][2]*n_2;  Rn_i
+ *     likewise from R;  T_i = An_i - Rn_i;  |T| = sqrt((T_0*T_0 + T_1*T_1) + T_2*T_2);  t = T / |T|.  |T| zero or not finite:
+ *     both candidates of that sign are invalid (all zero, never voted for).
+ *     c = 0: (R+, t+, n+), 1: (R+, -t+, -n+), 2: (R-, t-, n-), 3: (R-, -t-, -n-).
+ *  5. Vote.  A record is SUPPORTED iff it passes the inlier test of the homography section (trusted, forward and backward)
+ *     under models[j].H, models[j].G and params.max_dist2, word for word.  n_support counts them (kinds PLANE and ROTATION).
+ *     front[c] = the number of supported records that are IN FRONT by step 5 of the relative pose section under (R_c, t_c)
+ *     with K, and have nq = (n_0*q0 + n_1*q1) + n_2 > 0 for n = n_c (q the query ray of that step).  Negating (t, n) negates
+ *     n1, n2 and nq exactly, so for c = 1 and c = 3 the test is det > 0 && n1 < 0 && n2 < 0 && nq < 0 with the values of c - 1.
+ *  6. Selection.  The WINNER w is the valid candidate with the largest front, the lowest c on ties; every count 0: best = -1
+ *     and poses[j] is the "no pose" record.  runner = the largest front[c] over c != w.
+ *     ambiguous = uint64(runner) * ambiguous_den >= uint64(ambiguous_num) * front[w].  An ambiguous pair with priors != NULL
+ *     and priors[j].best >= 0 is RESOLVED: over the valid candidates with uint64(front[c]) * ambiguous_den >= uint64(ambiguous_num) *
+ *     front[w], c ascending, the score is s_c = (((P[0]*R_c[0] + P[1]*R_c[1]) + P[2]*R_c[2]) + ... ) + P[8]*R_c[8] with
+ *     P = priors[j].R; the first such candidate is kept, and a later one replaces it iff its score is > the kept score (a
+ *     NaN never replaces and is never replaced).  The kept candidate is then `best`, otherwise best = w.
+ *     poses[j] carries candidate `best` (R, t, n_front = front[best], best, valid = 1) iff the pair is not ambiguous or is
+ *     resolved; an ambiguous pair that is not resolved gets the "no pose" record, and info[j] reports the vote either way: a
+ *     coin flip never enters the trajectory.  The "no pose" record: R, t zero, n_front = 0, best = -1, n_matches = m, valid =
+ *     1 for kind PLANE and 0 otherwise.
+ *  7. Points and bits of a selected pair with poses[j].best >= 0: for a supported record, step 7 of the relative pose section
+ *     verbatim under (poses[j].R, poses[j].t), and its front bit is "in front" by step 5 of that section; a record that is
+ *     not supported gets front bit 0 and the quiet NaN in all three coordinates, as an untrusted record does there.  Rows
+ *     i < m are written; with best < 0 no row is written and the first (m + 63) / 64 front words are zero.
+ * Every NaN this stage writes is the quiet NaN 0x7ff8000000000000.  Every count is an integer and no floating-point sum
+ * crosses records: the result depends neither on how the records are split over lanes and workgroups nor on
+ * vslam_ctx_set_f32_fused / vslam_ctx_set_matrix_path. */
+#define VSLAM_HPOSE_NONE 0
+#define VSLAM_HPOSE_PLANE 1
+#define VSLAM_HPOSE_ROTATION 2
+typedef struct {
+    vslam_pose_params K;
+    double max_dist2;       /* H's symmetric transfer bound (the max_dist2 vslam_homography_dev ran with); finite and positive */
+    double min_spread;      /* spread below this: a pure rotation; finite and positive */
+    uint32_t ambiguous_num; /* ambiguous: runner / front[w] >= ambiguous_num / ambiguous_den */
+    uint32_t ambiguous_den; /* > 0 */
+    int32_t only_degenerate; /* 0: every pair with an H; 1: only the pairs the verdict judged degenerate */
+    uint32_t reserved;      /* must be 0 */
+} vslam_hpose_params;       /* 64 bytes */
+typedef struct {
+    double R[9];
+    double t[3];
+    double n[3];    /* the plane's unit normal in the query frame */
+    uint32_t front; /* supported records in front of both cameras and of the plane under this candidate */
+    int32_t valid;
+} vslam_hpose_cand; /* 128 bytes */
+typedef struct {
+    double R[9];           /* PLANE: the rotation of candidate `best` (zero when best < 0); ROTATION: the pair's rotation */
+    double n[3];           /* PLANE: the unit normal of candidate `best` in the query frame */
+    double inv_d;          /* PLANE: |T| of candidate `best`, the baseline over the plane's distance */
+    double spread;         /* l1 - l3 (PLANE and ROTATION) */
+    uint32_t n_matches;    /* min(match_counts[j], match_cap): the records considered */
+    uint32_t n_support;    /* the records H supports */
+    uint32_t front;        /* the vote's winner's count */
+    uint32_t front_runner; /* the runner-up's count */
+    int32_t kind;          /* VSLAM_HPOSE_NONE / _PLANE / _ROTATION; NONE: the whole record is zero */
+    int32_t best;          /* the candidate chosen, 0 .. 3 (the vote's winner unless resolved); -1: none */
+    int32_t ambiguous;
+    int32_t resolved;
+} vslam_hpose;             /* 144 bytes */
+/* Like vslam_pose_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;           /* = sizeof(vslam_hpose_out) */
+    vslam_pose* poses;            /* [n_pairs], required; written for selected pairs only */
+    size_t poses_bytes;
+    vslam_hpose* info;            /* [n_pairs], required; written for every pair */
+    size_t info_bytes;
+    vslam_hpose_cand* candidates; /* [n_pairs][4] optional; written for every pair (all zero unless the kind is PLANE) */
+    size_t candidates_bytes;
+    double* points;               /* [n_pairs][match_cap][3] optional: as vslam_pose_out's, selected pairs only */
+    size_t points_bytes;
+    uint64_t* front_bits;         /* [n_pairs][(match_cap + 63) / 64] optional: as vslam_pose_out's, selected pairs only */
+    size_t front_bits_bytes;
+} vslam_hpose_out;
+/* Pair j reads models[j] (H, G, best, degenerate), the lists as vslam_pose_dev does and, when given, priors[j] (R and best;
+ * DEVICE pointers, priors may be NULL; priors must not overlap poses or any other output: pair j's prior is read while other
+ * pairs' poses are written - to use the previous pairs' poses, pass a copy).  Asynchronous on the context stream, never waits on the host (the counts, the models
+ * and with them every pair's kind are read on the device, the grids are sized from the capacities); scratch belongs to the
+ * context.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null pointer, a wrong
+ * struct_size, n_pairs outside 0 .. 65535 (0 does nothing), an intrinsic that is not finite, fx or fy not positive, a max_dist2
+ * or min_spread that is not finite or not positive, ambiguous_den == 0, only_degenerate outside 0 .. 1, reserved != 0,
+ * match_cap / query_cap / train_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for
+ * stream capture. */
+int vslam_hpose_dev(vslam_ctx* ctx, const vslam_homography* models, const vslam_match* matches, const uint32_t* match_counts,
+                    uint32_t match_cap, const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points,
+                    uint32_t train_cap, int n_pairs, const vslam_pose* priors, const vslam_hpose_params* params,
+                    const vslam_hpose_out* out);
+/* The same call over HOST memory, synchronous (a convenience path: device buffers per call): matches [n_pairs][match_cap],
+ * query_points [n_pairs][query_cap], train_points [n_pairs][train_cap].  poses, points and front_bits go up before the call, so
+ * what it leaves untouched comes back as it went in.  Errors as for vslam_hpose_dev. */
+int vslam_hpose_host(vslam_ctx* ctx, const vslam_homography* models, const vslam_match* matches, const uint32_t* match_counts,
+                     uint32_t match_cap, const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points,
+                     uint32_t train_cap, int n_pairs, const vslam_pose* priors, const vslam_hpose_params* params,
+                     const vslam_hpose_out* out);
+
 /* ---------------------------------------------------------------- trajectory: pair poses chained into one world frame
  * The step after the relative pose.  vslam_pose_dev leaves every pair with |t| = 1 and its points in its own query camera's
  * frame and unit; this step recovers the scale of pair j relative to pair j - 1 from the points both pairs triangulated and

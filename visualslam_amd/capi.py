@@ -44,6 +44,13 @@ GUIDED_HF_PARAMS_DTYPE = np.dtype([("ratio2", "<f4"), ("max_desc_dist2", "<f4"),
 REFIT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4")], align=True)  # vslam_refit, 16 bytes
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
+HPOSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_hpose_cand, 128 bytes
+HPOSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("n", "<f8", (3,)), ("inv_d", "<f8"), ("spread", "<f8"), ("n_matches", "<u4"), ("n_support", "<u4"), ("front", "<u4"),
+                        ("front_runner", "<u4"), ("kind", "<i4"), ("best", "<i4"), ("ambiguous", "<i4"), ("resolved", "<i4")], align=True)  # vslam_hpose, 144 bytes
+HPOSE_NONE, HPOSE_PLANE, HPOSE_ROTATION = 0, 1, 2  # vslam_hpose.kind
+# What the tools pass unless told otherwise: min_spread is the geometric mean of the largest spread of the planted
+# pure rotations (6.527e-3) and the smallest of the planted planes (0.1273); a runner-up within 9 / 10 of the winner is a twin.
+HPOSE_MIN_SPREAD, HPOSE_AMBIGUOUS_NUM, HPOSE_AMBIGUOUS_DEN = 0.0288, 9, 10
 CHAIN_DTYPE = np.dtype([("W", "<f8", (9,)), ("w", "<f8", (3,)), ("C", "<f8", (3,)), ("Ct", "<f8", (3,)), ("scale", "<f8"), ("ratio", "<f8"), ("n_links", "<u4"),
                         ("segment", "<i4"), ("linked", "<i4"), ("valid", "<i4")], align=True)  # vslam_chain, 176 bytes
 RESECT_HYP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_resect_hyp, 104 bytes
@@ -221,6 +228,28 @@ class PoseOut(C.Structure):
                 ("front_bits_bytes", C.c_size_t)]
 
 
+class HposeParams(C.Structure):
+    _fields_ = [("K", PoseParams), ("max_dist2", C.c_double), ("min_spread", C.c_double), ("ambiguous_num", C.c_uint32), ("ambiguous_den", C.c_uint32),
+                ("only_degenerate", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class HposeCand(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("n", C.c_double * 3), ("front", C.c_uint32), ("valid", C.c_int32)]
+
+
+class Hpose(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("n", C.c_double * 3), ("inv_d", C.c_double), ("spread", C.c_double), ("n_matches", C.c_uint32),
+                ("n_support", C.c_uint32), ("front", C.c_uint32), ("front_runner", C.c_uint32), ("kind", C.c_int32), ("best", C.c_int32),
+                ("ambiguous", C.c_int32), ("resolved", C.c_int32)]
+
+
+class HposeOut(C.Structure):
+    """vslam_hpose_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("poses", C.c_void_p), ("poses_bytes", C.c_size_t), ("info", C.c_void_p), ("info_bytes", C.c_size_t),
+                ("candidates", C.c_void_p), ("candidates_bytes", C.c_size_t), ("points", C.c_void_p), ("points_bytes", C.c_size_t),
+                ("front_bits", C.c_void_p), ("front_bits_bytes", C.c_size_t)]
+
+
 class ChainParams(C.Structure):
     _fields_ = [("min_links", C.c_uint32)]
 
@@ -394,6 +423,8 @@ SIGNATURES = {
     "vslam_homography_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, _P, C.POINTER(HomographyParams), _P, _P, _P, _Z, C.POINTER(_Z), _P, _P]),
     "vslam_pose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(PoseParams), C.POINTER(PoseOut)]),
     "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
+    "vslam_hpose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, _P, C.POINTER(HposeParams), C.POINTER(HposeOut)]),
+    "vslam_hpose_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, _P, C.POINTER(HposeParams), C.POINTER(HposeOut)]),
     "vslam_chain_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
     "vslam_chain_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _I, C.POINTER(ChainParams), C.POINTER(ChainOut)]),
     "vslam_resect_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(ResectParams),
@@ -1320,6 +1351,61 @@ class Context:
         self._chk(lib().vslam_pose_host(self._h, mod.ctypes.data, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp), C.byref(prm), pose.ctypes.data,
                                         _ptr(cand), _ptr(pts), _ptr(bits)), "vslam_pose_host")
         return pose[0], cand, (pts[:m] if want_points and int(pose["best"][0]) >= 0 else None), bits
+
+    def hpose(self, models, matches, match_counts, query_points, train_points, intrinsics, max_dist2: float = 4.0, min_spread: float = HPOSE_MIN_SPREAD,
+              ambiguous_num: int = HPOSE_AMBIGUOUS_NUM, ambiguous_den: int = HPOSE_AMBIGUOUS_DEN, only_degenerate: bool = True, priors=None,
+              n_pairs: int | None = None, poses=None, info=None, candidates=None, points=None, front_bits=None):
+        """vslam_hpose_dev: pose from homography - (R, t), the plane and the 3-D points of the pairs a homography explains, written
+        into the tensors pose() wrote; asynchronous on the context stream.  models: the tensor homography() wrote (n_pairs * 168
+        bytes); matches / match_counts: the list pose() read; priors (optional): n_pairs * 112 bytes of POSE_DTYPE records, e.g. a COPY of
+        the previous pairs' poses - it must not overlap an output.  Outputs, CUDA tensors: poses n_pairs * 112 bytes and info n_pairs * 144 bytes (HPOSE_DTYPE), both
+        required; candidates n_pairs * 4 * 128 bytes (HPOSE_CAND_DTYPE), points float64 [n, match_cap, 3], front_bits int64
+        [n, (match_cap + 63) // 64].  Only the pairs the call selects are written in poses, points and front_bits."""
+        outs = dict(poses=poses, info=info, candidates=candidates, points=points, front_bits=front_bits)
+        n = self._two_view_lists("hpose", n_pairs, "poses", dict(models=models, matches=matches, match_counts=match_counts, query_points=query_points, train_points=train_points, priors=priors, **outs))
+        if info is None:
+            raise ValueError("hpose: info is required")
+        if models.numel() * models.element_size() < n * 168:
+            raise ValueError("hpose: models must hold n_pairs * 168 bytes")
+        if priors is not None and priors.numel() * priors.element_size() < n * 112:
+            raise ValueError("hpose: priors must hold n_pairs * 112 bytes")
+        ho = _fill_out(HposeOut(), outs)
+        prm = HposeParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), float(min_spread), int(ambiguous_num), int(ambiguous_den),
+                          int(bool(only_degenerate)), 0)
+        self._chk(lib().vslam_hpose_dev(self._h, models.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), matches.shape[1],
+                                        query_points.data_ptr(), query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n,
+                                        None if priors is None else priors.data_ptr(), C.byref(prm), C.byref(ho)), "vslam_hpose_dev")
+
+    def hpose_host(self, models, matches, match_counts, query_points, train_points, intrinsics, poses, max_dist2: float = 4.0,
+                   min_spread: float = HPOSE_MIN_SPREAD, ambiguous_num: int = HPOSE_AMBIGUOUS_NUM, ambiguous_den: int = HPOSE_AMBIGUOUS_DEN,
+                   only_degenerate: bool = True, priors=None, points=None, front_bits=None, want_candidates: bool = False):
+        """vslam_hpose_host: the same call over numpy arrays - models [n] HOMOGRAPHY_DTYPE, matches [n, match_cap] MATCH_DTYPE,
+        match_counts [n], query_points [n, query_cap] / train_points [n, train_cap] POINT_DTYPE, priors [n] POSE_DTYPE or None -
+        -> (info [n] HPOSE_DTYPE, candidates [n, 4] HPOSE_CAND_DTYPE or None).  poses [n] POSE_DTYPE, points float64
+        [n, match_cap, 3] and front_bits uint64 [n, (match_cap + 63) // 64] are written in place (C-contiguous arrays of exactly that
+        type; points and front_bits optional): what the call leaves untouched keeps its bytes."""
+        mod = _records(models, HOMOGRAPHY_DTYPE)
+        n = len(mod)
+        mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        qp, tp = np.ascontiguousarray(query_points, dtype=POINT_DTYPE), np.ascontiguousarray(train_points, dtype=POINT_DTYPE)
+        if mt.ndim != 2 or qp.ndim != 2 or tp.ndim != 2 or not (mt.shape[0] == qp.shape[0] == tp.shape[0] == n):
+            raise ValueError("hpose_host: matches, query_points and train_points must be [n, cap]")
+        cap, cnt = mt.shape[1], _counts(match_counts)
+        pri = None if priors is None else _records(priors, POSE_DTYPE)
+        if len(cnt) != n or (pri is not None and len(pri) != n):
+            raise ValueError("hpose_host: one count and one prior per pair")
+        _check_host_outs("hpose_host", (("poses", poses, POSE_DTYPE, n), ("points", points, np.float64, n * cap * 3),
+                                        ("front_bits", front_bits, np.uint64, n * ((cap + 63) // 64))))
+        if poses is None:
+            raise ValueError("hpose_host: poses is required")
+        info = np.zeros(max(n, 1), HPOSE_DTYPE)
+        cand = np.zeros((max(n, 1), 4), HPOSE_CAND_DTYPE) if want_candidates else None
+        ho = _fill_out(HposeOut(), dict(poses=poses, info=info, candidates=cand, points=points, front_bits=front_bits))
+        prm = HposeParams(PoseParams(*(float(v) for v in intrinsics)), float(max_dist2), float(min_spread), int(ambiguous_num), int(ambiguous_den),
+                          int(bool(only_degenerate)), 0)
+        self._chk(lib().vslam_hpose_host(self._h, mod.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, qp.ctypes.data, qp.shape[1], tp.ctypes.data,
+                                         tp.shape[1], n, None if pri is None else pri.ctypes.data, C.byref(prm), C.byref(ho)), "vslam_hpose_host")
+        return info[:n], (None if cand is None else cand[:n])
 
     def chain(self, poses, matches, match_counts, points, front_bits, point_cap: int, min_links: int = 16, n_pairs: int | None = None, chain=None,
               map=None, links=None, ratios=None):

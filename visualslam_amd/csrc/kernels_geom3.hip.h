@@ -164,6 +164,40 @@ __device__ __forceinline__ void refit_tree(double (&s)[N], double* lds) {
     }
 }
 
+// What the homography, pose and pose-from-homography kernels share per record (kernels_homography.hip.h, kernels_pose.hip.h,
+// kernels_hpose.hip.h): the symmetric transfer test and the two-ray solve, each stated once.
+// The inlier test of one record under (H, G); false for NaN coordinates (p2 > 0 fails) and for H = G = 0.
+__device__ __forceinline__ bool hom_inlier(const double (&H)[9], const double (&G)[9], const EpiXY& p, double max_dist2) {
+    const double p0 = (H[0] * p.x + H[1] * p.y) + H[2], p1 = (H[3] * p.x + H[4] * p.y) + H[5], p2 = (H[6] * p.x + H[7] * p.y) + H[8];
+    const double q0 = (G[0] * p.u + G[1] * p.v) + G[2], q1 = (G[3] * p.u + G[4] * p.v) + G[5], q2 = (G[6] * p.u + G[7] * p.v) + G[8];
+    const double dx = p0 - p.u * p2, dy = p1 - p.v * p2;
+    const double ex = q0 - p.x * q2, ey = q1 - p.y * q2;
+    const bool fwd = p2 > 0.0 && dx * dx + dy * dy < max_dist2 * (p2 * p2);
+    const bool bwd = q2 > 0.0 && ex * ex + ey * ey < max_dist2 * (q2 * q2);
+    return fwd && bwd;
+}
+
+// The two rays of one record (step 5): q = (q0, q1, 1), b = (b0, b1, 1).
+struct PoseRays {
+    double q0, q1, b0, b1;
+};
+__device__ __forceinline__ PoseRays pose_rays(const EpiXY& p, const vslam_pose_params& K) {
+    return PoseRays{(p.x - K.cx) / K.fx, (p.y - K.cy) / K.fy, (p.u - K.cx) / K.fx, (p.v - K.cy) / K.fy};
+}
+
+// det, n1, n2 of one record under (R, t) (step 5; the third component of q and b is 1, and x * 1 is x).
+__device__ __forceinline__ void pose_solve(const double (&R)[9], const double (&t)[3], const PoseRays& r, double& det, double& n1, double& n2) {
+    const double a0 = (R[0] * r.q0 + R[1] * r.q1) + R[2], a1 = (R[3] * r.q0 + R[4] * r.q1) + R[5], a2 = (R[6] * r.q0 + R[7] * r.q1) + R[8];
+    const double aa = (a0 * a0 + a1 * a1) + a2 * a2;
+    const double bb = (r.b0 * r.b0 + r.b1 * r.b1) + 1.0;
+    const double ab = (a0 * r.b0 + a1 * r.b1) + a2;
+    const double at = (a0 * t[0] + a1 * t[1]) + a2 * t[2];
+    const double bt = (r.b0 * t[0] + r.b1 * t[1]) + t[2];
+    det = aa * bb - ab * ab;
+    n1 = ab * bt - bb * at;
+    n2 = aa * bt - ab * at;
+}
+
 // A NaN leaves as the quiet NaN 0x7ff8000000000000: IEEE fixes neither the sign nor the payload of a NaN an operation makes.
 // (k_pose_points and the trajectory kernels, kernels_chain.hip.h.)
 __device__ __forceinline__ double pose_canonical(double x) { return x == x ? x : __longlong_as_double(0x7ff8000000000000ll); }

@@ -19,17 +19,6 @@
 
 namespace vslam {
 
-// The inlier test of one record under (H, G); false for NaN coordinates (p2 > 0 fails) and for H = G = 0.
-__device__ __forceinline__ bool hom_inlier(const double (&H)[9], const double (&G)[9], const EpiXY& p, double max_dist2) {
-    const double p0 = (H[0] * p.x + H[1] * p.y) + H[2], p1 = (H[3] * p.x + H[4] * p.y) + H[5], p2 = (H[6] * p.x + H[7] * p.y) + H[8];
-    const double q0 = (G[0] * p.u + G[1] * p.v) + G[2], q1 = (G[3] * p.u + G[4] * p.v) + G[5], q2 = (G[6] * p.u + G[7] * p.v) + G[8];
-    const double dx = p0 - p.u * p2, dy = p1 - p.v * p2;
-    const double ex = q0 - p.x * q2, ey = q1 - p.y * q2;
-    const bool fwd = p2 > 0.0 && dx * dx + dy * dy < max_dist2 * (p2 * p2);
-    const bool bwd = q2 > 0.0 && ex * ex + ey * ey < max_dist2 * (q2 * q2);
-    return fwd && bwd;
-}
-
 // Step 1 of the model for one side: the 4 values are read through `get(i)`.
 template <class GetX, class GetY>
 __device__ __forceinline__ bool hom_normalise(GetX gx, GetY gy, double& cx, double& cy, double& s) {

@@ -105,27 +105,6 @@ __global__ __launch_bounds__(POSE_PAIR_WG) void k_pose_candidates(const vslam_ep
     }
 }
 
-// The two rays of one record (step 5): q = (q0, q1, 1), b = (b0, b1, 1).
-struct PoseRays {
-    double q0, q1, b0, b1;
-};
-__device__ __forceinline__ PoseRays pose_rays(const EpiXY& p, const vslam_pose_params& K) {
-    return PoseRays{(p.x - K.cx) / K.fx, (p.y - K.cy) / K.fy, (p.u - K.cx) / K.fx, (p.v - K.cy) / K.fy};
-}
-
-// det, n1, n2 of one record under (R, t) (step 5; the third component of q and b is 1, and x * 1 is x).
-__device__ __forceinline__ void pose_solve(const double (&R)[9], const double (&t)[3], const PoseRays& r, double& det, double& n1, double& n2) {
-    const double a0 = (R[0] * r.q0 + R[1] * r.q1) + R[2], a1 = (R[3] * r.q0 + R[4] * r.q1) + R[5], a2 = (R[6] * r.q0 + R[7] * r.q1) + R[8];
-    const double aa = (a0 * a0 + a1 * a1) + a2 * a2;
-    const double bb = (r.b0 * r.b0 + r.b1 * r.b1) + 1.0;
-    const double ab = (a0 * r.b0 + a1 * r.b1) + a2;
-    const double at = (a0 * t[0] + a1 * t[1]) + a2 * t[2];
-    const double bt = (r.b0 * t[0] + r.b1 * t[1]) + t[2];
-    det = aa * bb - ab * ab;
-    n1 = ab * bt - bb * at;
-    n2 = aa * bt - ab * at;
-}
-
 // grid = (record blocks of 256, pairs).  The pair's candidates are read through addresses that are the same in every lane.
 // `cand` is read (R, t, valid) and written (front, by atomicAdd) here, so it is neither const nor restrict.
 __global__ __launch_bounds__(POSE_REC_WG) void k_pose_vote(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts,

@@ -62,6 +62,7 @@ static const char* const kKernelNames =
     "k_refit_init\nk_refit_count\nk_refit_begin\nk_refit_dist\nk_refit_scale\nk_refit_moments\nk_refit_solve\n"
     "k_hom_models\nk_hom_score\nk_hom_select\nk_hom_flags\nk_hom_verdict\n"
     "k_pose_candidates\nk_pose_vote\nk_pose_select\nk_pose_points\n"
+    "k_hpose_candidates\nk_hpose_vote\nk_hpose_select\nk_hpose_points\n"
     "k_chain_link\nk_chain_ratio\nk_chain_median\nk_chain_walk\nk_chain_map\n"
     "k_res_corr\nk_res_gather\nk_res_models\nk_res_score\nk_res_select\nk_res_flags\n"
     "k_rr_init\nk_rr_pass\nk_rr_step\nk_rr_flags_zero\nk_rr_flags\n"

@@ -19,7 +19,9 @@
 // accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
 // from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
 // candidate and the number of inliers in front of both cameras.
-//   usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves, default 4]
+// --hpose (after --homography and --pose) adds the pose of a pair the gate removed, from H itself (vslam::poseFromHomography
+// into a copy of that pose): an "hpose" object with kind, best, ambiguous, n_support, front, front_runner and the pose it left.
+//   usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy [--hpose]]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -103,6 +105,8 @@ int main(int argc, char** argv) {
                 throw std::runtime_error("--pose takes fx,fy,cx,cy");
             argc -= 2, argv += 2;
         }
+        const bool hpose = pose && homography && argc > 1 && std::strcmp(argv[1], "--hpose") == 0;
+        if (hpose) --argc, ++argv;
         Mat first, second;
         int w = 0, h = 0, next = 2;
         if (argc < 2) {
@@ -110,7 +114,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy [--hpose]]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -139,6 +143,8 @@ int main(int argc, char** argv) {
             }
             vslam_epipolar model = e.model;
             std::vector<vslam_match> inliers = e.inliers;
+            vslam_homography hmodel{};
+            hmodel.best = -1;
             if (homography) {
                 const vslam::Homography hg = vslam::findHomography(m.matches, q.points, t.points, &e.model);
                 std::snprintf(buf, sizeof buf, ", \"homography\": {\"n_inliers\": %u, \"best\": %d, \"n_valid\": %u, \"n_epipolar\": %u, \"degenerate\": %d, \"H\": [",
@@ -149,7 +155,7 @@ int main(int argc, char** argv) {
                     extra += buf;
                 }
                 extra += "]}";
-                model = hg.gated;
+                model = hg.gated, hmodel = hg.model;
                 if (guidedH) {
                     const vslam::Matches g = vslam::matchGuidedHF(q.descriptors, t.descriptors, q.points, t.points, &hg.gated, &hg.model, guidedHfParams,
                                                                   &q.defined, &t.defined);
@@ -186,6 +192,15 @@ int main(int argc, char** argv) {
                     extra += buf;
                 }
                 extra += "]}";
+                if (hpose) {
+                    vslam::Pose filled = p;
+                    const vslam::HomographyPose hp = vslam::poseFromHomography(hmodel, inliers, q.points, t.points, camera, filled);
+                    std::snprintf(buf, sizeof buf, ", \"hpose\": {\"kind\": %d, \"best\": %d, \"ambiguous\": %d, \"n_support\": %u, \"front\": %u, "
+                                  "\"front_runner\": %u, \"pose_best\": %d, \"pose_n_front\": %u}",
+                                  hp.info.kind, hp.info.best, hp.info.ambiguous, hp.info.n_support, hp.info.front, hp.info.front_runner, filled.pose.best,
+                                  filled.pose.n_front);
+                    extra += buf;
+                }
             }
         }
         const auto t1 = std::chrono::steady_clock::now();

@@ -1,5 +1,6 @@
 #include "vslam_cxx.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <mutex>
 
@@ -624,6 +625,45 @@ vslam::Pose vslam::relativePose(const vslam_epipolar& model, const std::vector<v
                                  out.points.empty() ? nullptr : out.points.data(), out.frontBits.empty() ? nullptr : out.frontBits.data()),
                  c, "relativePose");
     if (out.pose.best < 0) out.points.clear();
+    return out;
+}
+
+vslam::HomographyPose vslam::poseFromHomography(const vslam_homography& model, const std::vector<vslam_match>& matches,
+                                                const std::vector<SLAM::point>& queryPoints, const std::vector<SLAM::point>& trainPoints,
+                                                const vslam_pose_params& camera, vslam::Pose& pose, const vslam_pose* prior, double maxDist2,
+                                                double minSpread, uint32_t ambiguousNum, uint32_t ambiguousDen, bool onlyDegenerate) {
+    const size_t m = matches.size(), words = (m + 63) / 64;
+    require(m < (1u << 31) && queryPoints.size() < (1u << 31) && trainPoints.size() < (1u << 31), "poseFromHomography: too many records");
+    require(m == 0 || (!queryPoints.empty() && !trainPoints.empty()), "poseFromHomography: matches without points");
+    require(pose.pose.n_matches == m && (pose.points.empty() || pose.points.size() == m * 3) && (pose.frontBits.empty() || pose.frontBits.size() == words),
+            "poseFromHomography: pose is not relativePose's over these matches");
+    // the batched entry point takes capacities of at least one: an empty list goes up as one unused record
+    std::vector<vslam_match> mt(matches);
+    std::vector<SLAM::point> qp(queryPoints), tp(trainPoints);
+    mt.resize(std::max<size_t>(m, 1)), qp.resize(std::max<size_t>(qp.size(), 1)), tp.resize(std::max<size_t>(tp.size(), 1));
+    const uint32_t count = (uint32_t)m;
+    std::vector<double> points(mt.size() * 3, 0.0);
+    std::vector<uint64_t> bits((mt.size() + 63) / 64, 0);
+    vslam_pose rec = pose.pose;
+    vslam::HomographyPose out{};
+    vslam_hpose_out o{};
+    o.struct_size = sizeof(o);
+    o.poses = &rec, o.poses_bytes = sizeof(rec);
+    o.info = &out.info, o.info_bytes = sizeof(out.info);
+    o.candidates = out.candidates, o.candidates_bytes = sizeof(out.candidates);
+    o.points = points.data(), o.points_bytes = points.size() * sizeof(double);
+    o.front_bits = bits.data(), o.front_bits_bytes = bits.size() * sizeof(uint64_t);
+    const vslam_hpose_params params{camera, maxDist2, minSpread, ambiguousNum, ambiguousDen, onlyDegenerate ? 1 : 0, 0};
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_hpose_host(c, &model, mt.data(), &count, (uint32_t)mt.size(), reinterpret_cast<const vslam_point*>(qp.data()), (uint32_t)qp.size(),
+                                  reinterpret_cast<const vslam_point*>(tp.data()), (uint32_t)tp.size(), 1, prior, &params, &o),
+                 c, "poseFromHomography");
+    if (model.best >= 0 && (!onlyDegenerate || model.degenerate != 0)) {  // selected: the pair's record, points and bits are the call's
+        pose.pose = rec;
+        points.resize(rec.best >= 0 ? m * 3 : 0);
+        bits.resize(words);
+        pose.points.swap(points), pose.frontBits.swap(bits);
+    }
     return out;
 }
 

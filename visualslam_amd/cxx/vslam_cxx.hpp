@@ -264,6 +264,21 @@ struct Pose {
 Pose relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                   const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera);
 
+// The pose of a pair the gate took away from relativePose: the homography findHomography found, decomposed into (R, t, n), on
+// the GPU (vslam_hpose_host, one pair; the candidates, the vote, the ambiguity rule and the prior are stated in include/vslam.h,
+// "pose from homography").  `pose` is what relativePose gave for Homography::gated over the same `matches`: when the pair is
+// selected (model.best >= 0, and model.degenerate with params.only_degenerate) its record, points and front bits are replaced
+// - points empty when the new record has best < 0 -, otherwise it is left exactly as it was.  prior: a pose whose R resolves an
+// ambiguous pair, e.g. the pair before; may be null.  The default min_spread and ratio are the tools' (DESIGN 5.24).
+struct HomographyPose {
+    vslam_hpose info;                // kind, the vote, the plane's normal and baseline over distance; all zero: not selected
+    vslam_hpose_cand candidates[4];  // the four (R, t, n) with their counts
+};
+HomographyPose poseFromHomography(const vslam_homography& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                                  const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera, Pose& pose,
+                                  const vslam_pose* prior = nullptr, double maxDist2 = 4.0, double minSpread = 0.0288, uint32_t ambiguousNum = 9,
+                                  uint32_t ambiguousDen = 10, bool onlyDegenerate = true);
+
 // The step after that over a sequence: the poses and points of consecutive pairs (pair j: frames j and j + 1) chained with the
 // recovered scale into one world frame per segment, on the GPU (vslam_chain_host; the link, the median ratio, the walk and the
 // map are stated in include/vslam.h).  The inputs are what relativePose gave for every pair, laid side by side at one
