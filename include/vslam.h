@@ -886,7 +886,8 @@ int vslam_match_guided_host(vslam_ctx* ctx, const float* query, const uint8_t* q
  * pure rotation, a pure image translation), in which case F is one arbitrary member of a family and must not be decomposed.
  * The verdict acts through a GATE: a copy of the epipolar models in which a degenerate pair is the "no model" record, which
  * vslam_refit_dev copies through, vslam_pose_dev gives no pose and vslam_chain_dev starts a new segment at.  A fixed number
- * of hypotheses, no adaptive stop, no least-squares refit of H, no decomposition of H into R, t, n.  Coordinates, "trusted",
+ * of hypotheses, no adaptive stop; the least-squares refit of H (vslam_hrefit_dev) and the decomposition of H into R, t, n
+ * (vslam_hpose_dev) are stages of their own.  Coordinates, "trusted",
  * m = min(match_counts[j], match_cap) and mix() are those of the two-view geometry section.  The arithmetic is fixed here so
  * that a CPU can restate it bit for bit (tests/homref.py): IEEE f64, every + - * / sqrt rounded on its own (no fused
  * multiply-add), sums left to right as written.  Matrices are row-major, M[i][j] = M[3*i + j].
@@ -996,6 +997,110 @@ int vslam_homography_host(vslam_ctx* ctx, const vslam_match* matches, size_t n_m
                           const vslam_homography_params* params, vslam_homography* model, uint64_t* inlier_bits,
                           vslam_match* inliers, size_t inlier_cap, size_t* n_inliers, vslam_homography_hyp* hypotheses,
                           vslam_epipolar* gated_model);
+
+/* ---------------------------------------------------------------- homography: least-squares refit over the inliers
+ * The step after vslam_homography_dev, the sibling of vslam_refit_dev: the winning 4-point hypothesis is replaced by the
+ * normalised direct linear transform over ALL its inliers, the inliers are classified again under the new (H, G), and so on
+ * for a fixed number of rounds; a round whose model has fewer inliers than the one before it is dropped, so the result never
+ * has fewer inliers than the input.  What reads H afterwards - vslam_match_guided_hf_dev's window, vslam_hpose_dev's
+ * decomposition, the verdict against a refitted F - then reads the polished model.  Inputs: the `models` buffer
+ * vslam_homography_dev wrote, the FULL match list it read and the point lists.  No non-linear refinement of the transfer
+ * error.  The arithmetic is fixed here so that a CPU can restate it bit for bit (tests/hrefitref.py): IEEE f64, every
+ * + - * / sqrt rounded on its own (no fused multiply-add), sums of a few terms left to right as written.  Coordinates,
+ * "trusted" and m = min(match_counts[j], match_cap) are those of the two-view geometry section.  SUM(term) is the ordered sum
+ * of the refit section ("fundamental matrix: least-squares refit over the inliers"), verbatim: blocks of 4096 records, 256
+ * slots, the halving tree, the blocks added left to right; a record that is not a member contributes +0.0.
+ *
+ * A record is a MEMBER under (H, G) iff it is an inlier of the homography section's inlier test (symmetric transfer: trusted,
+ * forward and backward) under (H, G) with max_dist2.
+ *
+ * Per pair.  (H_cur, G_cur) = (models_in[j].H, models_in[j].G), n_cur = the number of members under it (an integer),
+ * n_before = n_cur, accepted = 0.  A pair with models_in[j].best < 0 is copied through unchanged with stop = 5 and
+ * n_before = n_after = accepted = 0.  Round 1 .. rounds, until a stop:
+ *  1. n_cur < 4: stop = 1.
+ *  2. Normalisation per side, members under (H_cur, G_cur): step 2 of the refit section word for word - n = (double)n_cur;
+ *     cx = SUM(x) / n; cy = SUM(y) / n; d = SUM(sqrt(dx*dx + dy*dy)) / n with dx = x - cx, dy = y - cy; d zero or not finite
+ *     (either side): stop = 2; s = 1.4142135623730951 / d; the normalised point is ((x - cx) * s, (y - cy) * s).  Both sides'
+ *     centroids come before either side's d is looked at.
+ *  3. Moment matrix, from 24 ordered sums.  With the member's normalised (x, y), (x', y'):  w = x'*x' + y'*y';
+ *     e = (x*x, x*y, x, y*y, y, 1.0), e_k for the index pairs k(a, b) = k(b, a) of (0,0), (0,1), (0,2), (1,1), (1,2), (2,2);
+ *       A_k = SUM(e_k);  B_k = SUM(x' * e_k);  C_k = SUM(y' * e_k);  D_k = SUM(w * e_k).
+ *     For a, b in 0 .. 2 with k = k(a, b):  M[a][b] = M[3+a][3+b] = A_k;  M[a][3+b] = +0.0;  M[a][6+b] = -B_k;
+ *     M[3+a][6+b] = -C_k;  M[6+a][6+b] = D_k;  mirrored below the diagonal blocks.  (This is A^T A of the two rows per member
+ *     of the homography section's step 2, written through its block structure; the definition above is the normative one,
+ *     not the expanded rows: the two round differently.  A_5 = SUM(1.0) = n_cur.)
+ *  4. Eigenvector.  Step 4 of the refit section verbatim on S = M: VSLAM_HREFIT_SWEEPS sweeps of the same cyclic Jacobi, a pair
+ *     with S[p][q] == 0 skipped; h = column k of V, k the smallest S[k][k] (lowest k on ties; a NaN is never smaller).
+ *  5. H_new from Hn = h (row-major) by steps 4 and 5 of the homography model verbatim - Tt^-1 Hn Tq with the (s, cx, cy) of step
+ *     2 here, Frobenius norm 1 -; the norm zero or not finite: stop = 3.  Sign: w = (H[2][0]*cqx + H[2][1]*cqy) + H[2][2] with
+ *     (cqx, cqy) the query centroid of step 2, in pixels; neither w > 0 nor w < 0: stop = 3; w < 0: all nine entries negated.
+ *     G_new = adj(H_new) by the nine expressions of step 7 there; wg = (G[2][0]*ctx + G[2][1]*cty) + G[2][2] with the train
+ *     centroid; wg zero or not finite: stop = 3; wg < 0: all nine entries of G negated.
+ *  6. n_new = the number of members under (H_new, G_new).  n_new >= n_cur: (H_cur, G_cur) = (H_new, G_new), n_cur = n_new,
+ *     accepted += 1; otherwise stop = 4.
+ * All rounds done without a stop: stop = 0.  After a stop the pair does nothing more.  Output: models[j] = models_in[j] with
+ * H = H_cur, G = G_cur and n_inliers = n_cur (n_matches, best, n_valid copied); n_after = n_cur >= n_before.  The inlier outputs
+ * are the members under the output (H, G), whatever its stop.
+ * Verdict.  With epipolar_models, n_epipolar and degenerate of models[j] are computed again by the homography section's
+ * integer rule from the new n_inliers, and gated_models - optional, may be the very pointer passed as epipolar_models - is
+ * the gate under that verdict.  Without epipolar_models both fields are copied from models_in[j].
+ * VSLAM_HREFIT_SWEEPS was fixed by measurement, as VSLAM_REFIT_SWEEPS was: from 7 sweeps on, every sweep count
+ * up to 20 gives the same h bit for bit on every planted scene and hostile fixture of the tests; the constant is that plus
+ * two. */
+#define VSLAM_HREFIT_SWEEPS 9
+typedef struct {
+    uint32_t rounds;         /* 1 .. 8 */
+    double max_dist2;        /* as vslam_homography_params: squared transfer error in pixels^2, each direction; finite and positive */
+    uint32_t degenerate_num; /* the verdict's ratio, as vslam_homography_params; read only with epipolar_models */
+    uint32_t degenerate_den; /* > 0 with epipolar_models */
+    uint32_t min_inliers;    /* fewer H-inliers than this: never degenerate */
+} vslam_hrefit_params;
+typedef struct {
+    uint32_t n_before, n_after; /* members under the input (H, G) / under the output (H, G) */
+    uint32_t accepted;          /* rounds whose refit was kept */
+    int32_t stop;               /* 0: ran all rounds, 1: fewer than 4 members, 2: degenerate normalisation, 3: model invalid
+                                 * (step 5), 4: the refit had fewer inliers, 5: no input model */
+} vslam_hrefit;                 /* 16 bytes: the fields and stop codes of vslam_refit */
+/* Like vslam_refit_out: every pointer with the bytes behind it, checked before anything is launched. */
+typedef struct {
+    size_t struct_size;        /* = sizeof(vslam_hrefit_out) */
+    vslam_homography* models;  /* [n_pairs], required; may be the very pointer passed as models_in, must not otherwise overlap it */
+    size_t models_bytes;
+    vslam_hrefit* info;        /* [n_pairs] optional */
+    size_t info_bytes;
+    uint64_t* inlier_bits;     /* [n_pairs][(match_cap + 63) / 64] optional: bit i % 64 of word i / 64 = record i is a member under
+                                * the output (H, G); the first (n_matches + 63) / 64 words of a pair are written, the rest untouched */
+    size_t inlier_bits_bytes;
+    vslam_match* inliers;      /* [n_pairs][inlier_cap] optional: the member records, list order kept */
+    size_t inliers_bytes;
+    uint32_t* inlier_counts;   /* [n_pairs], required with inliers: totals (may exceed inlier_cap) */
+    size_t inlier_counts_bytes;
+    uint32_t inlier_cap;
+    vslam_epipolar* gated_models; /* [n_pairs] optional, needs epipolar_models: the gate under the new verdict; may be the very
+                                   * pointer passed as epipolar_models, must not otherwise overlap it */
+    size_t gated_models_bytes;
+} vslam_hrefit_out;
+/* Pair j reads models_in[j], the lists as vslam_homography_dev does (DEVICE pointers) and, when given, epipolar_models[j].
+ * Asynchronous on the context stream, never waits on the host (the counts are read on the device, the grids are sized from
+ * the capacities, a stopped pair's workgroups leave at once); scratch belongs to the context.  VSLAM_ERR_INVALID before any
+ * launch - and before the context is looked at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does
+ * nothing), rounds outside 1 .. 8, a max_dist2 that is not finite or not positive, degenerate_den == 0 with epipolar_models,
+ * match_cap / query_cap / train_cap == 0, an undersized buffer, inliers without inlier_counts or with inlier_cap == 0,
+ * gated_models without epipolar_models; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_hrefit_dev(vslam_ctx* ctx, const vslam_homography* models_in, const vslam_match* matches, const uint32_t* match_counts,
+                     uint32_t match_cap, const vslam_point* query_points, uint32_t query_cap, const vslam_point* train_points,
+                     uint32_t train_cap, int n_pairs, const vslam_epipolar* epipolar_models, const vslam_hrefit_params* params,
+                     const vslam_hrefit_out* out);
+/* One pair in HOST memory, synchronous (a convenience path: device buffers per call).  model_in and model are required (they
+ * may be the same record); epipolar_model (one record, the verdict's input), info, inlier_bits [(n_matches + 63) / 64],
+ * (inliers [inlier_cap], n_inliers) and gated_model (one record, needs epipolar_model) are each optional; *n_inliers is the
+ * total, which may exceed inlier_cap.  n_query / n_train are the capacities the indices are checked against.  Errors as for
+ * vslam_hrefit_dev. */
+int vslam_hrefit_host(vslam_ctx* ctx, const vslam_homography* model_in, const vslam_match* matches, size_t n_matches,
+                      const vslam_point* query_points, size_t n_query, const vslam_point* train_points, size_t n_train,
+                      const vslam_epipolar* epipolar_model, const vslam_hrefit_params* params, vslam_homography* model,
+                      vslam_hrefit* info, uint64_t* inlier_bits, vslam_match* inliers, size_t inlier_cap, size_t* n_inliers,
+                      vslam_epipolar* gated_model);
 
 /* ---------------------------------------------------------------- guided matching under H or F
  * The guided pass for every pair of a batch, under the model that applies to it.  A pair the gate above judged degenerate - a
@@ -1153,7 +1258,8 @@ int vslam_pose_host(vslam_ctx* ctx, const vslam_epipolar* model, const vslam_mat
  * intended one is the inliers / inlier_counts / inlier_cap of vslam_epipolar_dev, which the gate leaves in place): row i of
  * points and bit i of front_bits then mean the same record for every pair, however it got its pose.  A pure rotation has no
  * baseline to triangulate from: it gets its rotation in `info`, the "no pose" record in poses, and still breaks the
- * trajectory's segment.  No refit of H, no plane carried from pair to pair.  Convention, coordinates, "trusted" and
+ * trajectory's segment.  H is decomposed as it is given (vslam_hrefit_dev refits it first), no plane carried from pair to pair.
+ * Convention, coordinates, "trusted" and
  * m = min(match_counts[j], match_cap) are the relative pose section's; the arithmetic is fixed here so that a CPU can restate
  * it bit for bit (tests/hposeref.py): IEEE f64, every + - * / sqrt rounded on its own (no fused multiply-add), sums left to
  * right as written.  Matrices are row-major, M[i][j] = M[3*i + j]; V[:, k] is column k.

@@ -42,6 +42,7 @@ GUIDED_PARAMS_DTYPE = np.dtype([("ratio2", "<f4"), ("max_desc_dist2", "<f4"), ("
 GUIDED_HF_PARAMS_DTYPE = np.dtype([("ratio2", "<f4"), ("max_desc_dist2", "<f4"), ("max_dist2", "<f8"), ("max_transfer2", "<f8"), ("same_octave", "<i4"),
                                    ("reserved", "<u4")], align=True)  # vslam_guided_hf_params, 32 bytes
 REFIT_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4")], align=True)  # vslam_refit, 16 bytes
+HREFIT_DTYPE = REFIT_DTYPE  # vslam_hrefit, 16 bytes: the fields and stop codes of vslam_refit
 POSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_pose_cand, 104 bytes
 POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_front", "<u4"), ("best", "<i4"), ("valid", "<i4")], align=True)  # vslam_pose, 112 bytes
 HPOSE_CAND_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n", "<f8", (3,)), ("front", "<u4"), ("valid", "<i4")], align=True)  # vslam_hpose_cand, 128 bytes
@@ -206,6 +207,23 @@ class HomographyOut(C.Structure):
                 ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t), ("inlier_counts", C.c_void_p),
                 ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t),
                 ("gated_models", C.c_void_p), ("gated_models_bytes", C.c_size_t)]
+
+
+class HRefitParams(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("max_dist2", C.c_double), ("degenerate_num", C.c_uint32), ("degenerate_den", C.c_uint32),
+                ("min_inliers", C.c_uint32)]
+
+
+class HRefit(C.Structure):
+    _fields_ = [("n_before", C.c_uint32), ("n_after", C.c_uint32), ("accepted", C.c_uint32), ("stop", C.c_int32)]
+
+
+class HRefitOut(C.Structure):
+    """vslam_hrefit_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("info", C.c_void_p), ("info_bytes", C.c_size_t),
+                ("inlier_bits", C.c_void_p), ("inlier_bits_bytes", C.c_size_t), ("inliers", C.c_void_p), ("inliers_bytes", C.c_size_t),
+                ("inlier_counts", C.c_void_p), ("inlier_counts_bytes", C.c_size_t), ("inlier_cap", C.c_uint32), ("gated_models", C.c_void_p),
+                ("gated_models_bytes", C.c_size_t)]
 
 
 class PoseParams(C.Structure):
@@ -421,6 +439,8 @@ SIGNATURES = {
     "vslam_refit_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(RefitParams), _P, _P, _P, _P, _Z, C.POINTER(_Z)]),
     "vslam_homography_dev": (_I, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, _P, C.POINTER(HomographyParams), C.POINTER(HomographyOut)]),
     "vslam_homography_host": (_I, [_P, _P, _Z, _P, _Z, _P, _Z, _P, C.POINTER(HomographyParams), _P, _P, _P, _Z, C.POINTER(_Z), _P, _P]),
+    "vslam_hrefit_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, _P, C.POINTER(HRefitParams), C.POINTER(HRefitOut)]),
+    "vslam_hrefit_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, _P, C.POINTER(HRefitParams), _P, _P, _P, _P, _Z, C.POINTER(_Z), _P]),
     "vslam_pose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, C.POINTER(PoseParams), C.POINTER(PoseOut)]),
     "vslam_pose_host": (_I, [_P, _P, _P, _Z, _P, _Z, _P, _Z, C.POINTER(PoseParams), _P, _P, _P, _P]),
     "vslam_hpose_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _I, _P, C.POINTER(HposeParams), C.POINTER(HposeOut)]),
@@ -1316,6 +1336,55 @@ class Context:
                                               C.byref(total) if want_inliers else None, _ptr(hyp), None if gated is None else gated.ctypes.data),
                   "vslam_homography_host")
         return (model[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None, hyp,
+                None if gated is None else gated[0])
+
+    def hrefit(self, models_in, matches, match_counts, query_points, train_points, n_pairs: int | None = None, rounds: int = 4, max_dist2: float = 4.0,
+               degenerate_num: int = 1, degenerate_den: int = 2, min_inliers: int = 16, epipolar_models=None, models=None, info=None,
+               inlier_bits=None, inliers=None, inlier_counts=None, gated_models=None):
+        """vslam_hrefit_dev: the least-squares refit of every pair's homography over its inliers, after homography() and before
+        match_guided_hf() / hpose(); asynchronous on the context stream.  models_in: the tensor homography() wrote; matches /
+        match_counts: the FULL list homography() read.  With epipolar_models (the tensor epipolar() or refit() wrote) the verdict is
+        computed again from the new inlier count.  Outputs, CUDA tensors: models n_pairs * 168 bytes (may be models_in itself), info
+        n_pairs * 16 bytes (HREFIT_DTYPE), inlier_bits / inliers / inlier_counts as homography()'s, under the output (H, G),
+        gated_models n_pairs * 88 bytes (may be epipolar_models itself)."""
+        outs = dict(models=models, info=info, inlier_bits=inlier_bits, inliers=inliers, inlier_counts=inlier_counts, gated_models=gated_models)
+        n = self._two_view_lists("hrefit", n_pairs, "models", dict(models_in=models_in, matches=matches, match_counts=match_counts, query_points=query_points, train_points=train_points, epipolar_models=epipolar_models, **outs))
+        if models_in.numel() * models_in.element_size() < n * 168:
+            raise ValueError("hrefit: models_in must hold n_pairs * 168 bytes")
+        if epipolar_models is not None and epipolar_models.numel() * epipolar_models.element_size() < n * 88:
+            raise ValueError("hrefit: epipolar_models must hold n_pairs * 88 bytes")
+        ro = _fill_out(HRefitOut(), outs)
+        if inliers is not None:
+            ro.inlier_cap = inliers.shape[1]
+        prm = HRefitParams(int(rounds), float(max_dist2), int(degenerate_num), int(degenerate_den), int(min_inliers))
+        self._chk(lib().vslam_hrefit_dev(self._h, models_in.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), matches.shape[1],
+                                         query_points.data_ptr(), query_points.shape[1], train_points.data_ptr(), train_points.shape[1], n,
+                                         None if epipolar_models is None else epipolar_models.data_ptr(), C.byref(prm), C.byref(ro)),
+                  "vslam_hrefit_dev")
+
+    def hrefit_host(self, model, matches, query_points, train_points, rounds: int = 4, max_dist2: float = 4.0, degenerate_num: int = 1,
+                    degenerate_den: int = 2, min_inliers: int = 16, epipolar_model=None, inlier_cap: int | None = None, want_bits: bool = True,
+                    want_inliers: bool = True):
+        """vslam_hrefit_host: one pair of numpy arrays (one HOMOGRAPHY_DTYPE record, MATCH_DTYPE, POINT_DTYPE, POINT_DTYPE; epipolar_model:
+        one EPIPOLAR_DTYPE record or None) -> (model: one HOMOGRAPHY_DTYPE record, info: one HREFIT_DTYPE record, inlier_bits uint64
+        [(m + 63) // 64] or None, inliers MATCH_DTYPE or None, total inliers or None, gated model: one EPIPOLAR_DTYPE record, or None
+        without epipolar_model)."""
+        mod = np.ascontiguousarray(model, dtype=HOMOGRAPHY_DTYPE).reshape(-1)[:1]
+        mt, qp, tp = _host_lists(matches, query_points, train_points)
+        m = len(mt)
+        cap = max(m, 1) if inlier_cap is None else int(inlier_cap)
+        epi = None if epipolar_model is None else np.ascontiguousarray(epipolar_model, dtype=EPIPOLAR_DTYPE).reshape(-1)[:1]
+        out, info = np.zeros(1, HOMOGRAPHY_DTYPE), np.zeros(1, HREFIT_DTYPE)
+        gated = None if epi is None else np.zeros(1, EPIPOLAR_DTYPE)
+        bits = np.zeros((m + 63) // 64, np.uint64) if want_bits else None
+        inl = np.zeros(cap, MATCH_DTYPE) if want_inliers else None
+        total = C.c_size_t()
+        prm = HRefitParams(int(rounds), float(max_dist2), int(degenerate_num), int(degenerate_den), int(min_inliers))
+        self._chk(lib().vslam_hrefit_host(self._h, mod.ctypes.data, _ptr(mt), m, _ptr(qp), len(qp), _ptr(tp), len(tp),
+                                          None if epi is None else epi.ctypes.data, C.byref(prm), out.ctypes.data, info.ctypes.data, _ptr(bits),
+                                          None if inl is None else inl.ctypes.data, cap, C.byref(total) if want_inliers else None,
+                                          None if gated is None else gated.ctypes.data), "vslam_hrefit_host")
+        return (out[0], info[0], bits, None if inl is None else inl[: min(total.value, cap)], total.value if want_inliers else None,
                 None if gated is None else gated[0])
 
     def pose(self, models, matches, match_counts, query_points, train_points, intrinsics, n_pairs: int | None = None, poses=None, candidates=None,

@@ -4,6 +4,8 @@
 // steps 1 (E = K^T F K: the same product and norm) and 2 (the same sweeps on E^T E).  Every + - * / sqrt is an IEEE operation
 // of its own and sums run left to right: the order written here is the ABI's.  Plain C++ - G3 is __host__ __device__ under
 // hipcc and nothing elsewhere - so a host compiler runs the same text (tests/geom3_driver.cpp, against tests/epiref.py).
+// Device only, further down: what the two least-squares refits share (the block of the ordered sum, the 9 x 9 Jacobi) and what
+// the homography stages share (the transfer test, steps 4 - 7 of the homography model).
 // The callers differ in one thing, on purpose: k_pose_candidates unrolls the six sweeps fully (UNROLL = 6), k_epi_models
 // does not (UNROLL = 1) - it stands at 257 VGPRs, 80 bytes of scratch and 55296 bytes of LDS, and that budget must not grow.
 #pragma once
@@ -11,6 +13,7 @@
 #include <cstddef>
 
 #include "vslam_epipolar_plan.h"
+#include "vslam_refit_plan.h"  // the block of the ordered sum: REFIT_WG, REFIT_PER_LANE, REFIT_BLOCK
 #ifdef __HIPCC__
 #define G3 __host__ __device__
 #else
@@ -164,6 +167,111 @@ __device__ __forceinline__ void refit_tree(double (&s)[N], double* lds) {
     }
 }
 
+// What the two least-squares refits share (kernels_refit.hip.h under F, kernels_hrefit.hip.h under (H, G)): one block of the
+// ordered sum, the pair's sum of its blocks, and the cyclic Jacobi on the symmetric 9 x 9 moment matrix.
+// One block of the ordered sum: member(p) is the stage's membership predicate, add(s, p) adds a member's N terms to the slot's
+// sums, in the header's order of records.  STRIDE: the f64 per block of the stage's scratch (its widest pass).
+template <int N, int STRIDE, class Member, class Add>
+__device__ __forceinline__ void refit_block_sums(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
+                                                 double* __restrict__ partial, unsigned int sum_blocks, double* lds, Member member, Add add) {
+    const int j = blockIdx.y;
+    const unsigned int m = g3_count(counts, j, mcap);
+    const size_t first = (size_t)blockIdx.x * REFIT_BLOCK;
+    const EpiXY* src = xy + (size_t)j * mcap;
+    double s[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = 0.0;
+#pragma unroll 4
+    for (unsigned int k = 0; k < REFIT_PER_LANE; ++k) {
+        const size_t i = first + (size_t)k * REFIT_WG + threadIdx.x;
+        if (i < m) {
+            const EpiXY p = src[i];
+            if (member(p)) add(s, p);  // (a record that is not a member adds +0.0: nothing)
+        }
+    }
+    refit_tree<N>(s, lds);
+    if (threadIdx.x == 0) {
+        double* out = partial + ((size_t)j * sum_blocks + blockIdx.x) * STRIDE;
+#pragma unroll
+        for (int k = 0; k < N; ++k) out[k] = s[k];
+    }
+}
+
+// The pair's sum of N block sums, ((B_0 + B_1) + B_2) + ...; +0.0 without a block.
+template <int N, int STRIDE>
+__device__ __forceinline__ void refit_pair_sums(const double* __restrict__ partial, int j, unsigned int sum_blocks, unsigned int m, double (&s)[N]) {
+    const unsigned int nb = (unsigned int)(((size_t)m + REFIT_BLOCK - 1) / REFIT_BLOCK);
+    const double* src = partial + (size_t)j * sum_blocks * STRIDE;
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = nb ? src[k] : 0.0;
+    for (unsigned int b = 1; b < nb; ++b) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] = s[k] + src[(size_t)b * STRIDE + k];
+    }
+}
+
+// The rest of step 2 of either refit from the pair's two distance sums: false = the normalisation is degenerate (stop 2).
+__device__ __forceinline__ bool refit_scales(const double (&s)[2], unsigned int n_cur, double& sq, double& st) {
+    const double nd = (double)n_cur;
+    const double dq = s[0] / nd, dt = s[1] / nd;
+    if (!g3_finite_nonzero(dq) || !g3_finite_nonzero(dt)) return false;
+    sq = 1.4142135623730951 / dq;
+    st = 1.4142135623730951 / dt;
+    return true;
+}
+
+// One Jacobi rotation of the pair (P, Q) of the symmetric 9 x 9 S (the upper triangle is kept: S[min][max]).  P and Q are
+// compile-time and every loop is unrolled, so S and V never leave the registers.
+template <int P, int Q>
+__device__ __forceinline__ void refit_rotate(double (&S)[9][9], double (&V)[9][9]) {
+    const double apq = S[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (S[Q][Q] - S[P][P]) / (2.0 * apq);
+    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    S[P][P] = S[P][P] - t * apq;
+    S[Q][Q] = S[Q][Q] + t * apq;
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+        if (r == P || r == Q) continue;
+        double& rp = r < P ? S[r][P] : S[P][r];
+        double& rq = r < Q ? S[r][Q] : S[Q][r];
+        const double nrp = c * rp - s * rq, nrq = s * rp + c * rq;
+        rp = nrp, rq = nrq;
+    }
+    S[P][Q] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const double vp = c * V[i][P] - s * V[i][Q], vq = s * V[i][P] + c * V[i][Q];
+        V[i][P] = vp, V[i][Q] = vq;
+    }
+}
+template <int P, int Q>
+__device__ __forceinline__ void refit_sweep_from(double (&S)[9][9], double (&V)[9][9]) {
+    refit_rotate<P, Q>(S, V);
+    if constexpr (Q < 8)
+        refit_sweep_from<P, Q + 1>(S, V);
+    else if constexpr (P < 7)
+        refit_sweep_from<P + 1, P + 2>(S, V);
+}
+// Step 4 of either refit: `sweeps` cyclic sweeps on the upper triangle of S (V comes in as the identity), then f = the column
+// of V at the smallest diagonal entry left, the lowest index on ties (a NaN is never smaller).
+__device__ __forceinline__ void refit_smallest_eigenvector(double (&S)[9][9], double (&V)[9][9], int sweeps, double (&f)[9]) {
+#pragma unroll 1
+    for (int sweep = 0; sweep < sweeps; ++sweep) refit_sweep_from<0, 1>(S, V);
+    double smin = S[0][0];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f[i] = V[i][0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k)
+        if (S[k][k] < smin) {
+            smin = S[k][k];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) f[i] = V[i][k];
+        }
+}
+
 // What the homography, pose and pose-from-homography kernels share per record (kernels_homography.hip.h, kernels_pose.hip.h,
 // kernels_hpose.hip.h): the symmetric transfer test and the two-ray solve, each stated once.
 // The inlier test of one record under (H, G); false for NaN coordinates (p2 > 0 fails) and for H = G = 0.
@@ -175,6 +283,53 @@ __device__ __forceinline__ bool hom_inlier(const double (&H)[9], const double (&
     const bool fwd = p2 > 0.0 && dx * dx + dy * dy < max_dist2 * (p2 * p2);
     const bool bwd = q2 > 0.0 && ex * ex + ey * ey < max_dist2 * (q2 * q2);
     return fwd && bwd;
+}
+
+// Steps 4 and 5 of the homography model (k_hom_models from its 4 records, k_hrefit_solve from the members): H = Tt^-1 Hn Tq
+// with Frobenius norm 1, before the sign; false: the norm is zero or not finite.
+__device__ __forceinline__ bool hom_denormalise(const double (&hn)[9], double cqx, double cqy, double sq, double ctx, double cty, double st,
+                                                double (&Hc)[9]) {
+    const double aq = -(sq * cqx), bq = -(sq * cqy), r = 1.0 / st;
+    double G1[9], M[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        G1[3 * i] = hn[3 * i] * sq, G1[3 * i + 1] = hn[3 * i + 1] * sq;
+        G1[3 * i + 2] = (hn[3 * i] * aq + hn[3 * i + 1] * bq) + hn[3 * i + 2];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        M[c] = r * G1[c] + ctx * G1[6 + c];
+        M[3 + c] = r * G1[3 + c] + cty * G1[6 + c];
+        M[6 + c] = G1[6 + c];
+    }
+    const double nrm = g3_frobenius(M);
+    if (!g3_finite_nonzero(nrm)) return false;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Hc[i] = M[i] / nrm;
+    return true;
+}
+// Step 6: H's sign from the query point (x0, y0) that must map to the front; false: neither w > 0 nor w < 0.
+__device__ __forceinline__ bool hom_sign(double (&Hc)[9], double x0, double y0) {
+    const double w = (Hc[6] * x0 + Hc[7] * y0) + Hc[8];
+    if (!(w > 0.0) && !(w < 0.0)) return false;
+    if (w < 0.0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Hc[i] = -Hc[i];
+    }
+    return true;
+}
+// Step 7: G = adj(H) with its sign from the train point (u0, v0); false: wg is zero or not finite.
+__device__ __forceinline__ bool hom_adjugate(const double (&Hc)[9], double u0, double v0, double (&Gc)[9]) {
+    Gc[0] = Hc[4] * Hc[8] - Hc[5] * Hc[7], Gc[1] = Hc[2] * Hc[7] - Hc[1] * Hc[8], Gc[2] = Hc[1] * Hc[5] - Hc[2] * Hc[4];
+    Gc[3] = Hc[5] * Hc[6] - Hc[3] * Hc[8], Gc[4] = Hc[0] * Hc[8] - Hc[2] * Hc[6], Gc[5] = Hc[2] * Hc[3] - Hc[0] * Hc[5];
+    Gc[6] = Hc[3] * Hc[7] - Hc[4] * Hc[6], Gc[7] = Hc[1] * Hc[6] - Hc[0] * Hc[7], Gc[8] = Hc[0] * Hc[4] - Hc[1] * Hc[3];
+    const double wg = (Gc[6] * u0 + Gc[7] * v0) + Gc[8];
+    if (!g3_finite_nonzero(fabs(wg))) return false;
+    if (wg < 0.0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Gc[i] = -Gc[i];
+    }
+    return true;
 }
 
 // The two rays of one record (step 5): q = (q0, q1, 1), b = (b0, b1, 1).

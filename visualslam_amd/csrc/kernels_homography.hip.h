@@ -138,44 +138,13 @@ __global__ __launch_bounds__(HOM_MODEL_WG) void k_hom_models(const EpiXY* __rest
         double hn[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) hn[i] = a[i][l];
-        // 4. undo the normalisation: M = Tt^-1 Hn Tq
-        const double aq = -(sq * cqx), bq = -(sq * cqy), r = 1.0 / st;
-        double G1[9], M[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            G1[3 * i] = hn[3 * i] * sq, G1[3 * i + 1] = hn[3 * i + 1] * sq;
-            G1[3 * i + 2] = (hn[3 * i] * aq + hn[3 * i + 1] * bq) + hn[3 * i + 2];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            M[c] = r * G1[c] + ctx * G1[6 + c];
-            M[3 + c] = r * G1[3 + c] + cty * G1[6 + c];
-            M[6 + c] = G1[6 + c];
-        }
-        // 5. Frobenius norm 1
-        const double nrm = g3_frobenius(M);
-        if (!g3_finite_nonzero(nrm)) break;
+        // 4. - 7. the normalisation undone, Frobenius norm 1, the sign (the sample's first record maps to the front), and the
+        // way back G = adj(H) under the same sign rule: kernels_geom3.hip.h's, shared with the refit of H
         double Hc[9], Gc[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Hc[i] = M[i] / nrm;
-        // 6. the sign: the sample's first record maps to the front
         const EpiXY p0 = pts[0][l];
-        const double w = (Hc[6] * p0.x + Hc[7] * p0.y) + Hc[8];
-        if (!(w > 0.0) && !(w < 0.0)) break;
-        if (w < 0.0) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Hc[i] = -Hc[i];
-        }
-        // 7. the way back: G = adj(H), the same sign rule
-        Gc[0] = Hc[4] * Hc[8] - Hc[5] * Hc[7], Gc[1] = Hc[2] * Hc[7] - Hc[1] * Hc[8], Gc[2] = Hc[1] * Hc[5] - Hc[2] * Hc[4];
-        Gc[3] = Hc[5] * Hc[6] - Hc[3] * Hc[8], Gc[4] = Hc[0] * Hc[8] - Hc[2] * Hc[6], Gc[5] = Hc[2] * Hc[3] - Hc[0] * Hc[5];
-        Gc[6] = Hc[3] * Hc[7] - Hc[4] * Hc[6], Gc[7] = Hc[1] * Hc[6] - Hc[0] * Hc[7], Gc[8] = Hc[0] * Hc[4] - Hc[1] * Hc[3];
-        const double wg = (Gc[6] * p0.u + Gc[7] * p0.v) + Gc[8];
-        if (!g3_finite_nonzero(fabs(wg))) break;
-        if (wg < 0.0) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) Gc[i] = -Gc[i];
-        }
+        if (!hom_denormalise(hn, cqx, cqy, sq, ctx, cty, st, Hc)) break;
+        if (!hom_sign(Hc, p0.x, p0.y)) break;
+        if (!hom_adjugate(Hc, p0.u, p0.v, Gc)) break;
 #pragma unroll
         for (int i = 0; i < 9; ++i) H[i] = Hc[i], G[i] = Gc[i];
         ok = true;

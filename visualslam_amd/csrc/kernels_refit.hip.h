@@ -23,35 +23,9 @@
 
 namespace vslam {
 
-// (refit_tree<N>, the tree of the ordered sum over the 256 slots, is kernels_geom3.hip.h's: the resection's refinement sums the same way.)
-
-// One block of the ordered sum: add(s, p) adds a member's N terms to the slot's sums, in the header's order of records.
-template <int N, class Add>
-__device__ __forceinline__ void refit_block_sums(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
-                                                 const double (&F)[9], double max_dist2, double* __restrict__ partial, unsigned int sum_blocks,
-                                                 double* lds, Add add) {
-    const int j = blockIdx.y;
-    const unsigned int m = g3_count(counts, j, mcap);
-    const size_t first = (size_t)blockIdx.x * REFIT_BLOCK;
-    const EpiXY* src = xy + (size_t)j * mcap;
-    double s[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = 0.0;
-#pragma unroll 4
-    for (unsigned int k = 0; k < REFIT_PER_LANE; ++k) {
-        const size_t i = first + (size_t)k * REFIT_WG + threadIdx.x;
-        if (i < m) {
-            const EpiXY p = src[i];
-            if (epi_inlier(F, p, max_dist2)) add(s, p);  // (a record that is not a member adds +0.0: nothing)
-        }
-    }
-    refit_tree<N>(s, lds);
-    if (threadIdx.x == 0) {
-        double* out = partial + ((size_t)j * sum_blocks + blockIdx.x) * REFIT_SUMS;
-#pragma unroll
-        for (int k = 0; k < N; ++k) out[k] = s[k];
-    }
-}
+// (refit_tree<N>, the tree of the ordered sum over the 256 slots, is kernels_geom3.hip.h's: the resection's refinement sums the same way.
+// So are refit_block_sums, refit_pair_sums, refit_scales and the 9 x 9 Jacobi: the refit of the homography, kernels_hrefit.hip.h,
+// runs the same text under its own membership predicate.)
 
 // true: this workgroup has nothing to do - its pair has stopped, or its block lies past the pair's count.
 __device__ __forceinline__ bool refit_idle(const RefitState* __restrict__ state, const unsigned int* __restrict__ counts, unsigned int mcap) {
@@ -66,7 +40,8 @@ __global__ __launch_bounds__(REFIT_WG) void k_refit_count(const EpiXY* __restric
     double F[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) F[k] = state[blockIdx.y].Fcand[k];
-    refit_block_sums<5>(xy, counts, mcap, F, max_dist2, partial, sum_blocks, lds, [](double (&s)[5], const EpiXY& p) {
+    const auto member = [&](const EpiXY& p) { return epi_inlier(F, p, max_dist2); };
+    refit_block_sums<5, (int)REFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [](double (&s)[5], const EpiXY& p) {
         s[0] = s[0] + p.x, s[1] = s[1] + p.y, s[2] = s[2] + p.u, s[3] = s[3] + p.v, s[4] = s[4] + 1.0;
     });
 }
@@ -81,7 +56,8 @@ __global__ __launch_bounds__(REFIT_WG) void k_refit_dist(const EpiXY* __restrict
 #pragma unroll
     for (int k = 0; k < 9; ++k) F[k] = st->Fcur[k];
     const double cqx = st->cqx, cqy = st->cqy, ctx = st->ctx, cty = st->cty;
-    refit_block_sums<2>(xy, counts, mcap, F, max_dist2, partial, sum_blocks, lds, [=](double (&s)[2], const EpiXY& p) {
+    const auto member = [&](const EpiXY& p) { return epi_inlier(F, p, max_dist2); };
+    refit_block_sums<2, (int)REFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [=](double (&s)[2], const EpiXY& p) {
         const double dx = p.x - cqx, dy = p.y - cqy, du = p.u - ctx, dv = p.v - cty;
         s[0] = s[0] + sqrt(dx * dx + dy * dy);
         s[1] = s[1] + sqrt(du * du + dv * dv);
@@ -98,7 +74,8 @@ __global__ __launch_bounds__(REFIT_WG) void k_refit_moments(const EpiXY* __restr
 #pragma unroll
     for (int k = 0; k < 9; ++k) F[k] = st->Fcur[k];
     const double cqx = st->cqx, cqy = st->cqy, ctx = st->ctx, cty = st->cty, sq = st->sq, stt = st->st;
-    refit_block_sums<(int)REFIT_SUMS>(xy, counts, mcap, F, max_dist2, partial, sum_blocks, lds, [=](double (&s)[REFIT_SUMS], const EpiXY& p) {
+    const auto member = [&](const EpiXY& p) { return epi_inlier(F, p, max_dist2); };
+    refit_block_sums<(int)REFIT_SUMS, (int)REFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [=](double (&s)[REFIT_SUMS], const EpiXY& p) {
         const double x = (p.x - cqx) * sq, y = (p.y - cqy) * sq, u = (p.u - ctx) * stt, v = (p.v - cty) * stt;
         const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
         int k = 0;
@@ -108,19 +85,6 @@ __global__ __launch_bounds__(REFIT_WG) void k_refit_moments(const EpiXY* __restr
             for (int q_ = p_; q_ < 9; ++q_, ++k) s[k] = s[k] + a[p_] * a[q_];
         }
     });
-}
-
-// The pair's sum of N block sums, ((B_0 + B_1) + B_2) + ...; +0.0 without a block.
-template <int N>
-__device__ __forceinline__ void refit_pair_sums(const double* __restrict__ partial, int j, unsigned int sum_blocks, unsigned int m, double (&s)[N]) {
-    const unsigned int nb = (unsigned int)(((size_t)m + REFIT_BLOCK - 1) / REFIT_BLOCK);
-    const double* src = partial + (size_t)j * sum_blocks * REFIT_SUMS;
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = nb ? src[k] : 0.0;
-    for (unsigned int b = 1; b < nb; ++b) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k] = s[k] + src[(size_t)b * REFIT_SUMS + k];
-    }
 }
 
 // grid = (pair blocks of 64), one lane per pair - as are the three kernels after it.
@@ -147,7 +111,7 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_begin(const double* __r
     RefitState* st = state + j;
     if (st->stop == REFIT_RUNNING) {
         double s[5];
-        refit_pair_sums<5>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
+        refit_pair_sums<5, (int)REFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
         const unsigned int n = (unsigned int)s[4];
         bool running = true;
         if (r == 0) {
@@ -192,51 +156,8 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_scale(const double* __r
     RefitState* st = state + j;
     if (st->stop != REFIT_RUNNING) return;
     double s[2];
-    refit_pair_sums<2>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
-    const double nd = (double)st->n_cur;
-    const double dq = s[0] / nd, dt = s[1] / nd;
-    if (!g3_finite_nonzero(dq) || !g3_finite_nonzero(dt)) {
-        st->stop = 2;
-        return;
-    }
-    st->sq = 1.4142135623730951 / dq;
-    st->st = 1.4142135623730951 / dt;
-}
-
-// One Jacobi rotation of the pair (P, Q) of the symmetric 9 x 9 S (the upper triangle is kept: S[min][max]).  P and Q are
-// compile-time and every loop is unrolled, so S and V never leave the registers.
-template <int P, int Q>
-__device__ __forceinline__ void refit_rotate(double (&S)[9][9], double (&V)[9][9]) {
-    const double apq = S[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (S[Q][Q] - S[P][P]) / (2.0 * apq);
-    const double den = fabs(theta) + sqrt(theta * theta + 1.0);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / den;
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    S[P][P] = S[P][P] - t * apq;
-    S[Q][Q] = S[Q][Q] + t * apq;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        if (r == P || r == Q) continue;
-        double& rp = r < P ? S[r][P] : S[P][r];
-        double& rq = r < Q ? S[r][Q] : S[Q][r];
-        const double nrp = c * rp - s * rq, nrq = s * rp + c * rq;
-        rp = nrp, rq = nrq;
-    }
-    S[P][Q] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const double vp = c * V[i][P] - s * V[i][Q], vq = s * V[i][P] + c * V[i][Q];
-        V[i][P] = vp, V[i][Q] = vq;
-    }
-}
-template <int P, int Q>
-__device__ __forceinline__ void refit_sweep_from(double (&S)[9][9], double (&V)[9][9]) {
-    refit_rotate<P, Q>(S, V);
-    if constexpr (Q < 8)
-        refit_sweep_from<P, Q + 1>(S, V);
-    else if constexpr (P < 7)
-        refit_sweep_from<P + 1, P + 2>(S, V);
+    refit_pair_sums<2, (int)REFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
+    if (!refit_scales(s, st->n_cur, st->sq, st->st)) st->stop = 2;
 }
 
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_solve(const double* __restrict__ partial, unsigned int sum_blocks,
@@ -250,7 +171,7 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_solve(const double* __r
     double S[9][9], V[9][9];
     {
         double s[REFIT_SUMS];
-        refit_pair_sums<(int)REFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
+        refit_pair_sums<(int)REFIT_SUMS, (int)REFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
         int k = 0;
 #pragma unroll
         for (int p = 0; p < 9; ++p) {
@@ -261,18 +182,8 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_solve(const double* __r
         }
     }
     // 4. the eigenvector of the smallest eigenvalue
-#pragma unroll 1
-    for (int sweep = 0; sweep < VSLAM_REFIT_SWEEPS; ++sweep) refit_sweep_from<0, 1>(S, V);
-    double f[9], smin = S[0][0];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) f[i] = V[i][0];
-#pragma unroll
-    for (int k = 1; k < 9; ++k)
-        if (S[k][k] < smin) {
-            smin = S[k][k];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) f[i] = V[i][k];
-        }
+    double f[9];
+    refit_smallest_eigenvector(S, V, VSLAM_REFIT_SWEEPS, f);
     // 5. F_new: rank 2, the normalisation undone, Frobenius norm 1
     g3_rank2(f);
     const double sq = st->sq, stt = st->st;

@@ -61,6 +61,7 @@ static const char* const kKernelNames =
     "k_epi_coords\nk_epi_models\nk_epi_score\nk_epi_select\nk_epi_flags\n"
     "k_refit_init\nk_refit_count\nk_refit_begin\nk_refit_dist\nk_refit_scale\nk_refit_moments\nk_refit_solve\n"
     "k_hom_models\nk_hom_score\nk_hom_select\nk_hom_flags\nk_hom_verdict\n"
+    "k_hrefit_init\nk_hrefit_count\nk_hrefit_begin\nk_hrefit_dist\nk_hrefit_scale\nk_hrefit_moments\nk_hrefit_solve\n"
     "k_pose_candidates\nk_pose_vote\nk_pose_select\nk_pose_points\n"
     "k_hpose_candidates\nk_hpose_vote\nk_hpose_select\nk_hpose_points\n"
     "k_chain_link\nk_chain_ratio\nk_chain_median\nk_chain_walk\nk_chain_map\n"

@@ -14,6 +14,21 @@
 
 using namespace vslam;
 
+int vslam::enqueue_hom_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_homography* models,
+                             double max_dist2, int n_pairs, unsigned long long* flags) {
+    const TwoViewPlan pl = twoview_plan(match_cap, n_pairs);
+    LAUNCH(c, "k_hom_flags", k_hom_flags, dim3(pl.rec_blocks, n_pairs), dim3(TWOVIEW_REC_WG), xy, match_counts, match_cap, models, max_dist2, flags,
+           pl.fwords);
+    return VSLAM_OK;
+}
+
+int vslam::enqueue_hom_verdict(vslam_ctx* c, const vslam_epipolar* epi, int n_pairs, unsigned int num, unsigned int den, unsigned int min_inliers,
+                               vslam_homography* models, vslam_epipolar* gated) {
+    LAUNCH(c, "k_hom_verdict", k_hom_verdict, dim3(hom_pair_blocks(n_pairs)), dim3(HOM_PAIR_WG), epi, n_pairs, num,
+           den, min_inliers, models, gated);
+    return VSLAM_OK;
+}
+
 extern "C" {
 
 int vslam_homography_dev(vslam_ctx* c, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
@@ -49,11 +64,8 @@ int vslam_homography_dev(vslam_ctx* c, const vslam_match* matches, const uint32_
            prm->max_dist2, hyp);
     LAUNCH(c, "k_hom_select", k_hom_select, dim3(n_pairs), dim3(256), hyp, match_counts, match_cap, H, out->models);
     if (epipolar_models)
-        LAUNCH(c, "k_hom_verdict", k_hom_verdict, dim3(pl.pair_blocks), dim3(HOM_PAIR_WG), epipolar_models, n_pairs, prm->degenerate_num,
-               prm->degenerate_den, prm->min_inliers, out->models, out->gated_models);
-    if (lists)
-        LAUNCH(c, "k_hom_flags", k_hom_flags, dim3(pl.rec_blocks, n_pairs), dim3(TWOVIEW_REC_WG), xy, match_counts, match_cap, out->models,
-               prm->max_dist2, flags, pl.fwords);
+        TRY(enqueue_hom_verdict(c, epipolar_models, n_pairs, prm->degenerate_num, prm->degenerate_den, prm->min_inliers, out->models, out->gated_models));
+    if (lists) TRY(enqueue_hom_flags(c, xy, match_counts, match_cap, out->models, prm->max_dist2, n_pairs, flags));
     if (out->inlier_counts)
         TRY(enqueue_inlier_list(c, flags, pl.fwords, matches, match_counts, match_cap, n_pairs, chunk_ws, out->inliers, out->inlier_cap,
                                 out->inlier_counts));

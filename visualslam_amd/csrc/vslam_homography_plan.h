@@ -43,11 +43,12 @@ struct HomographyPlan : EpipolarPlan {  // (model_blocks, score_blocks, tiles, n
     unsigned int pair_blocks;           // grid.x of k_hom_verdict
 };
 
+inline unsigned int hom_pair_blocks(int n_pairs) { return (unsigned int)(((size_t)n_pairs + HOM_PAIR_WG - 1) / HOM_PAIR_WG); }
 inline HomographyPlan homography_plan(uint32_t match_cap, int n_pairs, uint32_t n_hypotheses) {
     static_assert(HOM_MODEL_WG == EPI_MODEL_WG, "model_blocks is epipolar_plan's");
     HomographyPlan p{};
     static_cast<EpipolarPlan&>(p) = epipolar_plan(match_cap, n_pairs, n_hypotheses);
-    p.pair_blocks = (unsigned int)(((size_t)n_pairs + HOM_PAIR_WG - 1) / HOM_PAIR_WG);
+    p.pair_blocks = hom_pair_blocks(n_pairs);
     return p;
 }
 

@@ -58,6 +58,14 @@ int enqueue_epi_coords(vslam_ctx* c, const vslam_match* matches, const unsigned 
 // for them under its output models): flags [n_pairs][fwords], the words that hold a record below the count.
 int enqueue_epi_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_epipolar* models,
                       double max_dist2, int n_pairs, unsigned long long* flags);
+// The inlier ballot words of every pair under (models[j].H, models[j].G) (k_hom_flags, compiled in vslam_homography.hip;
+// vslam_hrefit_dev asks for them under its output models): flags [n_pairs][fwords], the words that hold a record below the count.
+int enqueue_hom_flags(vslam_ctx* c, const EpiXY* xy, const unsigned int* match_counts, unsigned int match_cap, const vslam_homography* models,
+                      double max_dist2, int n_pairs, unsigned long long* flags);
+// The degeneracy verdict and the gate (k_hom_verdict, compiled in vslam_homography.hip; vslam_hrefit_dev runs it again over
+// its output models): models[j].n_epipolar and .degenerate from models[j].n_inliers and epi[j]; gated may be null or epi itself.
+int enqueue_hom_verdict(vslam_ctx* c, const vslam_epipolar* epi, int n_pairs, unsigned int num, unsigned int den, unsigned int min_inliers,
+                        vslam_homography* models, vslam_epipolar* gated);
 // The structure side of the multi-view stages (vslam_chain_dev, vslam_resect_dev, vslam_tracks_dev, vslam_bundle_dev): what
 // vslam_pose_dev read and wrote for n_pairs consecutive pairs, and the capacity of the frames' point lists.
 struct StructLists {

@@ -14,14 +14,16 @@
 // it then read the gated model, so a degenerate pair gets no refit and no pose.  --guided-h [max_transfer2[,ratio[,max_desc_dist2]]]
 // (after --homography; defaults 4.0, 0.8, no bound) matches again under the model that applies to the pair - the band under the
 // gated F, or a window around H x when the pair is degenerate (vslam::matchGuidedHF) - and runs the RANSAC homography on that
-// list: "guided_hf_kind", "guided_hf_matches" and "guided_hf_h_inliers".  --refit ROUNDS (after these)
+// list: "guided_hf_kind", "guided_hf_matches" and "guided_hf_h_inliers".  --hrefit ROUNDS (straight after --homography) refits H
+// over all its inliers first (vslam::refitHomography) and prints an "hrefit" object with n_before, n_after, accepted, stop, the
+// verdict run again and the new H; --guided-h and --hpose then read the refitted model and its gate.  --refit ROUNDS (after these)
 // refits that model over all its inliers (vslam::refitFundamental) and prints a "refit" object with n_before, n_after,
 // accepted, stop and the new F.  --pose fx,fy,cx,cy (after --epipolar and --refit) adds the step after that: the camera motion
 // from the inlier matches - the refit's when --refit is given - (vslam::relativePose) as a "pose" object with R, t, the winning
 // candidate and the number of inliers in front of both cameras.
 // --hpose (after --homography and --pose) adds the pose of a pair the gate removed, from H itself (vslam::poseFromHomography
 // into a copy of that pose): an "hpose" object with kind, best, ambiguous, n_support, front, front_runner and the pose it left.
-//   usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy [--hpose]]] [first.pgm second.pgm | WxH] [octaves, default 4]
+//   usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--hrefit ROUNDS] [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy [--hpose]]] [first.pgm second.pgm | WxH] [octaves, default 4]
 //          (WxH: frames 0 and 1 of the synthetic stream)
 #include <chrono>
 #include <cstdio>
@@ -85,6 +87,13 @@ int main(int argc, char** argv) {
         }
         const bool homography = epipolar && argc > 1 && std::strcmp(argv[1], "--homography") == 0;
         if (homography) --argc, ++argv;
+        vslam_hrefit_params hrefitParams{0, 4.0, 1, 2, 16};
+        const bool hrefit = homography && argc > 2 && std::strcmp(argv[1], "--hrefit") == 0;
+        if (hrefit) {
+            if (std::sscanf(argv[2], "%u", &hrefitParams.rounds) != 1 || hrefitParams.rounds < 1 || hrefitParams.rounds > 8)
+                throw std::runtime_error("--hrefit takes the number of rounds, 1 .. 8");
+            argc -= 2, argv += 2;
+        }
         vslam_guided_hf_params guidedHfParams{0.64f, HUGE_VALF, 4.0, 4.0, 0, 0};
         const bool guidedH = homography && argc > 1 && std::strcmp(argv[1], "--guided-h") == 0;
         if (guidedH) {
@@ -114,7 +123,7 @@ int main(int argc, char** argv) {
         } else if (std::sscanf(argv[1], "%dx%d", &w, &h) == 2 && w > 0 && h > 0) {
             first = imgio::synthetic(h, w, 0), second = imgio::synthetic(h, w, 1);
         } else {
-            if (argc < 3) throw std::runtime_error("usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy [--hpose]]] [first.pgm second.pgm | WxH] [octaves]");
+            if (argc < 3) throw std::runtime_error("usage: Match [--mutual] [--epipolar [--guided [D2[,RATIO[,BOUND]]]] [--homography [--hrefit ROUNDS] [--guided-h [T2[,RATIO[,BOUND]]]]] [--refit ROUNDS] [--pose fx,fy,cx,cy [--hpose]]] [first.pgm second.pgm | WxH] [octaves]");
             first = imgio::read_pgm(argv[1]), second = imgio::read_pgm(argv[2]);
             next = 3;
         }
@@ -156,12 +165,25 @@ int main(int argc, char** argv) {
                 }
                 extra += "]}";
                 model = hg.gated, hmodel = hg.model;
+                if (hrefit) {
+                    const vslam::HomographyRefit hr = vslam::refitHomography(hg.model, m.matches, q.points, t.points, hrefitParams, &e.model);
+                    std::snprintf(buf, sizeof buf, ", \"hrefit\": {\"rounds\": %u, \"n_before\": %u, \"n_after\": %u, \"accepted\": %u, \"stop\": %d, "
+                                  "\"n_epipolar\": %u, \"degenerate\": %d, \"H\": [",
+                                  hrefitParams.rounds, hr.info.n_before, hr.info.n_after, hr.info.accepted, hr.info.stop, hr.model.n_epipolar, hr.model.degenerate);
+                    extra += buf;
+                    for (int i = 0; i < 9; ++i) {
+                        std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", hr.model.H[i]);
+                        extra += buf;
+                    }
+                    extra += "]}";
+                    model = hr.gated, hmodel = hr.model;
+                }
                 if (guidedH) {
-                    const vslam::Matches g = vslam::matchGuidedHF(q.descriptors, t.descriptors, q.points, t.points, &hg.gated, &hg.model, guidedHfParams,
+                    const vslam::Matches g = vslam::matchGuidedHF(q.descriptors, t.descriptors, q.points, t.points, &model, &hmodel, guidedHfParams,
                                                                   &q.defined, &t.defined);
                     const vslam::Homography gh = vslam::findHomography(g.matches, q.points, t.points);
                     std::snprintf(buf, sizeof buf, ", \"guided_hf_kind\": \"%s\", \"guided_hf_matches\": %zu, \"guided_hf_h_inliers\": %u",
-                                  hg.gated.best >= 0 ? "F" : hg.model.best >= 0 ? "H" : "none", g.matches.size(), gh.model.n_inliers);
+                                  model.best >= 0 ? "F" : hmodel.best >= 0 ? "H" : "none", g.matches.size(), gh.model.n_inliers);
                     extra += buf;
                 }
             }

@@ -613,6 +613,23 @@ vslam::Homography vslam::findHomography(const std::vector<vslam_match>& matches,
     return out;
 }
 
+vslam::HomographyRefit vslam::refitHomography(const vslam_homography& model, const std::vector<vslam_match>& matches,
+                                              const std::vector<SLAM::point>& queryPoints, const std::vector<SLAM::point>& trainPoints,
+                                              const vslam_hrefit_params& params, const vslam_epipolar* epipolarModel) {
+    vslam::HomographyRefit out{};
+    out.inliers.resize(matches.size());
+    size_t total = 0;
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_hrefit_host(c, &model, matches.empty() ? nullptr : matches.data(), matches.size(),
+                                   reinterpret_cast<const vslam_point*>(queryPoints.data()), queryPoints.size(),
+                                   reinterpret_cast<const vslam_point*>(trainPoints.data()), trainPoints.size(), epipolarModel, &params, &out.model,
+                                   &out.info, nullptr, out.inliers.empty() ? nullptr : out.inliers.data(), out.inliers.size(), &total,
+                                   epipolarModel ? &out.gated : nullptr),
+                 c, "refitHomography");
+    out.inliers.resize(total);
+    return out;
+}
+
 vslam::Pose vslam::relativePose(const vslam_epipolar& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
                                 const std::vector<SLAM::point>& trainPoints, const vslam_pose_params& camera) {
     vslam::Pose out{};

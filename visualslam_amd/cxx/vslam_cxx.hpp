@@ -232,6 +232,21 @@ Homography findHomography(const std::vector<vslam_match>& matches, const std::ve
                           const std::vector<SLAM::point>& trainPoints, const vslam_epipolar* epipolarModel = nullptr,
                           const vslam_homography_params& params = {512, 1, 4.0, 1, 2, 16});
 
+// After findHomography: the least-squares refit of H over all its inliers, the inliers classified again, for params.rounds
+// rounds, on the GPU (vslam_hrefit_host; the 24 ordered sums, the 9 x 9 Jacobi, the signs and the acceptance rule are stated in
+// include/vslam.h, "homography: least-squares refit over the inliers").  The result never has fewer inliers than `model`.
+// With `epipolarModel` the verdict is computed again from the new inlier count and `gated` is the gate under it; feed
+// HomographyRefit::model to matchGuidedHF / poseFromHomography and HomographyRefit::gated to refitFundamental / relativePose.
+struct HomographyRefit {
+    vslam_homography model;            // `model` with the refitted H, G, their inlier count and - with epipolarModel - the new verdict
+    vslam_hrefit info;                 // inliers before and after, rounds kept, why it stopped
+    vslam_epipolar gated;              // *epipolarModel, made "no model" when the pair is degenerate; all zero without one
+    std::vector<vslam_match> inliers;  // the matches the refitted model accepts, list order kept
+};
+HomographyRefit refitHomography(const vslam_homography& model, const std::vector<vslam_match>& matches, const std::vector<SLAM::point>& queryPoints,
+                                const std::vector<SLAM::point>& trainPoints, const vslam_hrefit_params& params = {4, 4.0, 1, 2, 16},
+                                const vslam_epipolar* epipolarModel = nullptr);
+
 // A second matching pass once the pair has a model: matchDescriptors restricted, per query descriptor, to the train descriptors
 // whose keypoint lies in the query keypoint's epipolar band under model.F, on the GPU (vslam_match_guided_host; the band, the
 // selection and the acceptance with its absolute bound are stated in include/vslam.h, "guided matching").  On repeated structure
