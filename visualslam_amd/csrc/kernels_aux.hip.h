@@ -120,39 +120,52 @@ __global__ __launch_bounds__(256) void k_extrema_w3(const uint8_t* __restrict__ 
     const int yc = min(3 * li + 1, rows - 1);        // padded row i+1
     const int c0 = blockIdx.x * EXT_SPAN - 16;       // image column of staged byte 0
     // Staging: a wave takes whole staged rows (wave w: rows w, w+4, ...), lane = 16-byte piece, so
-    // the level / image row / row base are scalar and a piece costs one load and one LDS write.
+    // the level / image row / row base are scalar and a piece costs one load and one LDS write:
+    // the load's address is one add of the scalar row base and the lane's 32-bit byte offset, the
+    // write one LDS address per thread with the rounds at constant offsets.
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int cpiece = c0 + 16 * lane;
-    const bool piece_ok = lane < EXT_PITCH / 16 && cpiece >= 0 && cpiece < cols;
+    uint32_t piece = 16u * (uint32_t)lane;
+    asm volatile("" : "+v"(piece));  // (kept 32 bits wide: no 64-bit copy of it is formed in front of the rounds)
+    // columns [0, cols): the piece in front of column 0 (workgroup 0, lane 0) wraps to a huge unsigned value
+    const bool piece_ok = lane < EXT_PITCH / 16 && (uint32_t)c0 + piece < (uint32_t)cols;
+    uint8_t* const sdst = srow + wave * EXT_PITCH + piece;
 #pragma unroll
     for (int i = 0; i < (NROW + 3) / 4; ++i) {
         const int rl = wave + 4 * i;  // rl = level*2 + row
         if (rl < NROW) {
             const int lev = rl < 10 ? (rl >> 1) : rl - 9, y = rl < 10 ? ((rl & 1) ? yb : ya) : yc;
-            const uint8_t* rowp = dog + (ptrdiff_t)(int)((uint32_t)lev * P + (uint32_t)y * (uint32_t)pitch + (uint32_t)c0);  // scalar
-            if (piece_ok)
-                *reinterpret_cast<uint4*>(srow + rl * EXT_PITCH + 16 * lane) =
-                    *reinterpret_cast<const uint4*>(rowp + (uint32_t)(16 * lane));  // may end in the row padding
+            // the row base stays scalar (opaque, so that the lane's piece is not folded into a 64-bit vector address in
+            // front of the rounds, with a second 64-bit add per round behind it)
+            uint64_t rowp = reinterpret_cast<uint64_t>(dog + (ptrdiff_t)(int)((uint32_t)lev * P + (uint32_t)y * (uint32_t)pitch + (uint32_t)c0));
+            asm volatile("" : "+s"(rowp));
+            typedef uint32_t piece_t __attribute__((ext_vector_type(4)));
+            typedef const piece_t __attribute__((address_space(1))) * global_piece;  // (built from an integer: still a global load)
+            if (piece_ok) *reinterpret_cast<piece_t*>(sdst + 4 * i * EXT_PITCH) = *reinterpret_cast<global_piece>(rowp + piece);  // may end in the row padding
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x < 10)  // column -1 replicates column 0 (padOctave)
-        srow[threadIdx.x * EXT_PITCH + 15] = dog[(threadIdx.x >> 1) * P + (uint32_t)((threadIdx.x & 1) ? yb : ya) * (uint32_t)pitch];
     __syncthreads();
     const int lc = g.lat_cols[o], wpr = g.wpr[o], lr = g.lat_rows[o];
     const int lj = blockIdx.x * 256 + threadIdx.x;
+    const int word = blockIdx.x * 4 + wave;  // = lj >> 6, wave-uniform
     bool cand[3] = {false, false, false}, listed[3] = {false, false, false};
     unsigned long long wcand[3], wlist[3];
     // Every lane runs the window test (lanes past the last site read staged bytes that are there
-    // but mean nothing) and the ballots are masked by the lanes that own a site: the masks stay
-    // in scalar registers, built from the compares themselves.
-    const unsigned long long owns = __builtin_amdgcn_ballot_w64(lj < lc);
+    // but mean nothing) and the ballots are masked by the lanes that own a site: the mask is the
+    // low lc - 64 word bits, formed once on the scalar unit.
+    const int nown = lc - 64 * word;
+    const unsigned long long owns = nown >= 64 ? ~0ull : nown > 0 ? (1ull << nown) - 1ull : 0ull;
     const int xa = 3 * (int)threadIdx.x - 1 + 16;       // byte offset of column 3lj-1 in a staged row
     uint32_t self[5];
     uint32_t up[5], left[5];  // LOC: padded (i-1, j) and (i, j-1) of each level, already in the window
     {
         const uint32_t s = xa & 3;
-        const uint32_t sel = 0x0c000c00u | s | ((s + 1) << 16);  // (byte s, 0, byte s+1, 0)
-        uint32_t mn[5], mx[5];
+        // column -1 replicates column 0 (padOctave): only site 0 of a row reads it (staged byte 15 of workgroup 0, which nobody
+        // writes; s = 3 there) and takes column 0, byte 4 of its dword pair, for both columns instead
+        int xfirst = blockIdx.x == 0 ? 16 : 0;
+        asm volatile("" : "+s"(xfirst));  // (one compare against a scalar, not a select between two selector constants)
+        const uint32_t sa = s + (xa < xfirst ? 1u : 0u);
+        const uint32_t sel = 0x0c010c00u + sa + (s << 16);  // (byte sa, 0, byte s+1, 0)
+        uint32_t plo[5], phi[5];  // min / max of each level's 2x2 window, still as (a:c, b:d) pairs
 #pragma unroll
         for (int l = 0; l < 5; ++l) {
             // one address per level: the level's second row is within ds_read2_b32's offset range of the first
@@ -161,15 +174,19 @@ __global__ __launch_bounds__(256) void k_extrema_w3(const uint8_t* __restrict__ 
             const uint32_t* q0 = reinterpret_cast<const uint32_t*>(srow + off);  // 4-byte aligned: ds_read2_b32
             const uint32_t* q1 = q0 + EXT_PITCH / 4;
             const uint32_t v0 = __builtin_amdgcn_perm(q0[1], q0[0], sel), v1 = __builtin_amdgcn_perm(q1[1], q1[0], sel);  // (a,b), (c,d)
-            const uint32_t lo = pk_min_u16(v0, v1), hi = pk_max_u16(v0, v1);
-            mn[l] = min(lo & 0xffffu, lo >> 16);
-            mx[l] = max(hi & 0xffffu, hi >> 16);
+            plo[l] = pk_min_u16(v0, v1), phi[l] = pk_max_u16(v0, v1);
             self[l] = v1 >> 16;  // (i, j) itself = d
             if (LOC) up[l] = v0 >> 16, left[l] = v1 & 0xffffu;
         }
+        // the three levels of a centre's window are folded while still packed (levels 1-2 and 3-4 shared), so a centre
+        // level pays one 16-bit-lane fold for its minimum and one for its maximum
+        const uint32_t lo12 = pk_min_u16(plo[1], plo[2]), hi12 = pk_max_u16(phi[1], phi[2]);
+        const uint32_t lo34 = pk_min_u16(plo[3], plo[4]), hi34 = pk_max_u16(phi[3], phi[4]);
+        const uint32_t wlo[3] = {pk_min_u16(plo[0], lo12), pk_min_u16(lo12, plo[3]), pk_min_u16(plo[2], lo34)};
+        const uint32_t whi[3] = {pk_max_u16(phi[0], hi12), pk_max_u16(hi12, phi[3]), pk_max_u16(phi[2], hi34)};
 #pragma unroll
         for (int L = 1; L <= 3; ++L) {
-            const uint32_t lo = min(mn[L - 1], min(mn[L], mn[L + 1])), hi = max(mx[L - 1], max(mx[L], mx[L + 1]));
+            const uint32_t lo = min(wlo[L - 1] & 0xffffu, wlo[L - 1] >> 16), hi = max(whi[L - 1] & 0xffffu, whi[L - 1] >> 16);
             wcand[L - 1] = (__builtin_amdgcn_ballot_w64(self[L] == lo) | __builtin_amdgcn_ballot_w64(self[L] == hi)) & owns;
             if (LOC) cand[L - 1] = lj < lc && (self[L] == lo || self[L] == hi);
             else wlist[L - 1] = wcand[L - 1] & __builtin_amdgcn_ballot_w64((int)self[L] >= g.min_contrast);
@@ -230,18 +247,21 @@ __global__ __launch_bounds__(256) void k_extrema_w3(const uint8_t* __restrict__ 
                 if (queued[L]) listed[L] = wk[L * 64 + lane] != 0;
         }
     }
-    const int word = blockIdx.x * 4 + wave;  // = lj >> 6, wave-uniform
-    if (word < wpr) {
-        const size_t w0 = f * bframe + g.bits_off[o] + (size_t)li * wpr + word;
+    if (LOC) {
 #pragma unroll
-        for (int L = 0; L < 3; ++L) {
-            const unsigned long long wc = wcand[L], wl = LOC ? __builtin_amdgcn_ballot_w64(listed[L]) : wlist[L];
-            if (lane == 0) {
-                const size_t w = w0 + (size_t)L * lr * wpr;
-                if (bits) bits[w] = wc;
-                lflags[w] = wl;
-            }
+        for (int L = 0; L < 3; ++L) wlist[L] = __builtin_amdgcn_ballot_w64(listed[L]);
+    }
+    // lane 0 writes the wave's six words: their indices are scalar, and the three words of a kind are one base and a stride apart
+    if (word < wpr && lane == 0) {
+        const uint32_t lw = (uint32_t)lr * (uint32_t)wpr, e0 = (uint32_t)li * (uint32_t)wpr + (uint32_t)word;  // word inside the octave
+        unsigned long long* const lf = lflags + f * bframe + g.bits_off[o] + e0;
+        if (bits) {
+            unsigned long long* const bw = bits + f * bframe + g.bits_off[o] + e0;
+#pragma unroll
+            for (int L = 0; L < 3; ++L) bw[(size_t)L * lw] = wcand[L];
         }
+#pragma unroll
+        for (int L = 0; L < 3; ++L) lf[(size_t)L * lw] = wlist[L];
     }
 }
 

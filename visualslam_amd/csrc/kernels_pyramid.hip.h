@@ -29,6 +29,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "diff_taps.gen.h"
 #include "kernels_generic.hip.h"
 
 namespace vslam {
@@ -36,6 +37,7 @@ namespace vslam {
 template <int TW_, int TH_, int N0, int N1, int N2, int N3, int N4, int N5>
 struct PyrCfg {
     static constexpr int TW = TW_, TH = TH_;
+    static constexpr int DO = 0;  // octave of diff_taps.gen.h whose taps are compiled in (PyrCfgConst), 0 = taps from the device table
     static constexpr int n(int l) { return l == 0 ? N0 : l == 1 ? N1 : l == 2 ? N2 : l == 3 ? N3 : l == 4 ? N4 : N5; }
     static constexpr int cmax(int a, int b) { return a > b ? a : b; }
     static constexpr int NMAX = cmax(cmax(cmax(N0, N1), cmax(N2, N3)), cmax(N4, N5));
@@ -69,6 +71,52 @@ struct PyrTaps {
     uint32_t tp[6][CFG::TPM];
 };
 
+// Quantised taps in the operand shapes described at the top (zero outside the n taps).
+// dword m of window alignment o: byte b = taps[4m + b - o], the operand of a vertical dot4
+static inline constexpr uint32_t pack_taps_u8x4(const uint16_t* t, int n, int m, int o) {
+    uint32_t w = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int k = 4 * m + b - o;
+        if (k >= 0 && k < n) w |= (uint32_t)(t[k] & 0xff) << (8 * b);
+    }
+    return w;
+}
+// taps (e-1, e) as a u16 pair, the operand of a horizontal dot2
+static inline constexpr uint32_t pack_taps_u16x2(const uint16_t* t, int n, int e) {
+    const uint32_t lo = (e >= 1 && e - 1 < n) ? t[e - 1] : 0, hi = (e >= 0 && e < n) ? t[e] : 0;
+    return lo | (hi << 16);
+}
+
+// A configuration whose taps are those of octave O of diff_taps.gen.h, compiled in: every tap operand is a literal the
+// register allocator can form again where it needs it, instead of a loaded value it has to keep.  The wide tap sets
+// (octave 1: up to 57 taps, 60 dwords of vertical operands per level) do not fit the SGPR file next to the rest of the
+// kernel as loaded values: the table-driven instantiations park the output pointer, the store masks of a thread's four rows
+// and some of level 5's tap pairs in vector lanes (v_writelane / v_readlane).
+// The host launches such a configuration only where the plan's taps equal the header's (hd_octave_matches).
+template <class BASE, int O>
+struct PyrCfgConst : BASE {
+    static constexpr int DO = O;
+};
+
+template <class CFG, int L>
+struct PyrLevelTaps {  // PyrTaps<CFG>'s t4[L] and tp[L] of the compiled-in octave
+    uint32_t t4[4][CFG::T4M];
+    uint32_t tp[CFG::TPM];
+    constexpr PyrLevelTaps() : t4{}, tp{} {
+        using LV = dtaps::Lvl<CFG::DO, L>;
+        static_assert(LV::n == CFG::n(L), "the compiled-in taps have the configuration's widths");
+        for (int o = 0; o < 4; ++o)
+            for (int m = 0; m < CFG::T4M; ++m) t4[o][m] = pack_taps_u8x4(LV::w, LV::n, m, o);
+        for (int e = 0; e < CFG::TPM; ++e) tp[e] = pack_taps_u16x2(LV::w, LV::n, e);
+    }
+};
+
+template <class CFG, int L>
+__device__ __forceinline__ const PyrLevelTaps<CFG, L>& level_taps() {
+    static constexpr PyrLevelTaps<CFG, L> k{};
+    return k;
+}
+
 // One Gaussian level of the tile: pass 1 into hp, pass 2 into registers, pack, DoG, store.
 template <class CFG, int L>
 __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps, const uint32_t* __restrict__ rp,
@@ -80,9 +128,10 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
     constexpr int NCG = CFG::ncg(L), M = CFG::m1(L), NB = CFG::nb(L);
     constexpr int RWP = CFG::RWP, HPP = CFG::HPP, TH = CFG::TH;
     const int tid = threadIdx.x;
-    uint32_t z1;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(z1));  // pins this pass's tap loads here
-    const uint32_t* __restrict__ t4 = &taps->t4[L][0][0] + z1;
+    constexpr bool CT = CFG::DO != 0;  // compiled-in taps: literals, nothing to load or pin
+    uint32_t z1 = 0;
+    if constexpr (!CT) asm volatile("s_mov_b32 %0, 0" : "=s"(z1));  // pins this pass's tap loads here
+    const uint32_t* __restrict__ t4 = CT ? nullptr : &taps->t4[L][0][0] + z1;
     const uint4* __restrict__ rp4 = reinterpret_cast<const uint4*>(rp);
 
     // ---- pass 1: vertical, item = 4 h-columns x 4 rows -------------------------------------
@@ -114,7 +163,9 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
             for (int j = 0; j < 4; ++j) {
                 const int s = dl + j, o = s & 3, mm = m - (s >> 2);
                 if (mm >= 0 && mm <= ((o + n - 1) >> 2)) {
-                    const uint32_t t = t4[o * CFG::T4M + mm];
+                    uint32_t t;
+                    if constexpr (CT) t = level_taps<CFG, L>().t4[o][mm];
+                    else t = t4[o * CFG::T4M + mm];
                     acc[j][0] = udot4(v.x, t, acc[j][0]);
                     acc[j][1] = udot4(v.y, t, acc[j][1]);
                     acc[j][2] = udot4(v.z, t, acc[j][2]);
@@ -133,9 +184,9 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
     __syncthreads();
 
     // ---- pass 2: horizontal, item = 8 columns x 4 rows (exactly one per thread) -------------
-    uint32_t z2;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(z2));
-    const uint32_t* __restrict__ tp = &taps->tp[L][0] + z2;
+    uint32_t z2 = 0;
+    if constexpr (!CT) asm volatile("s_mov_b32 %0, 0" : "=s"(z2));
+    const uint32_t* __restrict__ tp = CT ? nullptr : &taps->tp[L][0] + z2;
     const int xg = tid % (CFG::TW / 8), rg = tid / (CFG::TW / 8);
     uint32_t acc[4][8];
 #pragma unroll
@@ -149,7 +200,7 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
         // are pinned per 8-column block instead: block b reads tp[8b-7 .. 8b+7], loaded behind an
         // opaque zero defined one block earlier, so at most two blocks' pairs are live.
         uint32_t zb = 0;
-        if (CFG::TPM > 40 && (b & 1) == 0) asm volatile("s_mov_b32 %0, 0" : "=s"(zb));
+        if (!CT && CFG::TPM > 40 && (b & 1) == 0) asm volatile("s_mov_b32 %0, 0" : "=s"(zb));
         const uint32_t* __restrict__ tpb = CFG::TPM > 40 ? tp + zb : tp;
 #pragma unroll
         for (int jr = 0; jr < 4; ++jr) {
@@ -164,7 +215,10 @@ __device__ __forceinline__ void pyr_level(const PyrTaps<CFG>* __restrict__ taps,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int e = 2 * (4 * b + pp) - j - dl + 1;  // tap pair (e-1, e)
-                    if (e >= 0 && e <= n) acc[jr][j] = udot2(vv[pp], tpb[e], acc[jr][j]);
+                    if (e >= 0 && e <= n) {
+                        if constexpr (CT) acc[jr][j] = udot2(vv[pp], level_taps<CFG, L>().tp[e], acc[jr][j]);
+                        else acc[jr][j] = udot2(vv[pp], tpb[e], acc[jr][j]);
+                    }
                 }
             }
         }
@@ -304,22 +358,7 @@ __global__ __launch_bounds__(CFG::NT) void k_pyr_octave(const uint8_t* __restric
     pyr_level<CFG, 5>(taps, rp, hp, out, P, cols, pitch, rows, tile_x0, tile_y0, prev_e, prev_o, nb, nrows, ncols, npitch, row_off);
 }
 
-// Host side: pack quantised taps into the operand shapes described at the top (zero outside the n taps).
-// dword m of window alignment o: byte b = taps[4m + b - o], the operand of a vertical dot4
-static inline uint32_t pack_taps_u8x4(const uint16_t* t, int n, int m, int o) {
-    uint32_t w = 0;
-    for (int b = 0; b < 4; ++b) {
-        const int k = 4 * m + b - o;
-        if (k >= 0 && k < n) w |= (uint32_t)(t[k] & 0xff) << (8 * b);
-    }
-    return w;
-}
-// taps (e-1, e) as a u16 pair, the operand of a horizontal dot2
-static inline uint32_t pack_taps_u16x2(const uint16_t* t, int n, int e) {
-    const uint32_t lo = (e >= 1 && e - 1 < n) ? t[e - 1] : 0, hi = (e >= 0 && e < n) ? t[e] : 0;
-    return lo | (hi << 16);
-}
-
+// Host side: the device table of a tap set.
 template <class CFG>
 static void pyr_pack_taps(const uint16_t* const t[6], PyrTaps<CFG>& out) {
     for (int l = 0; l < 6; ++l) {
@@ -338,5 +377,8 @@ using PyrCfgOct0 = PyrCfg<128, 64, 9, 13, 15, 19, 23, 29>;
 using PyrCfgOct1 = PyrCfg<128, 64, 19, 23, 29, 37, 45, 57>;
 using PyrCfgOct0W = PyrCfg<256, 32, 9, 13, 15, 19, 23, 29>;
 using PyrCfgOct1W = PyrCfg<256, 32, 19, 23, 29, 37, 45, 57>;
+// ... and octave 1 of the default pyramid with its taps compiled in (no lane spills: profiles/valu_diet_isa.txt)
+using PyrCfgOct1C = PyrCfgConst<PyrCfgOct1, 1>;
+using PyrCfgOct1WC = PyrCfgConst<PyrCfgOct1W, 1>;
 
 }  // namespace vslam

@@ -202,6 +202,7 @@ struct OctPlan {
     int nmax = 0;                   // widest of ke
     int sh = 0;                     // rows per horizontal strip workgroup (strip_plan_sh)
     int hdiff = 0;                  // octave of diff_taps.gen.h with these taps: the difference-form horizontal pass (k_gauss_h_diff)
+    int ctaps = 0;                  // octave of diff_taps.gen.h with these taps: the octave kernel with its taps compiled in (PyrCfgConst)
     int mx = 0;                     // matrix-core configuration that runs these widths (mx_config_for), 0 = none; used on the opt-in path only
 };
 }  // namespace
@@ -235,6 +236,7 @@ static OctPlan plan_octave(double sigma0, int o, int rows, int cols) {
         pl.path = OctPath::Tile0;
     } else if (matches_cfg<PyrCfgOct1>(pl.ke)) {
         pl.path = OctPath::Tile1;
+        pl.ctaps = hd_octave_matches<1>(pl.taps) ? 1 : 0;  // the default pyramid's octave 1
     } else if (nmax <= STRIP_MAXN) {
         pl.sh = strip_plan_sh(rows, cols, nmax);
         if (pl.sh) pl.path = OctPath::Strip;
@@ -462,13 +464,14 @@ static void dog_scratch_plan(WsPlan& ws, const vslam_batch_layout& L, const std:
 // Fused LDS-tiled octave (kernels_pyramid.hip.h); the plan has already matched CFG's widths.
 template <class CFG>
 static int enqueue_pyr_octave(vslam_ctx* c, double sigma0, int o, const OctPlan& pl, const OctIO& io) {
-    const PyrTaps<CFG>* taps;
-    TRY(get_table(c, kTableTile, sigma0, o, "octave kernel", sizeof(PyrTaps<CFG>), [&](void* host) -> int {
-        const uint16_t* tp[6];
-        tap_pointers(pl.taps, tp);
-        pyr_pack_taps<CFG>(tp, *static_cast<PyrTaps<CFG>*>(host));
-        return VSLAM_OK;
-    }, &taps));
+    const PyrTaps<CFG>* taps = nullptr;  // (a configuration with compiled-in taps reads no table)
+    if constexpr (CFG::DO == 0)
+        TRY(get_table(c, kTableTile, sigma0, o, "octave kernel", sizeof(PyrTaps<CFG>), [&](void* host) -> int {
+            const uint16_t* tp[6];
+            tap_pointers(pl.taps, tp);
+            pyr_pack_taps<CFG>(tp, *static_cast<PyrTaps<CFG>*>(host));
+            return VSLAM_OK;
+        }, &taps));
     TRY(raise_dyn_lds(c, reinterpret_cast<const void*>(&k_pyr_octave<CFG>)));  // once per kernel (both tile shapes share the taps)
     const dim3 grid((io.cols + CFG::TW - 1) / CFG::TW, (io.rows + CFG::TH - 1) / CFG::TH, io.nf);
     LAUNCH_ON(c, "k_pyr_octave", o, c->stream, CFG::LDS_BYTES, k_pyr_octave<CFG>, grid, dim3(CFG::NT), io.base, io.bframe, io.oct, io.pframe, io.rows,
@@ -674,6 +677,8 @@ struct DogChunk {
             }
             if (pl.path == OctPath::Tile0)
                 return shape == 1 ? enqueue_pyr_octave<PyrCfgOct0W>(c, p.sigma0, o, pl, part) : enqueue_pyr_octave<PyrCfgOct0>(c, p.sigma0, o, pl, part);
+            if (pl.ctaps == 1)  // the plan's taps are the compiled-in ones
+                return shape == 1 ? enqueue_pyr_octave<PyrCfgOct1WC>(c, p.sigma0, o, pl, part) : enqueue_pyr_octave<PyrCfgOct1C>(c, p.sigma0, o, pl, part);
             return shape == 1 ? enqueue_pyr_octave<PyrCfgOct1W>(c, p.sigma0, o, pl, part) : enqueue_pyr_octave<PyrCfgOct1>(c, p.sigma0, o, pl, part);
         };
         // opt-in matrix path: also the octaves the default path runs through the strip kernels (no u16 scratch round trip)
