@@ -1,7 +1,7 @@
 // Host driver of tests/test_guided_hf_cpu.py: the argument checks and the grid and scratch sizing of vslam_match_guided_hf_dev
 // (visualslam_amd/csrc/vslam_guided_hf_plan.h) without a GPU, built with -fsanitize=address,undefined.  It sweeps query and
 // train capacities and pair counts up to their extremes and checks, per plan: every grid dimension within HIP's limits, the
-// tiles, row blocks and ballot words cover the capacities and no more, the split within 1 .. min(train tiles, GUIDED_MAX_SPLIT)
+// tiles, row blocks and ballot words cover the capacities and no more, the split within 1 .. min(train tiles, MT_MAX_SPLIT)
 // and equal to the guided plan's, and every scratch size equal to its product computed in 128 bits (nothing wrapped).  Then
 // every rejection of the ABI over pointers it never follows, with either model array absent, each output one record short at
 // the largest call, and the order of the checks by their messages.
@@ -57,12 +57,12 @@ int main() {
             for (int np : pairs) {
                 const GuidedHfPlan p = guided_hf_plan(qc, tc, np);
                 const unsigned __int128 q = qc, t = tc, n = (unsigned)np;
-                plan.expect((unsigned __int128)p.qtiles * GUIDED_Q >= q && p.qtiles >= 1 && ((unsigned __int128)p.qtiles - 1) * GUIDED_Q < q && p.qtiles < (1u << 31), "qtiles", qc, tc, np);
-                plan.expect((unsigned __int128)p.ttiles * GUIDED_T >= t && p.ttiles >= 1 && ((unsigned __int128)p.ttiles - 1) * GUIDED_T < t, "ttiles", qc, tc, np);
-                plan.expect(p.nsplit >= 1 && p.nsplit <= GUIDED_MAX_SPLIT && p.nsplit <= p.ttiles && p.nsplit <= 65535 && p.nsplit == guided_plan(qc, tc, np).nsplit, "nsplit", qc, tc, np);
+                plan.expect((unsigned __int128)p.qtiles * MT_Q >= q && p.qtiles >= 1 && ((unsigned __int128)p.qtiles - 1) * MT_Q < q && p.qtiles < (1u << 31), "qtiles", qc, tc, np);
+                plan.expect((unsigned __int128)p.ttiles * MT_T >= t && p.ttiles >= 1 && ((unsigned __int128)p.ttiles - 1) * MT_T < t, "ttiles", qc, tc, np);
+                plan.expect(p.nsplit >= 1 && p.nsplit <= (unsigned int)MT_MAX_SPLIT && p.nsplit <= p.ttiles && p.nsplit <= 65535 && p.nsplit == guided_plan(qc, tc, np).nsplit, "nsplit", qc, tc, np);
                 plan.expect((unsigned __int128)p.fwords * 64 >= q && ((unsigned __int128)p.fwords - 1) * 64 < q, "fwords", qc, tc, np);
-                plan.expect((unsigned __int128)p.qrow_blocks * GUIDED_ROW_WG >= q && ((unsigned __int128)p.qrow_blocks - 1) * GUIDED_ROW_WG < q && p.qrow_blocks < (1u << 31), "qrow_blocks", qc, tc, np);
-                plan.expect((unsigned __int128)p.trow_blocks * GUIDED_ROW_WG >= t && ((unsigned __int128)p.trow_blocks - 1) * GUIDED_ROW_WG < t && p.trow_blocks < (1u << 31), "trow_blocks", qc, tc, np);
+                plan.expect((unsigned __int128)p.qrow_blocks * MT_ROW_WG >= q && ((unsigned __int128)p.qrow_blocks - 1) * MT_ROW_WG < q && p.qrow_blocks < (1u << 31), "qrow_blocks", qc, tc, np);
+                plan.expect((unsigned __int128)p.trow_blocks * MT_ROW_WG >= t && ((unsigned __int128)p.trow_blocks - 1) * MT_ROW_WG < t && p.trow_blocks < (1u << 31), "trow_blocks", qc, tc, np);
                 plan.expect((unsigned __int128)p.q_elems == n * q && (unsigned __int128)p.q_elems * sizeof(GuidedRow) < ((unsigned __int128)1 << 63), "q_elems", qc, tc, np);
                 plan.expect((unsigned __int128)p.t_elems == n * t && (unsigned __int128)p.t_elems * sizeof(GuidedRow) < ((unsigned __int128)1 << 63), "t_elems", qc, tc, np);
                 plan.expect((unsigned __int128)p.part_elems == n * p.nsplit * q && (unsigned __int128)p.part_elems * 12 < ((unsigned __int128)1 << 63), "part_elems", qc, tc, np);

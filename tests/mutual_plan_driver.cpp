@@ -1,7 +1,7 @@
 // Host driver of tests/test_mutual_cpu.py: the argument checks and the grid and scratch sizing of vslam_match_mutual_dev
 // (visualslam_amd/csrc/vslam_mutual_plan.h) without a GPU, built with -fsanitize=address,undefined.  It sweeps query and train
 // capacities and pair counts up to their extremes and checks, per plan: every grid dimension within HIP's limits, the tiles, row
-// blocks and ballot words cover the capacities and no more, the split within 1 .. min(train tiles, MUTUAL_MAX_SPLIT), and every
+// blocks and ballot words cover the capacities and no more, the split within 1 .. min(train tiles, MT_MAX_SPLIT), and every
 // scratch size equal to its product computed in 128 bits (nothing wrapped).  Then every rejection of the ABI over pointers it
 // never follows, with its message byte for byte, each output one record short at the largest call, and the order of the checks.
 //   driver          "plan checked=N bad=B first=...", "args checked=N bad=B first=...", and one "size ..." line per plan the
@@ -66,12 +66,12 @@ int main() {
             for (int np : pairs) {
                 const MutualPlan p = mutual_plan(qc, tc, np);
                 const unsigned __int128 q = qc, t = tc, n = (unsigned)np;
-                plan.expect((unsigned __int128)p.qtiles * MUTUAL_Q >= q && p.qtiles >= 1 && ((unsigned __int128)p.qtiles - 1) * MUTUAL_Q < q && p.qtiles < (1u << 31), "qtiles", qc, tc, np);
-                plan.expect((unsigned __int128)p.ttiles * MUTUAL_T >= t && p.ttiles >= 1 && ((unsigned __int128)p.ttiles - 1) * MUTUAL_T < t, "ttiles", qc, tc, np);
-                plan.expect(p.nsplit >= 1 && p.nsplit <= MUTUAL_MAX_SPLIT && p.nsplit <= p.ttiles && p.nsplit <= 65535, "nsplit", qc, tc, np);
+                plan.expect((unsigned __int128)p.qtiles * MT_Q >= q && p.qtiles >= 1 && ((unsigned __int128)p.qtiles - 1) * MT_Q < q && p.qtiles < (1u << 31), "qtiles", qc, tc, np);
+                plan.expect((unsigned __int128)p.ttiles * MT_T >= t && p.ttiles >= 1 && ((unsigned __int128)p.ttiles - 1) * MT_T < t, "ttiles", qc, tc, np);
+                plan.expect(p.nsplit >= 1 && p.nsplit <= (unsigned int)MT_MAX_SPLIT && p.nsplit <= p.ttiles && p.nsplit <= 65535, "nsplit", qc, tc, np);
                 plan.expect((unsigned __int128)p.fwords * 64 >= q && ((unsigned __int128)p.fwords - 1) * 64 < q, "fwords", qc, tc, np);
-                plan.expect((unsigned __int128)p.qrow_blocks * MUTUAL_ROW_WG >= q && ((unsigned __int128)p.qrow_blocks - 1) * MUTUAL_ROW_WG < q && p.qrow_blocks < (1u << 31), "qrow_blocks", qc, tc, np);
-                plan.expect((unsigned __int128)p.trow_blocks * MUTUAL_ROW_WG >= t && ((unsigned __int128)p.trow_blocks - 1) * MUTUAL_ROW_WG < t && p.trow_blocks < (1u << 31), "trow_blocks", qc, tc, np);
+                plan.expect((unsigned __int128)p.qrow_blocks * MT_ROW_WG >= q && ((unsigned __int128)p.qrow_blocks - 1) * MT_ROW_WG < q && p.qrow_blocks < (1u << 31), "qrow_blocks", qc, tc, np);
+                plan.expect((unsigned __int128)p.trow_blocks * MT_ROW_WG >= t && ((unsigned __int128)p.trow_blocks - 1) * MT_ROW_WG < t && p.trow_blocks < (1u << 31), "trow_blocks", qc, tc, np);
                 plan.expect((unsigned __int128)p.q_elems == n * q && (unsigned __int128)p.t_elems == n * t, "norm elems", qc, tc, np);
                 plan.expect((unsigned __int128)p.part_elems == n * p.nsplit * q && (unsigned __int128)p.part_elems * 12 < ((unsigned __int128)1 << 63), "part_elems", qc, tc, np);
                 plan.expect((unsigned __int128)p.flag_words == n * p.fwords, "flag_words", qc, tc, np);

@@ -2,8 +2,8 @@
 // the same pass the REVERSE nearest of every train row - the query row of smallest d2, ties to the lowest query index.  d2 is
 // symmetric bit for bit, so the reverse nearest is what the matcher would write with the sets swapped, and the distance tile
 // that decides it is the one the forward search already holds.
-//   k_match_nn2_mutual   : a sibling of k_match_nn2 (kernels_match.hip.h): the same tiling, split dealing, MFMA chain, forward
-//                          update and MatchPart output.  In the epilogue a lane owns one train column of a 32 x 32 block and
+//   k_match_nn2_mutual   : k_match_nn2's walk (kernels_match.hip.h) over the same shared steps (kernels_match_common.hip.h): tiling,
+//                          split dealing, MFMA chain, forward update and MatchPart output.  In the epilogue a lane owns one train column of a 32 x 32 block and
 //                          walks 16 query rows of it: the column minimum is taken in that walk, over the rows that are in use
 //                          and defined (one ballot over the wave's 32 rows, a scalar mask), as (key, q) with key the ordered
 //                          integer map of d2.  The two halves of a wave merge by one 64-bit shuffle, the four waves through LDS,
@@ -11,14 +11,14 @@
 //                          rev [pair][train.cap].  A minimum over integers: no bit of rev depends on the order the workgroups
 //                          arrive in.  With SAME_OCT the query tile's octaves live in LDS (the parent's 16 registers per lane
 //                          and the column minimum do not fit together without scratch).
-//   k_match_mutual_merge : k_match_merge's fold and ratio test; the flag is accept && rev[index] names this query row
+//   k_match_mutual_merge : match_merge_rows; the acceptance adds that rev[index] names this query row
 //   k_match_rnn_write    : rev -> vslam_rnn for the train rows in use (the key mapped back to the bits of d2)
 // rev is preset to all ones (nothing offered) before every launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
-#include "kernels_match_common.hip.h"  // MT_Q, MT_T, MT_LD, MT_MAX_SPLIT, MatchPart, match_merge
+#include "kernels_match_common.hip.h"
 
 namespace vslam {
 
@@ -51,31 +51,17 @@ __global__ __launch_bounds__(256, 2) void k_match_nn2_mutual(const vslam_desc_se
     if (qbase >= nq) return;
     const float inf = match_inf();
 
-    // operand A: row (wave, col) of the query tile, the k of this lane's half
     float a[64];
-    {
-        const unsigned int qrow = qbase + wave * 32 + col;
-        const float4* src = reinterpret_cast<const float4*>(Q.desc + ((size_t)p * Q.cap + min(qrow, nq - 1)) * 128);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-            const float4 v0 = src[2 * m], v1 = src[2 * m + 1];
-            a[4 * m + 0] = h ? v0.y : v0.x;
-            a[4 * m + 1] = h ? v0.w : v0.z;
-            a[4 * m + 2] = h ? v1.y : v1.x;
-            a[4 * m + 3] = h ? v1.w : v1.z;
-        }
-    }
-    // the 16 query rows of this lane's accumulator registers (the C / D map of the 32 x 32 forms).  Rows past nq are loaded as
-    // clamped copies of row nq - 1: the forward search never publishes them, the reverse search must not hear of them, nor of a
-    // row whose `defined` byte is 0 - wmask below says which rows take part in the column minimum.
-    const unsigned int row0 = qbase + wave * 32 + 4 * h;  // query row of r: row0 + (r & 3) + 8 * (r >> 2), ascending in r
+    match_load_a(a, Q, p, min(qbase + wave * 32 + col, nq - 1), h);
+    // the 16 query rows of this lane's accumulator registers.  Rows past nq are loaded as clamped copies of row nq - 1: the forward
+    // search never publishes them, the reverse search must not hear of them, nor of a row whose `defined` byte is 0 - wmask below
+    // says which rows take part in the column minimum.
+    const unsigned int row0 = qbase + wave * 32 + 4 * h;  // query row of r: row0 + match_cd_row(r, 0), ascending in r
     float qn[16], best[16], second[16];
     int index[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const unsigned int own = row0 + (r & 3) + 8 * (r >> 2);
-        const unsigned int qrow = min(own, nq - 1);
-        qn[r] = qnorm[(size_t)p * Q.cap + qrow];
+        qn[r] = qnorm[(size_t)p * Q.cap + min(row0 + match_cd_row(r, 0), nq - 1)];
         best[r] = second[r] = inf;
         index[r] = -1;
     }
@@ -87,43 +73,10 @@ __global__ __launch_bounds__(256, 2) void k_match_nn2_mutual(const vslam_desc_se
         wmask = (unsigned int)__ballot(own < nq && (!Q.defined || Q.defined[(size_t)p * Q.cap + own]));
     }
 
-    // one train tile: 64 rows x 16 groups of eight floats, four groups per thread; norm and octave of row t by thread t < 64
     const unsigned int ntiles = (nt + MT_T - 1) / MT_T;
     float4 pf[8];
     float pnb = 0.0f;
     int ptk = 0;
-    auto gload = [&](unsigned int tile) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int g = t + 256 * it;
-            const unsigned int j = tile * MT_T + (g >> 4);
-            if (j < nt) {
-                const float4* src = reinterpret_cast<const float4*>(T.desc + ((size_t)p * T.cap + j) * 128 + 8 * (g & 15));
-                pf[2 * it] = src[0];
-                pf[2 * it + 1] = src[1];
-            } else {
-                pf[2 * it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                pf[2 * it + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-        if (t < MT_T) {
-            const unsigned int j = tile * MT_T + t;
-            const bool alive = j < nt && (!T.defined || T.defined[(size_t)p * T.cap + j]);
-            pnb = alive ? tnorm[(size_t)p * T.cap + j] : __int_as_float(0x7fc00000);  // NaN: a skipped row never wins, either way
-            ptk = SAME_OCT && j < nt ? T.points[(size_t)p * T.cap + j].octave : 0;
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int g = t + 256 * it;
-            float4* dst = s_b + ((g >> 4) * MT_LD + 8 * (g & 15)) / 4;
-            const float4 v0 = pf[2 * it], v1 = pf[2 * it + 1];
-            dst[0] = make_float4(v0.x, v0.z, v1.x, v1.z);
-            dst[1] = make_float4(v0.y, v0.w, v1.y, v1.w);
-        }
-        if (t < MT_T) s_nb[t] = pnb, s_tk[t] = ptk;
-    };
     // the four waves' column minima of train tile `done` lie in s_rev (written before the barrier the caller has just passed, not
     // written again before the next one): wave 0 folds them and offers train row done * MT_T + lane its winner
     auto publish = [&](unsigned int done) {
@@ -139,31 +92,19 @@ __global__ __launch_bounds__(256, 2) void k_match_nn2_mutual(const vslam_desc_se
         }
     };
 
-    const float4* b0p = s_b + (col * MT_LD) / 4 + h;
-    const float4* b1p = s_b + ((32 + col) * MT_LD) / 4 + h;
+    const float4 *b0p = match_b_ptr(s_b, 0, col, h), *b1p = match_b_ptr(s_b, 1, col, h);
     unsigned int tile = split;
     bool pending = false;
-    if (tile < ntiles) gload(tile);
+    if (tile < ntiles) match_tile_gload<SAME_OCT>(pf, pnb, ptk, T, tnorm, p, nt, tile, t);
     while (tile < ntiles) {
         __syncthreads();  // the previous tile has been read, and its column minima are in s_rev
         if (pending) publish(tile - nsplit);
-        lstore();
+        match_tile_lstore(pf, pnb, ptk, s_b, s_nb, s_tk, t);
         __syncthreads();
         const unsigned int next = tile + nsplit;
-        if (next < ntiles) gload(next);  // in flight under the MFMAs
-        f32x16 acc0 = 0.0f, acc1 = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-            const float4 b0 = b0p[2 * m], b1 = b1p[2 * m];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 0], b0.x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 0], b1.x, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 1], b0.y, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 1], b1.y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 2], b0.z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 2], b1.z, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 3], b0.w, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * m + 3], b1.w, acc1, 0, 0, 0);
-        }
+        if (next < ntiles) match_tile_gload<SAME_OCT>(pf, pnb, ptk, T, tnorm, p, nt, next, t);  // in flight under the MFMAs
+        f32x16 acc0, acc1;
+        match_mfma_chain(a, b0p, b1p, acc0, acc1);
         // epilogue: this lane's train column of each block against its 16 query rows, ascending train index for the forward
         // update, ascending query row for the column minimum (a strict < keeps the lowest row of a tie; NaN and +inf never pass)
         auto select = [&](const f32x16& acc, int blk) -> unsigned long long {
@@ -182,13 +123,9 @@ __global__ __launch_bounds__(256, 2) void k_match_nn2_mutual(const vslam_desc_se
                     const int qk = (r & 3) == 0 ? qk4.x : (r & 3) == 1 ? qk4.y : (r & 3) == 2 ? qk4.z : qk4.w;
                     if (qk != tk) d2 = inf;
                 }
-                const bool lt = d2 < best[r];
-                const float s2 = d2 < second[r] ? d2 : second[r];
-                second[r] = lt ? best[r] : s2;
-                index[r] = lt ? j : index[r];
-                best[r] = lt ? d2 : best[r];
-                const bool clt = d2 < cbest && (h ? (wmask >> ((r & 3) + 8 * (r >> 2) + 4)) & 1 : (wmask >> ((r & 3) + 8 * (r >> 2))) & 1);
-                crow = clt ? (r & 3) + 8 * (r >> 2) : crow;
+                match_nn2_update(best, second, index, r, d2, j);
+                const bool clt = d2 < cbest && (h ? (wmask >> match_cd_row(r, 1)) & 1 : (wmask >> match_cd_row(r, 0)) & 1);
+                crow = clt ? match_cd_row(r, 0) : crow;
                 cbest = clt ? d2 : cbest;
             }
             return cbest < inf ? ((unsigned long long)rev_key(cbest) << 32) | (row0 + crow) : REV_NONE;
@@ -208,53 +145,15 @@ __global__ __launch_bounds__(256, 2) void k_match_nn2_mutual(const vslam_desc_se
     __syncthreads();
     if (pending) publish(tile - nsplit);
 
-    // the 32 lanes of a half hold 32 disjoint sets of train rows for the same 16 query rows
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float ob = __shfl_xor(best[r], off), os = __shfl_xor(second[r], off);
-            const int oi = __shfl_xor(index[r], off);
-            match_merge(best[r], second[r], index[r], ob, os, oi);
-        }
-    }
-    if (col == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_res[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = MatchPart{best[r], second[r], index[r]};
-    }
-    __syncthreads();
-    if (t < MT_Q && qbase + t < nq) part[((size_t)p * nsplit + split) * Q.cap + qbase + t] = s_res[t];
+    match_finish(best, second, index, s_res, part, Q, p, nsplit, split, qbase, nq, t, wave, col, h);
 }
 
-// grid = (ceil(Q.cap / 256), pairs); flags: [pair][fwords], fwords = ceil(Q.cap / 64).  rev is complete: the launch follows
-// k_match_nn2_mutual on the same stream.
+// grid = (ceil(Q.cap / MT_ROW_WG), pairs).  rev is complete: the launch follows k_match_nn2_mutual on the same stream.
 __global__ __launch_bounds__(256) void k_match_mutual_merge(const vslam_desc_sets Q, const MatchPart* __restrict__ part, int nsplit, float ratio2,
                                                              const unsigned long long* __restrict__ rev, unsigned int tcap,
                                                              vslam_nn2* __restrict__ nn, unsigned long long* __restrict__ flags, unsigned int fwords) {
-    const int p = blockIdx.y;
-    const unsigned int q = blockIdx.x * 256 + threadIdx.x;
-    const unsigned int nq = min(Q.counts[p], Q.cap);
-    const float inf = match_inf();
-    bool accept = false;
-    if (q < nq) {
-        float b = inf, s = inf;
-        int i = -1;
-        if (!Q.defined || Q.defined[(size_t)p * Q.cap + q]) {
-            for (int k = 0; k < nsplit; ++k) {
-                const MatchPart o = part[((size_t)p * nsplit + k) * Q.cap + q];
-                match_merge(b, s, i, o.best, o.second, o.index);
-            }
-        }
-        vslam_nn2 r;
-        r.index = i;
-        r.dist2 = b;
-        r.second_dist2 = s;
-        nn[(size_t)p * Q.cap + q] = r;
-        accept = i >= 0 && (s == inf || b < __fmul_rn(ratio2, s));
-        accept = accept && (unsigned int)rev[(size_t)p * tcap + (unsigned int)i] == q;  // (i < the train count <= tcap)
-    }
-    const unsigned long long w = __ballot(accept);
-    if ((threadIdx.x & 63) == 0 && q / 64 < fwords) flags[(size_t)p * fwords + q / 64] = w;
+    match_merge_rows(Q, part, nsplit, ratio2, nn, flags, fwords,
+                     [=](int p, unsigned int q, float, int i) { return (unsigned int)rev[(size_t)p * tcap + (unsigned int)i] == q; });  // (i < the train count <= tcap)
 }
 
 // grid = (ceil(T.cap / 256), pairs).  Rows past the train count are left untouched.

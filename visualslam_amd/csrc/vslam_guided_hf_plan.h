@@ -26,18 +26,8 @@ inline const char* guided_hf_check_args(const vslam_desc_sets* Q, const vslam_de
     if (epipolar_models)
         if (const char* why = check_max_dist2(prm->max_dist2)) return why;
     if (homography_models && (!std::isfinite(prm->max_transfer2) || !(prm->max_transfer2 > 0.0))) return "max_transfer2 must be finite and positive";
-    for (const vslam_desc_sets* s : {Q, T}) {
-        if (!s->desc || !s->counts || s->cap == 0) return "a descriptor set needs desc, counts and a capacity";
-        if ((reinterpret_cast<uintptr_t>(s->desc) & 15) != 0) return "desc must be 16-byte aligned";
-        if (!s->points) return "the points of both sets are required";
-    }
-    const size_t np = (size_t)n_pairs;
-    if (!out->nn && !out->match_counts) return "no output requested";
-    if (out->nn && out->nn_bytes / sizeof(vslam_nn2) < np * Q->cap) return "nn buffer too small";
-    if (out->matches && (!out->match_counts || out->match_cap == 0)) return "matches needs match_counts and a match_cap";
-    if (out->matches && out->matches_bytes / sizeof(vslam_match) < np * out->match_cap) return "matches buffer too small";
-    if (out->match_counts && out->match_counts_bytes / sizeof(uint32_t) < np) return "match_counts buffer too small";
-    return nullptr;
+    if (const char* why = match_check_sets(Q, T, "the points of both sets are required")) return why;
+    return match_check_out(out, n_pairs, Q->cap);
 }
 
 // Grids and scratch of one valid call with n_pairs >= 1: the search has k_match_guided's tiling, one GuidedRow per row and one

@@ -125,9 +125,10 @@ class WsPlan {
 }  // namespace
 
 // What the entry points that work from host memory through per-call device buffers share - DevBufs: every *_host entry point;
-// HostPair: the single-pair ones (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host); HostMirror: the
-// batched ones (vslam_chain_host, vslam_resect_host, vslam_resect_refine_host, vslam_tracks_host, vslam_bundle_host) -, and the
-// answer of a device entry point whose caller has no HIP device.
+// HostPair: the single-pair ones (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host); HostSets: the
+// matchers' (vslam_match_host and its guided and mutual forms); HostMirror: the batched ones (vslam_chain_host, vslam_resect_host,
+// vslam_resect_refine_host, vslam_tracks_host, vslam_bundle_host) -, and the answer of a device entry point whose caller has no
+// HIP device.
 namespace {
 // No context can exist without a HIP device, so a caller that has none still gets the ABI's answer for that: checked
 // after the arguments, before the context is touched.
@@ -187,6 +188,73 @@ struct HostPair {
         TRY(dev.put(c, d_cnt, &h_cnt, 1));
         mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
         fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
+        return VSLAM_OK;
+    }
+};
+
+// The two host descriptor sets and the host outputs of the single-pair matcher entry points (vslam_match_host,
+// vslam_match_guided_host, vslam_match_guided_hf_host, vslam_match_mutual_host): the device copies as a vslam_desc_sets pair with
+// a capacity of at least 1, the nn / match_counts / matches buffers of the device entry point's `out`, and their way back.
+struct HostSets {
+    const float* desc[2];  // query, train
+    const uint8_t* defined[2];
+    const vslam_point* points[2];
+    size_t n[2];
+    vslam_nn2* nn;
+    vslam_match* matches;
+    size_t match_cap, *n_matches;
+    vslam_desc_sets Q{}, T{};
+    uint32_t h_cnt[2] = {0, 0};
+
+    // with_points: the points go up too (with no rows: one unread record, so that the set has its points)
+    int upload(vslam_ctx* c, DevBufs& dev, bool with_points) {
+        vslam_desc_sets* sets[2] = {&Q, &T};
+        for (int i = 0; i < 2; ++i) {
+            h_cnt[i] = (uint32_t)n[i];
+            float* d = nullptr;
+            uint8_t* f = nullptr;
+            vslam_point* q = nullptr;
+            TRY(dev.put(c, d, desc[i], n[i] * 128));
+            if (defined[i]) TRY(dev.put(c, f, defined[i], n[i]));
+            if (with_points) TRY(dev.put(c, q, points[i], n[i]));
+            *sets[i] = vslam_desc_sets{d, f, q, nullptr, std::max<uint32_t>(h_cnt[i], 1)};
+        }
+        uint32_t* d_cnt = nullptr;
+        TRY(dev.put(c, d_cnt, h_cnt, 2));
+        Q.counts = d_cnt, T.counts = d_cnt + 1;
+        return VSLAM_OK;
+    }
+    template <typename Out>  // vslam_match_out, vslam_match_mutual_out
+    int outputs(vslam_ctx* c, DevBufs& dev, Out& out) const {
+        out.struct_size = sizeof(out);
+        if (nn) {
+            TRY(dev.get(c, out.nn, n[0]));
+            out.nn_bytes = std::max<size_t>(n[0], 1) * sizeof(vslam_nn2);
+        }
+        if (n_matches) {
+            TRY(dev.get(c, out.match_counts, 1));
+            out.match_counts_bytes = sizeof(uint32_t);
+            if (matches) {
+                TRY(dev.get(c, out.matches, match_cap));
+                out.matches_bytes = match_cap * sizeof(vslam_match);
+                out.match_cap = (uint32_t)match_cap;
+            }
+        }
+        return VSLAM_OK;
+    }
+    // After the device entry point: nn, then `also` (a whole output of the entry point's own), the total, and the clamped list.
+    template <typename Out>
+    int download(vslam_ctx* c, const Out& out, void* also = nullptr, const void* d_also = nullptr, size_t also_bytes = 0) const {
+        uint32_t total = 0;
+        if (nn && n[0]) HIPCHK(c, hipMemcpyAsync(nn, out.nn, n[0] * sizeof(vslam_nn2), hipMemcpyDeviceToHost, c->stream));
+        if (also && also_bytes) HIPCHK(c, hipMemcpyAsync(also, d_also, also_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (n_matches) HIPCHK(c, hipMemcpyAsync(&total, out.match_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (n_matches) {
+            *n_matches = total;
+            const size_t m = std::min<size_t>(total, match_cap);
+            if (matches && m) HIPCHK(c, hipMemcpy(matches, out.matches, m * sizeof(vslam_match), hipMemcpyDeviceToHost));
+        }
         return VSLAM_OK;
     }
 };

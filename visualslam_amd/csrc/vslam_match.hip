@@ -9,6 +9,7 @@
 #include "kernels_match.hip.h"
 #include "vslam_ctx.h"
 #include "vslam_launch.h"
+#include "vslam_match_plan.h"
 
 using namespace vslam;
 
@@ -26,51 +27,37 @@ int vslam_match_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_desc_set
     ARGCHK(c, out->struct_size == sizeof(vslam_match_out), "match: out->struct_size is not sizeof(vslam_match_out)");
     ARGCHK(c, n_pairs >= 0 && n_pairs <= 65535, "match: 0 .. 65535 pairs per call");
     ARGCHK(c, std::isfinite(ratio2) && ratio2 > 0.0f, "match: ratio2 must be finite and positive");
-    for (const vslam_desc_sets* s : {Q, T}) {
-        ARGCHK(c, s->desc && s->counts && s->cap > 0, "match: a descriptor set needs desc, counts and a capacity");
-        ARGCHK(c, (reinterpret_cast<uintptr_t>(s->desc) & 15) == 0, "match: desc must be 16-byte aligned");
-        ARGCHK(c, !same_octave || s->points, "match: same_octave needs the points of both sets");
-    }
-    const size_t np = (size_t)n_pairs;
-    ARGCHK(c, out->nn || out->match_counts, "match: no output requested");
-    ARGCHK(c, !out->nn || out->nn_bytes / sizeof(vslam_nn2) >= np * Q->cap, "match: nn buffer too small");
-    ARGCHK(c, !out->matches || (out->match_counts && out->match_cap > 0), "match: matches needs match_counts and a match_cap");
-    ARGCHK(c, !out->matches || out->matches_bytes / sizeof(vslam_match) >= np * out->match_cap, "match: matches buffer too small");
-    ARGCHK(c, !out->match_counts || out->match_counts_bytes / sizeof(uint32_t) >= np, "match: match_counts buffer too small");
+    const char* why = match_check_sets(Q, T, same_octave ? "same_octave needs the points of both sets" : nullptr);
+    if (!why) why = match_check_out(out, n_pairs, Q->cap);
+    if (why) return fail(c, VSLAM_ERR_INVALID, std::string("match: ") + why);
     TRY(usable_ctx(c));
     if (n_pairs == 0) return VSLAM_OK;
 
-    // Train tiles are dealt out round robin to nsplit workgroups per query tile, so that one small pair still fills the chip
-    // (the counts live on the device: the grid is sized from the capacities).  The merge is exact for any nsplit.
-    const unsigned int qtiles = (Q->cap + MT_Q - 1) / MT_Q, ttiles = (T->cap + MT_T - 1) / MT_T;
-    const size_t wgs = (size_t)qtiles * np;
-    const int nsplit = (int)std::max<size_t>(1, std::min<size_t>({(2048 + wgs - 1) / wgs, (size_t)MT_MAX_SPLIT, (size_t)ttiles}));
-    const unsigned int fwords = (Q->cap + 63) / 64;
-
+    const MatchPlan pl = match_plan(Q->cap, T->cap, n_pairs);  // (the counts live on the device: the grid is sized from the capacities)
     float *qnorm = nullptr, *tnorm = nullptr;
     MatchPart* part = nullptr;
     vslam_nn2* nn_ws = nullptr;
     unsigned long long* flags = nullptr;
     unsigned int* chunk_ws = nullptr;
     WsPlan ws;
-    ws.add(qnorm, np * Q->cap);
-    ws.add(tnorm, np * T->cap);
-    ws.add(part, np * nsplit * Q->cap);
-    if (!out->nn) ws.add(nn_ws, np * Q->cap);
-    ws.add(flags, np * fwords);
-    ws.add(chunk_ws, match_list_ws_elems(fwords, n_pairs));
+    ws.add(qnorm, pl.q_elems);
+    ws.add(tnorm, pl.t_elems);
+    ws.add(part, pl.part_elems);
+    if (!out->nn) ws.add(nn_ws, pl.q_elems);
+    ws.add(flags, pl.flag_words);
+    ws.add(chunk_ws, match_list_ws_elems(pl.fwords, n_pairs));
     TRY(ws.commit(c));
     vslam_nn2* nn = out->nn ? out->nn : nn_ws;
 
     TRY(enqueue_desc_norms(c, *Q, n_pairs, qnorm));
     TRY(enqueue_desc_norms(c, *T, n_pairs, tnorm));
-    const dim3 grid(qtiles, nsplit, n_pairs);
+    const dim3 grid(pl.qtiles, pl.nsplit, n_pairs);
     if (same_octave)
-        LAUNCH(c, "k_match_nn2", k_match_nn2<true>, grid, dim3(256), *Q, *T, qnorm, tnorm, nsplit, part);
+        LAUNCH(c, "k_match_nn2", k_match_nn2<true>, grid, dim3(256), *Q, *T, qnorm, tnorm, (int)pl.nsplit, part);
     else
-        LAUNCH(c, "k_match_nn2", k_match_nn2<false>, grid, dim3(256), *Q, *T, qnorm, tnorm, nsplit, part);
-    LAUNCH(c, "k_match_merge", k_match_merge, dim3((Q->cap + 255) / 256, n_pairs), dim3(256), *Q, part, nsplit, ratio2, nn, flags, fwords);
-    if (out->match_counts) TRY(enqueue_match_list(c, flags, fwords, nn, Q->cap, n_pairs, chunk_ws, out->matches, out->match_cap, out->match_counts));
+        LAUNCH(c, "k_match_nn2", k_match_nn2<false>, grid, dim3(256), *Q, *T, qnorm, tnorm, (int)pl.nsplit, part);
+    LAUNCH(c, "k_match_merge", k_match_merge, dim3(pl.qrow_blocks, n_pairs), dim3(MT_ROW_WG), *Q, part, (int)pl.nsplit, ratio2, nn, flags, pl.fwords);
+    if (out->match_counts) TRY(enqueue_match_list(c, flags, pl.fwords, nn, Q->cap, n_pairs, chunk_ws, out->matches, out->match_cap, out->match_counts));
     return VSLAM_OK;
 }
 
@@ -85,59 +72,13 @@ int vslam_match_host(vslam_ctx* c, const float* query, const uint8_t* query_defi
     ARGCHK(c, !matches || (n_matches && match_cap > 0), "match_host: matches needs n_matches and a match_cap");
     TRY(usable_ctx(c));
 
+    HostSets hs{{query, train}, {query_defined, train_defined}, {query_points, train_points}, {nq, nt}, nn, matches, match_cap, n_matches};
     DevBufs dev;
-    const float* d_desc[2] = {nullptr, nullptr};
-    const uint8_t* d_def[2] = {nullptr, nullptr};
-    const vslam_point* d_pts[2] = {nullptr, nullptr};
-    uint32_t* d_cnt = nullptr;
-    const float* h_desc[2] = {query, train};
-    const uint8_t* h_def[2] = {query_defined, train_defined};
-    const vslam_point* h_pts[2] = {query_points, train_points};
-    const uint32_t h_cnt[2] = {(uint32_t)nq, (uint32_t)nt};
-    for (int i = 0; i < 2; ++i) {
-        float* d = nullptr;
-        TRY(dev.put(c, d, h_desc[i], (size_t)h_cnt[i] * 128));
-        d_desc[i] = d;
-        if (h_def[i]) {
-            uint8_t* q = nullptr;
-            TRY(dev.put(c, q, h_def[i], h_cnt[i]));
-            d_def[i] = q;
-        }
-        if (same_octave) {
-            vslam_point* q = nullptr;
-            TRY(dev.put(c, q, h_pts[i], h_cnt[i]));
-            d_pts[i] = q;
-        }
-    }
-    TRY(dev.put(c, d_cnt, h_cnt, 2));
-    const vslam_desc_sets Q{d_desc[0], d_def[0], d_pts[0], d_cnt, std::max<uint32_t>(h_cnt[0], 1)};
-    const vslam_desc_sets T{d_desc[1], d_def[1], d_pts[1], d_cnt + 1, std::max<uint32_t>(h_cnt[1], 1)};
     vslam_match_out out{};
-    out.struct_size = sizeof(out);
-    if (nn) {
-        TRY(dev.get(c, out.nn, nq));
-        out.nn_bytes = std::max<size_t>(nq, 1) * sizeof(vslam_nn2);
-    }
-    if (n_matches) {
-        TRY(dev.get(c, out.match_counts, 1));
-        out.match_counts_bytes = sizeof(uint32_t);
-        if (matches) {
-            TRY(dev.get(c, out.matches, match_cap));
-            out.matches_bytes = match_cap * sizeof(vslam_match);
-            out.match_cap = (uint32_t)match_cap;
-        }
-    }
-    TRY(vslam_match_dev(c, &Q, &T, 1, ratio2, same_octave, &out));
-    uint32_t total = 0;
-    if (nn && nq) HIPCHK(c, hipMemcpyAsync(nn, out.nn, nq * sizeof(vslam_nn2), hipMemcpyDeviceToHost, c->stream));
-    if (n_matches) HIPCHK(c, hipMemcpyAsync(&total, out.match_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_matches) {
-        *n_matches = total;
-        const size_t m = std::min<size_t>(total, match_cap);
-        if (matches && m) HIPCHK(c, hipMemcpy(matches, out.matches, m * sizeof(vslam_match), hipMemcpyDeviceToHost));
-    }
-    return VSLAM_OK;
+    TRY(hs.upload(c, dev, same_octave != 0));
+    TRY(hs.outputs(c, dev, out));
+    TRY(vslam_match_dev(c, &hs.Q, &hs.T, 1, ratio2, same_octave, &out));
+    return hs.download(c, out);
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ extern "C" {
 int vslam_match_mutual_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_desc_sets* T, int n_pairs, float ratio2, int same_octave,
                            const vslam_match_mutual_out* out) {
     static_assert(sizeof(vslam_rnn) == 8 && sizeof(vslam_nn2) == 12 && sizeof(MatchPart) == 12, "record layouts");
-    static_assert(MUTUAL_Q == MT_Q && MUTUAL_T == MT_T && MUTUAL_MAX_SPLIT == MT_MAX_SPLIT && MUTUAL_T == 64, "the plan's tiling is the kernels'");
+    static_assert(MT_T == 64, "one 64-lane atomic of the reverse table per train tile");
     if (const char* why = mutual_check_args(Q, T, n_pairs, ratio2, same_octave, out)) return fail(c, VSLAM_ERR_INVALID, std::string("match_mutual: ") + why);
     TRY(usable_ctx(c));
     if (n_pairs == 0) return VSLAM_OK;
@@ -49,9 +49,9 @@ int vslam_match_mutual_dev(vslam_ctx* c, const vslam_desc_sets* Q, const vslam_d
         LAUNCH(c, "k_match_nn2_mutual", k_match_nn2_mutual<true>, grid, dim3(256), *Q, *T, qnorm, tnorm, (int)pl.nsplit, part, rev);
     else
         LAUNCH(c, "k_match_nn2_mutual", k_match_nn2_mutual<false>, grid, dim3(256), *Q, *T, qnorm, tnorm, (int)pl.nsplit, part, rev);
-    LAUNCH(c, "k_match_mutual_merge", k_match_mutual_merge, dim3(pl.qrow_blocks, n_pairs), dim3(MUTUAL_ROW_WG), *Q, part, (int)pl.nsplit, ratio2, rev, T->cap,
+    LAUNCH(c, "k_match_mutual_merge", k_match_mutual_merge, dim3(pl.qrow_blocks, n_pairs), dim3(MT_ROW_WG), *Q, part, (int)pl.nsplit, ratio2, rev, T->cap,
            nn, flags, pl.fwords);
-    if (out->rnn) LAUNCH(c, "k_match_rnn_write", k_match_rnn_write, dim3(pl.trow_blocks, n_pairs), dim3(MUTUAL_ROW_WG), *T, rev, out->rnn);
+    if (out->rnn) LAUNCH(c, "k_match_rnn_write", k_match_rnn_write, dim3(pl.trow_blocks, n_pairs), dim3(MT_ROW_WG), *T, rev, out->rnn);
     if (out->match_counts)
         TRY(enqueue_match_list(c, flags, pl.fwords, nn, Q->cap, n_pairs, chunk_ws, out->matches, out->match_cap, out->match_counts));
     return VSLAM_OK;
@@ -68,64 +68,17 @@ int vslam_match_mutual_host(vslam_ctx* c, const float* query, const uint8_t* que
     ARGCHK(c, !matches || (n_matches && match_cap > 0), "match_mutual_host: matches needs n_matches and a match_cap");
     TRY(usable_ctx(c));
 
+    HostSets hs{{query, train}, {query_defined, train_defined}, {query_points, train_points}, {nq, nt}, nn, matches, match_cap, n_matches};
     DevBufs dev;
-    const float* d_desc[2] = {nullptr, nullptr};
-    const uint8_t* d_def[2] = {nullptr, nullptr};
-    const vslam_point* d_pts[2] = {nullptr, nullptr};
-    uint32_t* d_cnt = nullptr;
-    const float* h_desc[2] = {query, train};
-    const uint8_t* h_def[2] = {query_defined, train_defined};
-    const vslam_point* h_pts[2] = {query_points, train_points};
-    const uint32_t h_cnt[2] = {(uint32_t)nq, (uint32_t)nt};
-    for (int i = 0; i < 2; ++i) {
-        float* d = nullptr;
-        TRY(dev.put(c, d, h_desc[i], (size_t)h_cnt[i] * 128));
-        d_desc[i] = d;
-        if (h_def[i]) {
-            uint8_t* q = nullptr;
-            TRY(dev.put(c, q, h_def[i], h_cnt[i]));
-            d_def[i] = q;
-        }
-        if (same_octave) {
-            vslam_point* q = nullptr;
-            TRY(dev.put(c, q, h_pts[i], h_cnt[i]));
-            d_pts[i] = q;
-        }
-    }
-    TRY(dev.put(c, d_cnt, h_cnt, 2));
-    const vslam_desc_sets Q{d_desc[0], d_def[0], d_pts[0], d_cnt, std::max<uint32_t>(h_cnt[0], 1)};
-    const vslam_desc_sets T{d_desc[1], d_def[1], d_pts[1], d_cnt + 1, std::max<uint32_t>(h_cnt[1], 1)};
     vslam_match_mutual_out out{};
-    out.struct_size = sizeof(out);
-    if (nn) {
-        TRY(dev.get(c, out.nn, nq));
-        out.nn_bytes = std::max<size_t>(nq, 1) * sizeof(vslam_nn2);
-    }
+    TRY(hs.upload(c, dev, same_octave != 0));
+    TRY(hs.outputs(c, dev, out));
     if (rnn) {
         TRY(dev.get(c, out.rnn, nt));
         out.rnn_bytes = std::max<size_t>(nt, 1) * sizeof(vslam_rnn);
     }
-    if (n_matches) {
-        TRY(dev.get(c, out.match_counts, 1));
-        out.match_counts_bytes = sizeof(uint32_t);
-        if (matches) {
-            TRY(dev.get(c, out.matches, match_cap));
-            out.matches_bytes = match_cap * sizeof(vslam_match);
-            out.match_cap = (uint32_t)match_cap;
-        }
-    }
-    TRY(vslam_match_mutual_dev(c, &Q, &T, 1, ratio2, same_octave, &out));
-    uint32_t total = 0;
-    if (nn && nq) HIPCHK(c, hipMemcpyAsync(nn, out.nn, nq * sizeof(vslam_nn2), hipMemcpyDeviceToHost, c->stream));
-    if (rnn && nt) HIPCHK(c, hipMemcpyAsync(rnn, out.rnn, nt * sizeof(vslam_rnn), hipMemcpyDeviceToHost, c->stream));
-    if (n_matches) HIPCHK(c, hipMemcpyAsync(&total, out.match_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_matches) {
-        *n_matches = total;
-        const size_t m = std::min<size_t>(total, match_cap);
-        if (matches && m) HIPCHK(c, hipMemcpy(matches, out.matches, m * sizeof(vslam_match), hipMemcpyDeviceToHost));
-    }
-    return VSLAM_OK;
+    TRY(vslam_match_mutual_dev(c, &hs.Q, &hs.T, 1, ratio2, same_octave, &out));
+    return hs.download(c, out, rnn, out.rnn, nt * sizeof(vslam_rnn));
 }
 
 }  // extern "C"
