@@ -1904,6 +1904,107 @@ int vslam_bundle_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match
                       const vslam_point* frame_points, const vslam_track* tracks_in, const vslam_track_ref* refs,
                       const vslam_bundle_cam* cams_in, const vslam_bundle_params* params, const vslam_bundle_out* out);
 
+/* ---------------------------------------------------------------- place recognition
+ * The first question of loop closure: which EARLIER frame shows the same place as this one?  Three calls answer it from the
+ * descriptor buffers of vslam_detect_batch_dev: a vocabulary of K descriptor rows sampled from the data (vslam_vocab_sample_dev),
+ * the nearest vocabulary row - the "visual word" - of every descriptor with a histogram of words per frame (vslam_words_dev), and a
+ * short list of loop candidates per frame from the histograms (vslam_place_dev).  The word search is the matcher's arithmetic; all
+ * that follows it is unsigned integer arithmetic, so a CPU restates every byte (tests/placeref.py).  Verifying a candidate is the
+ * caller's: a one-pair vslam_match_dev / vslam_epipolar_dev call on the two sets.  No output depends on vslam_ctx_set_f32_fused or
+ * vslam_ctx_set_matrix_path, or on scheduling (the histogram is built with integer atomic adds only).
+ *
+ *   Vocabulary.  Word k < K is a copy of one row of the n_sets descriptor sets: the set is s = k % n_sets, the row is
+ *     r = (((k / n_sets) * 2654435761) mod 2^32) % rows_s with rows_s = min(counts[s], cap).  The word is DEFINED iff rows_s > 0
+ *     and the row's `defined` byte is not 0 (a set without `defined`: every row is).  vocab[k] is the row's 512 bytes, or 128 times
+ *     +0.0 for a word that is not defined.  Duplicate words and NaN words are allowed: the word rule never selects the second of
+ *     two equal words, and never a NaN word.
+ *   Words.  For every set f < n_sets and row q < min(counts[f], cap): word = `index` of the descriptor matching section's
+ *     selection, with the K vocabulary rows as the train rows of every set - d2 as defined there, word index ascending, strict <,
+ *     so ties keep the lowest index and a NaN or +inf distance never wins; a word whose vocab_defined byte is 0 is skipped; a query
+ *     row whose `defined` byte is 0 gets -1.  There is no second nearest and no ratio test.  word_dist2 is that d2 (+inf with -1).
+ *     REAL DESCRIPTORS CONTAIN ALL-NaN ROWS WHOSE `defined` BYTE IS SET: every distance of such a row is NaN, so it gets word -1
+ *     and counts in no histogram bin.  A vocabulary row that holds a NaN is a dead word: no row ever gets it, its bin stays 0.
+ *     hist[f][k] = the number of rows q of set f with word k; the call zeroes all of hist first.
+ *   Place.  hist_q [nq][K] are the histograms of the frames q_first + i, hist_db [nd][K] those of the frames db_first + j (the
+ *     two may be one buffer: a batch searched in itself; or a running database of earlier batches with its own offset).
+ *       df_k    = the number of db frames j with hist_db[j][k] > 0
+ *       w_k     = 0 if df_k == 0, else the bit length of nd / df_k (integer division): 1 .. 32, an integer idf
+ *       S(i, j) = sum over k of w_k * min(hist_q[i][k], hist_db[j][k]);  Sq_i = sum of w_k * hist_q[i][k];  Sd_j likewise:
+ *                 each sum is formed in uint64 (it cannot wrap: 2^16 words * 32 * 2^32) and then saturated to 2^31 - 1
+ *       j is ELIGIBLE for i iff db_first + j + min_gap <= q_first + i, in uint64
+ *       with N = max(Sq_i, Sd_j), an eligible j is ACCEPTED iff N > 0 and S >= min_score and S * den >= num * N (uint64)
+ *       candidate a RANKS BEFORE b iff S_a * N_b > S_b * N_a (uint64), equal products: the lower db frame first
+ *     candidates[i] holds the first min(accepted, max_candidates) accepted frames of i in rank order as {db_first + j, S, N}.
+ *     The norm is the LARGER self-score: under the smaller one a frame with few descriptors is swallowed by any frame with many. */
+typedef struct {
+    size_t struct_size;  /* = sizeof(vslam_words_out) */
+    int32_t* words;      /* [n_sets][cap] optional; rows past a set's count are left untouched */
+    size_t words_bytes;
+    float* word_dist2;   /* [n_sets][cap] optional; rows past a set's count are left untouched */
+    size_t word_dist2_bytes;
+    uint32_t* hist;      /* [n_sets][K] optional; written whole */
+    size_t hist_bytes;
+} vslam_words_out;
+typedef struct {
+    int32_t frame;        /* db_first + j */
+    uint32_t score, norm; /* S(i, j), N */
+} vslam_place_cand;      /* 12 bytes */
+typedef struct {
+    uint32_t min_gap;
+    uint32_t max_candidates; /* c, 1 .. 8 */
+    uint32_t num, den;       /* den > 0 */
+    uint32_t min_score;
+    uint32_t reserved;       /* 0 */
+} vslam_place_params;       /* 24 bytes */
+typedef struct {
+    size_t struct_size;           /* = sizeof(vslam_place_out) */
+    vslam_place_cand* candidates; /* [nq][c] optional, needs cand_counts; slots past a frame's count are left untouched */
+    size_t candidates_bytes;
+    uint32_t* cand_counts;        /* [nq] optional, <= c */
+    size_t cand_counts_bytes;
+    uint32_t* weights;            /* [K] optional */
+    size_t weights_bytes;
+    uint32_t* self_q;             /* [nq] optional */
+    size_t self_q_bytes;
+    uint32_t* self_db;            /* [nd] optional */
+    size_t self_db_bytes;
+    uint32_t* scores;             /* [nq][nd] optional: S(i, j) of EVERY (i, j), eligible or not */
+    size_t scores_bytes;
+} vslam_place_out;
+/* sets: DEVICE pointers, as for vslam_match_dev (points are not read); vocab [K][128] f32, 16-byte aligned, and vocab_defined [K]
+ * are DEVICE outputs, both required.  1 <= n_sets <= 65535, 1 <= K <= 65536.  Asynchronous on the context stream, never waits on
+ * the host.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null pointer, a set without
+ * desc, counts or a capacity, a misaligned desc or vocab, n_sets or K out of range, an undersized buffer; then VSLAM_ERR_HIP when
+ * there is no usable HIP device.  Not for stream capture. */
+int vslam_vocab_sample_dev(vslam_ctx* ctx, const vslam_desc_sets* sets, int n_sets, uint32_t K, float* vocab, size_t vocab_bytes,
+                           uint8_t* vocab_defined, size_t vocab_defined_bytes);
+/* sets, vocab [K][128] (16-byte aligned) and vocab_defined [K] (NULL = every word defined): DEVICE pointers, the vocabulary a
+ * caller's own or vslam_vocab_sample_dev's.  0 <= n_sets <= 65535 (0 does nothing), 1 <= K <= 65536; at least one output.
+ * Asynchronous on the context stream, never waits on the host (the counts are read on the device, the grids are sized from the
+ * capacities); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for
+ * a null struct, a wrong struct_size, n_sets or K out of range, a set without desc, counts or a capacity, a misaligned desc or
+ * vocab, no output at all, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_words_dev(vslam_ctx* ctx, const vslam_desc_sets* sets, int n_sets, const float* vocab, const uint8_t* vocab_defined,
+                    uint32_t K, const vslam_words_out* out);
+/* The same call over HOST arrays, synchronous (a convenience path: device buffers per call): desc [n_sets][cap][128], defined
+ * [n_sets][cap] or NULL, counts [n_sets], vocab [K][128], vocab_defined [K] or NULL, and the pointers of `out`.  The rows the
+ * device call leaves untouched keep the caller's bytes.  Errors as for vslam_words_dev (no alignment is asked of host arrays). */
+int vslam_words_host(vslam_ctx* ctx, const float* desc, const uint8_t* defined, const uint32_t* counts, uint32_t cap, int n_sets,
+                     const float* vocab, const uint8_t* vocab_defined, uint32_t K, const vslam_words_out* out);
+/* DEVICE pointers.  nq, nd <= 65535 (nq == 0 does nothing; nd == 0: an empty database, every weight and count 0), 1 <= K <=
+ * 65536, q_first + nq and db_first + nd at most 2^31 (a frame id fits `frame`).  Asynchronous on the context stream, never
+ * waits on the host; scratch belongs to the context (nq * nd scores when `scores` is absent, K weights, nq + nd self-scores).
+ * A 16 x 16 tile of (i, j) without an eligible pair is not scored when `scores` is absent.  VSLAM_ERR_INVALID before any launch
+ * - and before the context is looked at - for a null struct or histogram, a wrong struct_size, nq, nd, K or a frame id out of
+ * range, max_candidates outside 1 .. 8, den == 0, reserved != 0, no output at all, candidates without cand_counts, an
+ * undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_place_dev(vslam_ctx* ctx, const uint32_t* hist_q, uint32_t nq, uint32_t q_first, const uint32_t* hist_db, uint32_t nd,
+                    uint32_t db_first, uint32_t K, const vslam_place_params* params, const vslam_place_out* out);
+/* The same call over HOST arrays, synchronous.  The candidate slots the device call leaves untouched keep the caller's bytes.
+ * Errors as for vslam_place_dev. */
+int vslam_place_host(vslam_ctx* ctx, const uint32_t* hist_q, uint32_t nq, uint32_t q_first, const uint32_t* hist_db, uint32_t nd,
+                     uint32_t db_first, uint32_t K, const vslam_place_params* params, const vslam_place_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

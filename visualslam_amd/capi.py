@@ -32,6 +32,7 @@ KP_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("response", "<f4")], align
 NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4")], align=True)  # vslam_nn2
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 RNN_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4")], align=True)  # vslam_rnn, 8 bytes
+PLACE_CAND_DTYPE = np.dtype([("frame", "<i4"), ("score", "<u4"), ("norm", "<u4")], align=True)  # vslam_place_cand, 12 bytes
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
 HOMOGRAPHY_HYP_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_homography_hyp, 152 bytes
@@ -142,6 +143,29 @@ class MatchMutualOut(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("nn", C.c_void_p), ("nn_bytes", C.c_size_t), ("rnn", C.c_void_p), ("rnn_bytes", C.c_size_t),
                 ("matches", C.c_void_p), ("matches_bytes", C.c_size_t), ("match_counts", C.c_void_p), ("match_counts_bytes", C.c_size_t),
                 ("match_cap", C.c_uint32)]
+
+
+class WordsOut(C.Structure):
+    """vslam_words_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("words", C.c_void_p), ("words_bytes", C.c_size_t), ("word_dist2", C.c_void_p),
+                ("word_dist2_bytes", C.c_size_t), ("hist", C.c_void_p), ("hist_bytes", C.c_size_t)]
+
+
+class PlaceCand(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("score", C.c_uint32), ("norm", C.c_uint32)]
+
+
+class PlaceParams(C.Structure):
+    _fields_ = [("min_gap", C.c_uint32), ("max_candidates", C.c_uint32), ("num", C.c_uint32), ("den", C.c_uint32), ("min_score", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PlaceOut(C.Structure):
+    """vslam_place_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("candidates", C.c_void_p), ("candidates_bytes", C.c_size_t), ("cand_counts", C.c_void_p),
+                ("cand_counts_bytes", C.c_size_t), ("weights", C.c_void_p), ("weights_bytes", C.c_size_t), ("self_q", C.c_void_p),
+                ("self_q_bytes", C.c_size_t), ("self_db", C.c_void_p), ("self_db_bytes", C.c_size_t), ("scores", C.c_void_p),
+                ("scores_bytes", C.c_size_t)]
 
 
 class EpipolarHyp(C.Structure):
@@ -457,6 +481,11 @@ SIGNATURES = {
     "vslam_tracks_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, C.POINTER(TracksParams), C.POINTER(TracksOut)]),
     "vslam_bundle_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, _P, _P, _P, C.POINTER(BundleParams), C.POINTER(BundleOut)]),
     "vslam_bundle_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _I, _P, _P, _P, _P, _P, C.POINTER(BundleParams), C.POINTER(BundleOut)]),
+    "vslam_vocab_sample_dev": (_I, [_P, C.POINTER(DescSets), _I, C.c_uint32, _P, _Z, _P, _Z]),
+    "vslam_words_dev": (_I, [_P, C.POINTER(DescSets), _I, _P, _P, C.c_uint32, C.POINTER(WordsOut)]),
+    "vslam_words_host": (_I, [_P, _P, _P, _P, C.c_uint32, _I, _P, _P, C.c_uint32, C.POINTER(WordsOut)]),
+    "vslam_place_dev": (_I, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlaceParams), C.POINTER(PlaceOut)]),
+    "vslam_place_host": (_I, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlaceParams), C.POINTER(PlaceOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -1691,6 +1720,117 @@ class Context:
         prm = ResectRefineParams(int(rounds), float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
         self._chk(lib().vslam_resect_refine_host(self._h, mi.ctypes.data, cs.ctypes.data, ocap, n, C.byref(prm), C.byref(ro)), "vslam_resect_refine_host")
         return models[:n], info[:n]
+
+    def vocab_sample(self, sets: DescSets, vocab, vocab_defined, n_sets: int | None = None):
+        """vslam_vocab_sample_dev: a vocabulary of K = vocab.shape[0] words copied from the rows of `sets` (desc_sets()) by the header's
+        rule; asynchronous on the context stream.  vocab: float32 [K, 128], vocab_defined: uint8 [K], both outputs."""
+        stage = "vocab_sample"
+        _check_tensors(stage, self.where, dict(vocab=vocab, vocab_defined=vocab_defined), ("vocab", "vocab_defined"))
+        if vocab.dim() != 2 or vocab.shape[1] != 128 or vocab.element_size() != 4:
+            raise ValueError(f"{stage}: vocab must be float32 [K, 128]")
+        if vocab_defined.element_size() != 1:
+            raise ValueError(f"{stage}: vocab_defined must have 1-byte elements")
+        n = sets.n if n_sets is None else int(n_sets)
+        self._chk(lib().vslam_vocab_sample_dev(self._h, C.byref(sets), n, vocab.shape[0], vocab.data_ptr(), _nbytes(vocab), vocab_defined.data_ptr(),
+                                               _nbytes(vocab_defined)), "vslam_vocab_sample_dev")
+
+    def words(self, sets: DescSets, vocab, vocab_defined=None, n_sets: int | None = None, words=None, word_dist2=None, hist=None):
+        """vslam_words_dev: the nearest word of every row of `sets` (desc_sets()) among the K = vocab.shape[0] rows of vocab (float32
+        [K, 128]; vocab_defined uint8 [K] or None); asynchronous on the context stream.  words: int32 [n_sets, cap], word_dist2: float32
+        [n_sets, cap], hist: int32 [n_sets, K] (written whole) - each optional, at least one."""
+        stage = "words"
+        outs = dict(words=words, word_dist2=word_dist2, hist=hist)
+        _check_tensors(stage, self.where, dict(vocab=vocab, vocab_defined=vocab_defined, **outs), ("vocab",))
+        if vocab.dim() != 2 or vocab.shape[1] != 128 or vocab.element_size() != 4:
+            raise ValueError(f"{stage}: vocab must be float32 [K, 128]")
+        K = vocab.shape[0]
+        if vocab_defined is not None and (vocab_defined.element_size() != 1 or vocab_defined.numel() < K):
+            raise ValueError(f"{stage}: vocab_defined must be uint8 [K]")
+        for name, t in outs.items():
+            if t is not None and t.element_size() != 4:
+                raise ValueError(f"{stage}: {name} must have 4-byte elements")
+        if words is None and word_dist2 is None and hist is None:
+            raise ValueError(f"{stage}: no output requested")
+        n = sets.n if n_sets is None else int(n_sets)
+        _check_sets(stage, n, (), (), ((words, n * sets.cap * 4), (word_dist2, n * sets.cap * 4), (hist, n * K * 4)))
+        wo = _fill_out(WordsOut(), outs)
+        self._chk(lib().vslam_words_dev(self._h, C.byref(sets), n, vocab.data_ptr(), vocab_defined.data_ptr() if vocab_defined is not None else None,
+                                        K, C.byref(wo)), "vslam_words_dev")
+
+    def words_host(self, desc, counts, vocab, defined=None, vocab_defined=None, want_words: bool = True, want_dist2: bool = True,
+                   want_hist: bool = True, fill: int = -1):
+        """vslam_words_host: numpy desc [n_sets, cap, 128], counts [n_sets], vocab [K, 128] -> (words int32 [n_sets, cap], word_dist2
+        float32 [n_sets, cap], hist uint32 [n_sets, K]); an output that is not wanted is None.  Rows past a set's count keep `fill`
+        (words) and NaN (word_dist2)."""
+        stage = "words_host"
+        desc = np.ascontiguousarray(desc, dtype=np.float32)
+        vocab = np.ascontiguousarray(vocab, dtype=np.float32).reshape(-1, 128)
+        if desc.ndim != 3 or desc.shape[2] != 128:
+            raise ValueError(f"{stage}: desc must be [n_sets, cap, 128]")
+        n, cap, K = desc.shape[0], desc.shape[1], len(vocab)
+        counts = _counts(counts)
+        if len(counts) != n:
+            raise ValueError(f"{stage}: one count per set")
+        defined = None if defined is None else np.ascontiguousarray(defined, dtype=np.uint8)
+        vocab_defined = None if vocab_defined is None else np.ascontiguousarray(vocab_defined, dtype=np.uint8)
+        if (defined is not None and defined.size != n * cap) or (vocab_defined is not None and vocab_defined.size != K):
+            raise ValueError(f"{stage}: defined must have one entry per descriptor row, vocab_defined one per word")
+        words = np.full((n, cap), fill, np.int32) if want_words else None
+        dist2 = np.full((n, cap), np.nan, np.float32) if want_dist2 else None
+        hist = np.zeros((n, K), np.uint32) if want_hist else None
+        wo = _fill_out(WordsOut(), dict(words=words, word_dist2=dist2, hist=hist))
+        self._chk(lib().vslam_words_host(self._h, desc.ctypes.data, None if defined is None else defined.ctypes.data, counts.ctypes.data, cap, n,
+                                         vocab.ctypes.data, None if vocab_defined is None else vocab_defined.ctypes.data, K, C.byref(wo)),
+                  "vslam_words_host")
+        return words, dist2, hist
+
+    @staticmethod
+    def _place_params(min_gap, max_candidates, num, den, min_score):
+        return PlaceParams(int(min_gap), int(max_candidates), int(num), int(den), int(min_score), 0)
+
+    def place(self, hist_q, hist_db=None, q_first: int = 0, db_first: int = 0, min_gap: int = 1, max_candidates: int = 3, num: int = 1, den: int = 5,
+              min_score: int = 0, candidates=None, cand_counts=None, weights=None, self_q=None, self_db=None, scores=None):
+        """vslam_place_dev: loop candidates of the frames q_first + i (hist_q int32 [nq, K]) among the frames db_first + j (hist_db
+        [nd, K]; None: hist_q itself); asynchronous on the context stream.  candidates: int32 [nq, max_candidates, 3] (PLACE_CAND_DTYPE),
+        cand_counts [nq], weights [K], self_q [nq], self_db [nd], scores [nq, nd]: each optional, candidates needs cand_counts."""
+        stage = "place"
+        hist_db = hist_q if hist_db is None else hist_db
+        outs = dict(candidates=candidates, cand_counts=cand_counts, weights=weights, self_q=self_q, self_db=self_db, scores=scores)
+        _check_tensors(stage, self.where, dict(hist_q=hist_q, hist_db=hist_db, **outs), ("hist_q", "hist_db"))
+        for name, t in dict(hist_q=hist_q, hist_db=hist_db, **outs).items():
+            if t is not None and t.element_size() != 4:
+                raise ValueError(f"{stage}: {name} must have 4-byte elements")
+        if hist_q.dim() != 2 or hist_db.dim() != 2 or hist_q.shape[1] != hist_db.shape[1]:
+            raise ValueError(f"{stage}: hist_q and hist_db must be [frames, K] with one K")
+        if all(t is None for t in outs.values()):
+            raise ValueError(f"{stage}: no output requested")
+        if candidates is not None and cand_counts is None:
+            raise ValueError(f"{stage}: candidates needs cand_counts")
+        nq, nd, K = hist_q.shape[0], hist_db.shape[0], hist_q.shape[1]
+        po = _fill_out(PlaceOut(), outs)
+        pp = self._place_params(min_gap, max_candidates, num, den, min_score)
+        self._chk(lib().vslam_place_dev(self._h, hist_q.data_ptr(), nq, int(q_first), hist_db.data_ptr(), nd, int(db_first), K, C.byref(pp), C.byref(po)),
+                  "vslam_place_dev")
+
+    def place_host(self, hist_q, hist_db=None, q_first: int = 0, db_first: int = 0, min_gap: int = 1, max_candidates: int = 3, num: int = 1,
+                   den: int = 5, min_score: int = 0, want_scores: bool = True, fill: int = -1):
+        """vslam_place_host over numpy histograms [frames, K] -> dict(candidates [nq, c] PLACE_CAND_DTYPE, cand_counts, weights, self_q,
+        self_db, scores (None unless want_scores)).  Candidate slots past a frame's count keep `fill` in every field's bytes."""
+        stage = "place_host"
+        hq = np.ascontiguousarray(hist_q).astype(np.uint32, copy=False)
+        hd = hq if hist_db is None else np.ascontiguousarray(hist_db).astype(np.uint32, copy=False)
+        if hq.ndim != 2 or hd.ndim != 2 or hq.shape[1] != hd.shape[1]:
+            raise ValueError(f"{stage}: hist_q and hist_db must be [frames, K] with one K")
+        nq, nd, K = hq.shape[0], hd.shape[0], hq.shape[1]
+        c = int(max_candidates)
+        r = dict(candidates=np.full((nq, max(c, 0), 3), fill, np.int32).view(PLACE_CAND_DTYPE).reshape(nq, max(c, 0)),
+                 cand_counts=np.zeros(nq, np.uint32), weights=np.zeros(K, np.uint32), self_q=np.zeros(nq, np.uint32), self_db=np.zeros(nd, np.uint32),
+                 scores=np.zeros((nq, nd), np.uint32) if want_scores else None)
+        po = _fill_out(PlaceOut(), r)
+        pp = self._place_params(min_gap, max_candidates, num, den, min_score)
+        self._chk(lib().vslam_place_host(self._h, _ptr(hq), nq, int(q_first), _ptr(hd), nd, int(db_first), K, C.byref(pp), C.byref(po)),
+                  "vslam_place_host")
+        return r
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

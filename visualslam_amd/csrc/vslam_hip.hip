@@ -68,7 +68,9 @@ static const char* const kKernelNames =
     "k_res_corr\nk_res_gather\nk_res_models\nk_res_score\nk_res_select\nk_res_flags\n"
     "k_rr_init\nk_rr_pass\nk_rr_step\nk_rr_flags_zero\nk_rr_flags\n"
     "k_trk_next\nk_trk_walk\nk_trk_rows\n"
-    "k_ba_init\nk_ba_points\nk_ba_cam_pass\nk_ba_cam_step\nk_ba_member_bits\nk_ba_points_final";
+    "k_ba_init\nk_ba_points\nk_ba_cam_pass\nk_ba_cam_step\nk_ba_member_bits\nk_ba_points_final\n"
+    "k_vocab_gather\nk_words_nn\nk_words_merge\n"
+    "k_place_df\nk_place_self\nk_place_score\nk_place_top";
 
 
 // Runs `body` with the context's launch stream temporarily replaced (LAUNCH uses ctx->stream).

@@ -815,3 +815,100 @@ vslam::RefinedResection vslam::refineResection(const std::vector<vslam_resect>& 
     vslam::check(vslam_resect_refine_host(c, models.data(), correspondences.data(), obsCap, (int)n, &params, &o), c, "refineResection");
     return out;
 }
+
+// ---- place recognition (include/vslam.h, "place recognition") -----------------------------------------------------
+
+static void requireFrames(const vslam::DescriptorSets& frames, const vslam::DefinedSets* defined, const char* sizes, const char* row) {
+    require(!defined || defined->size() == frames.size(), sizes);
+    for (size_t f = 0; f < frames.size(); ++f) {
+        require(!defined || (*defined)[f].size() == frames[f].size(), sizes);
+        for (const auto& d : frames[f]) require(d.size() == 128, row);
+    }
+}
+
+vslam::Vocabulary vslam::sampleVocabulary(const DescriptorSets& frames, uint32_t K, const DefinedSets* defined) {
+    requireFrames(frames, defined, "sampleVocabulary: one defined flag per descriptor", "sampleVocabulary: a descriptor is not 128 floats");
+    require(!frames.empty() && frames.size() <= 65535 && K >= 1 && K <= 65536, "sampleVocabulary: 1 .. 65535 frames, 1 .. 65536 words");
+    vslam::Vocabulary v;
+    v.words.assign((size_t)K * 128, 0.0f);
+    v.defined.assign(K, 0);
+    const uint32_t n = (uint32_t)frames.size();
+    for (uint32_t k = 0; k < K; ++k) {
+        const uint32_t s = k % n, rows = (uint32_t)std::min<size_t>(frames[s].size(), 0xffffffffu);
+        if (rows == 0) continue;
+        const uint32_t r = (uint32_t)((k / n) * 2654435761u) % rows;
+        if (defined && !(*defined)[s][r]) continue;
+        std::copy(frames[s][r].begin(), frames[s][r].end(), v.words.begin() + (size_t)k * 128);
+        v.defined[k] = 1;
+    }
+    return v;
+}
+
+vslam::Words vslam::assignWords(const DescriptorSets& frames, const Vocabulary& vocabulary, const DefinedSets* defined) {
+    requireFrames(frames, defined, "assignWords: one defined flag per descriptor", "assignWords: a descriptor is not 128 floats");
+    const uint32_t K = vocabulary.size();
+    require(vocabulary.words.size() == (size_t)K * 128, "assignWords: 128 floats per word");
+    require(frames.size() <= 65535 && K >= 1 && K <= 65536, "assignWords: at most 65535 frames, 1 .. 65536 words");
+    const size_t n = frames.size();
+    size_t cap = 1;
+    for (const auto& f : frames) cap = std::max(cap, f.size());
+    require(cap <= 0xffffffffu, "assignWords: too many descriptors");
+    std::vector<float> desc(n * cap * 128, 0.0f), d2(n * cap, 0.0f);
+    std::vector<unsigned char> def(n * cap, 1);
+    std::vector<uint32_t> counts(n);
+    std::vector<int32_t> w(n * cap, -1);
+    for (size_t f = 0; f < n; ++f) {
+        counts[f] = (uint32_t)frames[f].size();
+        for (size_t r = 0; r < frames[f].size(); ++r) {
+            std::copy(frames[f][r].begin(), frames[f][r].end(), desc.begin() + (f * cap + r) * 128);
+            if (defined) def[f * cap + r] = (*defined)[f][r];
+        }
+    }
+    vslam::Words out;
+    out.K = K;
+    out.hist.assign(n * K, 0);
+    out.word.resize(n), out.dist2.resize(n);
+    if (n == 0) return out;
+    vslam_words_out o{};
+    o.struct_size = sizeof(o);
+    o.words = w.data(), o.words_bytes = w.size() * sizeof(int32_t);
+    o.word_dist2 = d2.data(), o.word_dist2_bytes = d2.size() * sizeof(float);
+    o.hist = out.hist.data(), o.hist_bytes = out.hist.size() * sizeof(uint32_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_words_host(c, desc.data(), def.data(), counts.data(), (uint32_t)cap, (int)n, vocabulary.words.data(), vocabulary.defined.data(), K, &o), c,
+                 "assignWords");
+    for (size_t f = 0; f < n; ++f) {
+        out.word[f].assign(w.begin() + f * cap, w.begin() + f * cap + counts[f]);
+        out.dist2[f].assign(d2.begin() + f * cap, d2.begin() + f * cap + counts[f]);
+    }
+    return out;
+}
+
+vslam::LoopCandidates vslam::findLoopCandidates(const std::vector<uint32_t>& histQ, uint32_t qFirst, const std::vector<uint32_t>& histDb, uint32_t dbFirst,
+                                                uint32_t K, const vslam_place_params& params) {
+    require(K >= 1 && K <= 65536, "findLoopCandidates: 1 .. 65536 words");
+    require(histQ.size() % K == 0 && histDb.size() % K == 0, "findLoopCandidates: K entries per frame");
+    const size_t nq = histQ.size() / K, nd = histDb.size() / K;
+    require(nq <= 65535 && nd <= 65535, "findLoopCandidates: at most 65535 frames on either side");
+    require(params.max_candidates >= 1 && params.max_candidates <= 8, "findLoopCandidates: max_candidates must be 1 .. 8");
+    const uint32_t cmax = params.max_candidates;
+    vslam::LoopCandidates out;
+    out.candidates.resize(nq);
+    out.weights.assign(K, 0), out.selfQuery.assign(nq, 0), out.selfDb.assign(nd, 0);
+    if (nq == 0) return out;
+    std::vector<vslam_place_cand> cands(nq * cmax);
+    std::vector<uint32_t> counts(nq, 0);
+    vslam_place_out o{};
+    o.struct_size = sizeof(o);
+    o.candidates = cands.data(), o.candidates_bytes = cands.size() * sizeof(vslam_place_cand);
+    o.cand_counts = counts.data(), o.cand_counts_bytes = counts.size() * sizeof(uint32_t);
+    o.weights = out.weights.data(), o.weights_bytes = out.weights.size() * sizeof(uint32_t);
+    o.self_q = out.selfQuery.data(), o.self_q_bytes = nq * sizeof(uint32_t);
+    if (nd) o.self_db = out.selfDb.data(), o.self_db_bytes = nd * sizeof(uint32_t);
+    vslam_ctx* c = vslam::default_context();
+    const bool same = &histQ == &histDb;
+    vslam::check(vslam_place_host(c, histQ.data(), (uint32_t)nq, qFirst, same ? histQ.data() : (nd ? histDb.data() : nullptr), (uint32_t)nd, dbFirst, K, &params,
+                                  &o), c, "findLoopCandidates");
+    for (size_t i = 0; i < nq; ++i) out.candidates[i].assign(cands.begin() + i * cmax, cands.begin() + i * cmax + std::min(counts[i], cmax));
+    return out;
+}

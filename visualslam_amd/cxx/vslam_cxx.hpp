@@ -363,4 +363,33 @@ struct RefinedResection {
 };
 RefinedResection refineResection(const std::vector<vslam_resect>& models, const std::vector<vslam_resect_corr>& correspondences, uint32_t obsCap,
                                  const vslam_resect_refine_params& params);
+
+// Place recognition (include/vslam.h, "place recognition"): which earlier frame shows the same place?  A frame is the descriptor
+// vector SIFT() fills, with its optional defined flags.
+using DescriptorSets = std::vector<std::vector<std::vector<float>>>;  // [frame][descriptor][128]
+using DefinedSets = std::vector<std::vector<unsigned char>>;         // [frame][descriptor]
+struct Vocabulary {
+    std::vector<float> words;            // [K][128]
+    std::vector<unsigned char> defined;  // [K]
+    uint32_t size() const { return (uint32_t)defined.size(); }
+};
+// K words copied from the frames' descriptors by the header's rule (set k % n, row ((k / n) * 2654435761 mod 2^32) % rows): the rule
+// is a gather, restated on the host here; vslam_vocab_sample_dev is the same rule over device buffers.
+Vocabulary sampleVocabulary(const DescriptorSets& frames, uint32_t K, const DefinedSets* defined = nullptr);
+struct Words {
+    std::vector<std::vector<int32_t>> word;  // [frame][descriptor]: the nearest word, -1: none
+    std::vector<std::vector<float>> dist2;   // [frame][descriptor]: its d2, +inf with -1
+    std::vector<uint32_t> hist;              // [frames][K]
+    uint32_t K = 0;
+};
+// The nearest word of every descriptor and the histogram of words per frame, on the GPU (vslam_words_host).
+Words assignWords(const DescriptorSets& frames, const Vocabulary& vocabulary, const DefinedSets* defined = nullptr);
+struct LoopCandidates {
+    std::vector<std::vector<vslam_place_cand>> candidates;  // [query frame]: at most params.max_candidates, rank order
+    std::vector<uint32_t> weights, selfQuery, selfDb;       // [K], [nq], [nd]
+};
+// Loop candidates of the frames qFirst + i (histQ [nq][K]) among the frames dbFirst + j (histDb [nd][K]), on the GPU
+// (vslam_place_host).  One batch searched in itself: the same vector twice.
+LoopCandidates findLoopCandidates(const std::vector<uint32_t>& histQ, uint32_t qFirst, const std::vector<uint32_t>& histDb, uint32_t dbFirst, uint32_t K,
+                                  const vslam_place_params& params = {4, 3, 1, 5, 0, 0});
 }  // namespace vslam
