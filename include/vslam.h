@@ -2005,6 +2005,70 @@ int vslam_place_dev(vslam_ctx* ctx, const uint32_t* hist_q, uint32_t nq, uint32_
 int vslam_place_host(vslam_ctx* ctx, const uint32_t* hist_q, uint32_t nq, uint32_t q_first, const uint32_t* hist_db, uint32_t nd,
                      uint32_t db_first, uint32_t K, const vslam_place_params* params, const vslam_place_out* out);
 
+/* ---------------------------------------------------------------- vocabulary training
+ * A sampled word (place recognition, above) is one noisy observation of one landmark.  vslam_vocab_kmeans_dev trains a vocabulary
+ * by Lloyd's algorithm: `rounds` times, every descriptor row goes to its nearest word and every word becomes the mean of its rows.
+ * The assignment is the Words rule above, unchanged; the mean is an f64 sum in a fixed order, every operation rounded on its own
+ * (no fused multiply-add, no reassociation), so a CPU restates every byte (tests/kmeansref.py).  No output depends on
+ * vslam_ctx_set_f32_fused or vslam_ctx_set_matrix_path, on scheduling, on the grid or on the scratch layout.
+ *
+ *   Rows in use: (f, q) with f < n_sets and q < min(counts[f], cap).  V_0 = vocab_in.  vocab_defined is an input, the same in every
+ *   round, and is never written; NULL: every word is defined.  Round t = 1 .. rounds:
+ *     1. Assign.  w_t(f, q) = the word of row (f, q) by the Words paragraph of the place recognition section against V_(t-1) and
+ *        vocab_defined: -1 for a row whose `defined` byte is 0 or whose every distance is NaN or +inf.
+ *     2. Report.  assigned = the rows in use with w_t >= 0.  changed = the rows in use with w_t != w_(t-1); in round 1 every row in
+ *        use counts, assigned or not.  If t > 1 and changed == 0 the call has CONVERGED: this round writes its record with ran = 1
+ *        and `empty` by step 6 from this round's assignment (which is the previous round's), updates nothing, and every later
+ *        round writes {0, 0, 0, 0}.  (The same assignment would give the same sums, so stopping changes no byte of the vocabulary.)
+ *     3. Members.  The members of word k are the rows in use with w_t == k, ordered by set ascending, then by row ascending; N_k is
+ *        their number.  A row with w_t == -1 is a member of no word.
+ *     4. Ordered sum.  For each word k and each d < 128: block b holds the members 256 b .. min(256 b + 255, N_k - 1).
+ *        B_b = +0.0, then B_b = B_b + (double)x[d] for the block's members x in member order; sum = B_0, then sum = sum + B_b for
+ *        b = 1, 2, .. in ascending order.  Every f64 addition is rounded to nearest even on its own.  The sum depends on the
+ *        member list alone.
+ *     5. Update.  N_k == 0: V_t[k] = V_(t-1)[k], byte for byte (an undefined word, a dead word, the second of two equal words
+ *        and a word no row is nearest to all keep their bytes in that round; once the first of two equal words has moved, the
+ *        second is a word of its own).  Otherwise V_t[k][d] = (float)(sum / (double)N_k): one f64 division, one rounding to f32
+ *        (nearest even; a subnormal result is kept).  The arithmetic is plain IEEE: a NaN or infinite sum would give a NaN or
+ *        infinite entry, and by the Words rule such a word is dead from the next round on - no row gets it, so it keeps those
+ *        bytes.  No row can bring that about: a member has a finite d2, so its norm and with it every entry is finite, and the
+ *        mean of finite f32 values is finite.  A word is dead only if vocab_in made it so.
+ *     6. empty = the words k whose vocab_defined byte is not 0 (NULL: every k) with N_k == 0; a dead word counts.
+ *   out->vocab = V_t and out->sizes[k] = N_k of the last round t that updated (round 1 always updates).  The rows are never
+ *   written.  n_sets == 0: vocab = vocab_in, every size 0, every report record {0, 0, 0, 0}. */
+typedef struct {
+    uint32_t rounds;   /* 1 .. 64 */
+    uint32_t reserved; /* 0 */
+} vslam_kmeans_params; /* 8 bytes */
+typedef struct {
+    uint32_t assigned, changed, empty, ran;
+} vslam_kmeans_round;  /* 16 bytes */
+typedef struct {
+    size_t struct_size;         /* = sizeof(vslam_kmeans_out) */
+    float* vocab;               /* [K][128] required, 16-byte aligned; may be vocab_in itself (in place), no other overlap */
+    size_t vocab_bytes;
+    uint32_t* sizes;            /* [K] optional */
+    size_t sizes_bytes;
+    vslam_kmeans_round* report; /* [rounds] optional */
+    size_t report_bytes;
+} vslam_kmeans_out;
+/* sets, vocab_in [K][128] (16-byte aligned), vocab_defined [K] or NULL and the pointers of `out`: DEVICE pointers.  0 <= n_sets <=
+ * 65535, 1 <= K <= 65536, n_sets * cap <= 2^32 - 1 (row ids and row counts fit 32 bits).  Asynchronous on the context stream, never waits on the
+ * host: convergence is decided on the device, and the launches of the rounds after it return at once.  Scratch belongs to the
+ * context: per row 12 bytes beside the word search's, per (set, word) 4 bytes, and 1 KiB per block of step 4, of which there are
+ * at most n_sets * cap / 256 + K.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null struct
+ * or vocabulary, a wrong struct_size, rounds outside 1 .. 64, reserved != 0, n_sets or K out of range, a set without desc, counts
+ * or a capacity, row ids past 32 bits, a misaligned desc, vocab_in or vocab, an undersized buffer, vocab overlapping vocab_in other
+ * than exactly; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_vocab_kmeans_dev(vslam_ctx* ctx, const vslam_desc_sets* sets, int n_sets, const float* vocab_in, const uint8_t* vocab_defined,
+                           uint32_t K, const vslam_kmeans_params* params, const vslam_kmeans_out* out);
+/* The same call over HOST arrays, synchronous (a convenience path: device buffers per call): desc [n_sets][cap][128], defined
+ * [n_sets][cap] or NULL, counts [n_sets], vocab_in [K][128], vocab_defined [K] or NULL, and the pointers of `out`.  Errors as for
+ * vslam_vocab_kmeans_dev (no alignment is asked of host arrays). */
+int vslam_vocab_kmeans_host(vslam_ctx* ctx, const float* desc, const uint8_t* defined, const uint32_t* counts, uint32_t cap, int n_sets,
+                            const float* vocab_in, const uint8_t* vocab_defined, uint32_t K, const vslam_kmeans_params* params,
+                            const vslam_kmeans_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

@@ -33,6 +33,7 @@ NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4"
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 RNN_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4")], align=True)  # vslam_rnn, 8 bytes
 PLACE_CAND_DTYPE = np.dtype([("frame", "<i4"), ("score", "<u4"), ("norm", "<u4")], align=True)  # vslam_place_cand, 12 bytes
+KMEANS_ROUND_DTYPE = np.dtype([(n, "<u4") for n in ("assigned", "changed", "empty", "ran")], align=True)  # vslam_kmeans_round, 16 bytes
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
 HOMOGRAPHY_HYP_DTYPE = np.dtype([("H", "<f8", (9,)), ("G", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_homography_hyp, 152 bytes
@@ -166,6 +167,20 @@ class PlaceOut(C.Structure):
                 ("cand_counts_bytes", C.c_size_t), ("weights", C.c_void_p), ("weights_bytes", C.c_size_t), ("self_q", C.c_void_p),
                 ("self_q_bytes", C.c_size_t), ("self_db", C.c_void_p), ("self_db_bytes", C.c_size_t), ("scores", C.c_void_p),
                 ("scores_bytes", C.c_size_t)]
+
+
+class KmeansParams(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KmeansRound(C.Structure):
+    _fields_ = [("assigned", C.c_uint32), ("changed", C.c_uint32), ("empty", C.c_uint32), ("ran", C.c_uint32)]
+
+
+class KmeansOut(C.Structure):
+    """vslam_kmeans_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("vocab", C.c_void_p), ("vocab_bytes", C.c_size_t), ("sizes", C.c_void_p), ("sizes_bytes", C.c_size_t),
+                ("report", C.c_void_p), ("report_bytes", C.c_size_t)]
 
 
 class EpipolarHyp(C.Structure):
@@ -485,6 +500,8 @@ SIGNATURES = {
     "vslam_words_dev": (_I, [_P, C.POINTER(DescSets), _I, _P, _P, C.c_uint32, C.POINTER(WordsOut)]),
     "vslam_words_host": (_I, [_P, _P, _P, _P, C.c_uint32, _I, _P, _P, C.c_uint32, C.POINTER(WordsOut)]),
     "vslam_place_dev": (_I, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlaceParams), C.POINTER(PlaceOut)]),
+    "vslam_vocab_kmeans_dev": (_I, [_P, C.POINTER(DescSets), _I, _P, _P, C.c_uint32, C.POINTER(KmeansParams), C.POINTER(KmeansOut)]),
+    "vslam_vocab_kmeans_host": (_I, [_P, _P, _P, _P, C.c_uint32, _I, _P, _P, C.c_uint32, C.POINTER(KmeansParams), C.POINTER(KmeansOut)]),
     "vslam_place_host": (_I, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlaceParams), C.POINTER(PlaceOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
@@ -1783,6 +1800,62 @@ class Context:
                                          vocab.ctypes.data, None if vocab_defined is None else vocab_defined.ctypes.data, K, C.byref(wo)),
                   "vslam_words_host")
         return words, dist2, hist
+
+    def vocab_kmeans(self, sets: DescSets, vocab_in, rounds: int, vocab_defined=None, n_sets: int | None = None, vocab=None, sizes=None,
+                     report=None):
+        """vslam_vocab_kmeans_dev: `rounds` rounds of Lloyd's algorithm over the rows of `sets` (desc_sets()) from the K = vocab_in.shape[0]
+        words of vocab_in (float32 [K, 128]; vocab_defined uint8 [K] or None); asynchronous on the context stream.  vocab: float32
+        [K, 128], the trained words (None: vocab_in itself, in place); sizes: int32 [K] and report: int32 [rounds, 4]
+        (KMEANS_ROUND_DTYPE), each optional."""
+        stage = "vocab_kmeans"
+        vocab = vocab_in if vocab is None else vocab
+        tensors = dict(vocab_in=vocab_in, vocab_defined=vocab_defined, vocab=vocab, sizes=sizes, report=report)
+        _check_tensors(stage, self.where, tensors, ("vocab_in", "vocab"))
+        for name in ("vocab_in", "vocab"):
+            t = tensors[name]
+            if t.dim() != 2 or t.shape[1] != 128 or t.element_size() != 4:
+                raise ValueError(f"{stage}: {name} must be float32 [K, 128]")
+        K = vocab_in.shape[0]
+        if vocab.shape[0] != K:
+            raise ValueError(f"{stage}: vocab must have vocab_in's K rows")
+        if vocab_defined is not None and (vocab_defined.element_size() != 1 or vocab_defined.numel() < K):
+            raise ValueError(f"{stage}: vocab_defined must be uint8 [K]")
+        for name in ("sizes", "report"):
+            if tensors[name] is not None and tensors[name].element_size() != 4:
+                raise ValueError(f"{stage}: {name} must have 4-byte elements")
+        n = sets.n if n_sets is None else int(n_sets)
+        _check_sets(stage, n, (), (), ((sizes, K * 4), (report, int(rounds) * 16)))
+        ko = _fill_out(KmeansOut(), dict(vocab=vocab, sizes=sizes, report=report))
+        kp = KmeansParams(int(rounds), 0)
+        self._chk(lib().vslam_vocab_kmeans_dev(self._h, C.byref(sets), n, vocab_in.data_ptr(), vocab_defined.data_ptr() if vocab_defined is not None else None,
+                                               K, C.byref(kp), C.byref(ko)), "vslam_vocab_kmeans_dev")
+
+    def vocab_kmeans_host(self, desc, counts, vocab_in, rounds: int, defined=None, vocab_defined=None, want_sizes: bool = True,
+                          want_report: bool = True):
+        """vslam_vocab_kmeans_host: numpy desc [n_sets, cap, 128], counts [n_sets], vocab_in [K, 128] -> (vocab float32 [K, 128], sizes
+        uint32 [K], report KMEANS_ROUND_DTYPE [rounds]); an output that is not wanted is None."""
+        stage = "vocab_kmeans_host"
+        desc = np.ascontiguousarray(desc, dtype=np.float32)
+        vocab_in = np.ascontiguousarray(vocab_in, dtype=np.float32).reshape(-1, 128)
+        if desc.ndim != 3 or desc.shape[2] != 128:
+            raise ValueError(f"{stage}: desc must be [n_sets, cap, 128]")
+        n, cap, K = desc.shape[0], desc.shape[1], len(vocab_in)
+        counts = _counts(counts)
+        if len(counts) != n:
+            raise ValueError(f"{stage}: one count per set")
+        defined = None if defined is None else np.ascontiguousarray(defined, dtype=np.uint8)
+        vocab_defined = None if vocab_defined is None else np.ascontiguousarray(vocab_defined, dtype=np.uint8)
+        if (defined is not None and defined.size != n * cap) or (vocab_defined is not None and vocab_defined.size != K):
+            raise ValueError(f"{stage}: defined must have one entry per descriptor row, vocab_defined one per word")
+        vocab = np.zeros((K, 128), np.float32)
+        sizes = np.zeros(K, np.uint32) if want_sizes else None
+        report = np.zeros(max(int(rounds), 0), KMEANS_ROUND_DTYPE) if want_report else None
+        ko = _fill_out(KmeansOut(), dict(vocab=vocab, sizes=sizes, report=report))
+        kp = KmeansParams(int(rounds), 0)
+        self._chk(lib().vslam_vocab_kmeans_host(self._h, desc.ctypes.data, None if defined is None else defined.ctypes.data, counts.ctypes.data, cap, n,
+                                                vocab_in.ctypes.data, None if vocab_defined is None else vocab_defined.ctypes.data, K, C.byref(kp),
+                                                C.byref(ko)), "vslam_vocab_kmeans_host")
+        return vocab, sizes, report
 
     @staticmethod
     def _place_params(min_gap, max_candidates, num, den, min_score):

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "vslam_ctx.h"
+#include "vslam_place_plan.h"
 
 // Launch on `stream` with `lds` bytes of dynamic LDS, bracketed for the timing hook as "name@tag".
 #define LAUNCH_ON(ctx, name, tag, stream, lds, kern, grid, block, ...)        \
@@ -85,6 +86,17 @@ int enqueue_chain_link(vslam_ctx* c, const StructLists& L, unsigned int* prev);
 // same paths): next [n_pairs - 1][match_cap] is preset to 0xffffffff and row j - 1 gets, per record of pair j - 1, the lowest
 // candidate of pair j.  prev: the link table above.  n_pairs >= 2.
 int enqueue_trk_next(vslam_ctx* c, const StructLists& L, const vslam_chain* chain, const unsigned int* prev, unsigned int* next);
+// The word search of vslam_words_dev (k_desc_norms, k_words_nn, k_words_merge; compiled in vslam_words.hip; every round of
+// vslam_vocab_kmeans_dev assigns with it): the word, its d2 and the histogram of n_sets >= 1 sets against the vocabulary V, a
+// one-set vslam_desc_sets of pl.m's train capacity whose count the caller has put on the device.  The scratch is the caller's, of
+// words_plan's sizes: qnorm pl.m.q_elems, vnorm pl.vnorm_elems, part pl.m.part_elems records of 8 bytes.  row_norms: qnorm is
+// computed here (the rows of a caller that asks again have not changed).  words, dist2 and hist may each be null; hist is zeroed.
+struct WordsScratch {
+    float *qnorm, *vnorm;
+    unsigned long long* part;
+};
+int enqueue_words(vslam_ctx* c, const vslam_desc_sets& sets, int n_sets, const vslam_desc_sets& V, const WordsPlan& pl, const WordsScratch& ws,
+                  bool row_norms, int* words, float* dist2, unsigned int* hist);
 }  // namespace vslam
 
 // The workspace buffers of one call.  add() states a buffer once - where its pointer goes, its type, its element count -

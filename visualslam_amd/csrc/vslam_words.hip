@@ -14,6 +14,20 @@
 
 using namespace vslam;
 
+namespace vslam {
+int enqueue_words(vslam_ctx* c, const vslam_desc_sets& sets, int n_sets, const vslam_desc_sets& V, const WordsPlan& pl, const WordsScratch& ws,
+                  bool row_norms, int* words, float* dist2, unsigned int* hist) {
+    static_assert(sizeof(WordPart) == sizeof(*ws.part), "record layout");
+    WordPart* part = reinterpret_cast<WordPart*>(ws.part);
+    if (hist) HIPCHK(c, hipMemsetAsync(hist, 0, pl.hist_elems * sizeof(uint32_t), c->stream));
+    if (row_norms) TRY(enqueue_desc_norms(c, sets, n_sets, ws.qnorm));
+    TRY(enqueue_desc_norms(c, V, 1, ws.vnorm));
+    LAUNCH(c, "k_words_nn", k_words_nn, dim3(pl.m.qtiles, pl.m.nsplit, n_sets), dim3(256), sets, V, ws.qnorm, ws.vnorm, (int)pl.m.nsplit, part);
+    LAUNCH(c, "k_words_merge", k_words_merge, dim3(pl.m.qrow_blocks, n_sets), dim3(MT_ROW_WG), sets, part, (int)pl.m.nsplit, V.cap, words, dist2, hist);
+    return VSLAM_OK;
+}
+}  // namespace vslam
+
 extern "C" {
 
 int vslam_vocab_sample_dev(vslam_ctx* c, const vslam_desc_sets* sets, int n_sets, uint32_t K, float* vocab, size_t vocab_bytes,
@@ -28,32 +42,24 @@ int vslam_vocab_sample_dev(vslam_ctx* c, const vslam_desc_sets* sets, int n_sets
 
 int vslam_words_dev(vslam_ctx* c, const vslam_desc_sets* sets, int n_sets, const float* vocab, const uint8_t* vocab_defined, uint32_t K,
                     const vslam_words_out* out) {
-    static_assert(sizeof(WordPart) == 8, "record layout");
     if (const char* why = words_check(sets, n_sets, vocab, K, out, true)) return fail(c, VSLAM_ERR_INVALID, std::string("words: ") + why);
     TRY(usable_ctx(c));
     if (n_sets == 0) return VSLAM_OK;
 
     const WordsPlan pl = words_plan(sets->cap, K, n_sets);  // (the counts live on the device: the grid is sized from the capacities)
-    float *qnorm = nullptr, *vnorm = nullptr;
-    WordPart* part = nullptr;
+    WordsScratch s{};
     uint32_t* vcount = nullptr;
     WsPlan ws;
-    ws.add(qnorm, pl.m.q_elems);
-    ws.add(vnorm, pl.vnorm_elems);
-    ws.add(part, pl.m.part_elems);
+    ws.add(s.qnorm, pl.m.q_elems);
+    ws.add(s.vnorm, pl.vnorm_elems);
+    ws.add(s.part, pl.m.part_elems);
     ws.add(vcount, 1);
     TRY(ws.commit(c));
 
     // the vocabulary as one descriptor set of K rows, all in use
     HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(vcount), (int)K, 1, c->stream));
     const vslam_desc_sets V{vocab, vocab_defined, nullptr, vcount, K};
-    if (out->hist) HIPCHK(c, hipMemsetAsync(out->hist, 0, pl.hist_elems * sizeof(uint32_t), c->stream));
-    TRY(enqueue_desc_norms(c, *sets, n_sets, qnorm));
-    TRY(enqueue_desc_norms(c, V, 1, vnorm));
-    LAUNCH(c, "k_words_nn", k_words_nn, dim3(pl.m.qtiles, pl.m.nsplit, n_sets), dim3(256), *sets, V, qnorm, vnorm, (int)pl.m.nsplit, part);
-    LAUNCH(c, "k_words_merge", k_words_merge, dim3(pl.m.qrow_blocks, n_sets), dim3(MT_ROW_WG), *sets, part, (int)pl.m.nsplit, K, out->words,
-           out->word_dist2, out->hist);
-    return VSLAM_OK;
+    return enqueue_words(c, *sets, n_sets, V, pl, s, true, out->words, out->word_dist2, out->hist);
 }
 
 int vslam_words_host(vslam_ctx* c, const float* desc, const uint8_t* defined, const uint32_t* counts, uint32_t cap, int n_sets, const float* vocab,

@@ -3,13 +3,17 @@
 // (vslam::sampleVocabulary), the visual word of every descriptor with a histogram per frame (vslam::assignWords), and the loop
 // candidates of every frame among the frames at least min_gap before it (vslam::findLoopCandidates; include/vslam.h, "place
 // recognition").  Prints one JSON line: the descriptor count of every frame and its candidates as [frame, score, norm].
-//   usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] (a.pgm b.pgm ... | WxH N)
+//   usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] [--kmeans R] (a.pgm b.pgm ... | WxH N)
 //          (WxH N: frames 0 .. N-1 of the synthetic stream; defaults: K 256, gap 4, 3 candidates, threshold 1/5, 3 octaves;
-//           --vocab-frames V: the vocabulary is sampled from the first V frames only, default all)
+//           --vocab-frames V: the vocabulary is sampled from the first V frames only, default all;
+//           --kmeans R: the sampled vocabulary is trained for R rounds on those frames before the words are taken
+//           (vslam::trainVocabulary; "vocabulary training"), and the line carries the report of every round as
+//           [assigned, changed, empty, ran])
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 
 #include "imgio.hpp"
 #include "vslam_cxx.hpp"
@@ -22,6 +26,7 @@ int main(int argc, char** argv) {
         vslam_place_params params{4, 3, 1, 5, 0, 0};
         int numOctaves = 3;
         size_t vocabFrames = 0;
+        uint32_t kmeansRounds = 0;
         while (argc > 2 && argv[1][0] == '-' && argv[1][1] == '-') {
             const std::string opt = argv[1];
             if (opt == "--words") K = (uint32_t)std::strtoul(argv[2], nullptr, 10);
@@ -29,6 +34,7 @@ int main(int argc, char** argv) {
             else if (opt == "--candidates") params.max_candidates = (uint32_t)std::strtoul(argv[2], nullptr, 10);
             else if (opt == "--octaves") numOctaves = std::atoi(argv[2]);
             else if (opt == "--vocab-frames") vocabFrames = (size_t)std::strtoul(argv[2], nullptr, 10);
+            else if (opt == "--kmeans") kmeansRounds = (uint32_t)std::strtoul(argv[2], nullptr, 10);
             else if (opt == "--threshold") {
                 if (std::sscanf(argv[2], "%u/%u", &params.num, &params.den) != 2) throw std::runtime_error("--threshold takes NUM/DEN");
             } else throw std::runtime_error("unknown option " + opt);
@@ -42,7 +48,7 @@ int main(int argc, char** argv) {
             for (int a = 1; a < argc; ++a) images.push_back(imgio::read_pgm(argv[a]));
         }
         if (images.empty())
-            throw std::runtime_error("usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] (a.pgm b.pgm ... | WxH N)");
+            throw std::runtime_error("usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] [--kmeans R] (a.pgm b.pgm ... | WxH N)");
 
         vslam::DescriptorSets frames(images.size());
         vslam::DefinedSets defined(images.size());
@@ -60,7 +66,13 @@ int main(int argc, char** argv) {
         if (vocabFrames == 0 || vocabFrames > frames.size()) vocabFrames = frames.size();
         const vslam::DescriptorSets vocabSets(frames.begin(), frames.begin() + vocabFrames);
         const vslam::DefinedSets vocabDefined(defined.begin(), defined.begin() + vocabFrames);
-        const vslam::Vocabulary vocabulary = vslam::sampleVocabulary(vocabSets, K, &vocabDefined);
+        vslam::Vocabulary vocabulary = vslam::sampleVocabulary(vocabSets, K, &vocabDefined);
+        std::vector<vslam_kmeans_round> report;
+        if (kmeansRounds) {
+            vslam::TrainedVocabulary trained = vslam::trainVocabulary(vocabSets, vocabulary, kmeansRounds, &vocabDefined);
+            vocabulary = std::move(trained.vocabulary);
+            report = std::move(trained.report);
+        }
         const vslam::Words words = vslam::assignWords(frames, vocabulary, &defined);
         const vslam::LoopCandidates loops = vslam::findLoopCandidates(words.hist, 0, words.hist, 0, K, params);
 
@@ -70,6 +82,12 @@ int main(int argc, char** argv) {
                         ", \"min_gap\": " + std::to_string(params.min_gap) + ", \"threshold\": [" + std::to_string(params.num) + ", " + std::to_string(params.den) +
                         "], \"descriptors\": [";
         for (size_t f = 0; f < frames.size(); ++f) s += (f ? ", " : "") + std::to_string(frames[f].size());
+        if (kmeansRounds) {
+            s += "], \"kmeans\": [";
+            for (size_t t = 0; t < report.size(); ++t)
+                s += (t ? ", [" : "[") + std::to_string(report[t].assigned) + ", " + std::to_string(report[t].changed) + ", " + std::to_string(report[t].empty) + ", " +
+                     std::to_string(report[t].ran) + "]";
+        }
         s += "], \"assigned\": [";
         for (size_t f = 0; f < frames.size(); ++f) {
             size_t n = 0;

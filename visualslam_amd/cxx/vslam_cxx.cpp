@@ -826,6 +826,28 @@ static void requireFrames(const vslam::DescriptorSets& frames, const vslam::Defi
     }
 }
 
+// The frames as the host arrays of the *_host entry points: desc [n][cap][128], defined [n][cap], counts [n]; cap >= 1.
+struct PackedFrames {
+    size_t cap = 1;
+    std::vector<float> desc;
+    std::vector<unsigned char> def;
+    std::vector<uint32_t> counts;
+    PackedFrames(const vslam::DescriptorSets& frames, const vslam::DefinedSets* defined, const char* tooMany) : counts(frames.size()) {
+        const size_t n = frames.size();
+        for (const auto& f : frames) cap = std::max(cap, f.size());
+        require(cap <= 0xffffffffu, tooMany);
+        desc.assign(n * cap * 128, 0.0f);
+        def.assign(n * cap, 1);
+        for (size_t f = 0; f < n; ++f) {
+            counts[f] = (uint32_t)frames[f].size();
+            for (size_t r = 0; r < frames[f].size(); ++r) {
+                std::copy(frames[f][r].begin(), frames[f][r].end(), desc.begin() + (f * cap + r) * 128);
+                if (defined) def[f * cap + r] = (*defined)[f][r];
+            }
+        }
+    }
+};
+
 vslam::Vocabulary vslam::sampleVocabulary(const DescriptorSets& frames, uint32_t K, const DefinedSets* defined) {
     requireFrames(frames, defined, "sampleVocabulary: one defined flag per descriptor", "sampleVocabulary: a descriptor is not 128 floats");
     require(!frames.empty() && frames.size() <= 65535 && K >= 1 && K <= 65536, "sampleVocabulary: 1 .. 65535 frames, 1 .. 65536 words");
@@ -850,20 +872,13 @@ vslam::Words vslam::assignWords(const DescriptorSets& frames, const Vocabulary& 
     require(vocabulary.words.size() == (size_t)K * 128, "assignWords: 128 floats per word");
     require(frames.size() <= 65535 && K >= 1 && K <= 65536, "assignWords: at most 65535 frames, 1 .. 65536 words");
     const size_t n = frames.size();
-    size_t cap = 1;
-    for (const auto& f : frames) cap = std::max(cap, f.size());
-    require(cap <= 0xffffffffu, "assignWords: too many descriptors");
-    std::vector<float> desc(n * cap * 128, 0.0f), d2(n * cap, 0.0f);
-    std::vector<unsigned char> def(n * cap, 1);
-    std::vector<uint32_t> counts(n);
+    const PackedFrames p(frames, defined, "assignWords: too many descriptors");
+    const size_t cap = p.cap;
+    const std::vector<float>& desc = p.desc;
+    const std::vector<unsigned char>& def = p.def;
+    const std::vector<uint32_t>& counts = p.counts;
+    std::vector<float> d2(n * cap, 0.0f);
     std::vector<int32_t> w(n * cap, -1);
-    for (size_t f = 0; f < n; ++f) {
-        counts[f] = (uint32_t)frames[f].size();
-        for (size_t r = 0; r < frames[f].size(); ++r) {
-            std::copy(frames[f][r].begin(), frames[f][r].end(), desc.begin() + (f * cap + r) * 128);
-            if (defined) def[f * cap + r] = (*defined)[f][r];
-        }
-    }
     vslam::Words out;
     out.K = K;
     out.hist.assign(n * K, 0);
@@ -910,5 +925,34 @@ vslam::LoopCandidates vslam::findLoopCandidates(const std::vector<uint32_t>& his
     vslam::check(vslam_place_host(c, histQ.data(), (uint32_t)nq, qFirst, same ? histQ.data() : (nd ? histDb.data() : nullptr), (uint32_t)nd, dbFirst, K, &params,
                                   &o), c, "findLoopCandidates");
     for (size_t i = 0; i < nq; ++i) out.candidates[i].assign(cands.begin() + i * cmax, cands.begin() + i * cmax + std::min(counts[i], cmax));
+    return out;
+}
+
+// ---- vocabulary training (include/vslam.h, "vocabulary training") --------------------------------------------------
+
+vslam::TrainedVocabulary vslam::trainVocabulary(const DescriptorSets& frames, const Vocabulary& vocabulary, uint32_t rounds, const DefinedSets* defined) {
+    requireFrames(frames, defined, "trainVocabulary: one defined flag per descriptor", "trainVocabulary: a descriptor is not 128 floats");
+    const uint32_t K = vocabulary.size();
+    require(vocabulary.words.size() == (size_t)K * 128, "trainVocabulary: 128 floats per word");
+    require(frames.size() <= 65535 && K >= 1 && K <= 65536, "trainVocabulary: at most 65535 frames, 1 .. 65536 words");
+    require(rounds >= 1 && rounds <= 64, "trainVocabulary: rounds must be 1 .. 64");
+    const PackedFrames p(frames, defined, "trainVocabulary: too many descriptors");
+    require((uint64_t)frames.size() * p.cap <= 0xffffffffull, "trainVocabulary: too many descriptors");
+    vslam::TrainedVocabulary out;
+    out.vocabulary.words.assign((size_t)K * 128, 0.0f);
+    out.vocabulary.defined = vocabulary.defined;
+    out.sizes.assign(K, 0);
+    out.report.assign(rounds, vslam_kmeans_round{0, 0, 0, 0});
+    const vslam_kmeans_params params{rounds, 0};
+    vslam_kmeans_out o{};
+    o.struct_size = sizeof(o);
+    o.vocab = out.vocabulary.words.data(), o.vocab_bytes = out.vocabulary.words.size() * sizeof(float);
+    o.sizes = out.sizes.data(), o.sizes_bytes = out.sizes.size() * sizeof(uint32_t);
+    o.report = out.report.data(), o.report_bytes = out.report.size() * sizeof(vslam_kmeans_round);
+    const uint32_t none = 0;  // (no frames: the entry point still asks for the two pointers)
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_vocab_kmeans_host(c, frames.empty() ? vocabulary.words.data() : p.desc.data(), frames.empty() ? nullptr : p.def.data(),
+                                         frames.empty() ? &none : p.counts.data(), (uint32_t)p.cap, (int)frames.size(), vocabulary.words.data(),
+                                         vocabulary.defined.data(), K, &params, &o), c, "trainVocabulary");
     return out;
 }

@@ -384,6 +384,15 @@ struct Words {
 };
 // The nearest word of every descriptor and the histogram of words per frame, on the GPU (vslam_words_host).
 Words assignWords(const DescriptorSets& frames, const Vocabulary& vocabulary, const DefinedSets* defined = nullptr);
+// Vocabulary training (include/vslam.h, "vocabulary training"): `rounds` rounds of Lloyd's algorithm over the frames' descriptors
+// from the words of `vocabulary` (sampleVocabulary's, say), on the GPU (vslam_vocab_kmeans_host).  The defined flags of the words
+// do not change.
+struct TrainedVocabulary {
+    Vocabulary vocabulary;
+    std::vector<uint32_t> sizes;             // [K]: the members of every word in the last round that updated
+    std::vector<vslam_kmeans_round> report;  // [rounds]
+};
+TrainedVocabulary trainVocabulary(const DescriptorSets& frames, const Vocabulary& vocabulary, uint32_t rounds, const DefinedSets* defined = nullptr);
 struct LoopCandidates {
     std::vector<std::vector<vslam_place_cand>> candidates;  // [query frame]: at most params.max_candidates, rank order
     std::vector<uint32_t> weights, selfQuery, selfDb;       // [K], [nq], [nd]
