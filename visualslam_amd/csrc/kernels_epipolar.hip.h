@@ -5,12 +5,15 @@
 //                  the workgroup walks record tiles staged in LDS (every lane reads the same address: a broadcast)
 //   k_epi_select : one workgroup per pair: the valid hypothesis with the most inliers, lowest index on ties
 //   k_epi_flags  : the winner's inlier ballot words; kernels_compact.hip.h (EpipolarEntries) turns them into the list
+// The last two are the shared RANSAC steps of kernels_estimate.hip.h under this stage's model; k_epi_score keeps its own text
+// (behind an inlined body its scalar prologue is scheduled otherwise: profiles/estimators_isa_identity.txt).
 // The arithmetic is the header's, operation for operation: every + - * / sqrt of f64 is an IEEE operation of its own (the
 // library is built with -ffp-contract=off; f64 division and sqrt are correctly rounded on gfx950), sums run left to right.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
+#include "kernels_estimate.hip.h"
 #include "kernels_geom3.hip.h"
 #include "vslam_epipolar_plan.h"
 
@@ -228,65 +231,18 @@ __global__ __launch_bounds__(EPI_SCORE_WG) void k_epi_score(const EpiXY* __restr
     if (h < H && count) atomicAdd(&mine->inliers, count);
 }
 
-// grid = (pairs).  key = valid ? (inliers + 1) << 16 | (65535 - h) : 0: the maximum is the most inliers, then the lowest h
-// (h < 65536; inliers + 1 < 2^33 needs 64 bits).
+// grid = (pairs)
 __global__ __launch_bounds__(256) void k_epi_select(const vslam_epipolar_hyp* __restrict__ hyp, const unsigned int* __restrict__ counts,
                                                      unsigned int mcap, unsigned int H, vslam_epipolar* __restrict__ models) {
-    __shared__ unsigned long long skey[4];
-    __shared__ unsigned int sval[4];
     const int j = blockIdx.x;
-    const vslam_epipolar_hyp* hy = hyp + (size_t)j * H;
-    unsigned long long key = 0;
-    unsigned int nvalid = 0;
-    for (unsigned int h = threadIdx.x; h < H; h += 256)
-        if (hy[h].valid) {
-            ++nvalid;
-            const unsigned long long k = ((unsigned long long)hy[h].inliers + 1ull) << 16 | (unsigned long long)(65535u - h);
-            key = max(key, k);
-        }
-    for (int off = 32; off >= 1; off >>= 1) {
-        key = max(key, (unsigned long long)__shfl_down(key, off));
-        nvalid += __shfl_down(nvalid, off);
-    }
-    if ((threadIdx.x & 63) == 0) skey[threadIdx.x >> 6] = key, sval[threadIdx.x >> 6] = nvalid;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        key = max(max(skey[0], skey[1]), max(skey[2], skey[3]));
-        vslam_epipolar out;
-        out.n_matches = g3_count(counts, j, mcap);
-        out.n_valid = sval[0] + sval[1] + sval[2] + sval[3];
-        if (key) {
-            const unsigned int best = 65535u - (unsigned int)(key & 0xffffull);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.F[i] = hy[best].F[i];
-            out.n_inliers = hy[best].inliers;
-            out.best = (int)best;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.F[i] = 0.0;
-            out.n_inliers = 0;
-            out.best = -1;
-        }
-        models[j] = out;
-    }
+    ransac_select<EpiModel>(hyp + (size_t)j * H, H, models + j, [&](vslam_epipolar& out) { out.n_matches = g3_count(counts, j, mcap); });
 }
 
-// grid = (record blocks, pairs): bit i % 64 of word i / 64 = record i is an inlier of the winner; the words that hold a record
-// below the count are written (all zero without a winner), the others left alone.
+// grid = (record blocks, pairs)
 __global__ __launch_bounds__(256) void k_epi_flags(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
                                                     const vslam_epipolar* __restrict__ models, double max_dist2,
                                                     unsigned long long* __restrict__ flags, unsigned int fwords) {
-    const int j = blockIdx.y;
-    const unsigned int m = g3_count(counts, j, mcap);
-    const size_t i = g3_record(blockIdx.x, 256, threadIdx.x);
-    if (!g3_wave_has_record(i, m)) return;
-    double F[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = models[j].F[k];
-    bool in = false;
-    if (i < m) in = epi_inlier(F, xy[(size_t)j * mcap + i], max_dist2);
-    const unsigned long long w = __ballot(in);
-    g3_store_word(flags, j, fwords, i, g3_first_lane(threadIdx.x), w);
+    ransac_flags<EpiModel>(xy, counts, mcap, models, max_dist2, flags, fwords);
 }
 
 }  // namespace vslam

@@ -6,14 +6,16 @@
 //   k_hom_select  : one workgroup per pair: the valid hypothesis with the most inliers, lowest index on ties
 //   k_hom_flags   : the winner's inlier ballot words; kernels_compact.hip.h (EpipolarEntries) turns them into the list
 //   k_hom_verdict : one lane per pair: n_epipolar, degenerate, and the gated copy of the epipolar model
-// The coordinate scratch is k_epi_coords' (vslam::enqueue_epi_coords).  The arithmetic is the header's, operation for
-// operation, as in kernels_epipolar.hip.h.  What is NOT shared with k_epi_models, on purpose: the normalisation over 4 points
+// k_hom_select and k_hom_flags are the shared RANSAC steps of kernels_estimate.hip.h under this stage's model; k_hom_score keeps
+// its own text, as k_epi_score does.  The coordinate scratch is k_epi_coords' (vslam::enqueue_epi_coords).  The arithmetic is
+// the header's, operation for operation, as in kernels_epipolar.hip.h.  What is NOT shared with k_epi_models, on purpose: the normalisation over 4 points
 // and the Gauss-Jordan loop are written out again here - k_epi_models stands at its register and scratch budget
 // (kernels_geom3.hip.h), and routing its lines through a shared function is what changed its allocation before.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
+#include "kernels_estimate.hip.h"
 #include "kernels_geom3.hip.h"
 #include "vslam_homography_plan.h"
 
@@ -187,68 +189,23 @@ __global__ __launch_bounds__(EPI_SCORE_WG) void k_hom_score(const EpiXY* __restr
     if (h < NH && count) atomicAdd(&mine->inliers, count);
 }
 
-// grid = (pairs).  key = valid ? (inliers + 1) << 16 | (65535 - h) : 0: the maximum is the most inliers, then the lowest h
-// (h < 65536; inliers + 1 < 2^33 needs 64 bits).  The verdict's two fields are written as "no verdict"; k_hom_verdict
-// overwrites them when the call has epipolar models.
+// grid = (pairs).  The verdict's two fields are written as "no verdict"; k_hom_verdict overwrites them when the call has
+// epipolar models.
 __global__ __launch_bounds__(256) void k_hom_select(const vslam_homography_hyp* __restrict__ hyp, const unsigned int* __restrict__ counts,
                                                      unsigned int mcap, unsigned int NH, vslam_homography* __restrict__ models) {
-    __shared__ unsigned long long skey[4];
-    __shared__ unsigned int sval[4];
     const int j = blockIdx.x;
-    const vslam_homography_hyp* hy = hyp + (size_t)j * NH;
-    unsigned long long key = 0;
-    unsigned int nvalid = 0;
-    for (unsigned int h = threadIdx.x; h < NH; h += 256)
-        if (hy[h].valid) {
-            ++nvalid;
-            const unsigned long long k = ((unsigned long long)hy[h].inliers + 1ull) << 16 | (unsigned long long)(65535u - h);
-            key = max(key, k);
-        }
-    for (int off = 32; off >= 1; off >>= 1) {
-        key = max(key, (unsigned long long)__shfl_down(key, off));
-        nvalid += __shfl_down(nvalid, off);
-    }
-    if ((threadIdx.x & 63) == 0) skey[threadIdx.x >> 6] = key, sval[threadIdx.x >> 6] = nvalid;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        key = max(max(skey[0], skey[1]), max(skey[2], skey[3]));
-        vslam_homography out;
+    ransac_select<HomModel>(hyp + (size_t)j * NH, NH, models + j, [&](vslam_homography& out) {
         out.n_matches = g3_count(counts, j, mcap);
-        out.n_valid = sval[0] + sval[1] + sval[2] + sval[3];
         out.n_epipolar = 0;
         out.degenerate = 0;
-        if (key) {
-            const unsigned int best = 65535u - (unsigned int)(key & 0xffffull);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.H[i] = hy[best].H[i], out.G[i] = hy[best].G[i];
-            out.n_inliers = hy[best].inliers;
-            out.best = (int)best;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.H[i] = 0.0, out.G[i] = 0.0;
-            out.n_inliers = 0;
-            out.best = -1;
-        }
-        models[j] = out;
-    }
+    });
 }
 
-// grid = (record blocks, pairs): bit i % 64 of word i / 64 = record i is an inlier of the winner; the words that hold a record
-// below the count are written (all zero without a winner), the others left alone.
+// grid = (record blocks, pairs)
 __global__ __launch_bounds__(256) void k_hom_flags(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
                                                     const vslam_homography* __restrict__ models, double max_dist2,
                                                     unsigned long long* __restrict__ flags, unsigned int fwords) {
-    const int j = blockIdx.y;
-    const unsigned int m = g3_count(counts, j, mcap);
-    const size_t i = g3_record(blockIdx.x, 256, threadIdx.x);
-    if (!g3_wave_has_record(i, m)) return;
-    double H[9], G[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] = models[j].H[k], G[k] = models[j].G[k];
-    bool in = false;
-    if (i < m) in = hom_inlier(H, G, xy[(size_t)j * mcap + i], max_dist2);
-    const unsigned long long w = __ballot(in);
-    g3_store_word(flags, j, fwords, i, g3_first_lane(threadIdx.x), w);
+    ransac_flags<HomModel>(xy, counts, mcap, models, max_dist2, flags, fwords);
 }
 
 // grid = (pair blocks of 64).  One lane per pair, integers only.  `gated` may be the very buffer `epi` points to (neither is

@@ -1,7 +1,8 @@
 // Least-squares refit of the homography (include/vslam.h, "homography: least-squares refit over the inliers").  The launch
 // structure is kernels_refit.hip.h's, a round = count -> begin -> dist -> scale -> moments -> solve, and so is everything the
-// two stages have in common (kernels_geom3.hip.h: refit_block_sums, refit_pair_sums, refit_tree, refit_scales, the 9 x 9
-// Jacobi; hom_inlier, hom_denormalise, hom_sign, hom_adjugate).  The streaming kernels, grid = (blocks of 4096 records, pairs),
+// two stages have in common (kernels_estimate.hip.h: the streaming pass, the count and distance sums, init, begin and scale;
+// kernels_geom3.hip.h: refit_block_sums, refit_pair_sums, refit_tree, refit_scales, the 9 x 9 Jacobi; hom_inlier,
+// hom_denormalise, hom_sign, hom_adjugate).  This stage's own: the add step of the moments pass and steps 3 - 5.  The streaming kernels, grid = (blocks of 4096 records, pairs),
 // 256 lanes = the 256 slots of the header's ordered sum, membership recomputed in every pass (hom_inlier under the pair's
 // (H, G), a broadcast read):
 //   k_hrefit_count   : SUM(x), SUM(y), SUM(x'), SUM(y') and SUM(1.0) - the member count, exact in f64 - under the CANDIDATE model
@@ -21,62 +22,30 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
+#include "kernels_estimate.hip.h"
 #include "kernels_geom3.hip.h"
 #include "vslam_hrefit_plan.h"
 
 namespace vslam {
 
-// true: this workgroup has nothing to do - its pair has stopped, or its block lies past the pair's count.
-__device__ __forceinline__ bool hrefit_idle(const HRefitState* __restrict__ state, const unsigned int* __restrict__ counts, unsigned int mcap) {
-    return state[blockIdx.y].stop != REFIT_RUNNING || (size_t)blockIdx.x * REFIT_BLOCK >= g3_count(counts, blockIdx.y, mcap);
-}
-
 __global__ __launch_bounds__(REFIT_WG) void k_hrefit_count(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
                                                             const HRefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
                                                             unsigned int sum_blocks) {
-    __shared__ double lds[5 * 128];
-    if (hrefit_idle(state, counts, mcap)) return;
-    double H[9], G[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] = state[blockIdx.y].Hcand[k], G[k] = state[blockIdx.y].Gcand[k];
-    const auto member = [&](const EpiXY& p) { return hom_inlier(H, G, p, max_dist2); };
-    refit_block_sums<5, (int)HREFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [](double (&s)[5], const EpiXY& p) {
-        s[0] = s[0] + p.x, s[1] = s[1] + p.y, s[2] = s[2] + p.u, s[3] = s[3] + p.v, s[4] = s[4] + 1.0;
-    });
+    refit_pass<5, true, RefitCountAdd>(xy, counts, mcap, state, max_dist2, partial, sum_blocks);
 }
 
 __global__ __launch_bounds__(REFIT_WG) void k_hrefit_dist(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
                                                            const HRefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
                                                            unsigned int sum_blocks) {
-    __shared__ double lds[2 * 128];
-    if (hrefit_idle(state, counts, mcap)) return;
-    const HRefitState* st = state + blockIdx.y;
-    double H[9], G[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] = st->Hcur[k], G[k] = st->Gcur[k];
-    const double cqx = st->cqx, cqy = st->cqy, ctx = st->ctx, cty = st->cty;
-    const auto member = [&](const EpiXY& p) { return hom_inlier(H, G, p, max_dist2); };
-    refit_block_sums<2, (int)HREFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [=](double (&s)[2], const EpiXY& p) {
-        const double dx = p.x - cqx, dy = p.y - cqy, du = p.u - ctx, dv = p.v - cty;
-        s[0] = s[0] + sqrt(dx * dx + dy * dy);
-        s[1] = s[1] + sqrt(du * du + dv * dv);
-    });
+    refit_pass<2, false, RefitDistAdd>(xy, counts, mcap, state, max_dist2, partial, sum_blocks);
 }
 
-// The sums lie as [A_0 .. A_5, B_0 .. B_5, C_0 .. C_5, D_0 .. D_5], k = the index pairs (0,0), (0,1), (0,2), (1,1), (1,2), (2,2).
-__global__ __launch_bounds__(REFIT_WG) void k_hrefit_moments(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
-                                                              const HRefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
-                                                              unsigned int sum_blocks) {
-    __shared__ double lds[HREFIT_SUMS * 128];  // 24576 bytes
-    if (hrefit_idle(state, counts, mcap)) return;
-    const HRefitState* st = state + blockIdx.y;
-    double H[9], G[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] = st->Hcur[k], G[k] = st->Gcur[k];
-    const double cqx = st->cqx, cqy = st->cqy, ctx = st->ctx, cty = st->cty, sq = st->sq, stt = st->st;
-    const auto member = [&](const EpiXY& p) { return hom_inlier(H, G, p, max_dist2); };
-    refit_block_sums<(int)HREFIT_SUMS, (int)HREFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [=](double (&s)[HREFIT_SUMS], const EpiXY& p) {
-        const double x = (p.x - cqx) * sq, y = (p.y - cqy) * sq, u = (p.u - ctx) * stt, v = (p.v - cty) * stt;
+// One member's 24 terms.  The sums lie as [A_0 .. A_5, B_0 .. B_5, C_0 .. C_5, D_0 .. D_5], k = the index pairs (0,0), (0,1),
+// (0,2), (1,1), (1,2), (2,2).
+struct HRefitMomentsAdd {
+    RefitNorm nm;
+    __device__ void operator()(double (&s)[HREFIT_SUMS], const EpiXY& p) const {
+        const double x = (p.x - nm.cqx) * nm.sq, y = (p.y - nm.cqy) * nm.sq, u = (p.u - nm.ctx) * nm.st, v = (p.v - nm.cty) * nm.st;
         const double w = u * u + v * v;
         const double e[6] = {x * x, x * y, x, y * y, y, 1.0};
 #pragma unroll
@@ -86,21 +55,17 @@ __global__ __launch_bounds__(REFIT_WG) void k_hrefit_moments(const EpiXY* __rest
             s[12 + k] = s[12 + k] + v * e[k];
             s[18 + k] = s[18 + k] + w * e[k];
         }
-    });
+    }
+};
+__global__ __launch_bounds__(REFIT_WG) void k_hrefit_moments(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
+                                                              const HRefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
+                                                              unsigned int sum_blocks) {
+    refit_pass<(int)HREFIT_SUMS, false, HRefitMomentsAdd>(xy, counts, mcap, state, max_dist2, partial, sum_blocks);
 }
 
 // grid = (pair blocks of 64), one lane per pair - as are the three kernels after it.
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_hrefit_init(const vslam_homography* __restrict__ models_in, int n_pairs, HRefitState* __restrict__ state) {
-    const int j = blockIdx.x * REFIT_PAIR_WG + threadIdx.x;
-    if (j >= n_pairs) return;
-    HRefitState s;
-    s.in = models_in[j];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s.Hcur[k] = s.Hcand[k] = s.in.H[k], s.Gcur[k] = s.Gcand[k] = s.in.G[k];
-    s.cqx = s.cqy = s.ctx = s.cty = s.sq = s.st = 0.0;
-    s.n_cur = s.n_before = s.accepted = 0;
-    s.stop = s.in.best < 0 ? 5 : REFIT_RUNNING;
-    state[j] = s;
+    refit_init(models_in, n_pairs, state);
 }
 
 // `models` may be the buffer k_hrefit_init read: it is written by the last launch only (r == rounds), so neither is __restrict__.
@@ -108,58 +73,13 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_hrefit_begin(const double* __
                                                                  const unsigned int* __restrict__ counts, unsigned int mcap, int n_pairs,
                                                                  unsigned int r, unsigned int rounds, HRefitState* __restrict__ state,
                                                                  vslam_homography* models, vslam_hrefit* __restrict__ info) {
-    const int j = blockIdx.x * REFIT_PAIR_WG + threadIdx.x;
-    if (j >= n_pairs) return;
-    HRefitState* st = state + j;
-    if (st->stop == REFIT_RUNNING) {
-        double s[5];
-        refit_pair_sums<5, (int)HREFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
-        const unsigned int n = (unsigned int)s[4];
-        bool running = true;
-        if (r == 0) {
-            st->n_before = st->n_cur = n;
-        } else if (n >= st->n_cur) {  // step 6
-#pragma unroll
-            for (int k = 0; k < 9; ++k) st->Hcur[k] = st->Hcand[k], st->Gcur[k] = st->Gcand[k];
-            st->n_cur = n;
-            st->accepted += 1;
-        } else {
-            st->stop = 4;
-            running = false;
-        }
-        if (running) {
-            if (r == rounds) {
-                st->stop = 0;
-            } else if (st->n_cur < 4) {  // step 1
-                st->stop = 1;
-            } else {  // step 2, the centroids
-                const double nd = (double)st->n_cur;
-                st->cqx = s[0] / nd, st->cqy = s[1] / nd, st->ctx = s[2] / nd, st->cty = s[3] / nd;
-            }
-        }
-    }
-    if (r == rounds) {
-        vslam_homography out = st->in;
-        if (st->stop != 5) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) out.H[k] = st->Hcur[k], out.G[k] = st->Gcur[k];
-            out.n_inliers = st->n_cur;
-        }
-        models[j] = out;
-        if (info) info[j] = vslam_hrefit{st->n_before, st->n_cur, st->accepted, st->stop};
-    }
+    refit_begin(partial, sum_blocks, counts, mcap, n_pairs, r, rounds, state, models, info);
 }
 
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_hrefit_scale(const double* __restrict__ partial, unsigned int sum_blocks,
                                                                  const unsigned int* __restrict__ counts, unsigned int mcap, int n_pairs,
                                                                  HRefitState* __restrict__ state) {
-    const int j = blockIdx.x * REFIT_PAIR_WG + threadIdx.x;
-    if (j >= n_pairs) return;
-    HRefitState* st = state + j;
-    if (st->stop != REFIT_RUNNING) return;
-    double s[2];
-    refit_pair_sums<2, (int)HREFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
-    if (!refit_scales(s, st->n_cur, st->sq, st->st)) st->stop = 2;
+    refit_scale(partial, sum_blocks, counts, mcap, n_pairs, state);
 }
 
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_hrefit_solve(const double* __restrict__ partial, unsigned int sum_blocks,
@@ -203,7 +123,7 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_hrefit_solve(const double* __
         return;
     }
 #pragma unroll
-    for (int i = 0; i < 9; ++i) st->Hcand[i] = Hn[i], st->Gcand[i] = Gn[i];
+    for (int i = 0; i < 9; ++i) st->cand.H[i] = Hn[i], st->cand.G[i] = Gn[i];
 }
 
 }  // namespace vslam

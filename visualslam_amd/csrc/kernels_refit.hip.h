@@ -18,65 +18,34 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
+#include "kernels_estimate.hip.h"
 #include "kernels_geom3.hip.h"
 #include "vslam_refit_plan.h"
 
 namespace vslam {
 
-// (refit_tree<N>, the tree of the ordered sum over the 256 slots, is kernels_geom3.hip.h's: the resection's refinement sums the same way.
-// So are refit_block_sums, refit_pair_sums, refit_scales and the 9 x 9 Jacobi: the refit of the homography, kernels_hrefit.hip.h,
-// runs the same text under its own membership predicate.)
-
-// true: this workgroup has nothing to do - its pair has stopped, or its block lies past the pair's count.
-__device__ __forceinline__ bool refit_idle(const RefitState* __restrict__ state, const unsigned int* __restrict__ counts, unsigned int mcap) {
-    return state[blockIdx.y].stop != REFIT_RUNNING || (size_t)blockIdx.x * REFIT_BLOCK >= g3_count(counts, blockIdx.y, mcap);
-}
+// (What the rounds of this stage and of the homography's share is stated once: kernels_estimate.hip.h has the streaming pass,
+// the count and distance sums and the per-pair steps init, begin and scale; kernels_geom3.hip.h the ordered sum - refit_tree,
+// refit_block_sums, refit_pair_sums -, refit_scales and the 9 x 9 Jacobi.  This stage's own: the add step of the moments pass
+// and steps 3 - 5.)
 
 __global__ __launch_bounds__(REFIT_WG) void k_refit_count(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
                                                            const RefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
                                                            unsigned int sum_blocks) {
-    __shared__ double lds[5 * 128];
-    if (refit_idle(state, counts, mcap)) return;
-    double F[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = state[blockIdx.y].Fcand[k];
-    const auto member = [&](const EpiXY& p) { return epi_inlier(F, p, max_dist2); };
-    refit_block_sums<5, (int)REFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [](double (&s)[5], const EpiXY& p) {
-        s[0] = s[0] + p.x, s[1] = s[1] + p.y, s[2] = s[2] + p.u, s[3] = s[3] + p.v, s[4] = s[4] + 1.0;
-    });
+    refit_pass<5, true, RefitCountAdd>(xy, counts, mcap, state, max_dist2, partial, sum_blocks);
 }
 
 __global__ __launch_bounds__(REFIT_WG) void k_refit_dist(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
                                                           const RefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
                                                           unsigned int sum_blocks) {
-    __shared__ double lds[2 * 128];
-    if (refit_idle(state, counts, mcap)) return;
-    const RefitState* st = state + blockIdx.y;
-    double F[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = st->Fcur[k];
-    const double cqx = st->cqx, cqy = st->cqy, ctx = st->ctx, cty = st->cty;
-    const auto member = [&](const EpiXY& p) { return epi_inlier(F, p, max_dist2); };
-    refit_block_sums<2, (int)REFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [=](double (&s)[2], const EpiXY& p) {
-        const double dx = p.x - cqx, dy = p.y - cqy, du = p.u - ctx, dv = p.v - cty;
-        s[0] = s[0] + sqrt(dx * dx + dy * dy);
-        s[1] = s[1] + sqrt(du * du + dv * dv);
-    });
+    refit_pass<2, false, RefitDistAdd>(xy, counts, mcap, state, max_dist2, partial, sum_blocks);
 }
 
-__global__ __launch_bounds__(REFIT_WG) void k_refit_moments(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
-                                                             const RefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
-                                                             unsigned int sum_blocks) {
-    __shared__ double lds[REFIT_SUMS * 128];  // 46080 bytes
-    if (refit_idle(state, counts, mcap)) return;
-    const RefitState* st = state + blockIdx.y;
-    double F[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) F[k] = st->Fcur[k];
-    const double cqx = st->cqx, cqy = st->cqy, ctx = st->ctx, cty = st->cty, sq = st->sq, stt = st->st;
-    const auto member = [&](const EpiXY& p) { return epi_inlier(F, p, max_dist2); };
-    refit_block_sums<(int)REFIT_SUMS, (int)REFIT_SUMS>(xy, counts, mcap, partial, sum_blocks, lds, member, [=](double (&s)[REFIT_SUMS], const EpiXY& p) {
-        const double x = (p.x - cqx) * sq, y = (p.y - cqy) * sq, u = (p.u - ctx) * stt, v = (p.v - cty) * stt;
+// One member's 45 products a[p] * a[q], p <= q, of its row a of step 3; the tree takes 45 x 128 x 8 = 46080 bytes of LDS.
+struct RefitMomentsAdd {
+    RefitNorm nm;
+    __device__ void operator()(double (&s)[REFIT_SUMS], const EpiXY& p) const {
+        const double x = (p.x - nm.cqx) * nm.sq, y = (p.y - nm.cqy) * nm.sq, u = (p.u - nm.ctx) * nm.st, v = (p.v - nm.cty) * nm.st;
         const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
         int k = 0;
 #pragma unroll
@@ -84,21 +53,17 @@ __global__ __launch_bounds__(REFIT_WG) void k_refit_moments(const EpiXY* __restr
 #pragma unroll
             for (int q_ = p_; q_ < 9; ++q_, ++k) s[k] = s[k] + a[p_] * a[q_];
         }
-    });
+    }
+};
+__global__ __launch_bounds__(REFIT_WG) void k_refit_moments(const EpiXY* __restrict__ xy, const unsigned int* __restrict__ counts, unsigned int mcap,
+                                                             const RefitState* __restrict__ state, double max_dist2, double* __restrict__ partial,
+                                                             unsigned int sum_blocks) {
+    refit_pass<(int)REFIT_SUMS, false, RefitMomentsAdd>(xy, counts, mcap, state, max_dist2, partial, sum_blocks);
 }
 
 // grid = (pair blocks of 64), one lane per pair - as are the three kernels after it.
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_init(const vslam_epipolar* __restrict__ models_in, int n_pairs, RefitState* __restrict__ state) {
-    const int j = blockIdx.x * REFIT_PAIR_WG + threadIdx.x;
-    if (j >= n_pairs) return;
-    RefitState s;
-    s.in = models_in[j];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s.Fcur[k] = s.Fcand[k] = s.in.F[k];
-    s.cqx = s.cqy = s.ctx = s.cty = s.sq = s.st = 0.0;
-    s.n_cur = s.n_before = s.accepted = 0;
-    s.stop = s.in.best < 0 ? 5 : REFIT_RUNNING;
-    state[j] = s;
+    refit_init(models_in, n_pairs, state);
 }
 
 // `models` may be the buffer k_refit_init read: it is written by the last launch only (r == rounds), so neither is __restrict__.
@@ -106,58 +71,13 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_begin(const double* __r
                                                                 const unsigned int* __restrict__ counts, unsigned int mcap, int n_pairs,
                                                                 unsigned int r, unsigned int rounds, RefitState* __restrict__ state,
                                                                 vslam_epipolar* models, vslam_refit* __restrict__ info) {
-    const int j = blockIdx.x * REFIT_PAIR_WG + threadIdx.x;
-    if (j >= n_pairs) return;
-    RefitState* st = state + j;
-    if (st->stop == REFIT_RUNNING) {
-        double s[5];
-        refit_pair_sums<5, (int)REFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
-        const unsigned int n = (unsigned int)s[4];
-        bool running = true;
-        if (r == 0) {
-            st->n_before = st->n_cur = n;
-        } else if (n >= st->n_cur) {  // step 6
-#pragma unroll
-            for (int k = 0; k < 9; ++k) st->Fcur[k] = st->Fcand[k];
-            st->n_cur = n;
-            st->accepted += 1;
-        } else {
-            st->stop = 4;
-            running = false;
-        }
-        if (running) {
-            if (r == rounds) {
-                st->stop = 0;
-            } else if (st->n_cur < 8) {  // step 1
-                st->stop = 1;
-            } else {  // step 2, the centroids
-                const double nd = (double)st->n_cur;
-                st->cqx = s[0] / nd, st->cqy = s[1] / nd, st->ctx = s[2] / nd, st->cty = s[3] / nd;
-            }
-        }
-    }
-    if (r == rounds) {
-        vslam_epipolar out = st->in;
-        if (st->stop != 5) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) out.F[k] = st->Fcur[k];
-            out.n_inliers = st->n_cur;
-        }
-        models[j] = out;
-        if (info) info[j] = vslam_refit{st->n_before, st->n_cur, st->accepted, st->stop};
-    }
+    refit_begin(partial, sum_blocks, counts, mcap, n_pairs, r, rounds, state, models, info);
 }
 
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_scale(const double* __restrict__ partial, unsigned int sum_blocks,
                                                                 const unsigned int* __restrict__ counts, unsigned int mcap, int n_pairs,
                                                                 RefitState* __restrict__ state) {
-    const int j = blockIdx.x * REFIT_PAIR_WG + threadIdx.x;
-    if (j >= n_pairs) return;
-    RefitState* st = state + j;
-    if (st->stop != REFIT_RUNNING) return;
-    double s[2];
-    refit_pair_sums<2, (int)REFIT_SUMS>(partial, j, sum_blocks, g3_count(counts, j, mcap), s);
-    if (!refit_scales(s, st->n_cur, st->sq, st->st)) st->stop = 2;
+    refit_scale(partial, sum_blocks, counts, mcap, n_pairs, state);
 }
 
 __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_solve(const double* __restrict__ partial, unsigned int sum_blocks,
@@ -195,7 +115,7 @@ __global__ __launch_bounds__(REFIT_PAIR_WG) void k_refit_solve(const double* __r
         return;
     }
 #pragma unroll
-    for (int i = 0; i < 9; ++i) st->Fcand[i] = Hm[i] / nrm;
+    for (int i = 0; i < 9; ++i) st->cand.F[i] = Hm[i] / nrm;
 }
 
 }  // namespace vslam

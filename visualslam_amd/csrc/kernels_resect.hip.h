@@ -11,12 +11,15 @@
 //   k_res_select : one workgroup per pair: the valid hypothesis with the most inliers, lowest index on ties
 //   k_res_flags  : one lane per observation record: usable and an inlier of the winner, the wave's ballot word
 // Kernel boundaries order everything: no flags or fences between workgroups, no floating-point atomics.  The arithmetic is the
-// header's, operation for operation, under the rules of kernels_epipolar.hip.h.  The Gauss-Jordan loop and the select kernel are
-// written out again, as in kernels_homography.hip.h: the sizes differ, and the existing kernels' allocation must not move.
+// header's, operation for operation, under the rules of kernels_epipolar.hip.h.  The Gauss-Jordan loop is written out again, as
+// in kernels_homography.hip.h: the sizes differ, and the existing kernels' allocation must not move.  k_res_select is the shared
+// RANSAC step of kernels_estimate.hip.h; k_res_score keeps its own text, as k_epi_score does, and k_res_flags recomputes the
+// correspondence and stays here.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/vslam.h"
+#include "kernels_estimate.hip.h"
 #include "kernels_geom3.hip.h"
 #include "vslam_resect_plan.h"
 
@@ -345,53 +348,16 @@ __global__ __launch_bounds__(EPI_SCORE_WG) void k_res_score(const vslam_resect_c
     if (h < NH && count) atomicAdd(&mine->inliers, count);
 }
 
-// grid = (pairs).  key = valid ? (inliers + 1) << 16 | (65535 - h) : 0: the maximum is the most inliers, then the lowest h.
+// grid = (pairs)
 __global__ __launch_bounds__(256) void k_res_select(const vslam_resect_hyp* __restrict__ hyp, const unsigned int* __restrict__ ocounts,
                                                      unsigned int ocap, const unsigned int* __restrict__ ncorr, unsigned int NH,
                                                      vslam_resect* __restrict__ models) {
-    __shared__ unsigned long long skey[4];
-    __shared__ unsigned int sval[4];
     const int j = blockIdx.x;
-    const vslam_resect_hyp* hy = hyp + (size_t)j * NH;
-    unsigned long long key = 0;
-    unsigned int nvalid = 0;
-    for (unsigned int h = threadIdx.x; h < NH; h += 256)
-        if (hy[h].valid) {
-            ++nvalid;
-            const unsigned long long k = ((unsigned long long)hy[h].inliers + 1ull) << 16 | (unsigned long long)(65535u - h);
-            key = max(key, k);
-        }
-    for (int off = 32; off >= 1; off >>= 1) {
-        key = max(key, (unsigned long long)__shfl_down(key, off));
-        nvalid += __shfl_down(nvalid, off);
-    }
-    if ((threadIdx.x & 63) == 0) skey[threadIdx.x >> 6] = key, sval[threadIdx.x >> 6] = nvalid;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        key = max(max(skey[0], skey[1]), max(skey[2], skey[3]));
-        vslam_resect out;
+    ransac_select<ResModel>(hyp + (size_t)j * NH, NH, models + j, [&](vslam_resect& out) {
         out.n_obs = g3_count(ocounts, j, ocap);
         out.n_corr = g3_count(ncorr, j, ocap);
-        out.n_valid = sval[0] + sval[1] + sval[2] + sval[3];
         out.reserved = 0;
-        if (key) {
-            const unsigned int best = 65535u - (unsigned int)(key & 0xffffull);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.R[i] = hy[best].R[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) out.t[i] = hy[best].t[i];
-            out.n_inliers = hy[best].inliers;
-            out.best = (int)best;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) out.R[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) out.t[i] = 0.0;
-            out.n_inliers = 0;
-            out.best = -1;
-        }
-        models[j] = out;
-    }
+    });
 }
 
 // grid = (record blocks of 256, pairs): bit b % 64 of word b / 64 = observation record b is usable and an inlier of the winner;

@@ -13,6 +13,13 @@ namespace vslam {
 struct __attribute__((aligned(16))) EpiXY {  // one record of the coordinate scratch: query (x, y), train (u, v); NaN: not trusted
     double x, y, u, v;
 };
+// The 3 x 3 blocks of a model, as a lane keeps them in registers and the refits' scratch carries them (kernels_estimate.hip.h).
+struct EpiModel {
+    double F[9];
+};
+struct HomModel {
+    double H[9], G[9];
+};
 
 constexpr unsigned int EPI_TILE = 256;      // match records a k_epi_score workgroup stages in LDS at a time (8 KiB)
 constexpr unsigned int EPI_SCORE_WG = 256;  // hypotheses (lanes) per k_epi_score workgroup
@@ -52,6 +59,15 @@ inline const char* check_intrinsics(const vslam_pose_params& K, const char* not_
 #define OUT_NEEDS(out, field, T, n)                   \
     if (!(out)->field) return #field " is required"; \
     OUT_FITS(out, field, T, n)
+// The list outputs that the `out` of every stage over match records has (epipolar, refit, homography, hrefit), in the ABI's order.
+template <class Out>
+inline const char* twoview_check_lists(const Out* out, size_t np, size_t fwords) {
+    OUT_FITS(out, inlier_bits, uint64_t, np * fwords);
+    if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "inliers needs inlier_counts and an inlier_cap";
+    OUT_FITS(out, inliers, vslam_match, np * out->inlier_cap);
+    OUT_FITS(out, inlier_counts, uint32_t, np);
+    return nullptr;
+}
 // The link table of enqueue_chain_link (vslam_launch.h): row j - 1 links pair j to pair j - 1.
 struct LinkTable {
     unsigned int link_pairs;  // n_pairs - 1: grid.y of k_chain_link (0: not launched)
@@ -72,10 +88,7 @@ inline const char* epipolar_check_args(const vslam_match* matches, const uint32_
     if (const char* why = twoview_check_inputs(matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
     OUT_NEEDS(out, models, vslam_epipolar, np);
-    OUT_FITS(out, inlier_bits, uint64_t, np * fwords);
-    if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "inliers needs inlier_counts and an inlier_cap";
-    OUT_FITS(out, inliers, vslam_match, np * out->inlier_cap);
-    OUT_FITS(out, inlier_counts, uint32_t, np);
+    if (const char* why = twoview_check_lists(out, np, fwords)) return why;
     OUT_FITS(out, hypotheses, vslam_epipolar_hyp, np * prm->n_hypotheses);
     return nullptr;
 }

@@ -46,17 +46,13 @@ int vslam_homography_dev(vslam_ctx* c, const vslam_match* matches, const uint32_
     const HomographyPlan pl = homography_plan(match_cap, n_pairs, H);
     EpiXY* xy = nullptr;
     vslam_homography_hyp* hyp_ws = nullptr;
-    unsigned long long* flags_ws = nullptr;
-    unsigned int* chunk_ws = nullptr;
-    const bool lists = out->inlier_bits || out->inlier_counts;
+    ListOut<vslam_homography_out> lists{out, pl.fwords, pl.flag_words, n_pairs};
     WsPlan ws;
     ws.add(xy, pl.coords_elems);
     if (!out->hypotheses) ws.add(hyp_ws, pl.hyp_elems);
-    if (lists && !out->inlier_bits) ws.add(flags_ws, pl.flag_words);
-    if (out->inlier_counts) ws.add(chunk_ws, match_list_ws_elems(pl.fwords, n_pairs));
+    lists.add(ws);
     TRY(ws.commit(c));
     vslam_homography_hyp* hyp = out->hypotheses ? out->hypotheses : hyp_ws;
-    unsigned long long* flags = out->inlier_bits ? reinterpret_cast<unsigned long long*>(out->inlier_bits) : flags_ws;
 
     TRY(enqueue_epi_coords(c, matches, match_counts, match_cap, query_points, query_cap, train_points, train_cap, n_pairs, xy));
     LAUNCH(c, "k_hom_models", k_hom_models, dim3(pl.model_blocks, n_pairs), dim3(HOM_MODEL_WG), xy, match_counts, match_cap, H, prm->seed, hyp);
@@ -65,11 +61,8 @@ int vslam_homography_dev(vslam_ctx* c, const vslam_match* matches, const uint32_
     LAUNCH(c, "k_hom_select", k_hom_select, dim3(n_pairs), dim3(256), hyp, match_counts, match_cap, H, out->models);
     if (epipolar_models)
         TRY(enqueue_hom_verdict(c, epipolar_models, n_pairs, prm->degenerate_num, prm->degenerate_den, prm->min_inliers, out->models, out->gated_models));
-    if (lists) TRY(enqueue_hom_flags(c, xy, match_counts, match_cap, out->models, prm->max_dist2, n_pairs, flags));
-    if (out->inlier_counts)
-        TRY(enqueue_inlier_list(c, flags, pl.fwords, matches, match_counts, match_cap, n_pairs, chunk_ws, out->inliers, out->inlier_cap,
-                                out->inlier_counts));
-    return VSLAM_OK;
+    if (lists.wanted()) TRY(enqueue_hom_flags(c, xy, match_counts, match_cap, out->models, prm->max_dist2, n_pairs, lists.flags()));
+    return lists.list(c, matches, match_counts, match_cap);
 }
 
 int vslam_homography_host(vslam_ctx* c, const vslam_match* matches, size_t n_matches, const vslam_point* query_points, size_t n_query,
@@ -95,19 +88,7 @@ int vslam_homography_host(vslam_ctx* c, const vslam_match* matches, size_t n_mat
     out.struct_size = sizeof(out);
     TRY(dev.get(c, out.models, 1));
     out.models_bytes = sizeof(vslam_homography);
-    if (inlier_bits) {
-        TRY(dev.get(c, out.inlier_bits, in.fwords));
-        out.inlier_bits_bytes = in.fwords * sizeof(uint64_t);
-    }
-    if (n_inliers) {
-        TRY(dev.get(c, out.inlier_counts, 1));
-        out.inlier_counts_bytes = sizeof(uint32_t);
-        if (inliers) {
-            TRY(dev.get(c, out.inliers, inlier_cap));
-            out.inliers_bytes = inlier_cap * sizeof(vslam_match);
-            out.inlier_cap = (uint32_t)inlier_cap;
-        }
-    }
+    TRY(in.lists(c, dev, out, inlier_bits, inliers, inlier_cap, n_inliers));
     if (hypotheses) {
         TRY(dev.get(c, out.hypotheses, prm->n_hypotheses));
         out.hypotheses_bytes = (size_t)prm->n_hypotheses * sizeof(vslam_homography_hyp);
@@ -117,19 +98,10 @@ int vslam_homography_host(vslam_ctx* c, const vslam_match* matches, size_t n_mat
         out.gated_models_bytes = sizeof(vslam_epipolar);
     }
     TRY(vslam_homography_dev(c, in.d_matches, in.d_cnt, in.mcap, in.d_q, in.qcap, in.d_t, in.tcap, 1, d_epi, prm, &out));
-    uint32_t total = 0;
     HIPCHK(c, hipMemcpyAsync(model, out.models, sizeof(vslam_homography), hipMemcpyDeviceToHost, c->stream));
-    if (inlier_bits && in.used_words) HIPCHK(c, hipMemcpyAsync(inlier_bits, out.inlier_bits, in.used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (hypotheses) HIPCHK(c, hipMemcpyAsync(hypotheses, out.hypotheses, out.hypotheses_bytes, hipMemcpyDeviceToHost, c->stream));
     if (gated_model) HIPCHK(c, hipMemcpyAsync(gated_model, out.gated_models, sizeof(vslam_epipolar), hipMemcpyDeviceToHost, c->stream));
-    if (n_inliers) HIPCHK(c, hipMemcpyAsync(&total, out.inlier_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_inliers) {
-        *n_inliers = total;
-        const size_t k = std::min<size_t>(total, inlier_cap);
-        if (inliers && k) HIPCHK(c, hipMemcpy(inliers, out.inliers, k * sizeof(vslam_match), hipMemcpyDeviceToHost));
-    }
-    return VSLAM_OK;
+    return in.download(c, out);
 }
 
 }  // extern "C"

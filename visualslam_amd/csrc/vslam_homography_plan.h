@@ -25,15 +25,11 @@ inline const char* homography_check_args(const vslam_match* matches, const uint3
     if (prm->degenerate_den == 0) return "degenerate_den must be positive";
     if (const char* why = twoview_check_inputs(matches && match_counts && query_points && train_points, match_cap, query_cap, train_cap)) return why;
     const size_t np = (size_t)n_pairs, fwords = twoview_fwords(match_cap);
-    if (!out->models) return "models is required";
-    if (out->models_bytes / sizeof(vslam_homography) < np) return "models buffer too small";
-    if (out->inlier_bits && out->inlier_bits_bytes / sizeof(uint64_t) < np * fwords) return "inlier_bits buffer too small";
-    if (out->inliers && (!out->inlier_counts || out->inlier_cap == 0)) return "inliers needs inlier_counts and an inlier_cap";
-    if (out->inliers && out->inliers_bytes / sizeof(vslam_match) < np * out->inlier_cap) return "inliers buffer too small";
-    if (out->inlier_counts && out->inlier_counts_bytes / sizeof(uint32_t) < np) return "inlier_counts buffer too small";
-    if (out->hypotheses && out->hypotheses_bytes / sizeof(vslam_homography_hyp) < np * prm->n_hypotheses) return "hypotheses buffer too small";
+    OUT_NEEDS(out, models, vslam_homography, np);
+    if (const char* why = twoview_check_lists(out, np, fwords)) return why;
+    OUT_FITS(out, hypotheses, vslam_homography_hyp, np * prm->n_hypotheses);
     if (out->gated_models && !epipolar_models) return "gated_models needs epipolar_models";
-    if (out->gated_models && out->gated_models_bytes / sizeof(vslam_epipolar) < np) return "gated_models buffer too small";
+    OUT_FITS(out, gated_models, vslam_epipolar, np);
     return nullptr;
 }
 

@@ -134,10 +134,36 @@ class WsPlan {
         return VSLAM_OK;
     }
 };
+
+// The list outputs that the `out` of the four stages over match records has (vslam_epipolar_dev, vslam_refit_dev,
+// vslam_homography_dev, vslam_hrefit_dev): inlier_bits, and inlier_counts with inliers.  add() asks for the scratch they need
+// - the ballot words when the caller gives no inlier_bits, the compaction's chunk counts -, flags() is where the stage's flags
+// kernel writes, list() the compaction.  Not moved between add() and commit(): the plan points at its members.
+template <typename Out>
+struct ListOut {
+    const Out* out;
+    unsigned int fwords;  // the plan's: ballot words per pair, and flag_words of them in all
+    size_t flag_words;
+    int n_pairs;
+    unsigned long long* flags_ws = nullptr;
+    unsigned int* chunk_ws = nullptr;
+
+    bool wanted() const { return out->inlier_bits || out->inlier_counts; }
+    void add(WsPlan& ws) {
+        if (wanted() && !out->inlier_bits) ws.add(flags_ws, flag_words);
+        if (out->inlier_counts) ws.add(chunk_ws, vslam::match_list_ws_elems(fwords, n_pairs));
+    }
+    unsigned long long* flags() const { return out->inlier_bits ? reinterpret_cast<unsigned long long*>(out->inlier_bits) : flags_ws; }
+    int list(vslam_ctx* c, const vslam_match* matches, const unsigned int* match_counts, unsigned int match_cap) const {
+        if (!out->inlier_counts) return VSLAM_OK;
+        return vslam::enqueue_inlier_list(c, flags(), fwords, matches, match_counts, match_cap, n_pairs, chunk_ws, out->inliers, out->inlier_cap,
+                                          out->inlier_counts);
+    }
+};
 }  // namespace
 
 // What the entry points that work from host memory through per-call device buffers share - DevBufs: every *_host entry point;
-// HostPair: the single-pair ones (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host); HostSets: the
+// HostPair: the single-pair ones (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_hrefit_host, vslam_pose_host); HostSets: the
 // matchers' (vslam_match_host and its guided and mutual forms); HostMirror: the batched ones (vslam_chain_host, vslam_resect_host,
 // vslam_resect_refine_host, vslam_tracks_host, vslam_bundle_host) -, and the answer of a device entry point whose caller has no
 // HIP device.
@@ -173,8 +199,10 @@ struct DevBufs {
     }
 };
 
-// One host pair of the two-view entry points (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_pose_host):
-// the checks they share, in the ABI's order, and the device copies of the three lists and of the count.
+// One host pair of the two-view entry points (vslam_epipolar_host, vslam_refit_host, vslam_homography_host, vslam_hrefit_host,
+// vslam_pose_host): the checks they share, in the ABI's order, the device copies of the three lists and of the count, and -
+// for the four that have them - the list outputs: lists() fills them into the device entry point's `out`, download() brings
+// them back.
 struct HostPair {
     const vslam_match* matches;
     const vslam_point *query_points, *train_points;
@@ -183,6 +211,9 @@ struct HostPair {
     vslam_point *d_q = nullptr, *d_t = nullptr;
     uint32_t *d_cnt = nullptr, h_cnt = 0, mcap = 0, qcap = 0, tcap = 0;  // a capacity of at least 1 on every side
     size_t fwords = 0, used_words = 0;                                    // ballot words of the capacity, and those that hold a record
+    uint64_t* h_bits = nullptr;                                           // the caller's list outputs, as lists() was given them
+    vslam_match* h_inliers = nullptr;
+    size_t h_cap = 0, *h_total = nullptr;
 
     // `more`: a further record count of the stage's; `own`: what a check of the stage's own, due before the last one here, found
     int check(vslam_ctx* c, const char* stage, size_t more = 0, const char* own = nullptr) const {
@@ -200,6 +231,41 @@ struct HostPair {
         TRY(dev.put(c, d_cnt, &h_cnt, 1));
         mcap = std::max<uint32_t>(h_cnt, 1), qcap = std::max<uint32_t>((uint32_t)n_query, 1), tcap = std::max<uint32_t>((uint32_t)n_train, 1);
         fwords = ((size_t)mcap + 63) / 64, used_words = (n_matches + 63) / 64;
+        return VSLAM_OK;
+    }
+    // After upload(): inlier_bits, inlier_counts, inliers and inlier_cap of `out` (vslam_epipolar_out, vslam_refit_out,
+    // vslam_homography_out, vslam_hrefit_out) for the host outputs the caller gave.
+    template <typename Out>
+    int lists(vslam_ctx* c, DevBufs& dev, Out& out, uint64_t* inlier_bits, vslam_match* inliers, size_t inlier_cap, size_t* n_inliers) {
+        h_bits = inlier_bits, h_inliers = inliers, h_cap = inlier_cap, h_total = n_inliers;
+        if (inlier_bits) {
+            TRY(dev.get(c, out.inlier_bits, fwords));
+            out.inlier_bits_bytes = fwords * sizeof(uint64_t);
+        }
+        if (n_inliers) {
+            TRY(dev.get(c, out.inlier_counts, 1));
+            out.inlier_counts_bytes = sizeof(uint32_t);
+            if (inliers) {
+                TRY(dev.get(c, out.inliers, inlier_cap));
+                out.inliers_bytes = inlier_cap * sizeof(vslam_match);
+                out.inlier_cap = (uint32_t)inlier_cap;
+            }
+        }
+        return VSLAM_OK;
+    }
+    // After the device entry point and the copies of the entry point's own outputs: the words that hold a record, the total,
+    // the wait for the stream, and the list clamped to the caller's capacity.
+    template <typename Out>
+    int download(vslam_ctx* c, const Out& out) const {
+        uint32_t total = 0;
+        if (h_bits && used_words) HIPCHK(c, hipMemcpyAsync(h_bits, out.inlier_bits, used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        if (h_total) HIPCHK(c, hipMemcpyAsync(&total, out.inlier_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_total) {
+            *h_total = total;
+            const size_t k = std::min<size_t>(total, h_cap);
+            if (h_inliers && k) HIPCHK(c, hipMemcpy(h_inliers, out.inliers, k * sizeof(vslam_match), hipMemcpyDeviceToHost));
+        }
         return VSLAM_OK;
     }
 };
@@ -274,7 +340,7 @@ struct HostSets {
 // The device mirror of one batched host-memory call: each input and each output is stated once - the host array, its element
 // count, where its device pointer goes -, and finish() brings the outputs back whole.  The first failure is kept and what is
 // stated after it is skipped: the entry point asks status() once, before the device entry point.  (The single-pair entry
-// points copy back parts of their lists and keep their own code.)
+// points copy back parts of their lists: HostPair::download.)
 class HostMirror {
     struct Back {
         void* host;

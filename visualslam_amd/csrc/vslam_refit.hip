@@ -29,17 +29,13 @@ int vslam_refit_dev(vslam_ctx* c, const vslam_epipolar* models_in, const vslam_m
     EpiXY* xy = nullptr;
     RefitState* state = nullptr;
     double* partial = nullptr;
-    unsigned long long* flags_ws = nullptr;
-    unsigned int* chunk_ws = nullptr;
-    const bool lists = out->inlier_bits || out->inlier_counts;
+    ListOut<vslam_refit_out> lists{out, pl.fwords, pl.flag_words, n_pairs};
     WsPlan ws;
     ws.add(xy, pl.coords_elems);
     ws.add(state, pl.state_elems);
     ws.add(partial, pl.partial_elems);
-    if (lists && !out->inlier_bits) ws.add(flags_ws, pl.flag_words);
-    if (out->inlier_counts) ws.add(chunk_ws, match_list_ws_elems(pl.fwords, n_pairs));
+    lists.add(ws);
     TRY(ws.commit(c));
-    unsigned long long* flags = out->inlier_bits ? reinterpret_cast<unsigned long long*>(out->inlier_bits) : flags_ws;
 
     const dim3 stream_grid(pl.sum_blocks, n_pairs), pair_grid(pl.pair_blocks);
     const double d2 = prm->max_dist2;
@@ -55,11 +51,8 @@ int vslam_refit_dev(vslam_ctx* c, const vslam_epipolar* models_in, const vslam_m
         LAUNCH(c, "k_refit_moments", k_refit_moments, stream_grid, dim3(REFIT_WG), xy, match_counts, match_cap, state, d2, partial, pl.sum_blocks);
         LAUNCH(c, "k_refit_solve", k_refit_solve, pair_grid, dim3(REFIT_PAIR_WG), partial, pl.sum_blocks, match_counts, match_cap, n_pairs, state);
     }
-    if (lists) TRY(enqueue_epi_flags(c, xy, match_counts, match_cap, out->models, d2, n_pairs, flags));
-    if (out->inlier_counts)
-        TRY(enqueue_inlier_list(c, flags, pl.fwords, matches, match_counts, match_cap, n_pairs, chunk_ws, out->inliers, out->inlier_cap,
-                                out->inlier_counts));
-    return VSLAM_OK;
+    if (lists.wanted()) TRY(enqueue_epi_flags(c, xy, match_counts, match_cap, out->models, d2, n_pairs, lists.flags()));
+    return lists.list(c, matches, match_counts, match_cap);
 }
 
 int vslam_refit_host(vslam_ctx* c, const vslam_epipolar* model_in, const vslam_match* matches, size_t n_matches, const vslam_point* query_points,
@@ -84,32 +77,11 @@ int vslam_refit_host(vslam_ctx* c, const vslam_epipolar* model_in, const vslam_m
         TRY(dev.get(c, out.info, 1));
         out.info_bytes = sizeof(vslam_refit);
     }
-    if (inlier_bits) {
-        TRY(dev.get(c, out.inlier_bits, in.fwords));
-        out.inlier_bits_bytes = in.fwords * sizeof(uint64_t);
-    }
-    if (n_inliers) {
-        TRY(dev.get(c, out.inlier_counts, 1));
-        out.inlier_counts_bytes = sizeof(uint32_t);
-        if (inliers) {
-            TRY(dev.get(c, out.inliers, inlier_cap));
-            out.inliers_bytes = inlier_cap * sizeof(vslam_match);
-            out.inlier_cap = (uint32_t)inlier_cap;
-        }
-    }
+    TRY(in.lists(c, dev, out, inlier_bits, inliers, inlier_cap, n_inliers));
     TRY(vslam_refit_dev(c, d_model, in.d_matches, in.d_cnt, in.mcap, in.d_q, in.qcap, in.d_t, in.tcap, 1, prm, &out));
-    uint32_t total = 0;
     HIPCHK(c, hipMemcpyAsync(model, out.models, sizeof(vslam_epipolar), hipMemcpyDeviceToHost, c->stream));
     if (info) HIPCHK(c, hipMemcpyAsync(info, out.info, sizeof(vslam_refit), hipMemcpyDeviceToHost, c->stream));
-    if (inlier_bits && in.used_words) HIPCHK(c, hipMemcpyAsync(inlier_bits, out.inlier_bits, in.used_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (n_inliers) HIPCHK(c, hipMemcpyAsync(&total, out.inlier_counts, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_inliers) {
-        *n_inliers = total;
-        const size_t k = std::min<size_t>(total, inlier_cap);
-        if (inliers && k) HIPCHK(c, hipMemcpy(inliers, out.inliers, k * sizeof(vslam_match), hipMemcpyDeviceToHost));
-    }
-    return VSLAM_OK;
+    return in.download(c, out);
 }
 
 }  // extern "C"
