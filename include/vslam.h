@@ -2069,6 +2069,106 @@ int vslam_vocab_kmeans_host(vslam_ctx* ctx, const float* desc, const uint8_t* de
                             const float* vocab_in, const uint8_t* vocab_defined, uint32_t K, const vslam_kmeans_params* params,
                             const vslam_kmeans_out* out);
 
+/* ---------------------------------------------------------------- loop verification
+ * A loop candidate of the place recognition section is a bag-of-words coincidence until geometry confirms it.  Four calls take the
+ * device-resident candidate list through the exact matcher and the RANSAC of the two-view section in one asynchronous pass: a table
+ * of (query set, train set) pairs from the candidates (vslam_loop_pairs_dev), the matcher over that table (vslam_match_pairs_dev),
+ * the points of the matched records gathered per pair (vslam_pair_points_dev) so that vslam_epipolar_dev and every stage after it
+ * run on the pairs unchanged, and the verdict (vslam_loop_verdict_dev).  The table serves any pairing a caller writes itself:
+ * keyframe against keyframe, frame j against j + 2.  Everything but the matcher's d2 is integer arithmetic and copies, so a CPU
+ * restates every byte (tests/loopref.py); no output depends on scheduling, vslam_ctx_set_f32_fused or vslam_ctx_set_matrix_path.
+ *
+ *   Pair.  Slot p of a table names set pairs[p].query_set of `query` and set pairs[p].train_set of `train`.  It is EMPTY iff
+ *     (uint32)query_set >= n_query_sets or (uint32)train_set >= n_train_sets (so {-1, -1} is empty against any sets).  Nothing is
+ *     read through an empty pair.  The two sides may be one buffer, a pair may name one set on both sides, and a set may appear in
+ *     any number of slots on either side.
+ *   Table from candidates.  candidates [nq][c] and cand_counts [nq] are vslam_place_dev's outputs for c = max_candidates; the query
+ *     sets are the nq query frames, the train sets the nd database frames.  Slot i * c + r is {i, candidates[i][r].frame - db_first}
+ *     iff r < min(cand_counts[i], c) and the difference, formed in int64, lies in 0 .. nd - 1; otherwise it is {-1, -1}.  A slot
+ *     past the count is not read.  Every one of the nq * c slots is written.
+ *   Match.  Pair p searches the rows of query set pairs[p].query_set among the rows of train set pairs[p].train_set: d2, the
+ *     selection, the skipped rows and ACCEPTED are the descriptor matching section's.  nn, matches and match_counts are indexed by
+ *     p exactly as vslam_match_dev indexes them by its pair.  An empty pair: match_counts[p] = 0, its nn and matches rows are left
+ *     untouched.
+ *   Gather.  For pair p that is not empty, with qs / ts its sets, and record i < min(match_counts[p], match_cap), m = matches[p][i]:
+ *       query_points_out[p][i] = query_points[qs][m.query]   if (uint32)m.query < query_cap, else 24 bytes of 0xff
+ *       train_points_out[p][i] = train_points[ts][m.train]   if (uint32)m.train < train_cap, else 24 bytes of 0xff
+ *       local[p][i]            = {i, i, m.dist2}
+ *     (the all-ones record has octave -1: the two-view section does not trust it).  Rows past the count and the rows of an empty
+ *     pair are left untouched.  Record i of `local` is record i of `matches`, and vslam_epipolar_dev(local, match_counts, match_cap,
+ *     query_points_out, match_cap, train_points_out, match_cap, n_pairs, ..) sees, record for record, the coordinates and the trust
+ *     that the pair's own lists give - so model, inlier bits and counts are those of the pair at index p of a batched call.
+ *   Verdict.  models [nq * c] are the models of the slots, n_train_sets the nd of the table.  Slot p = i * c + r is VERIFIED iff it
+ *     is not empty against (nq, n_train_sets), models[p].best >= 0, models[p].n_inliers >= min_inliers and
+ *     (uint64)n_inliers * den >= (uint64)num * n_matches.  The loop of query frame i is its verified slot with the most inliers,
+ *     equal counts: the lower r.  loops[i] = {pairs[p].query_set, pairs[p].train_set, p, n_matches, n_inliers} of that slot, or
+ *     {i, -1, -1, 0, 0} for a frame without one.  loop_list holds the frames i that have a loop, ascending, in its first n_loops
+ *     entries; the entries after them are left untouched. */
+typedef struct {
+    int32_t query_set, train_set;
+} vslam_set_pair;           /* 8 bytes */
+typedef struct {
+    uint32_t min_inliers;   /* >= 1 */
+    uint32_t num, den;      /* den > 0 */
+    uint32_t reserved;      /* 0 */
+} vslam_loop_params;        /* 16 bytes */
+typedef struct {
+    int32_t query_set, train_set, slot; /* slot = -1 and train_set = -1: no loop */
+    uint32_t n_matches, n_inliers;
+} vslam_loop;               /* 20 bytes */
+typedef struct {
+    size_t struct_size;     /* = sizeof(vslam_loop_out) */
+    vslam_loop* loops;      /* [nq] optional */
+    size_t loops_bytes;
+    int32_t* loop_list;     /* [nq] optional, needs n_loops */
+    size_t loop_list_bytes;
+    uint32_t* n_loops;      /* [1] optional */
+    size_t n_loops_bytes;
+} vslam_loop_out;
+/* DEVICE pointers.  nq <= 65535, 1 <= c <= 8, nd <= 65535; pairs [nq * c] is written whole (nq == 0 does nothing).  Asynchronous
+ * on the context stream, never waits on the host.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for
+ * a null pointer, nq, c or nd out of range, an undersized pairs buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not
+ * for stream capture. */
+int vslam_loop_pairs_dev(vslam_ctx* ctx, const vslam_place_cand* candidates, const uint32_t* cand_counts, uint32_t nq, uint32_t c,
+                         uint32_t db_first, uint32_t nd, vslam_set_pair* pairs, size_t pairs_bytes);
+/* query (n_query_sets sets), train (n_train_sets sets), pairs [n_pairs] and the pointers of `out` ([n_pairs] rows each): DEVICE
+ * pointers.  0 <= n_pairs <= 65535 (0 does nothing), 0 <= n_query_sets, n_train_sets <= 65535.  The norms are computed once per set,
+ * not once per pair.  Asynchronous on the context stream, never waits on the host (the counts and the table are read on the device,
+ * the grids are sized from the capacities); scratch belongs to the context.  VSLAM_ERR_INVALID before any launch - and before the
+ * context is looked at - for a null argument, a wrong struct_size, n_pairs or a set count out of range, a ratio2 that is not finite
+ * or not positive, a set without desc, counts or a capacity, a misaligned desc, same_octave without points, no output at all, matches
+ * without match_counts, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for stream capture. */
+int vslam_match_pairs_dev(vslam_ctx* ctx, const vslam_desc_sets* query, int n_query_sets, const vslam_desc_sets* train, int n_train_sets,
+                          const vslam_set_pair* pairs, int n_pairs, float ratio2, int same_octave, const vslam_match_out* out);
+/* The same call over HOST arrays, synchronous (a convenience path: device buffers per call): the pointers of query and train
+ * ([n][cap][128], [n][cap] or NULL, [n][cap] or NULL, [n]), pairs [n_pairs] and the pointers of `out` are host pointers.  The rows
+ * the device call leaves untouched keep the caller's bytes.  Errors as for vslam_match_pairs_dev (no alignment is asked of host
+ * arrays). */
+int vslam_match_pairs_host(vslam_ctx* ctx, const vslam_desc_sets* query, int n_query_sets, const vslam_desc_sets* train, int n_train_sets,
+                           const vslam_set_pair* pairs, int n_pairs, float ratio2, int same_octave, const vslam_match_out* out);
+/* DEVICE pointers: matches [n_pairs][match_cap] and match_counts [n_pairs] as vslam_match_pairs_dev wrote them, pairs [n_pairs],
+ * query_points [n_query_sets][query_cap], train_points [n_train_sets][train_cap]; the three outputs are [n_pairs][match_cap] each and
+ * all required.  0 <= n_pairs <= 65535 (0 does nothing).  Asynchronous on the context stream, never waits on the host.
+ * VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null pointer, n_pairs or a set count out of
+ * range, match_cap / query_cap / train_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for
+ * stream capture. */
+int vslam_pair_points_dev(vslam_ctx* ctx, const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap,
+                          const vslam_set_pair* pairs, int n_pairs, const vslam_point* query_points, uint32_t query_cap, int n_query_sets,
+                          const vslam_point* train_points, uint32_t train_cap, int n_train_sets, vslam_point* query_points_out,
+                          size_t query_points_out_bytes, vslam_point* train_points_out, size_t train_points_out_bytes, vslam_match* local,
+                          size_t local_bytes);
+/* DEVICE pointers: models [nq * c], pairs [nq * c].  nq <= 65535 (0: n_loops = 0, nothing else is written), 1 <= c <= 8,
+ * n_train_sets <= 65535.  Asynchronous on the context stream, never waits on the host.  VSLAM_ERR_INVALID before any launch - and
+ * before the context is looked at - for a null argument, a wrong struct_size, nq, c or n_train_sets out of range, min_inliers == 0,
+ * den == 0, reserved != 0, no output at all, loop_list without n_loops, an undersized buffer; then VSLAM_ERR_HIP when there is no
+ * usable HIP device.  Not for stream capture. */
+int vslam_loop_verdict_dev(vslam_ctx* ctx, const vslam_epipolar* models, const vslam_set_pair* pairs, uint32_t nq, uint32_t c,
+                           uint32_t n_train_sets, const vslam_loop_params* params, const vslam_loop_out* out);
+/* The same call over HOST arrays, synchronous.  The loop_list entries the device call leaves untouched keep the caller's bytes.
+ * Errors as for vslam_loop_verdict_dev. */
+int vslam_loop_verdict_host(vslam_ctx* ctx, const vslam_epipolar* models, const vslam_set_pair* pairs, uint32_t nq, uint32_t c,
+                            uint32_t n_train_sets, const vslam_loop_params* params, const vslam_loop_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

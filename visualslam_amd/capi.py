@@ -33,6 +33,8 @@ NN2_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4"), ("second_dist2", "<f4"
 MATCH_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("dist2", "<f4")], align=True)  # vslam_match
 RNN_DTYPE = np.dtype([("index", "<i4"), ("dist2", "<f4")], align=True)  # vslam_rnn, 8 bytes
 PLACE_CAND_DTYPE = np.dtype([("frame", "<i4"), ("score", "<u4"), ("norm", "<u4")], align=True)  # vslam_place_cand, 12 bytes
+SET_PAIR_DTYPE = np.dtype([("query_set", "<i4"), ("train_set", "<i4")], align=True)  # vslam_set_pair, 8 bytes
+LOOP_DTYPE = np.dtype([("query_set", "<i4"), ("train_set", "<i4"), ("slot", "<i4"), ("n_matches", "<u4"), ("n_inliers", "<u4")], align=True)  # vslam_loop, 20 bytes
 KMEANS_ROUND_DTYPE = np.dtype([(n, "<u4") for n in ("assigned", "changed", "empty", "ran")], align=True)  # vslam_kmeans_round, 16 bytes
 EPIPOLAR_HYP_DTYPE = np.dtype([("F", "<f8", (9,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_epipolar_hyp, 80 bytes
 EPIPOLAR_DTYPE = np.dtype([("F", "<f8", (9,)), ("n_matches", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"), ("n_valid", "<u4")], align=True)  # vslam_epipolar, 88 bytes
@@ -181,6 +183,24 @@ class KmeansOut(C.Structure):
     """vslam_kmeans_out: struct_size, then every pointer with the bytes behind it."""
     _fields_ = [("struct_size", C.c_size_t), ("vocab", C.c_void_p), ("vocab_bytes", C.c_size_t), ("sizes", C.c_void_p), ("sizes_bytes", C.c_size_t),
                 ("report", C.c_void_p), ("report_bytes", C.c_size_t)]
+
+
+class SetPair(C.Structure):
+    _fields_ = [("query_set", C.c_int32), ("train_set", C.c_int32)]
+
+
+class LoopParams(C.Structure):
+    _fields_ = [("min_inliers", C.c_uint32), ("num", C.c_uint32), ("den", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Loop(C.Structure):
+    _fields_ = [("query_set", C.c_int32), ("train_set", C.c_int32), ("slot", C.c_int32), ("n_matches", C.c_uint32), ("n_inliers", C.c_uint32)]
+
+
+class LoopOut(C.Structure):
+    """vslam_loop_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("loops", C.c_void_p), ("loops_bytes", C.c_size_t), ("loop_list", C.c_void_p),
+                ("loop_list_bytes", C.c_size_t), ("n_loops", C.c_void_p), ("n_loops_bytes", C.c_size_t)]
 
 
 class EpipolarHyp(C.Structure):
@@ -503,6 +523,12 @@ SIGNATURES = {
     "vslam_vocab_kmeans_dev": (_I, [_P, C.POINTER(DescSets), _I, _P, _P, C.c_uint32, C.POINTER(KmeansParams), C.POINTER(KmeansOut)]),
     "vslam_vocab_kmeans_host": (_I, [_P, _P, _P, _P, C.c_uint32, _I, _P, _P, C.c_uint32, C.POINTER(KmeansParams), C.POINTER(KmeansOut)]),
     "vslam_place_host": (_I, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PlaceParams), C.POINTER(PlaceOut)]),
+    "vslam_loop_pairs_dev": (_I, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _Z]),
+    "vslam_match_pairs_dev": (_I, [_P, C.POINTER(DescSets), _I, C.POINTER(DescSets), _I, _P, _I, _F, _I, C.POINTER(MatchOut)]),
+    "vslam_match_pairs_host": (_I, [_P, C.POINTER(DescSets), _I, C.POINTER(DescSets), _I, _P, _I, _F, _I, C.POINTER(MatchOut)]),
+    "vslam_pair_points_dev": (_I, [_P, _P, _P, C.c_uint32, _P, _I, _P, C.c_uint32, _I, _P, C.c_uint32, _I, _P, _Z, _P, _Z, _P, _Z]),
+    "vslam_loop_verdict_dev": (_I, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoopParams), C.POINTER(LoopOut)]),
+    "vslam_loop_verdict_host": (_I, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoopParams), C.POINTER(LoopOut)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -1904,6 +1930,140 @@ class Context:
         self._chk(lib().vslam_place_host(self._h, _ptr(hq), nq, int(q_first), _ptr(hd), nd, int(db_first), K, C.byref(pp), C.byref(po)),
                   "vslam_place_host")
         return r
+
+    # ---- loop verification: the defaults of min_inliers and num / den are the ones DESIGN 5.28 measures
+    LOOP_MIN_INLIERS, LOOP_NUM, LOOP_DEN = 12, 2, 5
+
+    def loop_pairs(self, candidates, cand_counts, pairs, db_first: int = 0, nd: int | None = None):
+        """vslam_loop_pairs_dev: the pair table of place()'s outputs; asynchronous on the context stream.  candidates: int32
+        [nq, c, 3], cand_counts: int32 [nq], pairs: int32 [nq * c, 2] (SET_PAIR_DTYPE), written whole.  nd: the database frames
+        (None: nq, a batch searched in itself)."""
+        stage = "loop_pairs"
+        _check_tensors(stage, self.where, dict(candidates=candidates, cand_counts=cand_counts, pairs=pairs), ("candidates", "cand_counts", "pairs"))
+        if candidates.dim() != 3 or candidates.shape[2] * candidates.element_size() != 12:
+            raise ValueError(f"{stage}: candidates must be [nq, c, 3] 4-byte elements")
+        nq, c = candidates.shape[0], candidates.shape[1]
+        _check_sets(stage, nq, (), (cand_counts,), ())
+        self._chk(lib().vslam_loop_pairs_dev(self._h, candidates.data_ptr(), cand_counts.data_ptr(), nq, c, int(db_first), nq if nd is None else int(nd),
+                                             pairs.data_ptr(), _nbytes(pairs)), "vslam_loop_pairs_dev")
+
+    def match_pairs(self, query: DescSets, train: DescSets, pairs, n_pairs: int | None = None, ratio2: float = 0.64, same_octave: bool = False,
+                    nn=None, matches=None, match_counts=None, n_query_sets: int | None = None, n_train_sets: int | None = None):
+        """vslam_match_pairs_dev: slot p of `pairs` (int32 [n_pairs, 2], SET_PAIR_DTYPE) matches set pairs[p].query_set of `query`
+        against set pairs[p].train_set of `train` (desc_sets(); the two may be one buffer); asynchronous on the context stream.
+        nn, matches, match_counts as match()'s, indexed by the slot."""
+        stage = "match_pairs"
+        outs = dict(nn=nn, matches=matches, match_counts=match_counts)
+        _check_tensors(stage, self.where, dict(pairs=pairs, **outs), ("pairs",))
+        for name, t in dict(pairs=pairs, **outs).items():
+            if t is not None and t.element_size() != 4:
+                raise ValueError(f"{stage}: {name} must have 4-byte elements")
+        n = pairs.numel() // 2 if n_pairs is None else int(n_pairs)
+        if pairs.numel() < 2 * n:
+            raise ValueError(f"{stage}: fewer slots than pairs")
+        mo = _fill_out(MatchOut(), outs)
+        if matches is not None:
+            mo.match_cap = matches.shape[1]
+        self._chk(lib().vslam_match_pairs_dev(self._h, C.byref(query), query.n if n_query_sets is None else int(n_query_sets), C.byref(train),
+                                              train.n if n_train_sets is None else int(n_train_sets), pairs.data_ptr(), n, float(ratio2),
+                                              int(bool(same_octave)), C.byref(mo)), "vslam_match_pairs_dev")
+
+    def match_pairs_host(self, query, query_counts, train, train_counts, pairs, ratio2: float = 0.64, same_octave: bool = False, query_defined=None,
+                         train_defined=None, query_points=None, train_points=None, match_cap: int | None = None, nn=None, matches=None):
+        """vslam_match_pairs_host over numpy arrays: query [nqs, qcap, 128], train [nts, tcap, 128] (may be the same array), counts [n],
+        defined [n, cap] / points [n, cap] (POINT_DTYPE) or None, pairs SET_PAIR_DTYPE [n_pairs] -> (nn [n_pairs, qcap] NN2_DTYPE,
+        matches [n_pairs, match_cap] MATCH_DTYPE, match_counts [n_pairs]).  nn / matches: arrays whose bytes the untouched rows keep
+        (None: zeros)."""
+        stage = "match_pairs_host"
+        same = train is query
+        q = np.ascontiguousarray(query, dtype=np.float32)
+        t = q if same else np.ascontiguousarray(train, dtype=np.float32)
+        if q.ndim != 3 or t.ndim != 3 or q.shape[2] != 128 or t.shape[2] != 128:
+            raise ValueError(f"{stage}: query and train must be [n_sets, cap, 128]")
+        pr = _records(pairs, SET_PAIR_DTYPE)
+        qc = _counts(query_counts)
+        tc = qc if same else _counts(train_counts)
+        if len(qc) != q.shape[0] or len(tc) != t.shape[0]:
+            raise ValueError(f"{stage}: one count per set")
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in
+               ((query_defined, np.uint8), (query_points, POINT_DTYPE), (train_defined, np.uint8), (train_points, POINT_DTYPE))]
+        for a, rows in zip(opt, (q.shape[0] * q.shape[1],) * 2 + (t.shape[0] * t.shape[1],) * 2):
+            if a is not None and a.size != rows:
+                raise ValueError(f"{stage}: defined / points must have one entry per descriptor row")
+        cap = max(q.shape[1], 1) if match_cap is None else int(match_cap)
+        n = len(pr)
+        nn = np.zeros((n, q.shape[1]), NN2_DTYPE) if nn is None else nn
+        matches = np.zeros((n, cap), MATCH_DTYPE) if matches is None else matches
+        _check_host_outs(stage, (("nn", nn, NN2_DTYPE, n * q.shape[1]), ("matches", matches, MATCH_DTYPE, n * cap)))
+        counts = np.zeros(n, np.uint32)
+        mo = _fill_out(MatchOut(), dict(nn=nn, matches=matches, match_counts=counts))
+        mo.match_cap = cap
+        Q = DescSets(q.ctypes.data, _ptr(opt[0]), _ptr(opt[1]), qc.ctypes.data, q.shape[1])
+        T = DescSets(t.ctypes.data, _ptr(opt[2]), _ptr(opt[3]), tc.ctypes.data, t.shape[1])
+        self._chk(lib().vslam_match_pairs_host(self._h, C.byref(Q), q.shape[0], C.byref(T), t.shape[0], pr.ctypes.data, n, float(ratio2),
+                                               int(bool(same_octave)), C.byref(mo)), "vslam_match_pairs_host")
+        return nn, matches, counts
+
+    def pair_points(self, matches, match_counts, pairs, query_points, train_points, query_points_out, train_points_out, local,
+                    n_pairs: int | None = None):
+        """vslam_pair_points_dev: the points of every matched record of every slot, gathered so that epipolar(local, match_counts,
+        query_points_out, train_points_out) and the stages after it run on the slots; asynchronous on the context stream.  matches
+        [n_pairs, match_cap, 3], match_counts int32 [n_pairs], pairs int32 [n_pairs, 2], query_points / train_points int32 [n_sets, cap, 6];
+        outputs: query_points_out / train_points_out int32 [n_pairs, match_cap, 6], local [n_pairs, match_cap, 3]."""
+        stage = "pair_points"
+        t = dict(matches=matches, match_counts=match_counts, pairs=pairs, query_points=query_points, train_points=train_points,
+                 query_points_out=query_points_out, train_points_out=train_points_out, local=local)
+        _check_tensors(stage, self.where, t, tuple(t))
+        _check_records(stage, "matches", matches, 12, "[n, match_cap, 3]")
+        _check_records(stage, "query_points", query_points, 24, "[n, cap, 6]")
+        _check_records(stage, "train_points", train_points, 24, "[n, cap, 6]")
+        n = matches.shape[0] if n_pairs is None else int(n_pairs)
+        _check_sets(stage, n, (matches,), (match_counts,), ((pairs, n * 8),))
+        self._chk(lib().vslam_pair_points_dev(self._h, matches.data_ptr(), match_counts.data_ptr(), matches.shape[1], pairs.data_ptr(), n,
+                                              query_points.data_ptr(), query_points.shape[1], query_points.shape[0], train_points.data_ptr(),
+                                              train_points.shape[1], train_points.shape[0], query_points_out.data_ptr(), _nbytes(query_points_out),
+                                              train_points_out.data_ptr(), _nbytes(train_points_out), local.data_ptr(), _nbytes(local)),
+                  "vslam_pair_points_dev")
+
+    def loop_verdict(self, models, pairs, nq: int, c: int, n_train_sets: int, min_inliers: int | None = None, num: int | None = None,
+                     den: int | None = None, loops=None, loop_list=None, n_loops=None):
+        """vslam_loop_verdict_dev: the verified loop of each of nq query frames from the models of its c slots (models: nq * c * 88
+        bytes as epipolar() wrote them, pairs int32 [nq * c, 2]); asynchronous on the context stream.  loops: int32 [nq, 5] (LOOP_DTYPE),
+        loop_list: int32 [nq], n_loops: int32 [1] - each optional, loop_list needs n_loops."""
+        stage = "loop_verdict"
+        outs = dict(loops=loops, loop_list=loop_list, n_loops=n_loops)
+        _check_tensors(stage, self.where, dict(models=models, pairs=pairs, **outs), ("models", "pairs"))
+        if all(t is None for t in outs.values()):
+            raise ValueError(f"{stage}: no output requested")
+        if loop_list is not None and n_loops is None:
+            raise ValueError(f"{stage}: loop_list needs n_loops")
+        _check_sets(stage, 0, (), (), ((models, nq * c * 88), (pairs, nq * c * 8)))
+        lp = self._loop_params(min_inliers, num, den)
+        lo = _fill_out(LoopOut(), outs)
+        self._chk(lib().vslam_loop_verdict_dev(self._h, models.data_ptr(), pairs.data_ptr(), int(nq), int(c), int(n_train_sets), C.byref(lp), C.byref(lo)),
+                  "vslam_loop_verdict_dev")
+
+    @classmethod
+    def _loop_params(cls, min_inliers, num, den):
+        return LoopParams(cls.LOOP_MIN_INLIERS if min_inliers is None else int(min_inliers), cls.LOOP_NUM if num is None else int(num),
+                          cls.LOOP_DEN if den is None else int(den), 0)
+
+    def loop_verdict_host(self, models, pairs, c: int, n_train_sets: int, min_inliers: int | None = None, num: int | None = None,
+                          den: int | None = None, fill: int = -1):
+        """vslam_loop_verdict_host over numpy records: models EPIPOLAR_DTYPE [nq * c], pairs SET_PAIR_DTYPE [nq * c] -> (loops LOOP_DTYPE
+        [nq], loop_list int32 [nq] whose entries past n_loops keep `fill`, n_loops)."""
+        stage = "loop_verdict_host"
+        md, pr = _records(models, EPIPOLAR_DTYPE), _records(pairs, SET_PAIR_DTYPE)
+        c = int(c)
+        if c < 1 or len(md) != len(pr) or len(pr) % c:
+            raise ValueError(f"{stage}: models and pairs must be [nq * c]")
+        nq = len(pr) // c
+        loops, lst, n = np.zeros(nq, LOOP_DTYPE), np.full(nq, fill, np.int32), np.zeros(1, np.uint32)
+        lp = self._loop_params(min_inliers, num, den)
+        lo = _fill_out(LoopOut(), dict(loops=loops, loop_list=lst, n_loops=n))
+        self._chk(lib().vslam_loop_verdict_host(self._h, md.ctypes.data if nq else loops.ctypes.data, pr.ctypes.data if nq else loops.ctypes.data, nq, c,
+                                                int(n_train_sets), C.byref(lp), C.byref(lo)), "vslam_loop_verdict_host")
+        return loops, lst, int(n[0])
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

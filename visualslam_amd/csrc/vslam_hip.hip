@@ -71,7 +71,8 @@ static const char* const kKernelNames =
     "k_ba_init\nk_ba_points\nk_ba_cam_pass\nk_ba_cam_step\nk_ba_member_bits\nk_ba_points_final\n"
     "k_vocab_gather\nk_words_nn\nk_words_merge\n"
     "k_place_df\nk_place_self\nk_place_score\nk_place_top\n"
-    "k_kmeans_init\nk_kmeans_count\nk_kmeans_columns\nk_kmeans_scan\nk_kmeans_members\nk_kmeans_block_sums\nk_kmeans_update";
+    "k_kmeans_init\nk_kmeans_count\nk_kmeans_columns\nk_kmeans_scan\nk_kmeans_members\nk_kmeans_block_sums\nk_kmeans_update\n"
+    "k_loop_pairs\nk_match_nn2_pairs\nk_match_merge_pairs\nk_pair_points\nk_loop_verdict";
 
 
 // Runs `body` with the context's launch stream temporarily replaced (LAUNCH uses ctx->stream).

@@ -3,12 +3,16 @@
 // (vslam::sampleVocabulary), the visual word of every descriptor with a histogram per frame (vslam::assignWords), and the loop
 // candidates of every frame among the frames at least min_gap before it (vslam::findLoopCandidates; include/vslam.h, "place
 // recognition").  Prints one JSON line: the descriptor count of every frame and its candidates as [frame, score, norm].
-//   usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] [--kmeans R] (a.pgm b.pgm ... | WxH N)
+//   usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] [--kmeans R] [--verify MIN_INLIERS]
+//                (a.pgm b.pgm ... | WxH N)
 //          (WxH N: frames 0 .. N-1 of the synthetic stream; defaults: K 256, gap 4, 3 candidates, threshold 1/5, 3 octaves;
 //           --vocab-frames V: the vocabulary is sampled from the first V frames only, default all;
 //           --kmeans R: the sampled vocabulary is trained for R rounds on those frames before the words are taken
 //           (vslam::trainVocabulary; "vocabulary training"), and the line carries the report of every round as
-//           [assigned, changed, empty, ran])
+//           [assigned, changed, empty, ran];
+//           --verify MIN_INLIERS: every candidate is matched and tested against a RANSAC fundamental matrix (vslam::verifyLoops;
+//           "loop verification", inlier share 2/5), and the line carries each frame's verified loop beside its candidates as
+//           "loops": [train frame, slot, matches, inliers] ([-1, -1, 0, 0]: none) and every slot's "verified": [matches, inliers, best])
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +30,7 @@ int main(int argc, char** argv) {
         vslam_place_params params{4, 3, 1, 5, 0, 0};
         int numOctaves = 3;
         size_t vocabFrames = 0;
-        uint32_t kmeansRounds = 0;
+        uint32_t kmeansRounds = 0, verifyMinInliers = 0;
         while (argc > 2 && argv[1][0] == '-' && argv[1][1] == '-') {
             const std::string opt = argv[1];
             if (opt == "--words") K = (uint32_t)std::strtoul(argv[2], nullptr, 10);
@@ -35,6 +39,10 @@ int main(int argc, char** argv) {
             else if (opt == "--octaves") numOctaves = std::atoi(argv[2]);
             else if (opt == "--vocab-frames") vocabFrames = (size_t)std::strtoul(argv[2], nullptr, 10);
             else if (opt == "--kmeans") kmeansRounds = (uint32_t)std::strtoul(argv[2], nullptr, 10);
+            else if (opt == "--verify") {
+                verifyMinInliers = (uint32_t)std::strtoul(argv[2], nullptr, 10);
+                if (verifyMinInliers == 0) throw std::runtime_error("--verify takes MIN_INLIERS >= 1");
+            }
             else if (opt == "--threshold") {
                 if (std::sscanf(argv[2], "%u/%u", &params.num, &params.den) != 2) throw std::runtime_error("--threshold takes NUM/DEN");
             } else throw std::runtime_error("unknown option " + opt);
@@ -48,10 +56,11 @@ int main(int argc, char** argv) {
             for (int a = 1; a < argc; ++a) images.push_back(imgio::read_pgm(argv[a]));
         }
         if (images.empty())
-            throw std::runtime_error("usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] [--kmeans R] (a.pgm b.pgm ... | WxH N)");
+            throw std::runtime_error("usage: Place [--words K] [--gap G] [--candidates C] [--threshold NUM/DEN] [--octaves N] [--vocab-frames V] [--kmeans R] [--verify MIN_INLIERS] (a.pgm b.pgm ... | WxH N)");
 
         vslam::DescriptorSets frames(images.size());
         vslam::DefinedSets defined(images.size());
+        std::vector<std::vector<SLAM::point>> points(images.size());
         for (size_t f = 0; f < images.size(); ++f) {
             GaussPyramid pyramid{images[f], numOctaves, 1.6};
             for (int octave = 0; octave < pyramid.getNumOctaves(); ++octave) {
@@ -60,6 +69,7 @@ int main(int argc, char** argv) {
                 filterKeypoints(pyramid, octave, keypoints, reducedKeypoints);
                 std::vector<unsigned char> def;
                 SIFT(reducedKeypoints, frames[f], pyramid, octave, &def);
+                points[f].insert(points[f].end(), reducedKeypoints.begin(), reducedKeypoints.end());
                 defined[f].insert(defined[f].end(), def.begin(), def.end());
             }
         }
@@ -102,6 +112,25 @@ int main(int argc, char** argv) {
                 s += (r ? ", [" : "[") + std::to_string(c.frame) + ", " + std::to_string(c.score) + ", " + std::to_string(c.norm) + "]";
             }
             s += "]";
+        }
+        if (verifyMinInliers) {
+            const vslam::VerifiedLoops v = vslam::verifyLoops(frames, points, loops.candidates, params.max_candidates, 0, vslam_loop_params{verifyMinInliers, 2, 5, 0},
+                                                              vslam_epipolar_params{512, 1, 4.0}, 0.8f, &defined);
+            s += "], \"loops\": [";
+            for (size_t f = 0; f < frames.size(); ++f) {
+                const vslam_loop& l = v.loops[f];
+                s += (f ? ", [" : "[") + std::to_string(l.train_set) + ", " + std::to_string(l.slot) + ", " + std::to_string(l.n_matches) + ", " +
+                     std::to_string(l.n_inliers) + "]";
+            }
+            s += "], \"verified\": [";
+            for (size_t f = 0; f < frames.size(); ++f) {
+                s += f ? ", [" : "[";
+                for (size_t r = 0; r < loops.candidates[f].size(); ++r) {
+                    const vslam_epipolar& m = v.models[f * params.max_candidates + r];
+                    s += (r ? ", [" : "[") + std::to_string(m.n_matches) + ", " + std::to_string(m.n_inliers) + ", " + std::to_string(m.best) + "]";
+                }
+                s += "]";
+            }
         }
         std::printf("%s]}\n", s.c_str());
     } catch (const std::exception& e) {

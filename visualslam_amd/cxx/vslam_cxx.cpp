@@ -956,3 +956,94 @@ vslam::TrainedVocabulary vslam::trainVocabulary(const DescriptorSets& frames, co
                                          vocabulary.defined.data(), K, &params, &o), c, "trainVocabulary");
     return out;
 }
+
+// ---- loop verification (include/vslam.h, "loop verification") -------------------------------------------------------
+
+static bool emptyPair(const vslam_set_pair& pr, size_t nQuery, size_t nTrain) { return (uint32_t)pr.query_set >= nQuery || (uint32_t)pr.train_set >= nTrain; }
+
+vslam::PairMatches vslam::matchPairs(const DescriptorSets& query, const DescriptorSets& train, const std::vector<vslam_set_pair>& pairs, float ratio,
+                                     const DefinedSets* queryDefined, const DefinedSets* trainDefined) {
+    requireFrames(query, queryDefined, "matchPairs: one defined flag per descriptor", "matchPairs: a descriptor is not 128 floats");
+    const bool same = &query == &train && queryDefined == trainDefined;
+    if (!same) requireFrames(train, trainDefined, "matchPairs: one defined flag per descriptor", "matchPairs: a descriptor is not 128 floats");
+    require(query.size() <= 65535 && train.size() <= 65535 && pairs.size() <= 65535, "matchPairs: at most 65535 frames on either side and 65535 pairs");
+    require(std::isfinite(ratio) && ratio > 0.0f, "matchPairs: ratio must be finite and positive");
+    vslam::PairMatches out;
+    out.nn.resize(pairs.size()), out.matches.resize(pairs.size());
+    if (pairs.empty()) return out;
+    const PackedFrames q(query, queryDefined, "matchPairs: too many descriptors");
+    const vslam::DescriptorSets noFrames;
+    const PackedFrames t(same ? noFrames : train, same ? nullptr : trainDefined, "matchPairs: too many descriptors");
+    static const float noRow[128] = {};  // (a side without frames is never read: the entry point still asks for its pointers)
+    static const uint32_t noCount = 0;
+    auto sets = [&](const PackedFrames& f, size_t n) {
+        return vslam_desc_sets{n ? f.desc.data() : noRow, n ? f.def.data() : nullptr, nullptr, n ? f.counts.data() : &noCount, (uint32_t)f.cap};
+    };
+    const vslam_desc_sets Q = sets(q, query.size()), T = same ? Q : sets(t, train.size());
+    const size_t n = pairs.size(), cap = q.cap;
+    std::vector<vslam_nn2> nn(n * cap);
+    std::vector<vslam_match> matches(n * cap);
+    std::vector<uint32_t> counts(n, 0);
+    vslam_match_out o{};
+    o.struct_size = sizeof(o);
+    o.nn = nn.data(), o.nn_bytes = nn.size() * sizeof(vslam_nn2);
+    o.matches = matches.data(), o.matches_bytes = matches.size() * sizeof(vslam_match), o.match_cap = (uint32_t)cap;
+    o.match_counts = counts.data(), o.match_counts_bytes = counts.size() * sizeof(uint32_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_match_pairs_host(c, &Q, (int)query.size(), &T, (int)train.size(), pairs.data(), (int)n, ratio * ratio, 0, &o), c, "matchPairs");
+    for (size_t p = 0; p < n; ++p) {
+        if (emptyPair(pairs[p], query.size(), train.size())) continue;
+        out.nn[p].assign(nn.begin() + p * cap, nn.begin() + p * cap + q.counts[pairs[p].query_set]);
+        out.matches[p].assign(matches.begin() + p * cap, matches.begin() + p * cap + std::min<size_t>(counts[p], cap));
+    }
+    return out;
+}
+
+vslam::VerifiedLoops vslam::verifyLoops(const DescriptorSets& frames, const std::vector<std::vector<SLAM::point>>& points,
+                                        const std::vector<std::vector<vslam_place_cand>>& candidates, uint32_t maxCandidates, uint32_t dbFirst,
+                                        const vslam_loop_params& params, const vslam_epipolar_params& ransac, float ratio, const DefinedSets* defined) {
+    const size_t n = frames.size(), cmax = maxCandidates;
+    require(points.size() == n && candidates.size() == n, "verifyLoops: one point list and one candidate list per frame");
+    for (size_t f = 0; f < n; ++f) require(points[f].size() == frames[f].size(), "verifyLoops: one keypoint per descriptor");
+    require(cmax >= 1 && cmax <= 8, "verifyLoops: maxCandidates must be 1 .. 8");
+    require(n * cmax <= 65535, "verifyLoops: at most 65535 slots");
+    require(params.min_inliers >= 1 && params.den > 0 && params.reserved == 0, "verifyLoops: min_inliers and den must be positive, reserved 0");
+    vslam::VerifiedLoops out;
+    out.pairs.assign(n * cmax, vslam_set_pair{-1, -1});
+    for (size_t i = 0; i < n; ++i)
+        for (size_t r = 0; r < std::min(candidates[i].size(), cmax); ++r) {
+            const long long d = (long long)candidates[i][r].frame - (long long)dbFirst;
+            if (d >= 0 && d < (long long)n) out.pairs[i * cmax + r] = vslam_set_pair{(int32_t)i, (int32_t)d};
+        }
+    out.matches = vslam::matchPairs(frames, frames, out.pairs, ratio, defined, defined).matches;
+    out.models.assign(n * cmax, vslam_epipolar{});
+    out.loops.resize(n);
+    if (n == 0) return out;
+    for (size_t p = 0; p < out.pairs.size(); ++p) {
+        out.models[p].best = -1;
+        if (emptyPair(out.pairs[p], n, n)) continue;
+        // the gather: record i of the local list is record i of the slot's matches
+        const std::vector<vslam_match>& m = out.matches[p];
+        std::vector<vslam_match> local(m.size());
+        std::vector<SLAM::point> qp(m.size()), tp(m.size());
+        for (size_t i = 0; i < m.size(); ++i) {
+            local[i] = vslam_match{(int32_t)i, (int32_t)i, m[i].dist2};
+            qp[i] = points[out.pairs[p].query_set][m[i].query];
+            tp[i] = points[out.pairs[p].train_set][m[i].train];
+        }
+        vslam_epipolar_params prm = ransac;
+        prm.seed = ransac.seed + (uint32_t)p;  // hypothesis h of pair 0 under seed + p draws what pair p draws under seed
+        out.models[p] = vslam::fundamentalRansac(local, qp, tp, prm).model;
+    }
+    std::vector<int32_t> list(n, -1);
+    uint32_t count = 0;
+    vslam_loop_out o{};
+    o.struct_size = sizeof(o);
+    o.loops = out.loops.data(), o.loops_bytes = out.loops.size() * sizeof(vslam_loop);
+    o.loop_list = list.data(), o.loop_list_bytes = list.size() * sizeof(int32_t);
+    o.n_loops = &count, o.n_loops_bytes = sizeof(count);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_loop_verdict_host(c, out.models.data(), out.pairs.data(), (uint32_t)n, (uint32_t)cmax, (uint32_t)n, &params, &o), c, "verifyLoops");
+    out.loopList.assign(list.begin(), list.begin() + std::min<size_t>(count, n));
+    return out;
+}

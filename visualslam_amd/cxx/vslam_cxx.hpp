@@ -401,4 +401,30 @@ struct LoopCandidates {
 // (vslam_place_host).  One batch searched in itself: the same vector twice.
 LoopCandidates findLoopCandidates(const std::vector<uint32_t>& histQ, uint32_t qFirst, const std::vector<uint32_t>& histDb, uint32_t dbFirst, uint32_t K,
                                   const vslam_place_params& params = {4, 3, 1, 5, 0, 0});
+
+// Loop verification (include/vslam.h, "loop verification"): a candidate is a coincidence of words until geometry confirms it.
+// matchPairs is the matcher over a table of (query frame, train frame) pairs, on the GPU (vslam_match_pairs_host): slot p gets the
+// nearest two of every descriptor of frame pairs[p].query_set of `query` among those of frame pairs[p].train_set of `train` (the two
+// may be one object).  A slot that names no frame on either side is empty: its lists are.
+struct PairMatches {
+    std::vector<std::vector<vslam_nn2>> nn;         // [slot][query descriptor]
+    std::vector<std::vector<vslam_match>> matches;  // [slot]: the accepted queries, ascending query order
+};
+PairMatches matchPairs(const DescriptorSets& query, const DescriptorSets& train, const std::vector<vslam_set_pair>& pairs, float ratio = 0.8f,
+                       const DefinedSets* queryDefined = nullptr, const DefinedSets* trainDefined = nullptr);
+// The whole chain from candidates to loops over one sequence of frames searched in itself: the table of LoopCandidates::candidates
+// (c = maxCandidates slots per frame, frame ids from dbFirst), matchPairs, the points of every matched record gathered, the
+// fundamental matrix of every slot by RANSAC (vslam_epipolar_host with seed + slot: the sampling of slot p of one batched
+// vslam_epipolar_dev call) and the verdict, on the GPU (vslam_loop_verdict_host).  points[f]: one keypoint per descriptor of frame f.
+struct VerifiedLoops {
+    std::vector<vslam_set_pair> pairs;              // [frames * c]
+    std::vector<std::vector<vslam_match>> matches;  // [slot]
+    std::vector<vslam_epipolar> models;             // [slot]
+    std::vector<vslam_loop> loops;                  // [frame]: slot = -1 and train_set = -1 without a loop
+    std::vector<int32_t> loopList;                  // the frames that have a loop, ascending
+};
+VerifiedLoops verifyLoops(const DescriptorSets& frames, const std::vector<std::vector<SLAM::point>>& points,
+                          const std::vector<std::vector<vslam_place_cand>>& candidates, uint32_t maxCandidates, uint32_t dbFirst = 0,
+                          const vslam_loop_params& params = {12, 2, 5, 0}, const vslam_epipolar_params& ransac = {512, 1, 4.0}, float ratio = 0.8f,
+                          const DefinedSets* defined = nullptr);
 }  // namespace vslam
