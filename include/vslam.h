@@ -2169,6 +2169,185 @@ int vslam_loop_verdict_dev(vslam_ctx* ctx, const vslam_epipolar* models, const v
 int vslam_loop_verdict_host(vslam_ctx* ctx, const vslam_epipolar* models, const vslam_set_pair* pairs, uint32_t nq, uint32_t c,
                             uint32_t n_train_sets, const vslam_loop_params* params, const vslam_loop_out* out);
 
+/* ---------------------------------------------------------------- frame structure: the trajectory's output seen per frame
+ * vslam_chain_dev keeps its cameras and world points per PAIR and per record; a loop names FRAMES.  This step gives each of the
+ * n_frames = n_pairs + 1 frames of a chained run one camera and one table from feature index to world point, without copying a
+ * point.  The inputs are what vslam_chain_dev read and wrote for n_pairs consecutive pairs: poses, matches, match_counts,
+ * match_cap, front_bits, point_cap, and chain [n_pairs].  The LIVE rule is the trajectory section's, verbatim.  A CPU restates
+ * every byte (tests/sim3ref.py): the arithmetic is the two product rules of the trajectory's step 4.
+ *
+ *   Source of frame f: pair f, query side (side 0), iff f < n_pairs and chain[f].valid != 0; else pair f - 1, train side (side 1),
+ *     iff f >= 1 and chain[f - 1].valid != 0; else none.
+ *   cams[f], query side:  W = chain[f].W, w = chain[f].w, segment = chain[f].segment, pair = f, side = 0, valid = 1  (copies).
+ *   cams[f], train side, with (R, t, s) = (poses[f - 1].R, poses[f - 1].t, chain[f - 1].scale) and (W, w) of chain[f - 1]:
+ *       W'[i][k] = (R[i][0]*W[0][k] + R[i][1]*W[1][k]) + R[i][2]*W[2][k];
+ *       w'[i]    = ((R[i][0]*w0 + R[i][1]*w1) + R[i][2]*w2) + s*t_i;
+ *     segment = chain[f - 1].segment, pair = f - 1, side = 1, valid = 1.  Every NaN is written as 0x7ff8000000000000.
+ *   cams[f], no source:  all twelve doubles 0.0, segment = pair = -1, side = 0, valid = 0.
+ *   index[f][k], k < point_cap: the LOWEST record i of the source pair that is live and whose query == k (query side) or
+ *     train == k (train side); -1 where there is none, and -1 for every k of a frame without a source.  Every entry of index is
+ *     written.  (An integer minimum: the same in any order.)  An entry is the record number as int32: with match_cap above 2^31 a
+ *     record i >= 2^31 reads back negative, and the loop alignment section, which asks for 0 <= entry < map_cap, does not use it.
+ * The world point of feature k of frame f is then map[cams[f].pair][index[f][k]] of vslam_chain_dev's `map` output. */
+typedef struct {
+    double W[9], w[3]; /* x_camera = W x_world + w, in the segment's world frame and unit */
+    int32_t segment;   /* the pair the segment started at: two frames share a world frame iff their segments are equal; -1: none */
+    int32_t pair;      /* the pair whose map rows hold this frame's points; -1: none */
+    int32_t side;      /* 0: the pair's query frame, 1: its train frame */
+    int32_t valid;
+} vslam_frame_cam; /* 112 bytes */
+typedef struct {
+    size_t struct_size;    /* = sizeof(vslam_frame_world_out) */
+    vslam_frame_cam* cams; /* [n_pairs + 1], required */
+    size_t cams_bytes;
+    int32_t* index;        /* [n_pairs + 1][point_cap], required */
+    size_t index_bytes;
+} vslam_frame_world_out;
+/* DEVICE pointers, all required.  Asynchronous on the context stream, never waits on the host (the counts are read on the
+ * device, the grids are sized from the capacities).  VSLAM_ERR_INVALID before any launch - and before the context is looked
+ * at - for a null pointer, a wrong struct_size, n_pairs outside 0 .. 65535 (0 does nothing: without a pair there is no
+ * trajectory), match_cap or point_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when there is no usable HIP device.  Not for
+ * stream capture. */
+int vslam_frame_world_dev(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                          uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, const vslam_chain* chain, int n_pairs,
+                          const vslam_frame_world_out* out);
+/* The same call over HOST arrays, synchronous (a convenience path: device buffers per call).  Errors as for vslam_frame_world_dev. */
+int vslam_frame_world_host(vslam_ctx* ctx, const vslam_pose* poses, const vslam_match* matches, const uint32_t* match_counts,
+                           uint32_t match_cap, const uint64_t* front_bits, uint32_t point_cap, const vslam_chain* chain, int n_pairs,
+                           const vslam_frame_world_out* out);
+
+/* ---------------------------------------------------------------- loop alignment: RANSAC Sim(3) between the two ends of a loop
+ * The two ends of a verified loop lie in world frames that have drifted apart, or in two segments with a world frame and a unit
+ * of their own.  This step estimates, per slot of a set-pair table, the similarity (s, R, t) that maps the 3-D structure seen
+ * from the query frame onto the structure seen from the train frame:  y_train_world = s R x_query_world + t  - the edge a pose
+ * graph needs, and the quantity that re-links two segments.  A RANSAC over 3-point samples (Horn's closed form with the symmetric
+ * scale), scored by reprojection into both cameras; a fixed number of hypotheses, no adaptive stop, no refit over the inliers.
+ * Slot p names query frame qs = pairs[p].query_set of `query` and train frame ts = pairs[p].train_set of `train`; the EMPTY rule
+ * is the loop verification section's, against (query->n_frames, train->n_frames).  Nothing is read through an empty slot.
+ *   A side is one vslam_sim3_side: cams and index as vslam_frame_world_dev wrote them, map as vslam_chain_dev wrote it
+ *   ([n_map_pairs][map_cap][3]), and points [n_frames][points_cap], the vslam_point lists of the frames.  Both sides may be the
+ *   same buffers, a slot may name one frame on both sides, and a frame may appear in any number of slots.
+ *   matches [n_pairs][match_cap] and match_counts [n_pairs] are vslam_match_pairs_dev's, with real feature indices;
+ *   m_p = min(match_counts[p], match_cap), 0 for an empty slot.  select_bits [n_pairs][(match_cap + 63) / 64], optional: record b
+ *   is SELECTED iff there are no select_bits or bit b % 64 of word b / 64 of the slot is set (the inlier_bits vslam_epipolar_dev
+ *   wrote over vslam_pair_points_dev's `local` list are exactly that).
+ * The arithmetic is fixed here so that a CPU can restate it bit for bit (tests/sim3ref.py): IEEE f64, every + - * / sqrt rounded
+ * on its own (no fused multiply-add), sums left to right as written, matrices row-major.  mix() is the two-view section's.
+ *
+ *  1. Correspondence of record b < m_p, (query, train) its indices as unsigned.  A camera cams[f] is TRUSTED iff valid != 0 and
+ *     (uint32)pair < n_map_pairs of its side.  link_q = index_q[qs][query] iff query < min(point_cap, points_cap) of the query
+ *     side, else -1; link_t likewise from train and the train side.  The record is USABLE iff it is selected, both cameras are
+ *     trusted, 0 <= link_q < map_cap of the query side and 0 <= link_t < map_cap of the train side, the octaves of
+ *     points_q[qs][query] and points_t[ts][train] are in 0 .. 31, and all six coordinates of X = map_q[cams_q[qs].pair][link_q]
+ *     and Y = map_t[cams_t[ts].pair][link_t] are finite.  With (x, y) the exact coordinate of a point (two-view section):
+ *       uq = (x_q - cx)/fx;  vq = (y_q - cy)/fy;  ut = (x_t - cx)/fx;  vt = (y_t - cy)/fy.
+ *     The usable records, in list order, are the slot's dense list of n_corr correspondences {X, Y, uq, vq, ut, vt, b}.
+ *  2. Sample.  Step 3 of the resection section with 3 kept indices: base = mix(mix(seed + p) + h); draw d = 0, 1, ... gives
+ *     r = mix(base + d) and the index (uint64(r) * n_corr) >> 32, kept if it is not among the indices kept so far; the sample is
+ *     the first 3 kept, in that order.  Fewer than 3 after 64 draws: invalid.  n_corr < 3: every hypothesis is invalid.
+ *  3. Model from the 3 correspondences (Xi, Yi):
+ *       cX_k = ((X0_k + X1_k) + X2_k) / 3, cY_k likewise;   A_i = Xi - cX,  B_i = Yi - cY   (componentwise);
+ *       |A_i|^2 = (A_i0*A_i0 + A_i1*A_i1) + A_i2*A_i2;   a2 = (|A_0|^2 + |A_1|^2) + |A_2|^2,  b2 likewise from B;
+ *       a2 or b2 zero or not finite: invalid;   s = sqrt(b2 / a2);   si = 1 / s;
+ *       M[r][c] = (B_0r*A_0c + B_1r*A_1c) + B_2r*A_2c.
+ *     R is step 5 of the resection section applied to this M, verbatim up to and including R[i][j] (the rules for n1 and n2
+ *     stay; there is no lambda): the two leading eigen-directions of M^T M, so the rank-2 M of a 3-point sample is its normal
+ *     case, and R is a proper rotation whatever the sign of det(M).
+ *       t_i = cY_i - s * ((R[i][0]*cX_0 + R[i][1]*cX_1) + R[i][2]*cX_2).
+ *     Any of s, si, the nine R, the three t not finite: invalid.  An invalid hypothesis has s = R = t = 0 and no inliers.
+ *  4. Composition, once per hypothesis, with (Wq, wq) = cams_q[qs] and (Wt, wt) = cams_t[ts]:
+ *       P[i][k] = (Wt[i][0]*R[0][k] + Wt[i][1]*R[1][k]) + Wt[i][2]*R[2][k];     Af[i][k] = s * P[i][k];
+ *       af_i = ((Wt[i][0]*t_0 + Wt[i][1]*t_1) + Wt[i][2]*t_2) + wt_i;
+ *       Q[i][k] = (Wq[i][0]*R[k][0] + Wq[i][1]*R[k][1]) + Wq[i][2]*R[k][2];     Ab[i][k] = si * Q[i][k]   (si = 1 / s);
+ *       ab_i = wq_i - ((Ab[i][0]*t_0 + Ab[i][1]*t_1) + Ab[i][2]*t_2).
+ *     (Af, af) takes a query-world point into the train camera, (Ab, ab) a train-world point into the query camera.
+ *  5. Inlier test.  A correspondence is an inlier iff step 6 of the resection section holds both ways: under (R, t) = (Af, af)
+ *     for the point X against (u, v) = (ut, vt), and under (Ab, ab) for the point Y against (uq, vq).
+ *  6. Selection: the valid hypothesis with the most inliers, the lowest h on ties.  Counts are integers, so the result does not
+ *     depend on how the correspondences are split over lanes and workgroups.
+ * Every double of a model or a hypothesis is finite or 0.0; every double of a correspondence is finite.
+ *
+ * Scratch (the context's): 24 bytes per record of capacity (n_pairs * match_cap), 88 more without a correspondences buffer,
+ * and n_pairs * n_hypotheses * 112 bytes without a hypotheses buffer; an allocation that fails is VSLAM_ERR_NOMEM. */
+typedef struct {
+    const vslam_frame_cam* cams; /* [n_frames] */
+    const int32_t* index;        /* [n_frames][point_cap] */
+    const double* map;           /* [n_map_pairs][map_cap][3]: vslam_chain_dev's map */
+    const vslam_point* points;   /* [n_frames][points_cap] */
+    uint32_t map_cap;            /* the match capacity of the chained pairs */
+    uint32_t point_cap;          /* the row pitch of index */
+    uint32_t points_cap;
+    uint32_t n_map_pairs;        /* 1 .. 65535: the rows of map */
+    int32_t n_frames;            /* 0 .. 65536 */
+    int32_t reserved;            /* 0 */
+} vslam_sim3_side;               /* 56 bytes */
+typedef struct {
+    uint32_t n_hypotheses; /* 1 .. 65535 */
+    uint32_t seed;
+    double max_dist2;      /* squared reprojection error in pixels^2, finite and positive */
+    vslam_pose_params K;   /* all finite, fx and fy positive */
+} vslam_sim3_params;
+typedef struct {
+    double s;         /* 0 when not valid, like R and t */
+    double R[9];
+    double t[3];
+    uint32_t inliers;
+    int32_t valid;
+} vslam_sim3_hyp; /* 112 bytes */
+typedef struct {
+    double X[3];       /* the query frame's world point */
+    double Y[3];       /* the train frame's world point */
+    double uq, vq;     /* the calibrated observation in the query frame */
+    double ut, vt;     /* ... in the train frame */
+    uint32_t b;        /* the match record it came from */
+    uint32_t reserved; /* 0 */
+} vslam_sim3_corr; /* 88 bytes */
+typedef struct {
+    double s;              /* the winner; s, R and t all zero when best < 0 */
+    double R[9];
+    double t[3];
+    uint32_t n_matches;    /* m_p */
+    uint32_t n_corr;       /* usable correspondences */
+    uint32_t n_inliers;    /* the winner's count, 0 when best < 0 */
+    int32_t best;          /* winning hypothesis, -1: none (always for an empty slot) */
+    uint32_t n_valid;      /* hypotheses that produced a model */
+    int32_t query_segment; /* cams_q[qs].segment and cams_t[ts].segment, copied; -1 both for an empty slot */
+    int32_t train_segment;
+    uint32_t reserved;     /* 0 */
+} vslam_sim3;              /* 136 bytes */
+typedef struct {
+    size_t struct_size;      /* = sizeof(vslam_sim3_out) */
+    vslam_sim3* models;      /* [n_pairs], required */
+    size_t models_bytes;
+    uint64_t* inlier_bits;   /* [n_pairs][(match_cap + 63) / 64] optional: bit b % 64 of word b / 64 = record b is usable and an
+                              * inlier of the winner; the first (m_p + 63) / 64 words of a slot are written (all zero when
+                              * best < 0), the rest untouched */
+    size_t inlier_bits_bytes;
+    vslam_sim3_hyp* hypotheses; /* [n_pairs][n_hypotheses] optional: every hypothesis with its count */
+    size_t hypotheses_bytes;
+    vslam_sim3_corr* correspondences; /* [n_pairs][match_cap] optional: the first n_corr rows of a slot are written */
+    size_t correspondences_bytes;
+    int32_t* links;          /* [n_pairs][match_cap][2] optional: for b < m_p {link_q, link_t} of step 1; the rest untouched */
+    size_t links_bytes;
+} vslam_sim3_out;
+/* query, train, params and out are HOST structs whose pointers, like pairs, matches, match_counts and select_bits, are DEVICE
+ * pointers; all but select_bits and the optional outputs are required.  Asynchronous on the context stream, never waits on the
+ * host (the counts and the tables are read on the device, the grids are sized from the capacities); scratch belongs to the
+ * context.  VSLAM_ERR_INVALID before any launch - and before the context is looked at - for a null argument, a wrong
+ * struct_size, n_pairs outside 0 .. 65535 (0 does nothing), n_hypotheses outside 1 .. 65535, a max_dist2 that is not finite or not
+ * positive, an intrinsic that is not finite, fx or fy not positive, a side with a null pointer, a zero capacity, n_frames outside
+ * 0 .. 65536, n_map_pairs outside 1 .. 65535 or reserved != 0, match_cap == 0, an undersized buffer; then VSLAM_ERR_HIP when
+ * there is no usable HIP device.  Not for stream capture. */
+int vslam_sim3_dev(vslam_ctx* ctx, const vslam_sim3_side* query, const vslam_sim3_side* train, const vslam_set_pair* pairs,
+                   const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap, const uint64_t* select_bits,
+                   int n_pairs, const vslam_sim3_params* params, const vslam_sim3_out* out);
+/* The same call over HOST arrays, synchronous (a convenience path: device buffers per call): the pointers of query and train are
+ * host arrays of the sizes above (a side given twice - query == train, or two equal structs - goes up once).  The rows the device
+ * call leaves untouched keep the caller's bytes.  Errors as for vslam_sim3_dev. */
+int vslam_sim3_host(vslam_ctx* ctx, const vslam_sim3_side* query, const vslam_sim3_side* train, const vslam_set_pair* pairs,
+                    const vslam_match* matches, const uint32_t* match_counts, uint32_t match_cap, const uint64_t* select_bits,
+                    int n_pairs, const vslam_sim3_params* params, const vslam_sim3_out* out);
+
 /* Timing hook for bench.py: when enabled, the context brackets every launch of the
  * named kernel with HIP events on the stream the launch goes to (the context's stream or one of the
  * batched path's side streams); vslam_kernel_timing_read synchronises and returns launches and total

@@ -64,6 +64,15 @@ RESECT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_obs", "<u4"
                          ("n_valid", "<u4"), ("reserved", "<u4")], align=True)  # vslam_resect, 120 bytes
 RESECT_REFINE_DTYPE = np.dtype([("n_before", "<u4"), ("n_after", "<u4"), ("accepted", "<u4"), ("stop", "<i4"), ("cost_before", "<f8"),
                                 ("cost_after", "<f8")], align=True)  # vslam_resect_refine, 32 bytes
+FRAME_CAM_DTYPE = np.dtype([("W", "<f8", (9,)), ("w", "<f8", (3,)), ("segment", "<i4"), ("pair", "<i4"), ("side", "<i4"), ("valid", "<i4")],
+                           align=True)  # vslam_frame_cam, 112 bytes
+SIM3_HYP_DTYPE = np.dtype([("s", "<f8"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("inliers", "<u4"), ("valid", "<i4")], align=True)  # vslam_sim3_hyp, 112 bytes
+SIM3_CORR_DTYPE = np.dtype([("X", "<f8", (3,)), ("Y", "<f8", (3,)), ("uq", "<f8"), ("vq", "<f8"), ("ut", "<f8"), ("vt", "<f8"), ("b", "<u4"),
+                            ("reserved", "<u4")], align=True)  # vslam_sim3_corr, 88 bytes
+SIM3_DTYPE = np.dtype([("s", "<f8"), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_matches", "<u4"), ("n_corr", "<u4"), ("n_inliers", "<u4"), ("best", "<i4"),
+                       ("n_valid", "<u4"), ("query_segment", "<i4"), ("train_segment", "<i4"), ("reserved", "<u4")], align=True)  # vslam_sim3, 136 bytes
+# What the tools pass unless told otherwise: the squared reprojection threshold of loop alignment, in pixels^2.
+SIM3_MAX_DIST2 = 16.0
 TRACK_DTYPE = np.dtype([("X", "<f8", (3,)), ("det", "<f8"), ("n_views", "<u4"), ("n_ok", "<u4"), ("status", "<u4"), ("reserved", "<u4")],
                        align=True)  # vslam_track, 48 bytes
 TRACK_REF_DTYPE = np.dtype([("head_record", "<u4"), ("pos", "<u4")], align=True)  # vslam_track_ref, 8 bytes
@@ -201,6 +210,43 @@ class LoopOut(C.Structure):
     """vslam_loop_out: struct_size, then every pointer with the bytes behind it."""
     _fields_ = [("struct_size", C.c_size_t), ("loops", C.c_void_p), ("loops_bytes", C.c_size_t), ("loop_list", C.c_void_p),
                 ("loop_list_bytes", C.c_size_t), ("n_loops", C.c_void_p), ("n_loops_bytes", C.c_size_t)]
+
+
+class FrameCam(C.Structure):
+    _fields_ = [("W", C.c_double * 9), ("w", C.c_double * 3), ("segment", C.c_int32), ("pair", C.c_int32), ("side", C.c_int32), ("valid", C.c_int32)]
+
+
+class FrameWorldOut(C.Structure):
+    """vslam_frame_world_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("cams", C.c_void_p), ("cams_bytes", C.c_size_t), ("index", C.c_void_p), ("index_bytes", C.c_size_t)]
+
+
+class Sim3Side(C.Structure):
+    """vslam_sim3_side: one end of the loops behind device (or, for sim3_host, host) pointers (sim3_side() fills one)."""
+    _fields_ = [("cams", C.c_void_p), ("index", C.c_void_p), ("map", C.c_void_p), ("points", C.c_void_p), ("map_cap", C.c_uint32),
+                ("point_cap", C.c_uint32), ("points_cap", C.c_uint32), ("n_map_pairs", C.c_uint32), ("n_frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Sim3Hyp(C.Structure):
+    _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("inliers", C.c_uint32), ("valid", C.c_int32)]
+
+
+class Sim3Corr(C.Structure):
+    _fields_ = [("X", C.c_double * 3), ("Y", C.c_double * 3), ("uq", C.c_double), ("vq", C.c_double), ("ut", C.c_double), ("vt", C.c_double),
+                ("b", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Sim3(C.Structure):
+    _fields_ = [("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("n_matches", C.c_uint32), ("n_corr", C.c_uint32),
+                ("n_inliers", C.c_uint32), ("best", C.c_int32), ("n_valid", C.c_uint32), ("query_segment", C.c_int32), ("train_segment", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class Sim3Out(C.Structure):
+    """vslam_sim3_out: struct_size, then every pointer with the bytes behind it."""
+    _fields_ = [("struct_size", C.c_size_t), ("models", C.c_void_p), ("models_bytes", C.c_size_t), ("inlier_bits", C.c_void_p),
+                ("inlier_bits_bytes", C.c_size_t), ("hypotheses", C.c_void_p), ("hypotheses_bytes", C.c_size_t), ("correspondences", C.c_void_p),
+                ("correspondences_bytes", C.c_size_t), ("links", C.c_void_p), ("links_bytes", C.c_size_t)]
 
 
 class EpipolarHyp(C.Structure):
@@ -366,6 +412,10 @@ class ResectOut(C.Structure):
                 ("correspondences_bytes", C.c_size_t), ("links", C.c_void_p), ("links_bytes", C.c_size_t)]
 
 
+class Sim3Params(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_uint32), ("seed", C.c_uint32), ("max_dist2", C.c_double), ("K", PoseParams)]
+
+
 class ResectRefineParams(C.Structure):
     _fields_ = [("rounds", C.c_uint32), ("max_dist2", C.c_double), ("K", PoseParams)]
 
@@ -529,6 +579,10 @@ SIGNATURES = {
     "vslam_pair_points_dev": (_I, [_P, _P, _P, C.c_uint32, _P, _I, _P, C.c_uint32, _I, _P, C.c_uint32, _I, _P, _Z, _P, _Z, _P, _Z]),
     "vslam_loop_verdict_dev": (_I, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoopParams), C.POINTER(LoopOut)]),
     "vslam_loop_verdict_host": (_I, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(LoopParams), C.POINTER(LoopOut)]),
+    "vslam_frame_world_dev": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _I, C.POINTER(FrameWorldOut)]),
+    "vslam_frame_world_host": (_I, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _I, C.POINTER(FrameWorldOut)]),
+    "vslam_sim3_dev": (_I, [_P, C.POINTER(Sim3Side), C.POINTER(Sim3Side), _P, _P, _P, C.c_uint32, _P, _I, C.POINTER(Sim3Params), C.POINTER(Sim3Out)]),
+    "vslam_sim3_host": (_I, [_P, C.POINTER(Sim3Side), C.POINTER(Sim3Side), _P, _P, _P, C.c_uint32, _P, _I, C.POINTER(Sim3Params), C.POINTER(Sim3Out)]),
     "vslam_kernel_timing_enable": (_I, [_P, C.c_char_p]),
     "vslam_kernel_timing_read": (_I, [_P, C.POINTER(_I), C.POINTER(_D)]),
     "vslam_kernel_names": (C.c_char_p, []),
@@ -690,6 +744,36 @@ def desc_sets(desc, counts, defined=None, points=None) -> DescSets:
                  counts.data_ptr(), cap)
     s.n = n
     return s
+
+
+def sim3_side(cams, index, map, points, n_frames: int | None = None) -> Sim3Side:
+    """A vslam_sim3_side over CUDA tensors (kept alive on the returned struct): cams - any contiguous tensor of n_frames * 112 bytes
+    as frame_world() wrote it -, index int32 [n_frames, point_cap], map float64 [n_map_pairs, map_cap, 3] as chain() wrote it,
+    points int32 [n_frames, points_cap, 6], the frames' point lists."""
+    ok = all(t.is_contiguous() for t in (cams, index, map, points))
+    ok = ok and index.dim() == 2 and index.element_size() == 4 and map.dim() == 3 and map.shape[2] * map.element_size() == 24
+    ok = ok and points.dim() == 3 and points.shape[2] * points.element_size() == 24
+    if not ok:
+        raise ValueError("sim3_side: contiguous cams, index [n_frames, point_cap] int32, map [n_map_pairs, map_cap, 3] float64 and points "
+                         "[n_frames, points_cap, 6] int32")
+    nf = index.shape[0] if n_frames is None else int(n_frames)
+    if cams.numel() * cams.element_size() < nf * 112 or index.shape[0] < nf or points.shape[0] < nf:
+        raise ValueError("sim3_side: fewer rows than frames")
+    s = Sim3Side(cams.data_ptr(), index.data_ptr(), map.data_ptr(), points.data_ptr(), map.shape[1], index.shape[1], points.shape[1], map.shape[0], nf, 0)
+    s.keep = (cams, index, map, points)
+    return s
+
+
+def _host_sim3_side(stage, side, keep):
+    """A vslam_sim3_side over the numpy arrays of a side dict (cams, index, map, points); the converted arrays are appended to keep."""
+    cams, points = _records(side["cams"], FRAME_CAM_DTYPE), np.ascontiguousarray(side["points"], dtype=POINT_DTYPE)
+    index, mp = np.ascontiguousarray(side["index"], dtype=np.int32), np.ascontiguousarray(side["map"], dtype=np.float64)
+    nf = len(cams)
+    if index.ndim != 2 or points.ndim != 2 or mp.ndim != 3 or mp.shape[2] != 3 or index.shape[0] != nf or points.shape[0] != nf:
+        raise ValueError(f"{stage}: a side is cams [nf], index [nf, point_cap], map [n_map_pairs, map_cap, 3] and points [nf, points_cap]")
+    keep += [cams, index, mp, points]
+    return Sim3Side(cams.ctypes.data, index.ctypes.data, mp.ctypes.data, points.ctypes.data, mp.shape[1], index.shape[1], points.shape[1], mp.shape[0],
+                    nf, 0)
 
 
 def _u8(a):
@@ -2064,6 +2148,94 @@ class Context:
         self._chk(lib().vslam_loop_verdict_host(self._h, md.ctypes.data if nq else loops.ctypes.data, pr.ctypes.data if nq else loops.ctypes.data, nq, c,
                                                 int(n_train_sets), C.byref(lp), C.byref(lo)), "vslam_loop_verdict_host")
         return loops, lst, int(n[0])
+
+    def frame_world(self, poses, matches, match_counts, front_bits, point_cap: int, chain, cams, index, n_pairs: int | None = None):
+        """vslam_frame_world_dev: the output of chain() seen per frame - cams, any contiguous tensor of (n + 1) * 112 bytes
+        (FRAME_CAM_DTYPE after .cpu().numpy().view), and index int32 [n + 1, point_cap], the lowest live record of a frame's source
+        pair per feature or -1; asynchronous on the context stream.  poses, matches [n, match_cap, 3], match_counts, front_bits and
+        point_cap are what chain() read, chain the tensor it wrote (n * 176 bytes).  The world point of feature k of frame f is
+        map[cams[f].pair][index[f][k]] of chain()'s map."""
+        stage = "frame_world"
+        tensors = dict(poses=poses, matches=matches, match_counts=match_counts, front_bits=front_bits, chain=chain, cams=cams, index=index)
+        _check_tensors(stage, self.where, tensors, tuple(tensors))
+        _check_records(stage, "matches", matches, 12, "[n, match_cap, 3]")
+        n, cap = matches.shape[0] if n_pairs is None else int(n_pairs), matches.shape[1]
+        nf = n + 1 if n else 0
+        _check_sets(stage, n, (matches,), (match_counts,), ((poses, n * 112), (front_bits, n * ((cap + 63) // 64) * 8), (chain, n * 176),
+                                                              (cams, nf * 112), (index, nf * int(point_cap) * 4)))
+        fo = _fill_out(FrameWorldOut(), dict(cams=cams, index=index))
+        self._chk(lib().vslam_frame_world_dev(self._h, poses.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap, front_bits.data_ptr(),
+                                              int(point_cap), chain.data_ptr(), n, C.byref(fo)), "vslam_frame_world_dev")
+
+    def frame_world_host(self, poses, matches, match_counts, front_bits, point_cap: int, chain):
+        """vslam_frame_world_host: the same call over numpy arrays - poses [n] POSE_DTYPE, matches [n, match_cap] MATCH_DTYPE,
+        match_counts [n], front_bits uint64 [n, (match_cap + 63) // 64], chain [n] CHAIN_DTYPE - -> (cams [n + 1] FRAME_CAM_DTYPE, index
+        int32 [n + 1, point_cap]); both empty for n == 0."""
+        ps, mt, n, cap = _host_structure("frame_world_host", poses, matches)
+        cnt, fb, ch = _counts(match_counts), _words(front_bits), _records(chain, CHAIN_DTYPE)
+        if len(cnt) != n or fb.size != n * ((cap + 63) // 64) or len(ch) != n:
+            raise ValueError("frame_world_host: one count, one chain record and (match_cap + 63) // 64 words per pair")
+        nf = n + 1 if n else 0
+        cams, index = np.zeros(max(nf, 1), FRAME_CAM_DTYPE), np.full((max(nf, 1), int(point_cap)), -1, np.int32)
+        fo = _fill_out(FrameWorldOut(), dict(cams=cams, index=index))
+        self._chk(lib().vslam_frame_world_host(self._h, ps.ctypes.data, mt.ctypes.data, cnt.ctypes.data, cap, fb.ctypes.data, int(point_cap),
+                                               ch.ctypes.data, n, C.byref(fo)), "vslam_frame_world_host")
+        return cams[:nf], index[:nf]
+
+    def sim3(self, query: Sim3Side, train: Sim3Side, pairs, matches, match_counts, intrinsics, select_bits=None, n_hypotheses: int = 512,
+             seed: int = 0, max_dist2: float = SIM3_MAX_DIST2, n_pairs: int | None = None, models=None, inlier_bits=None, hypotheses=None,
+             correspondences=None, links=None):
+        """vslam_sim3_dev: one similarity (s, R, t), y_train_world = s R x_query_world + t, per slot of a set-pair table, by RANSAC
+        over the 3-D points the two frames of a slot have in their own world frames; asynchronous on the context stream.  query and
+        train: sim3_side() of each end (the same object for loops inside one run); pairs int32 [n, 2]; matches [n, match_cap, 3] and
+        match_counts as match_pairs() wrote them; select_bits [n, (match_cap + 63) // 64] 8-byte words, optional (epipolar()'s
+        inlier_bits over pair_points()'s local list); intrinsics = (fx, fy, cx, cy).  Outputs, CUDA tensors: models - any contiguous
+        tensor of n * 136 bytes (SIM3_DTYPE after .cpu().numpy().view), inlier_bits [n, (match_cap + 63) // 64] 8-byte words,
+        hypotheses n * n_hypotheses * 112 bytes (SIM3_HYP_DTYPE), correspondences n * match_cap * 88 bytes (SIM3_CORR_DTYPE), links
+        int32 [n, match_cap, 2]."""
+        stage = "sim3"
+        tensors = dict(pairs=pairs, matches=matches, match_counts=match_counts, select_bits=select_bits, models=models, inlier_bits=inlier_bits,
+                       hypotheses=hypotheses, correspondences=correspondences, links=links)
+        _check_tensors(stage, self.where, tensors, ("pairs", "matches", "match_counts", "models"))
+        _check_records(stage, "matches", matches, 12, "[n, match_cap, 3]")
+        n, cap = matches.shape[0] if n_pairs is None else int(n_pairs), matches.shape[1]
+        _check_sets(stage, n, (matches,), (match_counts,), ((pairs, n * 8), (select_bits, n * ((cap + 63) // 64) * 8)))
+        so = _fill_out(Sim3Out(), dict(models=models, inlier_bits=inlier_bits, hypotheses=hypotheses, correspondences=correspondences, links=links))
+        prm = Sim3Params(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
+        self._chk(lib().vslam_sim3_dev(self._h, C.byref(query), C.byref(train), pairs.data_ptr(), matches.data_ptr(), match_counts.data_ptr(), cap,
+                                       None if select_bits is None else select_bits.data_ptr(), n, C.byref(prm), C.byref(so)), "vslam_sim3_dev")
+
+    def sim3_host(self, query, train, pairs, matches, match_counts, intrinsics, select_bits=None, n_hypotheses: int = 512, seed: int = 0,
+                  max_dist2: float = SIM3_MAX_DIST2, inlier_bits=None, hypotheses=None, correspondences=None, links=None):
+        """vslam_sim3_host: the same call over numpy arrays.  query and train: dicts of cams [nf] FRAME_CAM_DTYPE, index int32 [nf,
+        point_cap], map float64 [n_map_pairs, map_cap, 3] and points [nf, points_cap] POINT_DTYPE (one dict for both: the side goes up
+        once); pairs [n] SET_PAIR_DTYPE, matches [n, match_cap] MATCH_DTYPE, match_counts [n], select_bits uint64 [n, (match_cap + 63)
+        // 64] or None -> models [n] SIM3_DTYPE.  inlier_bits uint64 [n, words], hypotheses [n, n_hypotheses] SIM3_HYP_DTYPE,
+        correspondences [n, match_cap] SIM3_CORR_DTYPE and links int32 [n, match_cap, 2] are written in place when given (C-contiguous
+        arrays of exactly that type); the rows the call leaves untouched keep their bytes."""
+        stage = "sim3_host"
+        keep = []
+        sq = _host_sim3_side(stage, query, keep)
+        st = sq if train is query else _host_sim3_side(stage, train, keep)
+        pr, mt = _records(pairs, SET_PAIR_DTYPE), np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(pr)
+        if mt.ndim != 2 or mt.shape[0] != n:
+            raise ValueError(f"{stage}: matches must be [n, match_cap]")
+        cap, cnt = mt.shape[1], _counts(match_counts)
+        words = (cap + 63) // 64
+        sel = None if select_bits is None else _words(select_bits)
+        if len(cnt) != n or (sel is not None and sel.size != n * words):
+            raise ValueError(f"{stage}: one count and (match_cap + 63) // 64 select words per slot")
+        outs = (("inlier_bits", inlier_bits, np.uint64, n * words), ("hypotheses", hypotheses, SIM3_HYP_DTYPE, n * int(n_hypotheses)),
+                ("correspondences", correspondences, SIM3_CORR_DTYPE, n * cap), ("links", links, np.int32, n * cap * 2))
+        _check_host_outs(stage, outs)
+        models = np.zeros(max(n, 1), SIM3_DTYPE)
+        so = _fill_out(Sim3Out(), dict(models=models, inlier_bits=inlier_bits, hypotheses=hypotheses, correspondences=correspondences, links=links))
+        prm = Sim3Params(int(n_hypotheses), int(seed) & 0xFFFFFFFF, float(max_dist2), PoseParams(*(float(v) for v in intrinsics)))
+        at = lambda a: a.ctypes.data if a.size else models.ctypes.data  # (no slots: a pointer that is never followed)
+        self._chk(lib().vslam_sim3_host(self._h, C.byref(sq), C.byref(st), at(pr), at(mt), at(cnt), cap, None if sel is None else sel.ctypes.data, n,
+                                        C.byref(prm), C.byref(so)), "vslam_sim3_host")
+        return models[:n]
 
     def kernel_timing_enable(self, name: str | None):
         self._chk(lib().vslam_kernel_timing_enable(self._h, name.encode() if name else None), "vslam_kernel_timing_enable")

@@ -1,12 +1,12 @@
 // The steps that the model-estimation stages share, each stated once.  A stage's __global__ kernels (kernels_epipolar.hip.h,
-// kernels_homography.hip.h, kernels_resect.hip.h; kernels_refit.hip.h, kernels_hrefit.hip.h) are a few lines over these
+// kernels_homography.hip.h, kernels_resect.hip.h, kernels_sim3.hip.h; kernels_refit.hip.h, kernels_hrefit.hip.h) are a few lines over these
 // bodies: every body is inlined, and a kernel's name, signature and device code are what they were when it was written out
 // (profiles/estimators_isa_identity.txt).
 //   RANSAC       : ransac_select (the winner of a pair), ransac_flags (its ballot words)
 //   refit rounds : refit_pass (a streaming pass: the idle test, the model, one block of the ordered sum) with the add steps of
 //                  the count and distance passes, and the per-pair steps refit_init, refit_begin, refit_scale
 // A stage is named by its model: the 3 x 3 blocks a lane keeps in registers (EpiModel, HomModel: vslam_epipolar_plan.h;
-// ResModel: here).  model_copy<Model> copies them between any two things that name the blocks as the ABI does - a model, a
+// ResModel, Sim3Model: here).  model_copy<Model> copies them between any two things that name the blocks as the ABI does - a model, a
 // hypothesis, a pair's record -, and the stages over EpiXY records have model_inlier.  What stays with its stage: the *_models
 // kernels (k_epi_models stands at its register budget, kernels_geom3.hip.h), the *_score kernels (behind an inlined body their
 // scalar prologue is scheduled otherwise), k_res_flags (it recomputes the correspondence), k_hom_verdict, the add step of the
@@ -27,6 +27,9 @@ namespace vslam {
 struct ResModel {  // the pose of a resection hypothesis or pair
     double R[9], t[3];
 };
+struct Sim3Model {  // the similarity of a loop alignment hypothesis or slot
+    double s, R[9], t[3];
+};
 // d's blocks = s's: the blocks are Model's, d and s anything that names them so.
 template <class Model, class D, class S>
 __device__ __forceinline__ void model_copy(D& d, const S& s) {
@@ -37,11 +40,12 @@ __device__ __forceinline__ void model_copy(D& d, const S& s) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) d.H[i] = s.H[i], d.G[i] = s.G[i];
     } else {
-        static_assert(std::is_same<Model, ResModel>::value, "EpiModel, HomModel or ResModel");
+        static_assert(std::is_same<Model, ResModel>::value || std::is_same<Model, Sim3Model>::value, "EpiModel, HomModel, ResModel or Sim3Model");
 #pragma unroll
         for (int i = 0; i < 9; ++i) d.R[i] = s.R[i];
 #pragma unroll
         for (int i = 0; i < 3; ++i) d.t[i] = s.t[i];
+        if constexpr (std::is_same<Model, Sim3Model>::value) d.s = s.s;
     }
 }
 // A record whose every block reads 0.0: the "no model" of the ABI.
@@ -49,6 +53,7 @@ struct ZeroBlocks {
     struct Block {
         __device__ double operator[](int) const { return 0.0; }
     } F, H, G, R, t;
+    static constexpr double s = 0.0;  // (the scale of a Sim3Model; not a member of the record: the layout stays)
 };
 __device__ __forceinline__ bool model_inlier(const EpiModel& m, const EpiXY& p, double max_dist2) { return epi_inlier(m.F, p, max_dist2); }
 __device__ __forceinline__ bool model_inlier(const HomModel& m, const EpiXY& p, double max_dist2) { return hom_inlier(m.H, m.G, p, max_dist2); }

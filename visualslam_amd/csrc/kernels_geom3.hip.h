@@ -78,6 +78,61 @@ G3 inline void g3_rank2(double (&f)[9]) {
     }
 }
 
+// The rotation nearest to M from its two leading eigen-directions (step 5 of the resection section up to and including
+// R[i][j]; step 3 of the loop alignment section): the sweeps on M^T M, v1 and v2 the columns of V beside the smallest
+// diagonal entry (lowest index on ties), v3 = v1 x v2; u1 = M v1 normalised, u2 = M v2 made orthogonal to u1 and normalised,
+// u3 = u1 x u2; R = u1 v1^T + u2 v2^T + u3 v3^T - a proper rotation whatever the sign of det(M), and the rank-2 M of a 3-point
+// sample is its normal case.  n = (n1, n2, n3), the norms of M v1, of the orthogonalised M v2 and of M v3; false: n1 or n2 is
+// zero or not finite (R is not written; n3 is set only on success).  k_sim3_models calls this; k_res_models keeps the same
+// lines in its own body (routed through this function its device code changes: profiles/sim3_isa_identity.txt).
+G3 inline void g3_cross(const double (&a)[3], const double (&b)[3], double (&o)[3]) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+G3 inline void g3_mul(const double (&M)[9], const double (&v)[3], double (&w)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w[i] = (M[3 * i] * v[0] + M[3 * i + 1] * v[1]) + M[3 * i + 2] * v[2];
+}
+G3 inline double g3_norm(const double (&w)[3]) { return sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]); }
+G3 inline bool g3_nearest_rotation(const double (&M)[9], double (&R)[9], double (&n)[3]) {
+    double S[3], V[3][3];
+    g3_gram_jacobi<1>(M, S, V);
+    int k = 0;
+    double smin = S[0];
+    if (S[1] < smin) k = 1, smin = S[1];
+    if (S[2] < smin) k = 2, smin = S[2];
+    double v1[3], v2[3], v3[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        v1[i] = k == 0 ? V[i][1] : V[i][0];
+        v2[i] = k == 2 ? V[i][1] : V[i][2];
+    }
+    g3_cross(v1, v2, v3);
+    double w1[3], w2[3], w3[3], u1[3], u2[3], u3[3];
+    g3_mul(M, v1, w1);
+    n[0] = g3_norm(w1);
+    if (!g3_finite_nonzero(n[0])) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u1[i] = w1[i] / n[0];
+    g3_mul(M, v2, w2);
+    const double g = (u1[0] * w2[0] + u1[1] * w2[1]) + u1[2] * w2[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w2[i] = w2[i] - g * u1[i];
+    n[1] = g3_norm(w2);
+    if (!g3_finite_nonzero(n[1])) return false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u2[i] = w2[i] / n[1];
+    g3_cross(u1, u2, u3);
+    g3_mul(M, v3, w3);
+    n[2] = g3_norm(w3);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[3 * i + c] = (u1[i] * v1[c] + u2[i] * v2[c]) + u3[i] * v3[c];
+    return true;
+}
+
 struct G3Affine {  // the matrix [[sx, 0, ax], [0, sy, ay], [0, 0, 1]]: a normalisation, or the intrinsics
     double sx, sy, ax, ay;
 };

@@ -72,7 +72,8 @@ static const char* const kKernelNames =
     "k_vocab_gather\nk_words_nn\nk_words_merge\n"
     "k_place_df\nk_place_self\nk_place_score\nk_place_top\n"
     "k_kmeans_init\nk_kmeans_count\nk_kmeans_columns\nk_kmeans_scan\nk_kmeans_members\nk_kmeans_block_sums\nk_kmeans_update\n"
-    "k_loop_pairs\nk_match_nn2_pairs\nk_match_merge_pairs\nk_pair_points\nk_loop_verdict";
+    "k_loop_pairs\nk_match_nn2_pairs\nk_match_merge_pairs\nk_pair_points\nk_loop_verdict\n"
+    "k_frame_index\nk_frame_cams\nk_sim3_corr\nk_sim3_gather\nk_sim3_models\nk_sim3_score\nk_sim3_select\nk_sim3_flags";
 
 
 // Runs `body` with the context's launch stream temporarily replaced (LAUNCH uses ctx->stream).

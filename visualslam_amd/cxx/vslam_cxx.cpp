@@ -1047,3 +1047,63 @@ vslam::VerifiedLoops vslam::verifyLoops(const DescriptorSets& frames, const std:
     out.loopList.assign(list.begin(), list.begin() + std::min<size_t>(count, n));
     return out;
 }
+
+vslam::FrameWorld vslam::frameWorld(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                                    uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain) {
+    const size_t n = poses.size();
+    require(n <= 65535 && matchCounts.size() == n && chain.size() == n && matches.size() == n * matchCap &&
+                frontBits.size() == n * (((size_t)matchCap + 63) / 64),
+            "frameWorld: one count, one chain record, matchCap records and (matchCap + 63) / 64 words per pair");
+    vslam::FrameWorld out;
+    if (n == 0) return out;
+    out.cams.resize(n + 1);
+    out.index.assign((n + 1) * pointCap, -1);
+    vslam_frame_world_out o{};
+    o.struct_size = sizeof(o);
+    o.cams = out.cams.data(), o.cams_bytes = out.cams.size() * sizeof(vslam_frame_cam);
+    o.index = out.index.data(), o.index_bytes = out.index.size() * sizeof(int32_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_frame_world_host(c, poses.data(), matches.data(), matchCounts.data(), matchCap, frontBits.data(), pointCap, chain.data(), (int)n, &o),
+                 c, "frameWorld");
+    return out;
+}
+
+static vslam_sim3_side sim3Side(const vslam::WorldSide& s, const char* sizes) {
+    const size_t nf = s.frames.cams.size();
+    require(nf <= 65536 && s.pointCap && s.mapCap && s.pointsCap && s.frames.index.size() == nf * s.pointCap && s.points.size() == nf * s.pointsCap &&
+                !s.map.empty() && s.map.size() % ((size_t)s.mapCap * 3) == 0 && s.map.size() / ((size_t)s.mapCap * 3) <= 65535,
+            sizes);
+    return vslam_sim3_side{s.frames.cams.data(), s.frames.index.data(), s.map.data(), reinterpret_cast<const vslam_point*>(s.points.data()), s.mapCap,
+                           s.pointCap, s.pointsCap, (uint32_t)(s.map.size() / ((size_t)s.mapCap * 3)), (int32_t)nf, 0};
+}
+
+vslam::LoopAlignment vslam::alignLoops(const vslam::WorldSide& query, const vslam::WorldSide& train, const std::vector<vslam_set_pair>& pairs,
+                                       const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts, uint32_t matchCap,
+                                       const vslam_sim3_params& params, const std::vector<uint64_t>* selectBits) {
+    const size_t n = pairs.size(), recs = n * matchCap, words = n * (((size_t)matchCap + 63) / 64);
+    require(n <= 65535 && matchCap > 0 && matchCounts.size() == n && matches.size() == recs && (!selectBits || selectBits->size() == words),
+            "alignLoops: one count, matchCap records and (matchCap + 63) / 64 select words per slot");
+    const vslam_pose_params& K = params.K;
+    require(params.n_hypotheses >= 1 && params.n_hypotheses <= 65535 && std::isfinite(params.max_dist2) && params.max_dist2 > 0.0 && std::isfinite(K.fx) &&
+                std::isfinite(K.fy) && std::isfinite(K.cx) && std::isfinite(K.cy) && K.fx > 0.0 && K.fy > 0.0,
+            "alignLoops: 1 .. 65535 hypotheses, a finite positive max_dist2, finite intrinsics with positive fx and fy");
+    const char* sizes = "alignLoops: a side is frames [frames] with index [frames][pointCap], map [pairs][mapCap][3] and points [frames][pointsCap]";
+    const vslam_sim3_side q = sim3Side(query, sizes), t = &train == &query ? q : sim3Side(train, sizes);
+    vslam::LoopAlignment out;
+    out.models.resize(n);
+    out.inlierBits.assign(words, 0);
+    out.correspondences.resize(recs);
+    out.links.assign(recs * 2, -1);
+    if (n == 0) return out;
+    vslam_sim3_out o{};
+    o.struct_size = sizeof(o);
+    o.models = out.models.data(), o.models_bytes = n * sizeof(vslam_sim3);
+    o.inlier_bits = out.inlierBits.data(), o.inlier_bits_bytes = words * sizeof(uint64_t);
+    o.correspondences = out.correspondences.data(), o.correspondences_bytes = recs * sizeof(vslam_sim3_corr);
+    o.links = out.links.data(), o.links_bytes = out.links.size() * sizeof(int32_t);
+    vslam_ctx* c = vslam::default_context();
+    vslam::check(vslam_sim3_host(c, &q, &t, pairs.data(), matches.data(), matchCounts.data(), matchCap, selectBits ? selectBits->data() : nullptr, (int)n,
+                                 &params, &o),
+                 c, "alignLoops");
+    return out;
+}

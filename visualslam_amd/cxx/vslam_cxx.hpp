@@ -427,4 +427,37 @@ VerifiedLoops verifyLoops(const DescriptorSets& frames, const std::vector<std::v
                           const std::vector<std::vector<vslam_place_cand>>& candidates, uint32_t maxCandidates, uint32_t dbFirst = 0,
                           const vslam_loop_params& params = {12, 2, 5, 0}, const vslam_epipolar_params& ransac = {512, 1, 4.0}, float ratio = 0.8f,
                           const DefinedSets* defined = nullptr);
+// Frame structure (include/vslam.h, "frame structure"): what chainPoses read and wrote, seen per frame, on the GPU
+// (vslam_frame_world_host): one camera per frame of the pairs + 1 frames and, per feature index, the lowest live record of the
+// frame's source pair, or -1.  The world point of feature k of frame f is map[cams[f].pair][index[f][k]] of Trajectory::map.
+struct FrameWorld {
+    std::vector<vslam_frame_cam> cams;  // [pairs + 1]; empty without a pair
+    std::vector<int32_t> index;         // [pairs + 1][pointCap]
+};
+FrameWorld frameWorld(const std::vector<vslam_pose>& poses, const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts,
+                      uint32_t matchCap, const std::vector<uint64_t>& frontBits, uint32_t pointCap, const std::vector<vslam_chain>& chain);
+
+// Loop alignment (include/vslam.h, "loop alignment"): per slot of a set-pair table the similarity (s, R, t) with
+// y_train_world = s R x_query_world + t between the world points of the slot's two frames, by RANSAC on the GPU (vslam_sim3_host;
+// the sample, Horn's closed form, the composition with the two cameras and the two reprojection tests are stated in the header).
+// One end of the loops: the frames of a chained run.  For loops inside one run both ends are one object.
+struct WorldSide {
+    FrameWorld frames;               // of frameWorld
+    uint32_t pointCap = 0;           // as given to frameWorld
+    std::vector<double> map;         // Trajectory::map, [pairs][mapCap][3]
+    uint32_t mapCap = 0;             // the matchCap of the chained pairs
+    std::vector<SLAM::point> points; // [pairs + 1][pointsCap]: the frames' point lists
+    uint32_t pointsCap = 0;
+};
+struct LoopAlignment {
+    std::vector<vslam_sim3> models;               // [slot]
+    std::vector<uint64_t> inlierBits;             // [slot][(matchCap + 63) / 64]: the winner's inliers among the match records
+    std::vector<vslam_sim3_corr> correspondences; // [slot][matchCap]: the first n_corr rows of a slot
+    std::vector<int32_t> links;                   // [slot][matchCap][2]: the two map records of a match record, or -1
+};
+// matches [slots][matchCap] and matchCounts [slots] with real feature indices (PairMatches laid side by side); selectBits, when
+// given, [slots][(matchCap + 63) / 64]: only the records whose bit is set take part.
+LoopAlignment alignLoops(const WorldSide& query, const WorldSide& train, const std::vector<vslam_set_pair>& pairs,
+                         const std::vector<vslam_match>& matches, const std::vector<uint32_t>& matchCounts, uint32_t matchCap,
+                         const vslam_sim3_params& params, const std::vector<uint64_t>* selectBits = nullptr);
 }  // namespace vslam
